@@ -83,9 +83,6 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
                                                                 int block_mode, uint32_t block_thr,
                                                                 uint32_t* __restrict__ block_table,
                                                                 unsigned long long* __restrict__ counters,
-                                                                const uint4* __restrict__ pstage, const uint32_t* __restrict__ ptcount2,
-                                                                const uint32_t* __restrict__ ptpre, uint32_t pnwt,
-                                                                uint4* __restrict__ hits, uint64_t hits_cap,
                                                                 const uint32_t* __restrict__ rdx) {
   (void)rdx;  // (reads with X stay with k_match_t)
   constexpr int W = 2, NW = 8, NIN = CTX_INLINE;
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
   // The wave's buffer, 512 x 16 bytes, by phase:
   //   F1 / F2  [0, 512)    the window's 64 bucket lines, swizzled
   //   F3       [0, 192)    the overflow entries in hand: three planes of 64 x 16 bytes
-  //            [192, 256)  the first 64 tuples the PREVIOUS batch's launch staged for this wave-tile, on their way to `hits`
+  //            [192, 256)  free (r02-r03: the previous batch's tuples on their way to `hits`, a scheme since retired)
   //            [256, 384)  the next wave-tile's records
   //            [384, 400)  best[64]: smallest mismatch count the entries' pass reported per read
   //            [400, 416)  phase D: cnt[64]      [416, 432)  base[64]
@@ -292,19 +289,6 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
     return w;
   };
 
-  // The tuples the PREVIOUS batch's launch staged (pstage != nullptr: same grid, same regions, the other stage buffer)
-  // move to their final place in `hits` from inside this launch (the protocol of match_ctx_pass, as in k_match_t): a
-  // wave-tile's first 64 ride in F3's flight through the buffer, the rest (rare) by plain loads behind its wait
-  bool pcopy = pstage != nullptr;
-  unsigned long long pbase = 0;
-  if (pcopy) {
-    pbase = counters[2];
-    if (pbase + ptpre[pnwt] > hits_cap) {  // cannot happen on a sized pass
-      if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&counters[3], 2ull);
-      pcopy = false;
-    }
-  }
-  uint64_t pused = 0;  // tuples of the previous batch this wave has moved (its region is consumed in order)
   // ---- state that crosses a wave-tile boundary: the record, buckets and meta word of the wave-tile in hand
   Rec<RW> rec_cur;
   rec_cur.zero();
@@ -584,22 +568,9 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
           glds16(rd + (r0 + (i < n ? i : 0)) * (uint64_t)RW + 4u * (g % (uint32_t)(RW / 4)), zb + (uint32_t)q * 1024u);
         }
       }
-      uint32_t cpm = 0, cpd = 0;
-      if (pcopy && wt < pnwt) {
-        const uint32_t wtu = (uint32_t)__builtin_amdgcn_readfirstlane((int)wt);
-        cpm = ptcount2[wtu];
-        cpd = ptpre[wtu];
-        if (cpm) glds16(pstage + region0 + pused + (lane < cpm ? lane : 0u), lds_addr(line_l + 192));
-      }
       PF(7)
-      if (total || have_next || cpm) wait_vm0();
+      if (total || have_next) wait_vm0();
       PF(8)
-      if (cpm) {
-        uint4* __restrict__ dst = hits + pbase + cpd;
-        if (lane < cpm) dst[lane] = line_l[192 + lane];
-        for (uint32_t i = 64 + lane; i < cpm; i += 64) dst[i] = pstage[region0 + pused + i];  // a tile with more than 64 tuples
-        pused += cpm;
-      }
       if (have_next) {
         const uint4* src = line_l + 256 + lane * (RW / 4);
 #pragma unroll
@@ -749,16 +720,6 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
            gw, pf_tiles, (__builtin_amdgcn_s_memtime() - pstart) / pf_tiles, pf[0] / pf_tiles, pf[1] / pf_tiles, pf[2] / pf_tiles, pf[3] / pf_tiles,
            pf[4] / pf_tiles, pf[5] / pf_tiles, pf[6] / pf_tiles, pf[7] / pf_tiles, pf[8] / pf_tiles, pf[9] / pf_tiles, pf[10] / pf_tiles, pf[11] / pf_tiles);
 #endif
-  if (pcopy) {
-    const uint32_t mine = gw < nwt ? (nwt - gw + nw - 1) / nw : 0u;  // wave-tiles of this batch this wave has walked
-    for (uint32_t wt = gw + mine * nw; wt < pnwt; wt += nw) {
-      const uint32_t wtu = (uint32_t)__builtin_amdgcn_readfirstlane((int)wt);
-      const uint32_t m = ptcount2[wtu], d = ptpre[wtu];
-      const uint32_t lane = opaque(threadIdx.x) & 63;
-      for (uint32_t i = lane; i < m; i += 64) hits[pbase + d + i] = pstage[region0 + pused + i];
-      pused += m;
-    }
-  }
   // one reduction per workgroup and a handful of atomics from its first thread (as in k_match_t)
   {
     __shared__ unsigned long long s_red[NWAVE][8];

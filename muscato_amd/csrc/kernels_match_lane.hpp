@@ -100,9 +100,6 @@ __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* 
                                                                 int block_mode, uint32_t block_thr,
                                                                 uint32_t* __restrict__ block_table,
                                                                 unsigned long long* __restrict__ counters,
-                                                                const uint4* __restrict__ pstage, const uint32_t* __restrict__ ptcount2,
-                                                                const uint32_t* __restrict__ ptpre, uint32_t pnwt,
-                                                                uint4* __restrict__ hits, uint64_t hits_cap,
                                                                 const uint32_t* __restrict__ rdx) {
   static_assert(W >= 1 && W <= CTX_MAX_W, "context buckets serve at most CTX_MAX_W windows");
   // XM: 0 = neither side holds an X; 1 = reads may (their xpos words, rdx); 2 = the database does (flagged
@@ -280,38 +277,6 @@ __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* 
       if (i < 4) a[i] = make_uint4(x.x, x.y, x.z, x.w);
       else b2[i - 4] = make_uint4(x.x, x.y, x.z, x.w);
     }
-  };
-
-  // The tuples the PREVIOUS batch's launch staged (pstage != nullptr: same grid, same regions, the
-  // other stage buffer) move to their final place in `hits` from inside this launch (the protocol of match_ctx_pass)
-  bool pcopy = pstage != nullptr;
-  unsigned long long pbase = 0;
-  if (pcopy) {
-    pbase = counters[2];
-    if (pbase + ptpre[pnwt] > hits_cap) {  // cannot happen on a sized pass
-      if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&counters[3], 2ull);
-      pcopy = false;
-    }
-  }
-  uint64_t pused = 0;  // tuples of the previous batch this wave has moved (its region is consumed in order)
-  auto pcopy_begin = [&](uint32_t wt, uint4& v, uint32_t& m, uint32_t& d) __attribute__((always_inline)) {
-    m = 0;
-    d = 0;
-    if (pcopy && wt < pnwt) {
-      const uint32_t wtu = (uint32_t)__builtin_amdgcn_readfirstlane((int)wt);
-      m = ptcount2[wtu];
-      d = ptpre[wtu];
-      const uint32_t lane = opaque(threadIdx.x) & 63;
-      if (lane < m) v = pstage[region0 + pused + lane];
-    }
-  };
-  auto pcopy_end = [&](const uint4& v, uint32_t m, uint32_t d) __attribute__((always_inline)) {
-    if (!m) return;
-    const uint32_t lane = opaque(threadIdx.x) & 63;
-    uint4* __restrict__ dst = hits + pbase + d;
-    if (lane < m) put_tuple(&dst[lane], v.x, v.y, v.z, v.w);
-    for (uint32_t i = 64 + lane; i < m; i += 64) dst[i] = pstage[region0 + pused + i];  // a tile with more than 64 tuples
-    pused += m;
   };
 
   // What a comparison through window k reads of the host's tables (MatchParams), fetched in ONE batch
@@ -882,8 +847,6 @@ __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* 
       PF(7)
     };
 
-    uint4 cpv = make_uint4(0, 0, 0, 0);
-    uint32_t cpm = 0, cpd = 0;
     uint32_t nlist = 0;           // reported candidates of cur so far (wave-uniform)
     uint32_t kc = 0, k0w = NX_REJECT, k0g = 0, k0p = 0, k1w = NX_REJECT, k1g = 0, k1p = 0;  // this lane's own first candidates of cur
     uint32_t best = 0xFFFFFFFFu;  // smallest mismatch count reported for this lane's read by the in-lane comparisons
@@ -894,7 +857,6 @@ __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* 
     for (int k = 0; k < W; k++) wc[k] = oc[k] = ovf[k] = 0, bb_nx[k] = WB_NONE;
 
     if (have_cur) {
-      pcopy_begin(wt, cpv, cpm, cpd);
       const bool active = wt * WT + lane < n;
       // this wave-tile's per-read state: registers of the read's lane; the meta word and the xpos word
       // also go to LDS, where the overflow entries pick up their reads'
@@ -1083,7 +1045,6 @@ __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* 
       finish_prev();
     }
     wave_lds_sync();
-    if (have_cur) pcopy_end(cpv, cpm, cpd);
     // ---- cur becomes prev
     have_prev = have_cur;
     if (have_cur) {
@@ -1123,14 +1084,6 @@ __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* 
            (__builtin_amdgcn_s_memtime() - pstart) / pf_tiles, pf[0] / pf_tiles, pf[1] / pf_tiles, pf[2] / pf_tiles, pf[8] / pf_tiles,
            pf[6] / pf_tiles, pf[7] / pf_tiles, pf[3] / pf_tiles, pf[9] / pf_tiles, pf[4] / pf_tiles, pf[5] / pf_tiles);
 #endif
-  if (pcopy) {
-    for (; wt < pnwt; wt += nw) {
-      uint4 cpv = make_uint4(0, 0, 0, 0);
-      uint32_t cpm, cpd;
-      pcopy_begin(wt, cpv, cpm, cpd);
-      pcopy_end(cpv, cpm, cpd);
-    }
-  }
   // one reduction per workgroup and a handful of atomics from its first thread (as in k_match)
   {
     __shared__ unsigned long long s_red[NWAVE][8];

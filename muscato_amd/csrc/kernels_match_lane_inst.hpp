@@ -28,6 +28,12 @@ struct SpecGeom<1> {  // BASELINE configs 2-4: WindowWidth 15, Windows 0,20, 100
 };
 #define MUSC_SPEC_GEOMS 1  // geometries 1 .. MUSC_SPEC_GEOMS exist
 
+// Every fused-kernel instance, k_match_t's and k_match_g's alike, takes these arguments
+#define MUSC_MATCH_ARGS                                                                                              \
+  (const uint32_t*, uint64_t, uint32_t, const MatchParams*, const uint16_t*, const CtxBucket*, const CtxEntry*, uint4*, \
+   uint64_t, uint4*, uint64_t, uint32_t*, uint32_t*, int, uint32_t, uint32_t*, unsigned long long*, const uint32_t*)
+typedef void (*match_kernel_t) MUSC_MATCH_ARGS;
+
 template <int RW, int W, int XM, bool WIDE, int SG>
 __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* __restrict__ rd, uint64_t r0, uint32_t n,
                                                                 const MatchParams* __restrict__ mp,
@@ -39,9 +45,6 @@ __global__ __launch_bounds__(TILE, MATCHT_WAVES) void k_match_t(const uint32_t* 
                                                                 int block_mode, uint32_t block_thr,
                                                                 uint32_t* __restrict__ block_table,
                                                                 unsigned long long* __restrict__ counters,
-                                                                const uint4* __restrict__ pstage, const uint32_t* __restrict__ ptcount2,
-                                                                const uint32_t* __restrict__ ptpre, uint32_t pnwt,
-                                                                uint4* __restrict__ hits, uint64_t hits_cap,
                                                                 const uint32_t* __restrict__ rdx);
 // k_match_g (kernels_match_dma.hpp): the same kernel at three waves per SIMD -- lines, overflow entries and records by
 // LDS-DMA -- for two windows on 120-base buckets without X (BASELINE configs 2-4); general (SG = 0) and specialised
@@ -67,34 +70,23 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
                                                                 int block_mode, uint32_t block_thr,
                                                                 uint32_t* __restrict__ block_table,
                                                                 unsigned long long* __restrict__ counters,
-                                                                const uint4* __restrict__ pstage, const uint32_t* __restrict__ ptcount2,
-                                                                const uint32_t* __restrict__ ptpre, uint32_t pnwt,
-                                                                uint4* __restrict__ hits, uint64_t hits_cap,
                                                                 const uint32_t* __restrict__ rdx);
-#define MUSC_DMA_ARGS                                                                                                  \
-  (const uint32_t*, uint64_t, uint32_t, const MatchParams*, const uint16_t*, const CtxBucket*, const CtxEntry*, uint4*, \
-   uint64_t, uint4*, uint64_t, uint32_t*, uint32_t*, int, uint32_t, uint32_t*, unsigned long long*, const uint4*,   \
-   const uint32_t*, const uint32_t*, uint32_t, uint4*, uint64_t, const uint32_t*)
 #define MUSC_DMA_INSTANCES(X)                            \
-  X template __global__ void k_match_g<8, 0> MUSC_DMA_ARGS; \
-  X template __global__ void k_match_g<8, 1> MUSC_DMA_ARGS;
-#define MUSC_LANE_ARGS                                                                                              \
-  (const uint32_t*, uint64_t, uint32_t, const MatchParams*, const uint16_t*, const CtxBucket*, const CtxEntry*, uint4*, \
-   uint64_t, uint4*, uint64_t, uint32_t*, uint32_t*, int, uint32_t, uint32_t*, unsigned long long*, const uint4*,   \
-   const uint32_t*, const uint32_t*, uint32_t, uint4*, uint64_t, const uint32_t*)
+  X template __global__ void k_match_g<8, 0> MUSC_MATCH_ARGS; \
+  X template __global__ void k_match_g<8, 1> MUSC_MATCH_ARGS;
 #define MUSC_LANE_INSTANCES_WD(X, RW, WD)                                \
-  X template __global__ void k_match_t<RW, 1, 0, WD, 0> MUSC_LANE_ARGS; \
-  X template __global__ void k_match_t<RW, 2, 0, WD, 0> MUSC_LANE_ARGS; \
-  X template __global__ void k_match_t<RW, 3, 0, WD, 0> MUSC_LANE_ARGS; \
-  X template __global__ void k_match_t<RW, 4, 0, WD, 0> MUSC_LANE_ARGS; \
-  X template __global__ void k_match_t<RW, 1, 1, WD, 0> MUSC_LANE_ARGS;  \
-  X template __global__ void k_match_t<RW, 2, 1, WD, 0> MUSC_LANE_ARGS;  \
-  X template __global__ void k_match_t<RW, 3, 1, WD, 0> MUSC_LANE_ARGS;  \
-  X template __global__ void k_match_t<RW, 4, 1, WD, 0> MUSC_LANE_ARGS;  \
-  X template __global__ void k_match_t<RW, 1, 2, WD, 0> MUSC_LANE_ARGS;     \
-  X template __global__ void k_match_t<RW, 2, 2, WD, 0> MUSC_LANE_ARGS;     \
-  X template __global__ void k_match_t<RW, 3, 2, WD, 0> MUSC_LANE_ARGS;     \
-  X template __global__ void k_match_t<RW, 4, 2, WD, 0> MUSC_LANE_ARGS;
+  X template __global__ void k_match_t<RW, 1, 0, WD, 0> MUSC_MATCH_ARGS; \
+  X template __global__ void k_match_t<RW, 2, 0, WD, 0> MUSC_MATCH_ARGS; \
+  X template __global__ void k_match_t<RW, 3, 0, WD, 0> MUSC_MATCH_ARGS; \
+  X template __global__ void k_match_t<RW, 4, 0, WD, 0> MUSC_MATCH_ARGS; \
+  X template __global__ void k_match_t<RW, 1, 1, WD, 0> MUSC_MATCH_ARGS;  \
+  X template __global__ void k_match_t<RW, 2, 1, WD, 0> MUSC_MATCH_ARGS;  \
+  X template __global__ void k_match_t<RW, 3, 1, WD, 0> MUSC_MATCH_ARGS;  \
+  X template __global__ void k_match_t<RW, 4, 1, WD, 0> MUSC_MATCH_ARGS;  \
+  X template __global__ void k_match_t<RW, 1, 2, WD, 0> MUSC_MATCH_ARGS;     \
+  X template __global__ void k_match_t<RW, 2, 2, WD, 0> MUSC_MATCH_ARGS;     \
+  X template __global__ void k_match_t<RW, 3, 2, WD, 0> MUSC_MATCH_ARGS;     \
+  X template __global__ void k_match_t<RW, 4, 2, WD, 0> MUSC_MATCH_ARGS;
 // 120-base context buckets: records of 4, 8, 12 words; wide (200 bases): 4 (distant windows), 8, 12, 16.
 // One translation unit per line.
 #define MUSC_LANE_INSTANCES_4(X) MUSC_LANE_INSTANCES_WD(X, 4, false) MUSC_LANE_INSTANCES_WD(X, 4, true)
@@ -104,4 +96,4 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
 #define MUSC_LANE_INSTANCES_12W(X) MUSC_LANE_INSTANCES_WD(X, 12, true)
 #define MUSC_LANE_INSTANCES_16W(X) MUSC_LANE_INSTANCES_WD(X, 16, true)
 // the geometry-specialised instances (one translation unit: match_lane_rw8s.hip)
-#define MUSC_LANE_INSTANCES_SPEC(X) X template __global__ void k_match_t<8, 2, 0, false, 1> MUSC_LANE_ARGS;
+#define MUSC_LANE_INSTANCES_SPEC(X) X template __global__ void k_match_t<8, 2, 0, false, 1> MUSC_MATCH_ARGS;

@@ -167,10 +167,8 @@ struct EnvKnobs {
   int debug_grid = 0;         // MUSC_DEBUG_GRID (0: not set)
   bool debug_sync = false;    // MUSC_DEBUG_SYNC
   int graph = -1;             // MUSC_GRAPH: -1 not set, else its value
-  bool fused_compact = false; // MUSC_FUSED_COMPACT=1: the previous batch's tuples move into `hits` from inside the next batch's match launch (r02-r03's default); default: a k_compact_w per batch
   bool pipeline = false;      // MUSC_PIPELINE > 0
   bool no_spec = false;       // MUSC_NO_SPEC: never pick a geometry-specialised kernel instance
-  int grid_rounds = 0;        // MUSC_GRID_ROUNDS: the fused kernels' grid = this many times the resident workgroups (0: the default)
   long batch_reads = 0;       // MUSC_BATCH_READS (0: not set)
   void read() {
     *this = EnvKnobs();
@@ -188,10 +186,8 @@ struct EnvKnobs {
     if ((e = getenv("MUSC_DEBUG_GRID"))) debug_grid = atoi(e);
     debug_sync = getenv("MUSC_DEBUG_SYNC") != nullptr;
     if ((e = getenv("MUSC_GRAPH"))) graph = atoi(e);
-    if ((e = getenv("MUSC_FUSED_COMPACT"))) fused_compact = atoi(e) > 0;
     if ((e = getenv("MUSC_PIPELINE"))) pipeline = atoi(e) > 0;
     no_spec = getenv("MUSC_NO_SPEC") != nullptr;
-    if ((e = getenv("MUSC_GRID_ROUNDS"))) grid_rounds = atoi(e);
     if ((e = getenv("MUSC_BATCH_READS"))) batch_reads = atol(e);
   }
 };
@@ -290,9 +286,6 @@ struct musc_ctx {
   hipEvent_t ev_ready[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_join = nullptr;
   DevBuf<uint32_t> scan_tmp, tcount2, tpre;
   DevBuf<uint4> stage;
-  // k_match_t moves the tuples a batch staged from inside the NEXT batch's launch: a second set
-  DevBuf<uint32_t> tcount2_b, tpre_b;
-  DevBuf<uint4> stage_b;
   DevBuf<uint32_t> p_nx;
   DevBuf<uint16_t> nmiss_tab;
   DevBuf<uint32_t> block_table;
@@ -543,6 +536,51 @@ bool screen_lane(const musc_ctx* c, bool mask) {
   return c->idx_lines && !mask && !c->rdm && (c->rw == 4 || c->rw == 8 || c->rw == 12 || c->rw == 16) && !c->env.screen_wg;
 }
 
+// f(std::integral_constant<int, RW>{}) for the record strides that have kernel instances of their own (RW = 0: any other)
+template <class F>
+auto by_rw(int rw, F&& f) {
+  switch (rw) {
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    default: return f(std::integral_constant<int, 0>{});
+  }
+}
+
+// The instance of each two-kernel-path kernel a run launches: one resolver per kernel, which the launch
+// (and for k_screen_t the occupancy query of screen_grid) takes it from
+typedef decltype(&k_screen_t<8>) screen_t_fn;
+typedef decltype(&k_screen<0, false, false, false>) screen_fn;
+typedef decltype(&k_confirm<0, false, false>) confirm_fn;
+
+screen_t_fn screen_t_kernel(const musc_ctx* c) {  // (screen_lane: only the strides k_screen_t is built for)
+  return by_rw(c->rw, [](auto rw) -> screen_t_fn {
+    if constexpr (decltype(rw)::value != 0) return k_screen_t<decltype(rw)::value>;
+    else return nullptr;
+  });
+}
+
+screen_fn screen_kernel(const musc_ctx* c, int W) {
+  const int m = c->rdm != nullptr, one = W <= 2, ln = c->idx_lines;
+  return by_rw(c->rw, [&](auto rw) -> screen_fn {
+    constexpr int RW = decltype(rw)::value;
+    static const screen_fn k[2][2][2] = {
+        {{k_screen<RW, false, false, false>, k_screen<RW, false, false, true>}, {k_screen<RW, false, true, false>, k_screen<RW, false, true, true>}},
+        {{k_screen<RW, true, false, false>, k_screen<RW, true, false, true>}, {k_screen<RW, true, true, false>, k_screen<RW, true, true, true>}}};
+    return k[m][one][ln];
+  });
+}
+
+confirm_fn confirm_kernel(const musc_ctx* c, bool mask, int W) {
+  const int w2 = W <= 2;
+  return by_rw(c->rw, [&](auto rw) -> confirm_fn {
+    constexpr int RW = decltype(rw)::value;
+    static const confirm_fn k[2][2] = {{k_confirm<RW, false, false>, k_confirm<RW, false, true>}, {k_confirm<RW, true, false>, k_confirm<RW, true, true>}};
+    return k[mask][w2];
+  });
+}
+
 // workgroups of the screen stage: the descriptor buffer is cut into that many regions.  k_screen_t's
 // workgroups are single waves that stay for the whole launch: as many as are resident at once (a
 // second, thinner round of them would cost what a full one does).
@@ -551,8 +589,7 @@ unsigned screen_grid(musc_ctx* c, uint32_t n, bool mask) {
   if (screen_lane(c, mask)) {
     if (!c->scrt_resident) {
       int per_cu = 0, ncu = 0;
-      const void* fn = c->rw == 4 ? reinterpret_cast<const void*>(&k_screen_t<4>) : c->rw == 8 ? reinterpret_cast<const void*>(&k_screen_t<8>)
-                       : c->rw == 12 ? reinterpret_cast<const void*>(&k_screen_t<12>) : reinterpret_cast<const void*>(&k_screen_t<16>);
+      const void* fn = reinterpret_cast<const void*>(screen_t_kernel(c));
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 8; }
       if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu < 1) ncu = 256;
       c->scrt_resident = (unsigned)per_cu * (unsigned)ncu;
@@ -564,58 +601,29 @@ unsigned screen_grid(musc_ctx* c, uint32_t n, bool mask) {
   return g;
 }
 
-template <int RW>
-void launch_path(musc_ctx* c, int stage, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
-  const dim3 block(TILE);
-  if (stage == 0) {
-    const dim3 sgrid(screen_grid(c, n, mask));
-    if constexpr (RW == 4 || RW == 8 || RW == 12 || RW == 16) {
-      if (screen_lane(c, mask)) {
-        hipLaunchKernelGGL((k_screen_t<RW>), sgrid, dim3(64), 0, c->stream, c->rd, r0, n, c->d_pp, c->nmiss_tab.p,
-                           reinterpret_cast<const LineBucket*>(c->idx_T), c->idx_E, c->bs[c->cur].cdesc.p, c->bs[c->cur].cdesc.cap,
-                           c->bs[c->cur].rvalid.p, c->bs[c->cur].wb.p, c->bs[c->cur].tbase.p, c->bs[c->cur].tcount.p,
-                           c->counters + 8, c->counters + 3);
-        return;
-      }
-    }
-#define MUSC_LAUNCH_SCREEN(M, O)                                                                                  \
-    do { if (c->idx_lines) MUSC_LAUNCH_SCREEN2(M, O, true); else MUSC_LAUNCH_SCREEN2(M, O, false); } while (0)
-#define MUSC_LAUNCH_SCREEN2(M, O, LN)                                                                             \
-    hipLaunchKernelGGL((k_screen<RW, M, O, LN>), sgrid, block, 0, c->stream, c->rd, c->rdm, r0, n, c->rw, c->d_pp, \
-                       c->nmiss_tab.p, c->idx_T, c->idx_E, c->bs[c->cur].cdesc.p, c->bs[c->cur].cdesc.cap,        \
-                       c->bs[c->cur].rvalid.p, c->bs[c->cur].wb.p, c->bs[c->cur].tbase.p, c->bs[c->cur].tcount.p, \
-                       c->counters + 8, c->counters + 3)
-    const bool one = pp.W <= 2;
-    if (c->rdm) { if (one) MUSC_LAUNCH_SCREEN(true, true); else MUSC_LAUNCH_SCREEN(true, false); }
-    else { if (one) MUSC_LAUNCH_SCREEN(false, true); else MUSC_LAUNCH_SCREEN(false, false); }
-#undef MUSC_LAUNCH_SCREEN
-#undef MUSC_LAUNCH_SCREEN2
-  } else {
-    // persistent over tiles; the MaxMatches screening threshold assumes at most MAX_GRID workgroups
-    const dim3 grid(std::min(nblk(n, TILE), MAX_GRID));
-    static_assert((1u << 24) / TILE / MAX_GRID <= CONF_TILES, "a k_confirm workgroup keeps its tile list in LDS");
-    const size_t lds = c->cur_block_mode ? (size_t)TILE * pp.W * 4 : 0;
-#define MUSC_LAUNCH_CONFIRM(M, W2)                                                                                 \
-    hipLaunchKernelGGL((k_confirm<RW, M, W2>), grid, block, lds, c->s_confirm, c->rd, c->rdm, c->db2, c->dbm2,      \
-                       c->dbx, r0, n, c->rw, c->d_pp, c->nmiss_tab.p, c->bs[c->cur].cdesc.p, c->bs[c->cur].rvalid.p,     \
-                       c->p_nx.p, c->bs[c->cur].tbase.p, c->bs[c->cur].tcount.p, c->bs[c->cur].wb.p,                \
-                       c->cur_block_mode, c->cur_block_thr, c->block_table.p, c->seq_off, c->stage.p, c->tcount2.p, \
-                       c->counters)
-    const bool w2 = pp.W <= 2;
-    if (mask) { if (w2) MUSC_LAUNCH_CONFIRM(true, true); else MUSC_LAUNCH_CONFIRM(true, false); }
-    else { if (w2) MUSC_LAUNCH_CONFIRM(false, true); else MUSC_LAUNCH_CONFIRM(false, false); }
-#undef MUSC_LAUNCH_CONFIRM
-  }
+void launch_screen(musc_ctx* c, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
+  const dim3 sgrid(screen_grid(c, n, mask));
+  auto& b = c->bs[c->cur];
+  if (screen_lane(c, mask))
+    hipLaunchKernelGGL(screen_t_kernel(c), sgrid, dim3(64), 0, c->stream, c->rd, r0, n, c->d_pp, c->nmiss_tab.p,
+                       reinterpret_cast<const LineBucket*>(c->idx_T), c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p,
+                       b.tbase.p, b.tcount.p, c->counters + 8, c->counters + 3);
+  else
+    hipLaunchKernelGGL(screen_kernel(c, pp.W), sgrid, dim3(TILE), 0, c->stream, c->rd, c->rdm, r0, n, c->rw, c->d_pp,
+                       c->nmiss_tab.p, c->idx_T, c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p, b.tbase.p, b.tcount.p,
+                       c->counters + 8, c->counters + 3);
 }
 
-void launch_stage(musc_ctx* c, int stage, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
-  switch (c->rw) {
-    case 4: launch_path<4>(c, stage, mask, r0, n, pp); break;
-    case 8: launch_path<8>(c, stage, mask, r0, n, pp); break;
-    case 12: launch_path<12>(c, stage, mask, r0, n, pp); break;
-    case 16: launch_path<16>(c, stage, mask, r0, n, pp); break;
-    default: launch_path<0>(c, stage, mask, r0, n, pp); break;
-  }
+void launch_confirm(musc_ctx* c, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
+  // persistent over tiles; the MaxMatches screening threshold assumes at most MAX_GRID workgroups
+  const dim3 grid(std::min(nblk(n, TILE), MAX_GRID));
+  static_assert((1u << 24) / TILE / MAX_GRID <= CONF_TILES, "a k_confirm workgroup keeps its tile list in LDS");
+  const size_t lds = c->cur_block_mode ? (size_t)TILE * pp.W * 4 : 0;
+  auto& b = c->bs[c->cur];
+  hipLaunchKernelGGL(confirm_kernel(c, mask, pp.W), grid, dim3(TILE), lds, c->s_confirm, c->rd, c->rdm, c->db2, c->dbm2,
+                     c->dbx, r0, n, c->rw, c->d_pp, c->nmiss_tab.p, b.cdesc.p, b.rvalid.p, c->p_nx.p, b.tbase.p, b.tcount.p,
+                     b.wb.p, c->cur_block_mode, c->cur_block_thr, c->block_table.p, c->seq_off, c->stage.p, c->tcount2.p,
+                     c->counters);
 }
 
 }  // namespace
@@ -697,7 +705,6 @@ void musc_destroy(musc_ctx* c) {
     c->bs[i].cdesc.release();
   }
   c->scan_tmp.release(); c->tcount2.release(); c->tpre.release(); c->stage.release(); c->rdx.release();
-  c->tcount2_b.release(); c->tpre_b.release(); c->stage_b.release();
   c->p_nx.release();
   c->nmiss_tab.release();
   c->block_table.release();
@@ -1089,9 +1096,6 @@ static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide) {
 }
 
 // Which of the two fused kernels on context buckets runs
-#ifndef MATCH_GRID_ROUNDS
-#define MATCH_GRID_ROUNDS 1
-#endif
 enum MatchKind { MK_LANE = 2, MK_DMA = 3 };
 // MK_LANE = k_match_t (kernels_match_lane.hpp): every run on context buckets.  MK_DMA = k_match_g
 // (kernels_match_dma.hpp): the same comparisons at three to four waves per SIMD, everything from memory by LDS-DMA --
@@ -1190,10 +1194,9 @@ static bool ctx_eligible(musc_ctx* c, const musc_params* P, uint32_t max_len, in
   if (c->env.index != EnvKnobs::IDX_AUTO) return false;  // the two-kernel path
   // (the planes themselves may exist without an X: an all-zero one is made for the side that has
   // none when the other side does, and the database's stays for the context's lifetime)
-  const bool lane = true;  // (both fused kernels read flagged entries, xpos words and wide buckets' runs: k_match_g only takes runs without them)
   // a database with X: k_match_t only (an entry whose context holds an X is flagged in bit 31 of its
   // position, the X's place or "several: see the mask plane" in the top byte of its target number)
-  if (c->db_has_x && (!lane || c->max_tlen >= 0x80000000ull || c->nseq > (1u << 24) || c->env.no_x_context)) return false;
+  if (c->db_has_x && (c->max_tlen >= 0x80000000ull || c->nseq > (1u << 24) || c->env.no_x_context)) return false;
   if (c->nbases >= 0xFFFFFFF0ull || c->env.force_wide) return false;
   if (P->n_windows > CTX_MAX_W) return false;
   int q1min = P->windows[0], q1max = P->windows[0];
@@ -1205,15 +1208,15 @@ static bool ctx_eligible(musc_ctx* c, const musc_params* P, uint32_t max_len, in
   const int wenv = c->env.context;  // experiments: "narrow" (1) keeps runs beyond 120 bases on the two-kernel path, "wide" (2) puts every run on wide buckets
   *CL = q1max;
   *wide = 0;
-  if (span > CTX_BASES || q1max > CTX_BASES || (wenv == 2 && lane)) {
+  if (span > CTX_BASES || q1max > CTX_BASES || wenv == 2) {
     // wide buckets: k_match_t only; records of up to 16 words hold 200-base reads and their length word
-    if (!lane || wenv == 1) return false;
+    if (wenv == 1) return false;
     if (span > CTXW_BASES || q1max > CTXW_BASES) return false;
     *wide = 1;
   }
   // reads with X: k_match_t handles them, and only while every read either lists all its X
   // in its xpos word or has more X than mismatches allowed (reads_x_fit, cached per reads + budget)
-  if (c->reads_have_x && !(lane && (c->db_has_x ? reads_x_fit_db(c, P, *wide) : reads_x_fit(c, P, max_len, *wide)))) return false;
+  if (c->reads_have_x && !(c->db_has_x ? reads_x_fit_db(c, P, *wide) : reads_x_fit(c, P, max_len, *wide))) return false;
   return true;
 }
 
@@ -1461,43 +1464,38 @@ static size_t match_dyn_lds(int kind, int W, int block_mode) {
   return block_mode ? wcnt + (block_mode == 1 ? (4u << MATCH_SKETCH_BITS) : 0u) : 0u;
 }
 
-// the kernel a pass launches, as a function pointer (occupancy queries and attributes)
-template <int RW>
-static const void* match_fn(const musc_ctx* c, int W) {
-  const int kind = match_kind(c, W);
-  const bool rx = c->reads_have_x;
-  if (kind == MK_DMA) {
-    if constexpr (RW == 8) return c->spec_geom == 1 ? reinterpret_cast<const void*>(&k_match_g<8, 1>) : reinterpret_cast<const void*>(&k_match_g<8, 0>);
+// The fused-kernel instance a pass launches (nullptr: none is built for the run); the occupancy query and the launch
+// both take it from here.  Instances (kernels_match_lane_inst.hpp): k_match_t on 120-base buckets for records of 4, 8,
+// 12 words and on wide ones for 4 to 16, each for 1-4 windows and three X modes; the geometry-specialised
+// k_match_t<8, 2, 0, false, 1>; k_match_g<8, 0 | 1>.
+template <int RW, bool WD>
+static match_kernel_t lane_kernel(int W, int xm) {
+  static const match_kernel_t k[4][3] = {
+      {k_match_t<RW, 1, 0, WD, 0>, k_match_t<RW, 1, 1, WD, 0>, k_match_t<RW, 1, 2, WD, 0>},
+      {k_match_t<RW, 2, 0, WD, 0>, k_match_t<RW, 2, 1, WD, 0>, k_match_t<RW, 2, 2, WD, 0>},
+      {k_match_t<RW, 3, 0, WD, 0>, k_match_t<RW, 3, 1, WD, 0>, k_match_t<RW, 3, 2, WD, 0>},
+      {k_match_t<RW, 4, 0, WD, 0>, k_match_t<RW, 4, 1, WD, 0>, k_match_t<RW, 4, 2, WD, 0>}};
+  return k[(W >= 1 && W <= 3 ? W : 4) - 1][xm];
+}
+
+static match_kernel_t match_kernel(const musc_ctx* c, int W) {
+  if (match_kind(c, W) == MK_DMA) return c->spec_geom == 1 ? k_match_g<8, 1> : k_match_g<8, 0>;
+  if (c->spec_geom == 1) return k_match_t<8, 2, 0, false, 1>;  // (chosen by spec_geom_matches: every specialised quantity equals the run's)
+  const int xm = c->db_has_x ? 2 : c->reads_have_x ? 1 : 0;
+  return by_rw(c->rw, [&](auto rw) -> match_kernel_t {
+    constexpr int RW = decltype(rw)::value;
+    if constexpr (RW == 0) return nullptr;
+    else if (c->idx_wide) return lane_kernel<RW, true>(W, xm);
+    else if constexpr (RW <= 12) return lane_kernel<RW, false>(W, xm);
     else return nullptr;
-  }
-  if (kind == MK_LANE) {
-    if constexpr (RW == 8) {
-      if (c->spec_geom == 1) return reinterpret_cast<const void*>(&k_match_t<8, 2, 0, false, 1>);
-    }
-    // (instances: 120-base buckets for records of 4, 8, 12 words; wide ones for 4 to 16)
-#define MUSC_LANE_FN2(WN, WD) (c->db_has_x ? reinterpret_cast<const void*>(&k_match_t<RW, WN, 2, WD, 0>) : rx ? reinterpret_cast<const void*>(&k_match_t<RW, WN, 1, WD, 0>) : reinterpret_cast<const void*>(&k_match_t<RW, WN, 0, WD, 0>))
-#define MUSC_LANE_FN(WN)                                  \
-  if (c->idx_wide) return MUSC_LANE_FN2(WN, true);        \
-  if constexpr (RW <= 12) return MUSC_LANE_FN2(WN, false); \
-  return nullptr;
-    switch (W) {
-      case 1: MUSC_LANE_FN(1)
-      case 2: MUSC_LANE_FN(2)
-      case 3: MUSC_LANE_FN(3)
-      default: MUSC_LANE_FN(4)
-    }
-#undef MUSC_LANE_FN
-#undef MUSC_LANE_FN2
-  }
-  return nullptr;
+  });
 }
 
 // workgroups of the kernel that are resident at once on this device: the persistent grid
-template <int RW>
-static unsigned match_resident(musc_ctx* c, int W, int block_mode) {
+static unsigned match_resident(musc_ctx* c, match_kernel_t kern, int W, int block_mode) {
   int per_cu = 0, ncu = 0;
   const size_t lds = match_dyn_lds(match_kind(c, W), W, block_mode);
-  const void* fn = match_fn<RW>(c, W);
+  const void* fn = reinterpret_cast<const void*>(kern);
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TILE, lds);
   if (e != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; }
   // The occupancy query counts LDS to the byte; the hardware hands it out in larger pieces
@@ -1520,61 +1518,13 @@ static unsigned match_resident(musc_ctx* c, int W, int block_mode) {
   return resident;
 }
 
-// set: which staging buffers the launch fills (0: stage / tcount2, 1: stage_b / tcount2_b);
-// prev_tiles > 0: the launch also moves the other set's tuples (the previous batch's) into `hits`
-template <int RW>
-static void launch_match(musc_ctx* c, uint64_t r0, uint32_t n, int W, int block_mode, uint32_t block_thr,
-                         unsigned ngrid, int set = 0, uint32_t prev_tiles = 0) {
-  const dim3 grid(ngrid), block(TILE);
-  const int kind = match_kind(c, W);
-  const size_t lds = match_dyn_lds(kind, W, block_mode);
-  DevBuf<uint4>& st = set ? c->stage_b : c->stage;
-  DevBuf<uint32_t>& tc = set ? c->tcount2_b : c->tcount2;
-#define MUSC_LAUNCH_MATCH(K, ...)                                                                                 \
-  hipLaunchKernelGGL(K, grid, block, lds, c->stream, c->rd, r0, n, c->d_mp, c->nmiss_tab.p,                       \
-                     c->ctx_T, c->ctx_E, st.p, c->stage.cap, c->spill.p, c->spill.cap, c->bs[0].tbase.p,          \
-                     tc.p, block_mode, block_thr, c->block_table.p, c->counters, ##__VA_ARGS__)
-  {
-    const uint4* pst = prev_tiles ? (set ? c->stage.p : c->stage_b.p) : nullptr;
-    const uint32_t* ptc = set ? c->tcount2.p : c->tcount2_b.p;
-    const uint32_t* ptp = set ? c->tpre.p : c->tpre_b.p;
-    uint4* const hp = reinterpret_cast<uint4*>(c->hits.p);
-    const uint32_t* const rdx = c->reads_have_x ? (const uint32_t*)c->rdx.p : (const uint32_t*)nullptr;
-    if (kind == MK_DMA) {
-      if constexpr (RW == 8) {
-        if (c->spec_geom == 1) MUSC_LAUNCH_MATCH((k_match_g<8, 1>), pst, ptc, ptp, prev_tiles, hp, c->hits.cap, rdx);
-        else MUSC_LAUNCH_MATCH((k_match_g<8, 0>), pst, ptc, ptp, prev_tiles, hp, c->hits.cap, rdx);
-      }
-      return;
-    }
-    if (kind == MK_LANE) {
-      if constexpr (RW == 8) {
-        if (c->spec_geom == 1) {  // (chosen by spec_geom_matches: every specialised quantity equals the run's)
-          MUSC_LAUNCH_MATCH((k_match_t<8, 2, 0, false, 1>), pst, ptc, ptp, prev_tiles, hp, c->hits.cap, rdx);
-          return;
-        }
-      }
-#define MUSC_LAUNCH_LANE2(WN, WD)                                                                                 \
-      if (c->db_has_x) MUSC_LAUNCH_MATCH((k_match_t<RW, WN, 2, WD, 0>), pst, ptc, ptp, prev_tiles, hp, c->hits.cap, rdx); \
-      else if (c->reads_have_x) MUSC_LAUNCH_MATCH((k_match_t<RW, WN, 1, WD, 0>), pst, ptc, ptp, prev_tiles, hp, c->hits.cap, rdx); \
-      else MUSC_LAUNCH_MATCH((k_match_t<RW, WN, 0, WD, 0>), pst, ptc, ptp, prev_tiles, hp, c->hits.cap, rdx)
-#define MUSC_LAUNCH_LANE(WN)                                      \
-      do {                                                        \
-        if (c->idx_wide) { MUSC_LAUNCH_LANE2(WN, true); }         \
-        else if constexpr (RW <= 12) { MUSC_LAUNCH_LANE2(WN, false); } \
-      } while (0)
-      switch (W) {
-        case 1: MUSC_LAUNCH_LANE(1); break;
-        case 2: MUSC_LAUNCH_LANE(2); break;
-        case 3: MUSC_LAUNCH_LANE(3); break;
-        default: MUSC_LAUNCH_LANE(4); break;
-      }
-#undef MUSC_LAUNCH_LANE2
-#undef MUSC_LAUNCH_LANE
-      return;
-    }
-  }
-#undef MUSC_LAUNCH_MATCH
+static void launch_match(musc_ctx* c, match_kernel_t kern, uint64_t r0, uint32_t n, int W, int block_mode, uint32_t block_thr,
+                         unsigned ngrid) {
+  const size_t lds = match_dyn_lds(match_kind(c, W), W, block_mode);
+  const uint32_t* const rdx = c->reads_have_x ? (const uint32_t*)c->rdx.p : (const uint32_t*)nullptr;
+  hipLaunchKernelGGL(kern, dim3(ngrid), dim3(TILE), lds, c->stream, c->rd, r0, n, c->d_mp, c->nmiss_tab.p, c->ctx_T,
+                     c->ctx_E, c->stage.p, c->stage.cap, c->spill.p, c->spill.cap, c->bs[0].tbase.p, c->tcount2.p,
+                     block_mode, block_thr, c->block_table.p, c->counters, rdx);
 }
 }  // extern "C++"
 
@@ -1603,13 +1553,11 @@ static int spec_geom_matches(const musc_ctx* c, const MatchParams& mp) {
   return 0;
 }
 
-static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& pp, int block_mode, uint32_t block_thr_unused,
-                          uint64_t max_matches, uint64_t planned_batches, uint64_t* nhits) {
+static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& pp, int block_mode, uint64_t max_matches, uint64_t planned_batches, uint64_t* nhits) {
   int rc = 0;
   if (c->rw != 4 && c->rw != 8 && c->rw != 12 && !(c->rw == 16 && c->idx_wide))
     return fail(c, 12, "internal: record stride %d on the context path", c->rw);
-  (void)block_thr_unused;
-  // the run's parameter block (and with it the kernel instance: match_fn looks at c->spec_geom)
+  // the run's parameter block (and with it the kernel instance: match_kernel looks at c->spec_geom)
   {
     static thread_local MatchParams mp;  // 16 KB with its mask tables: not on the stack
     memset(&mp, 0, sizeof mp);
@@ -1632,17 +1580,13 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
   // the persistent grid = the workgroups that are resident at once (every wave then sees many
   // wave-tiles and the end-of-kernel atomics stay few); the MaxMatches screening threshold is per
   // workgroup-launch, so it follows the grid
-  const unsigned resident1 = c->rw == 4 ? match_resident<4>(c, pp.W, block_mode)
-                             : c->rw == 8 ? match_resident<8>(c, pp.W, block_mode)
-                             : c->rw == 12 ? match_resident<12>(c, pp.W, block_mode)
-                                           : match_resident<16>(c, pp.W, block_mode);
-  // MUSC_GRID_ROUNDS (an experiment knob; default 1): a grid of that many times the resident workgroups.  The waves
-  // of a launch do not run at one speed (r04: the slowest wave of a cfg3 launch takes 1.2-1.3 x the mean), which
-  // looks like a tail a dynamically dispatched grid would remove -- it does not: 2 / 4 / 8 / 16 rounds run the cfg3
-  // launch in 1.03 / 1.04 / 1.06 / 1.11 ms against 0.98-0.99 (profiles/r04_ab_shape_spec_dma.txt).  The memory system
-  // is the shared resource: the waves that finish early leave their share to the slow ones, nothing idles.
-  const unsigned rounds = c->env.debug_grid >= 1 ? 1u : (c->env.grid_rounds >= 1 && c->env.grid_rounds <= 64 ? (unsigned)c->env.grid_rounds : (unsigned)MATCH_GRID_ROUNDS);
-  const unsigned resident = resident1 * rounds;
+  // (The waves of a launch do not run at one speed -- r04: the slowest wave of a cfg3 launch takes 1.2-1.3 x the mean --
+  // which looks like a tail a dynamically dispatched grid would remove.  It does not: 2 / 4 / 8 / 16 times the resident
+  // workgroups run the cfg3 launch in 1.03 / 1.04 / 1.06 / 1.11 ms against 0.98-0.99 (profiles/r04_ab_shape_spec_dma.txt).
+  // The memory system is the shared resource: the waves that finish early leave their share to the slow ones.)
+  const match_kernel_t kern = match_kernel(c, pp.W);
+  if (!kern) return fail(c, 12, "internal: no fused kernel instance for record stride %d, %d windows", c->rw, pp.W);
+  const unsigned resident = match_resident(c, kern, pp.W, block_mode);
   uint32_t block_thr = (uint32_t)std::min<uint64_t>(max_matches / (planned_batches * resident), 0x7FFFFFFFull);
   if (block_mode == 1 && block_thr < 2) block_mode = 2;
   if (block_mode == 2 && !c->block_table.p) {
@@ -1662,20 +1606,11 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
     (void)hipGraphExecDestroy(c->graph_exec);
     c->graph_exec = nullptr;
   }
-  // Where a batch's staged tuples go to their place in `hits`: a k_compact_w per batch (the default since r04), or
-  // -- MUSC_FUSED_COMPACT=1, r02 / r03's default -- from inside the NEXT batch's match launch.  Measured on cfg3 / the cfg4
-  // shard (profiles/r04_ab_shape_spec_dma.txt): the pass takes the same time either way (3.09-3.24 against 3.25 ms; 1.78
-  // against 1.74), but a launch that also moves 12 M tuples takes 0.96-1.00 ms instead of 0.94-0.95 for work its
-  // algorithmic bytes do not bill: the separate kernel keeps the match kernel's accounting exact.
-  const bool fuse_ok = c->env.fused_compact;
-  if (sized && fuse_ok && c->nreads > bsz) {  // the second staging set (allocated outside any capture)
-    if ((rc = ensure(c, c->stage_b, c->stage.cap)) || (rc = ensure(c, c->tcount2_b, c->tcount2.cap)) ||
-        (rc = ensure(c, c->tpre_b, c->tpre.cap)))
-      return rc;
-  }
+  // A batch's staged tuples go to their place in `hits` by a k_compact_w of their own.  (r02 / r03 moved them from inside
+  // the NEXT batch's match launch instead; r04's A/B on cfg3 / the cfg4 shard, profiles/r04_ab_shape_spec_dma.txt: the pass
+  // takes the same time either way, but the match launch grows by work its algorithmic bytes do not bill.)
   for (int attempt = 0;; attempt++) {
     if (attempt > 40) return fail(c, 12, "internal: the context pass did not converge on buffer sizes");
-    const bool fuse = fuse_ok && c->nreads > bsz;  // (a sizing pass may have halved the batch size)
     Timer tm(c);
     hipEvent_t ev0 = pool_event(c), ev1 = pool_event(c);
     if (!ev0 || !ev1) return fail(c, 10, "hipEventCreate failed");
@@ -1707,8 +1642,6 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
       HIPCHK(c, hipMemsetAsync(c->counters, 0, 16 * sizeof(unsigned long long), c->stream));
       if (block_mode == 2) HIPCHK(c, hipMemsetAsync(c->block_table.p, 0, (1ull << BLOCK_TABLE_BITS) * 4, c->stream));
     }
-    int set = 0;
-    uint32_t pending_tiles = 0;  // wave-tiles of the previous batch whose tuples are still staged
     while (!replay && r0 < c->nreads) {
       const uint32_t n = (uint32_t)std::min<uint64_t>(bsz, c->nreads - r0);
       const uint32_t ntiles = nblk(n, WT);  // wave-tiles of 64 reads
@@ -1721,35 +1654,16 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
         if ((rc = ensure(c, c->tpre, (uint64_t)ntiles + 1))) return rc;
         if ((rc = ensure(c, c->stage, std::max<uint64_t>(2ull * n, swaves * 64)))) return rc;
         if ((rc = ensure(c, c->spill, swaves * 32))) return rc;
-        if (fuse && ((rc = ensure(c, c->stage_b, c->stage.cap)) || (rc = ensure(c, c->tcount2_b, c->tcount2.cap)) ||
-                     (rc = ensure(c, c->tpre_b, c->tpre.cap))))
-          return rc;
         HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8 * sizeof(unsigned long long), c->stream));
       }
-      // A pass of k_match_t over several batches: the tuples batch b staged are moved into
-      // `hits` by the launch of batch b + 1 (other staging set, same grid so the same regions);
-      // only the last batch needs k_compact_w.
-      const bool more = r0 + n < c->nreads;
-      const uint64_t next_grid = more ? std::min<uint64_t>(nblk((uint32_t)std::min<uint64_t>(bsz, c->nreads - r0 - n), TILE), resident) : 0;
-      const bool defer = fuse && more && next_grid == sgrid;  // this batch's tuples wait for the next launch
       if ((rc = upload_prepare(c, r0, n, c->stream))) return rc;  // (reads still on their way from the host)
       tm.begin(0);
       {
         Range rg("k_match");
-      switch (c->rw) {
-        case 4: launch_match<4>(c, r0, n, pp.W, block_mode, block_thr, (unsigned)sgrid, set, pending_tiles); break;
-        case 8: launch_match<8>(c, r0, n, pp.W, block_mode, block_thr, (unsigned)sgrid, set, pending_tiles); break;
-        case 12: launch_match<12>(c, r0, n, pp.W, block_mode, block_thr, (unsigned)sgrid, set, pending_tiles); break;
-        default: launch_match<16>(c, r0, n, pp.W, block_mode, block_thr, (unsigned)sgrid, set, pending_tiles); break;
-      }
+        launch_match(c, kern, r0, n, pp.W, block_mode, block_thr, (unsigned)sgrid);
       }
       HIPCHK(c, hipGetLastError());
       tm.end(0);
-      if (pending_tiles) {  // the previous batch is in `hits` now
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, c->stream, set ? c->tpre.p : c->tpre_b.p, pending_tiles, c->counters);
-        HIPCHK(c, hipGetLastError());
-        pending_tiles = 0;
-      }
       c->stats.match_launches++;
       c->stats.n_batches++;
       if (!sized) {
@@ -1782,21 +1696,15 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
       Range rgc("scan + k_compact_w");
       tm.begin(4);
       tm.begin(1);
-      rc = scan_u32(c, set ? c->tcount2_b.p : c->tcount2.p, set ? c->tpre_b.p : c->tpre.p, (uint64_t)ntiles + 1, false,
-                    c->scan_tmp.p, c->stream);
+      rc = scan_u32(c, c->tcount2.p, c->tpre.p, (uint64_t)ntiles + 1, false, c->scan_tmp.p, c->stream);
       if (rc) return rc;
       tm.end(1);
-      if (defer) {
-        pending_tiles = ntiles;
-        set ^= 1;
-      } else {
-        hipLaunchKernelGGL(k_compact_w, dim3(std::min(nblk(ntiles, 4), 4u * MAX_GRID)), dim3(256), 0, c->stream, ntiles,
-                           c->bs[0].tbase.p, set ? c->tcount2_b.p : c->tcount2.p, set ? c->tpre_b.p : c->tpre.p,
-                           set ? c->stage_b.p : c->stage.p, reinterpret_cast<uint4*>(c->hits.p), c->hits.cap, c->counters);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, c->stream, set ? c->tpre_b.p : c->tpre.p, ntiles, c->counters);
-        HIPCHK(c, hipGetLastError());
-      }
+      hipLaunchKernelGGL(k_compact_w, dim3(std::min(nblk(ntiles, 4), 4u * MAX_GRID)), dim3(256), 0, c->stream, ntiles,
+                         c->bs[0].tbase.p, c->tcount2.p, c->tpre.p, c->stage.p, reinterpret_cast<uint4*>(c->hits.p),
+                         c->hits.cap, c->counters);
+      HIPCHK(c, hipGetLastError());
+      hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, c->stream, c->tpre.p, ntiles, c->counters);
+      HIPCHK(c, hipGetLastError());
       tm.end(4);
       r0 += n;
     }
@@ -1976,7 +1884,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
                              ? ((1ull << c->idx_bits) + 1) * sizeof(CtxBucket) + ctx_entries_bytes(c->idx_novf + 16, c->idx_wide)
                              : ((1ull << c->idx_bits) + 1) * (c->idx_lines ? sizeof(LineBucket) : sizeof(Bucket)) + (c->idx_novf + 16) * sizeof(uint4);
   if (c->idx_kind == 1)
-    return match_ctx_pass(c, P, pp, block_mode, block_thr, max_matches, planned_batches, nhits);
+    return match_ctx_pass(c, P, pp, block_mode, max_matches, planned_batches, nhits);
 
   Timer tm(c);
   hipEvent_t ev0 = pool_event(c), ev1 = pool_event(c);
@@ -2051,7 +1959,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
     tm.begin(0);
     {
       Range rg("k_screen");
-      launch_stage(c, 0, mask, r0, n, pp);
+      launch_screen(c, mask, r0, n, pp);
     }
     HIPCHK(c, hipGetLastError());
     tm.end(0);
@@ -2095,7 +2003,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
       tm.begin(3, sB);
       {
         Range rg("k_confirm");
-        launch_stage(c, 2, mask, r0, n, pp);
+        launch_confirm(c, mask, r0, n, pp);
       }
       HIPCHK(c, hipGetLastError());
       tm.end(3, sB);

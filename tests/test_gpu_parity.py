@@ -885,11 +885,10 @@ def test_graph_replay_of_the_sized_pass(monkeypatch):
 
 def test_batches_of_heavy_tiles_move_their_tuples_in_the_next_launch(monkeypatch):
     """Families of near-identical targets: a read has dozens of tuples, a wave-tile thousands (copy
-    loops past the first 64, candidate lists spilling past LDS), in many small batches.  From the
-    second pass on k_match_t moves a batch's staged tuples from inside the next batch's launch
-    (last batch: k_compact_w; a last batch with a smaller grid: k_compact_w for the one before as
-    well).  Every pass must return the single-batch list of the two-kernel path, in read-major
-    order, with and without best + MMTol."""
+    loops past the first 64, candidate lists spilling past LDS), in many small batches, each
+    batch's staged tuples moved into `hits` by its own k_compact_w (r02-r03 moved them from inside
+    the next batch's launch, hence the name).  Every pass must return the single-batch list of the
+    two-kernel path, in read-major order, with and without best + MMTol."""
     from muscato_amd import Engine, sorted_hits
     rng = np.random.default_rng(77)
     bases = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -915,11 +914,9 @@ def test_batches_of_heavy_tiles_move_their_tuples_in_the_next_launch(monkeypatch
         exp_best = sorted_hits(ref.match(to_cfg(ocfg), apply_mmtol=True))
     assert len(exp_all) > 20 * len(reads)
     monkeypatch.delenv("MUSC_INDEX", raising=False)
-    # (the in-launch move is opt-in since r04 -- a k_compact_w per batch is the default -- and stays covered here, with
-    # both fused kernels; the plain form runs in every other multi-batch test)
-    for batch, fused, kern in (("4099", "1", ""), ("8192", "1", "dma"), ("7000", "1", ""), ("7000", "1", "dma"), ("4099", "0", "")):  # 7000: the last batch of 30 000 has a smaller grid
+    # (both fused kernels, each batch's tuples moved by a k_compact_w of its own)
+    for batch, kern in (("4099", ""), ("8192", "dma"), ("7000", ""), ("7000", "dma")):  # 7000: the last batch of 30 000 has a smaller grid
         monkeypatch.setenv("MUSC_BATCH_READS", batch)  # read at musc_init
-        monkeypatch.setenv("MUSC_FUSED_COMPACT", fused)
         if kern:
             monkeypatch.setenv("MUSC_MATCH", kern)
         else:
