@@ -164,6 +164,7 @@ struct EnvKnobs {
   bool no_x_context = false;  // MUSC_NO_X_CONTEXT
   bool force_wide = false;    // MUSC_DEBUG_FORCE_WIDE
   int index_bits = 0;         // MUSC_DEBUG_INDEX_BITS (0: not set)
+  bool ctx_direct = false;    // MUSC_DEBUG_CTX_DIRECT: a direct context table whatever the database size (tests)
   int debug_grid = 0;         // MUSC_DEBUG_GRID (0: not set)
   bool debug_sync = false;    // MUSC_DEBUG_SYNC
   int graph = -1;             // MUSC_GRAPH: -1 not set, else its value
@@ -183,6 +184,7 @@ struct EnvKnobs {
     no_x_context = getenv("MUSC_NO_X_CONTEXT") != nullptr;
     force_wide = getenv("MUSC_DEBUG_FORCE_WIDE") != nullptr;
     if ((e = getenv("MUSC_DEBUG_INDEX_BITS"))) index_bits = atoi(e);
+    ctx_direct = (e = getenv("MUSC_DEBUG_CTX_DIRECT")) && atoi(e) > 0;
     if ((e = getenv("MUSC_DEBUG_GRID"))) debug_grid = atoi(e);
     debug_sync = getenv("MUSC_DEBUG_SYNC") != nullptr;
     if ((e = getenv("MUSC_GRAPH"))) graph = atoi(e);
@@ -974,17 +976,12 @@ int musc_db_build_index(musc_ctx* c, int32_t ww) {
 // Returns 0 and leaves idx_kind == 1 on success; 100 when the table does not fit the device's
 // free memory (the caller then builds the classic index); anything else is an error.
 static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide) {
-  if (c->idx_kind == 1 && c->idx_ww == ww && c->idx_CL == CL && c->idx_wide == wide && c->ctx_T) return 0;
-  // (ctx_E_cap counts 40-byte CtxEntry; a wide index asks for its 60-byte entries in those units)
-  const uint64_t esz = wide ? sizeof(CtxEntryW) : sizeof(CtxEntry);
-  free_index(c);
-  c->wide = 0;
   // 4^ww buckets with the key as the bucket (exact) when that is at most twice the database's
   // window count; else about one bucket per base under a 64-bit mix (a colliding key fails the
   // window comparison in k_match: the context includes the window bases)
   int bits, direct = 0;
   const uint64_t floor_bases = std::max<uint64_t>(c->nbases, 1ull << 9);
-  if (2 * ww <= 30 && (1ull << (2 * ww)) <= 2 * floor_bases) {
+  if (2 * ww <= 30 && ((1ull << (2 * ww)) <= 2 * floor_bases || c->env.ctx_direct)) {  // tests: MUSC_DEBUG_CTX_DIRECT
     bits = 2 * ww;
     direct = 1;
   } else {
@@ -992,6 +989,15 @@ static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide) {
     while (bits < 30 && (1ull << bits) < c->nbases) bits++;
   }
   if (c->env.index_bits >= 8 && c->env.index_bits <= 30) { bits = c->env.index_bits; direct = 0; }  // experiments only: force a hashed table size
+  // (the table kind is part of the comparison: a musc_reload_env that flips MUSC_DEBUG_CTX_DIRECT or
+  // MUSC_DEBUG_INDEX_BITS rebuilds the resident table on the next pass)
+  if (c->idx_kind == 1 && c->idx_ww == ww && c->idx_CL == CL && c->idx_wide == wide && c->idx_bits == bits &&
+      c->idx_direct == direct && c->ctx_T)
+    return 0;
+  // (ctx_E_cap counts 40-byte CtxEntry; a wide index asks for its 60-byte entries in those units)
+  const uint64_t esz = wide ? sizeof(CtxEntryW) : sizeof(CtxEntry);
+  free_index(c);
+  c->wide = 0;
   const uint64_t nb = 1ull << bits;
   // memory: the table, 8 B + 4 B per bucket of build temporaries, and the overflow entries (their
   // number is known only after the counting pass: assume a third of the windows for the estimate)

@@ -61,3 +61,25 @@ def make_case(seed):
         reads.add(r)
     reads.add(rand_seq(rng, maxlen, alphabet))  # every window has a valid read
     return cfg, sorted(reads), targets
+
+
+def hot_probes(reads, targets, cfg, full):
+    """(read, window) of the probes whose (window, key) block accepts more than cfg.MaxMatches pairs, counted as
+    orc.match_direct counts them, from `full`, every accepted (read, gene, pos, nmiss) tuple without truncation: a
+    tuple counts in window k's block when the read's window k passes its gate, equals the target's bases at
+    jx = pos + q1 and that window's fit rule holds (at jx = 0 the literal 100)."""
+    ww = cfg.WindowWidth
+    counts = [{} for _ in cfg.Windows]
+    valid = [[orc.window_valid(r, k, cfg) for k in range(len(cfg.Windows))] for r in reads]
+    for ri, g, p, _ in (full.tolist() if hasattr(full, "tolist") else full):
+        r, t = reads[ri], targets[g]
+        for k, q1 in enumerate(cfg.Windows):
+            jx = p + q1
+            key = r[q1:q1 + ww]
+            if not valid[ri][k] or t[jx:jx + ww] != key:
+                continue
+            if jx == 0 and len(r) > min(100 - (q1 + ww), len(t)):
+                continue
+            counts[k][key] = counts[k].get(key, 0) + 1
+    hot = [{key for key, n in d.items() if n > cfg.MaxMatches} for d in counts]
+    return {(ri, k) for ri, r in enumerate(reads) for k, q1 in enumerate(cfg.Windows) if valid[ri][k] and r[q1:q1 + ww] in hot[k]}

@@ -17,7 +17,7 @@ import pytest
 from oracle import literal
 from oracle import muscato_oracle as orc
 
-from cases import make_case, rand_seq
+from cases import hot_probes, make_case, rand_seq
 
 
 @pytest.mark.parametrize("seed", range(120))
@@ -101,6 +101,33 @@ def test_maxmatches_overflow_literal(mode):
         # candidates arrive in bytewise order of "key\tleft\tright\tgene\tpos"
         order = sorted(range(12), key=lambda g: (targets[g][4:], g))
         assert sorted(h[1] for h in lit) == sorted(order[:6])
+
+
+@pytest.mark.parametrize("seed", range(0, 60, 2))
+def test_hot_probes_agree_with_the_block_counts_of_match_direct(seed):
+    """cases.hot_probes (the GPU tests' expected overflow_probes) recounts the (window, key) blocks from the tuple set:
+    its verdict must be match_direct's at every MaxMatches, and its probes exactly those of the blocks that
+    match_direct counts past the limit."""
+    cfg, reads, targets = make_case(seed)
+    full = sorted(orc.match_direct(reads, targets, cfg, check_overflow=False))
+    for mm in (1, 2, 4, 1000000):
+        cfg.MaxMatches = mm
+        hot = hot_probes(reads, targets, cfg, full)
+        try:
+            orc.match_direct(reads, targets, cfg)
+            overflow = False
+        except OverflowError:
+            overflow = True
+        assert bool(hot) == overflow, (seed, mm)
+        # independently: a probe is hot when its read's block holds more than mm accepted (read, gene, pos)
+        for k, q1 in enumerate(cfg.Windows):
+            one = orc.Config(**dict(cfg.__dict__, Windows=[q1]))
+            block = {}
+            for ri, g, p, nx in orc.match_direct(reads, targets, one, check_overflow=False):
+                key = reads[ri][q1:q1 + cfg.WindowWidth]
+                block[key] = block.get(key, 0) + 1
+            want = {ri for ri, r in enumerate(reads) if orc.window_valid(r, 0, one) and block.get(r[q1:q1 + cfg.WindowWidth], 0) > mm}
+            assert {ri for ri, kk in hot if kk == k} == want, (seed, mm, k)
 
 
 MUSCATO_CASES = [("00", False), ("01", False), ("02", False), ("03", False), ("04", True)]
