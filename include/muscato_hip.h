@@ -171,6 +171,25 @@ int musc_db_build_index(musc_ctx* ctx, int32_t window_width);
  * the environment forces the window-start buckets, MUSC_NO_X_CONTEXT=1 only for runs with X. */
 int musc_db_build_index_for(musc_ctx* ctx, const musc_params* params, int32_t max_read_len);
 
+/* Partitions (an addition: the reference streams the database from disk and has no index to fit).  A database whose
+ * index does not fit the device is matched in partitions: contiguous ranges of whole targets, each of whose index is
+ * built in turn while the packed database stays resident; every pass runs over all reads, and the tuples are merged
+ * on the device into exactly what one pass over an index of the whole database returns -- the same tuples (with
+ * apply_mmtol the global best + MMTol), read-major (within a read: partition order), gene_idx the global target
+ * number, and the same MaxMatches verdict (n_overflow_blocks, musc_overflow_probes) over the whole database.
+ * With one partition -- the default whenever the index fits -- nothing changes.  With several, musc_stats sums the
+ * counters, bytes and times (ms_index_build included) over the partitions; n_hits and n_overflow_blocks are those of
+ * the merged result, index_kind / match_variant / index_bytes those of the partitions (one kind and table size per
+ * pass).
+ * musc_db_set_partition_bases: at most max_bases target bases per partition (a longer target is a partition of its
+ * own); 0 = automatic (the default: one partition if the index fits, else the fewest ranges of about equal bases
+ * whose index does).  It takes effect at the next build or match; musc_db_build_index_for then builds the first
+ * partition's index.  More than 4096 partitions is an error. */
+int musc_db_set_partition_bases(musc_ctx* ctx, uint64_t max_bases);
+/* The plan of the last build or match: *n partitions, partition p = targets [first_target[p], first_target[p+1]);
+ * n + 1 boundaries are written when first_target is not NULL (cap = room for boundaries).  *n = 0 before any. */
+int musc_db_partitions(musc_ctx* ctx, uint32_t* first_target, uint32_t cap, uint32_t* n);
+
 /* ---- reads: replaces reading reads_sorted.txt.sz (cmd/muscato_screen/main.go:120-191,
  * cmd/muscato_window_reads/main.go:94-141).  Reads must already be prepared as the
  * reference does (non-ACGT -> X, truncated to MaxReadLength, de-duplicated); read_idx in the

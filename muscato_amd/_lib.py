@@ -56,6 +56,7 @@ class MuscStats(ctypes.Structure):
 SYMBOLS = [
     "musc_abi_version", "musc_init", "musc_destroy", "musc_last_error", "musc_reload_env",
     "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for",
+    "musc_db_set_partition_bases", "musc_db_partitions",
     "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique",
     "musc_match_device", "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_free_hits",
     "musc_get_stats", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
@@ -101,6 +102,8 @@ def load() -> ctypes.CDLL:
     lib.musc_db_load_packed.argtypes = [vp, vp, vp, vp, ctypes.c_uint32]
     lib.musc_db_build_index.argtypes = [vp, i32]
     lib.musc_db_build_index_for.argtypes = [vp, ctypes.POINTER(MuscParams), i32]
+    lib.musc_db_set_partition_bases.argtypes = [vp, u64]
+    lib.musc_db_partitions.argtypes = [vp, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.musc_reads_load_ascii.argtypes = [vp, vp, vp, u64, ctypes.c_int]
     lib.musc_reads_load_packed.argtypes = [vp, vp, vp, vp, u64]
     lib.musc_reads_load_packed32.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u64, ctypes.c_int]
@@ -124,6 +127,7 @@ def load() -> ctypes.CDLL:
     lib.musc_gather_rccl.argtypes = lib.musc_gather.argtypes
     lib.musc_rccl_probe.argtypes = [ctypes.c_char_p, ctypes.c_uint64]
     for name in ("musc_init", "musc_reload_env", "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for", "musc_db_build_index_for",
+                 "musc_db_set_partition_bases", "musc_db_partitions",
                  "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique", "musc_match_device",
                  "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_get_stats",
                  "musc_gather", "musc_gather_rccl", "musc_rccl_probe"):

@@ -50,6 +50,9 @@ class Config:
     NoCleanTemp: bool = False
     CPUProfile: bool = False
     MaxMismatch: int = -1  # addition: absolute mismatch budget (overrides PMatch when >= 0)
+    # addition: most target bases indexed at once.  A value > 0 is applied to the Engine by match / build_index_for
+    # (Engine.set_partition_bases); 0 leaves the engine's setting, which is automatic unless set_partition_bases changed it
+    DbPartitionBases: int = 0
 
     @classmethod
     def from_json(cls, text) -> "Config":
@@ -88,6 +91,8 @@ class Config:
             raise MuscatoError("MatchMode must be 'first' or 'best'")
         if c.ResultsFileName == "":
             c.ResultsFileName = "results.txt"
+        if c.DbPartitionBases < 0:
+            raise MuscatoError("DbPartitionBases must be >= 0")
         return c
 
     def to_params(self, apply_mmtol: bool, skip_block_check: bool = False, n_shards: int = 1) -> _lib.MuscParams:
@@ -208,10 +213,37 @@ class Engine:
         self._check(self._lib.musc_db_build_index(self._h, int(window_width)), "musc_db_build_index")
 
     def build_index_for(self, cfg: "Config", max_read_len: int = 0) -> None:
-        """Build the index match() will pick for `cfg` (context buckets when the run fits them)."""
+        """Build the index match() will pick for `cfg` (context buckets when the run fits them; with several
+        partitions, the first one's)."""
         p = cfg.to_params(True)
+        self._apply_partition_bases(cfg)
         self._check(self._lib.musc_db_build_index_for(self._h, ctypes.byref(p), int(max_read_len)),
                     "musc_db_build_index_for")
+
+    def set_partition_bases(self, max_bases: int) -> None:
+        """Most target bases indexed at once (musc_db_set_partition_bases): the database is matched in partitions of
+        whole targets and the tuples merged into what one unpartitioned pass returns.  0 = automatic: one partition
+        whenever the index fits the device."""
+        if max_bases < 0:
+            raise MuscatoError("partition bases must be >= 0")
+        self._check(self._lib.musc_db_set_partition_bases(self._h, int(max_bases)), "musc_db_set_partition_bases")
+
+    def partitions(self) -> List[int]:
+        """The plan of the last build or match: partition boundaries as target numbers (n partitions, n + 1 entries;
+        empty before any)."""
+        n = ctypes.c_uint32()
+        self._check(self._lib.musc_db_partitions(self._h, None, 0, ctypes.byref(n)), "musc_db_partitions")
+        if not n.value:
+            return []
+        out = (ctypes.c_uint32 * (n.value + 1))()
+        self._check(self._lib.musc_db_partitions(self._h, out, n.value + 1, ctypes.byref(n)), "musc_db_partitions")
+        return list(out)
+
+    def _apply_partition_bases(self, cfg: "Config") -> None:
+        # (Config.DbPartitionBases > 0 is applied; 0 leaves the engine's setting: automatic, unless set_partition_bases
+        # chose a limit -- call set_partition_bases(0) to return to the automatic plan)
+        if cfg.DbPartitionBases:
+            self.set_partition_bases(int(cfg.DbPartitionBases))
 
     # ---- reads (already prepared: X-substituted, truncated, unique)
     def load_reads(self, seqs: Sequence[bytes]) -> None:
@@ -283,6 +315,7 @@ class Engine:
         n_shards = number of read shards the (window,key) blocks are split over (world size of a
         one-process-per-GPU run): the MaxMatches proof then holds for the union of the shards."""
         p = cfg.to_params(apply_mmtol, skip_block_check, n_shards)
+        self._apply_partition_bases(cfg)
         n = ctypes.c_uint64()
         self._check(self._lib.musc_match_device(self._h, ctypes.byref(p), ctypes.byref(n)), "musc_match_device")
         return int(n.value)

@@ -54,6 +54,7 @@ struct Config {
   int MaxMismatch = -1;  // --MaxMismatch: nmiss budget for every read instead of PMatch
   int GPUs = 1;          // --GPUs: shard the unique reads over this many devices
   int Device = 0;        // --Device: first device ordinal
+  long long DbPartitionBases = 0;  // --DbPartitionBases: most target bases indexed at once, 0 = automatic
 };
 
 struct Die : std::runtime_error {
@@ -136,6 +137,7 @@ inline void config_from_json(const std::string& text, Config& c) {
       else if (key == "sortpar") c.SortPar = (int)d; else if (key == "nocleantemp") c.NoCleanTemp = b;
       else if (key == "cpuprofile") c.CPUProfile = b; else if (key == "maxmismatch") c.MaxMismatch = (int)d;
       else if (key == "gpus") c.GPUs = (int)d; else if (key == "device") c.Device = (int)d;
+      else if (key == "dbpartitionbases") c.DbPartitionBases = (long long)d;
     }
   } while (j.eat(','));
   j.need('}');
@@ -170,7 +172,8 @@ inline std::string config_to_json(const Config& c) {
          N("MaxConfirmProcs", c.MaxConfirmProcs) + "," + N("MMTol", c.MMTol) + "," + S("MatchMode", c.MatchMode) +
          "," + N("SortPar", c.SortPar) + "," + S("SortTemp", c.SortTemp) + "," + S("SortMem", c.SortMem) + "," +
          B("NoCleanTemp", c.NoCleanTemp) + "," + B("CPUProfile", c.CPUProfile) + "," +
-         N("MaxMismatch", c.MaxMismatch) + "," + N("GPUs", c.GPUs) + "," + N("Device", c.Device) + "}\n";
+         N("MaxMismatch", c.MaxMismatch) + "," + N("GPUs", c.GPUs) + "," + N("Device", c.Device) + "," +
+         N("DbPartitionBases", c.DbPartitionBases) + "}\n";
 }
 
 // ---- Go `flag` syntax: -name, --name, -name=value, -name value; bools take no value unless
@@ -206,6 +209,7 @@ inline const std::vector<FlagSpec>& muscato_flags() {
       {"MaxMismatch", 'i', "(addition) absolute mismatch budget per read; overrides PMatch when >= 0"},
       {"GPUs", 'i', "(addition) number of GPUs to shard the reads over"},
       {"Device", 'i', "(addition) first GPU ordinal"},
+      {"DbPartitionBases", 'i', "(addition) most target bases indexed at once; 0 = automatic"},
   };
   return f;
 }
@@ -297,6 +301,7 @@ inline Config handle_args(int argc, char** argv) {
   if (has("MaxMismatch")) c.MaxMismatch = I("MaxMismatch");
   if (has("GPUs") && I("GPUs")) c.GPUs = I("GPUs");
   if (has("Device")) c.Device = I("Device");
+  if (has("DbPartitionBases")) c.DbPartitionBases = strtoll(fl["DbPartitionBases"].c_str(), nullptr, 0);
   if (c.ResultsFileName.empty()) {
     c.ResultsFileName = "results.txt";
     fputs("ResultsFileName not specified, defaulting to 'results.txt'\n", stderr);
@@ -344,6 +349,7 @@ inline void check_args(Config& c) {
   if ((int)c.Windows.size() > MUSC_MAX_WINDOWS)
     throw Die(1, "at most " + std::to_string(MUSC_MAX_WINDOWS) + " windows are supported by this build\n");
   if (c.GPUs < 1) c.GPUs = 1;
+  if (c.DbPartitionBases < 0) throw Die(1, "DbPartitionBases must be >= 0 (0 = automatic)\n");
 }
 
 // ------------------------------------------------------------------------------------
@@ -929,6 +935,7 @@ inline std::vector<musc_hit> run_hot_path(const Config& cfg, const std::vector<U
       musc_ctx* c = nullptr;
       if (musc_init(cfg.Device + g, &c)) { errs[g] = musc_last_error(nullptr); return; }
       ctxs[g] = c;
+      musc_db_set_partition_bases(c, (uint64_t)cfg.DbPartitionBases);  // (the MaxMatches replay below reuses ctxs[0])
       const Concat rd = concat(reads.begin() + lo, reads.begin() + hi, [](const UniqueRead& u) -> const std::string& { return u.seq; });
       uint64_t n = 0;
       if (musc_db_load_ascii(c, db.buf.data(), db.off.data(), (uint32_t)targets.size(), 0) ||
@@ -965,12 +972,23 @@ inline std::vector<musc_hit> run_hot_path(const Config& cfg, const std::vector<U
     for (int g = 0; g < G; g++) {
       musc_stats s;
       musc_get_stats(ctxs[g], &s);
+      // the partition plan (several partitions: a database whose index does not fit, or -DbPartitionBases)
+      uint32_t nparts = 0;
+      musc_db_partitions(ctxs[g], nullptr, 0, &nparts);
+      if (nparts > 1) {
+        std::vector<uint32_t> first(nparts + 1);
+        musc_db_partitions(ctxs[g], first.data(), nparts + 1, &nparts);
+        std::string plan;
+        for (uint32_t p = 0; p < nparts; p++)
+          plan += (p ? " " : "") + std::to_string(first[p]) + "-" + std::to_string(first[p + 1] - 1);
+        log.printf("gpu %d: database in %u partitions (targets %s)", cfg.Device + g, nparts, plan.c_str());
+      }
       char pb[1024];
       snprintf(pb, sizeof pb,
-               "%s{\"gpu\":%d,\"index_kind\":%u,\"index_bytes\":%llu,\"reads\":%llu,\"read_windows\":%llu,\"index_entries_walked\":%llu,"
+               "%s{\"gpu\":%d,\"partitions\":%u,\"index_kind\":%u,\"index_bytes\":%llu,\"reads\":%llu,\"read_windows\":%llu,\"index_entries_walked\":%llu,"
                "\"pairs_compared\":%llu,\"accepted\":%llu,\"tuples\":%llu,\"batches\":%u,\"ms_total\":%.4f,\"ms_screen_or_match\":%.4f,"
                "\"ms_confirm\":%.4f,\"ms_scan\":%.4f,\"ms_compact\":%.4f,\"ms_index_build\":%.3f,\"confirm_bytes\":%llu,\"match_bytes\":%llu}",
-               g ? "," : "", cfg.Device + g, s.index_kind, (unsigned long long)s.index_bytes, (unsigned long long)s.n_reads,
+               g ? "," : "", cfg.Device + g, nparts, s.index_kind, (unsigned long long)s.index_bytes, (unsigned long long)s.n_reads,
                (unsigned long long)s.n_read_windows, (unsigned long long)s.n_candidates, (unsigned long long)s.n_pairs,
                (unsigned long long)s.n_accepted, (unsigned long long)s.n_hits, s.n_batches, s.ms_total, s.ms_screen, s.ms_confirm,
                s.ms_scan, s.ms_select, s.ms_index_build, (unsigned long long)s.confirm_bytes, (unsigned long long)s.match_bytes);

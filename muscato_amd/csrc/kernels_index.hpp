@@ -66,14 +66,15 @@ template <bool SCATTER, class BT>
 __global__ __launch_bounds__(256) void k_index(const uint32_t* __restrict__ db2,
                                                const uint32_t* __restrict__ dbm2,
                                                const uint64_t* __restrict__ seq_off, uint32_t nseq,
-                                               uint64_t nbases, int ww, int bits, int direct, int wide,
+                                               uint64_t g_lo, uint64_t g_hi, int ww, int bits, int direct, int wide,
                                                BT* __restrict__ T, uint4* __restrict__ E) {
-  // one chunk of 256 consecutive bases per iteration (a dispatch holds fewer than 2^32
-  // work-items, so a thread per base cannot cover a database of 2^32 bases or more)
+  // the window starts of bases [g_lo, g_hi): whole targets (a partition of the database, or all of it); entries keep
+  // global target numbers and positions.  One chunk of 256 consecutive bases per iteration (a dispatch holds fewer
+  // than 2^32 work-items, so a thread per base cannot cover a database of 2^32 bases or more)
   __shared__ uint32_t s_g0;
-  const uint64_t nchunks = (nbases + blockDim.x - 1) / blockDim.x;
+  const uint64_t nchunks = (g_hi - g_lo + blockDim.x - 1) / blockDim.x;
   for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-    const uint64_t gfirst = chunk * blockDim.x;
+    const uint64_t gfirst = g_lo + chunk * blockDim.x;
     __syncthreads();  // the previous chunk's readers of s_g0 are done
     if (threadIdx.x == 0) {
       uint32_t lo = 0, hi = nseq;  // largest i < nseq with seq_off[i] <= gfirst
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(256) void k_index(const uint32_t* __restrict__ db2,
     }
     __syncthreads();
     const uint64_t g = gfirst + threadIdx.x;
-    if (g >= nbases) continue;
+    if (g >= g_hi) continue;
     uint32_t gene = s_g0;
     while (seq_off[gene + 1] <= g) gene++;
     const uint64_t s = seq_off[gene], e = seq_off[gene + 1];

@@ -147,13 +147,15 @@ template <bool SCATTER, bool WIDE>
 __global__ __launch_bounds__(256) void k_index_ctx(const uint32_t* __restrict__ db2, const uint32_t* __restrict__ dbm2,
                                                    const uint32_t* __restrict__ dbx,
                                                    const uint64_t* __restrict__ seq_off, uint32_t nseq,
-                                                   uint64_t nbases, int ww, int bits, int direct, int CL,
-                                                   CtxBucket* __restrict__ T, void* __restrict__ Ev,
+                                                   uint64_t nbases, uint64_t g_lo, uint64_t g_hi, int ww, int bits,
+                                                   int direct, int CL, CtxBucket* __restrict__ T, void* __restrict__ Ev,
                                                    uint32_t* __restrict__ cursor) {
+  // (the window starts of bases [g_lo, g_hi): whole targets, as k_index; a context reaches across the range's ends
+  // into the rest of the resident database exactly as it does without partitions)
   __shared__ uint32_t s_g0;
-  const uint64_t nchunks = (nbases + blockDim.x - 1) / blockDim.x;
+  const uint64_t nchunks = (g_hi - g_lo + blockDim.x - 1) / blockDim.x;
   for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-    const uint64_t gfirst = chunk * blockDim.x;
+    const uint64_t gfirst = g_lo + chunk * blockDim.x;
     __syncthreads();
     if (threadIdx.x == 0) {
       uint32_t lo = 0, hi = nseq;  // largest i < nseq with seq_off[i] <= gfirst
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(256) void k_index_ctx(const uint32_t* __restrict__ 
     }
     __syncthreads();
     const uint64_t g = gfirst + threadIdx.x;
-    if (g >= nbases) continue;
+    if (g >= g_hi) continue;
     uint32_t gene = s_g0;
     while (seq_off[gene + 1] <= g) gene++;
     const uint64_t s = seq_off[gene], e = seq_off[gene + 1];

@@ -43,6 +43,7 @@
 #include "kernels_match.hpp"
 #include "kernels_match_lane_inst.hpp"  // k_match_t: declaration only (defined in match_lane_rw*.hip)
 #include "kernels_screen_lane.hpp"
+#include "kernels_partition.hpp"
 MUSC_LANE_INSTANCES_4(extern)
 MUSC_LANE_INSTANCES_8(extern)
 MUSC_LANE_INSTANCES_12(extern)
@@ -171,6 +172,7 @@ struct EnvKnobs {
   bool pipeline = false;      // MUSC_PIPELINE > 0
   bool no_spec = false;       // MUSC_NO_SPEC: never pick a geometry-specialised kernel instance
   long batch_reads = 0;       // MUSC_BATCH_READS (0: not set)
+  long index_budget_mb = 0;   // MUSC_DEBUG_INDEX_BUDGET_MB: caps the memory the index fit checks and the partition planner see (tests)
   void read() {
     *this = EnvKnobs();
     auto is = [](const char* v, const char* w) { return v && !strcmp(v, w); };
@@ -191,6 +193,7 @@ struct EnvKnobs {
     if ((e = getenv("MUSC_PIPELINE"))) pipeline = atoi(e) > 0;
     no_spec = getenv("MUSC_NO_SPEC") != nullptr;
     if ((e = getenv("MUSC_BATCH_READS"))) batch_reads = atol(e);
+    if ((e = getenv("MUSC_DEBUG_INDEX_BUDGET_MB"))) index_budget_mb = atol(e);
   }
 };
 
@@ -225,9 +228,25 @@ struct musc_ctx {
   uint32_t nseq = 0;
   uint64_t nbases = 0;
   uint64_t db_words = 0;
+  std::vector<uint64_t> h_seq_off;  // seq_off on the host: the partition planner cuts at target boundaries
+
+  // Partitions: a database whose index does not fit is matched one range of whole targets at a time;
+  // the packed database stays resident, each range's index is built in turn and the tuples are merged on the device
+  uint64_t part_bases = 0;           // musc_db_set_partition_bases: most bases per partition, 0 = automatic
+  std::vector<uint32_t> part_first;  // the plan of the last pass: partition p = targets [part_first[p], part_first[p + 1])
+  int part_kind = 0;                 // several partitions: the index kind all of them build (PK_*), settled on the largest
+  uint64_t part_size = 0;            // bases of the largest partition: the size-dependent choices are made on it
+  uint32_t cur_part = 0;             // the partition ensure_index builds
+  // (the buffers of the merge below live for one partitioned pass: match_partitioned releases them)
+  DevBuf<musc_hit> pacc;             // the partitions' tuple lists, appended segment after segment
+  DevBuf<uint32_t> pbest;            // per read: fewest mismatches over the partitions so far
+  DevBuf<uint64_t> pcnt, padj;       // per read: survivors -> output cursor; run offset of the segment in hand
+  DevBuf<uint32_t> pflags, pflags_tmp;  // one segment's survivor flags and their scan
+  DevBuf<uint32_t> block_acc;        // the exact MaxMatches block counters summed over the partitions
 
   // index
   int idx_ww = 0, idx_bits = 0, idx_direct = 0;
+  uint32_t idx_g0 = 0, idx_g1 = 0;  // the targets the resident index covers (the whole database or one partition)
   int wide = 0;  // database >= 2^32 bases: 40-bit positions, gene numbers < 2^24
   Bucket* idx_T = nullptr;  // 2^idx_bits buckets: 64-byte Bucket, or (idx_lines) 128-byte LineBucket
   uint4* idx_E = nullptr;   // overflow entries
@@ -349,11 +368,15 @@ int fail(musc_ctx* c, int code, const char* fmt, ...) {
   return code;
 }
 
+// (a failed call also leaves its error as the thread's last error: cleared here, so that the next call on the
+// context -- a smaller plan after an index that did not fit -- does not report it again)
 #define HIPCHK(c, expr)                                                                 \
   do {                                                                                  \
     hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
+    if (e_ != hipSuccess) {                                                             \
+      (void)hipGetLastError();                                                          \
       return fail((c), 10, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    }                                                                                   \
   } while (0)
 
 template <class T>
@@ -458,6 +481,8 @@ void free_db(musc_ctx* c) {
   c->seq_off = nullptr;
   c->nseq = 0;
   c->nbases = 0;
+  c->h_seq_off.clear();
+  c->part_first.clear();
   c->data_epoch++;
 }
 
@@ -710,6 +735,8 @@ void musc_destroy(musc_ctx* c) {
   c->p_nx.release();
   c->nmiss_tab.release();
   c->block_table.release();
+  c->pacc.release(); c->pbest.release(); c->pcnt.release(); c->padj.release(); c->pflags.release(); c->pflags_tmp.release();
+  c->block_acc.release();
   c->hits.release();
   c->packed.release();
   c->gathered.release();
@@ -781,6 +808,9 @@ static int db_alloc(musc_ctx* c, const uint64_t* offsets, uint32_t nseq, int on_
   c->nseq = nseq;
   c->nbases = last;
   c->db_words = (last + 15) / 16;
+  c->h_seq_off.resize((size_t)nseq + 1);
+  if (on_device) HIPCHK(c, hipMemcpy(c->h_seq_off.data(), offsets, ((uint64_t)nseq + 1) * 8, hipMemcpyDeviceToHost));
+  else memcpy(c->h_seq_off.data(), offsets, ((uint64_t)nseq + 1) * 8);
   const uint64_t alloc_words = c->db_words + 64;  // slack: k_confirm reads a whole span past the last base
   HIPCHK(c, hipMalloc((void**)&c->db2, alloc_words * 4));
   HIPCHK(c, hipMalloc((void**)&c->dbm2, alloc_words * 4));
@@ -841,29 +871,95 @@ int musc_db_load_packed(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nm
 }
 
 extern "C++" {
+// The targets (and their bases) an index build covers, and the base count its size-dependent choices are made on:
+// the whole database, or one partition of a pass (then `size` is the largest partition's, so that every partition
+// builds the same kind and size of table)
+struct IdxRange {
+  uint32_t g0, g1;
+  uint64_t b0, b1, size;
+};
+static IdxRange whole_db(const musc_ctx* c) { return IdxRange{0, c->nseq, 0, c->nbases, c->nbases}; }
+
+// Device memory an index may take: what is free plus what the resident tables hold, less `reserve` (the pass's
+// buffers).  MUSC_DEBUG_INDEX_BUDGET_MB caps it (tests of the partition planner on small databases).
+static uint64_t index_room(musc_ctx* c, uint64_t reserve) {
+  size_t mfree = 0, mtotal = 0;
+  if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  const uint64_t have = (uint64_t)mfree + c->idx_T_bytes + c->idx_E_cap * sizeof(uint4) +
+                        (c->ctx_T ? c->ctx_T_cap * sizeof(CtxBucket) : 0) + (c->ctx_E ? c->ctx_E_cap * sizeof(CtxEntry) : 0);
+  uint64_t room = have > reserve ? have - reserve : 0;
+  if (c->env.index_budget_mb > 0) room = std::min<uint64_t>(room, (uint64_t)c->env.index_budget_mb << 20);
+  return room;
+}
+
+// What each bucket layout takes for a table of nb buckets over `bases` bases (the fit checks and the planner):
+// line buckets -- the table, the entries beyond the seventh in runs of eight (assume every bucket wastes half a run),
+// 8 B per bucket of build temporaries -- with 12 GiB for the pass's buffers; 64-byte buckets -- the table, its build
+// temporaries and at most one overflow entry per base -- with 4 GiB
+static uint64_t lines_need(uint64_t nb, uint64_t bases) {
+  return (nb + 1) * (sizeof(LineBucket) + 8) + (bases > 7 * nb ? (bases - 7 * nb) * 16 : 0) + nb * 64;
+}
+static uint64_t classic64_need(uint64_t nb, uint64_t bases) { return (nb + 1) * (sizeof(Bucket) + 16) + bases * sizeof(uint4); }
+static const uint64_t LINES_RESERVE = 12ull << 30, CLASSIC_RESERVE = 4ull << 30, CTX_RESERVE = 4ull << 30;
+
 // Which bucket layout the two-kernel index uses for this database and window width: line buckets
 // (LineBucket: a 128-byte line of seven entries + aligned overflow runs) when the direct table has
 // four or more window starts per key on average and the table fits, 64-byte buckets otherwise.
 // MUSC_INDEX=lines / classic64 force one or the other.
-static bool want_line_buckets(musc_ctx* c, int32_t ww, int bits, int direct) {
+static bool want_line_buckets(musc_ctx* c, int32_t ww, int bits, int direct, uint64_t bases) {
   if (c->env.index == EnvKnobs::IDX_LINES) return true;
   if (c->env.index == EnvKnobs::IDX_CLASSIC64) return false;
   if (!direct) return false;
   (void)ww;
   const uint64_t nb = 1ull << bits;
-  if (c->nbases < 4 * nb) return false;
-  size_t mfree = 0, mtotal = 0;
-  if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) return false;
-  const uint64_t have = (uint64_t)mfree + c->idx_T_bytes + c->idx_E_cap * sizeof(uint4) +
-                        (c->ctx_T ? c->ctx_T_cap * sizeof(CtxBucket) : 0) + (c->ctx_E ? c->ctx_E_cap * sizeof(CtxEntry) : 0);
-  // the table, the entries beyond the seventh in runs of eight (assume every bucket wastes half a run),
-  // 8 B per bucket of build temporaries, and room for the pass's buffers
-  const uint64_t need = (nb + 1) * (sizeof(LineBucket) + 8) + (c->nbases > 7 * nb ? (c->nbases - 7 * nb) * 16 : 0) + nb * 64 + (12ull << 30);
-  return need <= have;
+  if (bases < 4 * nb) return false;
+  return lines_need(nb, bases) <= index_room(c, LINES_RESERVE);
+}
+
+// The window-start table for width ww over `bases` bases: direct addressing (bucket = the 2*ww-bit key itself: exact,
+// and bytewise-sorted reads walk the table front to back) when that table is at most 32x the database and at most
+// 2^30 buckets (64 GiB; line buckets: 128 GiB); otherwise a hashed table with about one bucket per base, at most 2^31
+// buckets (128 GiB; longer lists go to the overflow array).
+static void classic_table(const musc_ctx* c, int32_t ww, uint64_t bases, int* bits, int* direct) {
+  *direct = 0;
+  const uint64_t floor_bases = std::max<uint64_t>(bases, 1ull << 19);
+  if (2 * ww <= 30 && (1ull << (2 * ww)) <= 32 * floor_bases) {
+    *bits = 2 * ww;
+    *direct = 1;
+  } else {
+    *bits = 10;
+    while (*bits < 31 && (1ull << *bits) < bases) (*bits)++;
+  }
+  if (c->env.index_bits >= 8 && c->env.index_bits <= 31) { *bits = c->env.index_bits; *direct = 0; }  // experiments only: force a hashed table size
+}
+
+// The context-bucket table for width ww over `bases` bases: 4^ww buckets with the key as the bucket (exact) when that
+// is at most twice the database's window count; else about one bucket per base under a 64-bit mix (a colliding key
+// fails the window comparison in k_match: the context includes the window bases)
+static void ctx_table(const musc_ctx* c, int32_t ww, uint64_t bases, int* bits, int* direct) {
+  *direct = 0;
+  const uint64_t floor_bases = std::max<uint64_t>(bases, 1ull << 9);
+  if (2 * ww <= 30 && ((1ull << (2 * ww)) <= 2 * floor_bases || c->env.ctx_direct)) {  // tests: MUSC_DEBUG_CTX_DIRECT
+    *bits = 2 * ww;
+    *direct = 1;
+  } else {
+    *bits = 10;
+    while (*bits < 30 && (1ull << *bits) < bases) (*bits)++;
+  }
+  if (c->env.index_bits >= 8 && c->env.index_bits <= 30) { *bits = c->env.index_bits; *direct = 0; }  // experiments only: force a hashed table size
+}
+// memory: the table, 8 B + 4 B per bucket of build temporaries, and the overflow entries (their number is known only
+// after the counting pass: assume a third of the windows for the estimate)
+static uint64_t ctx_need(int bits, int wide, uint64_t bases) {
+  const uint64_t esz = wide ? sizeof(CtxEntryW) : sizeof(CtxEntry);
+  return ((1ull << bits) + 1) * (sizeof(CtxBucket) + 12) + bases / (wide ? 2 : 3) * esz;
 }
 
 template <class BT>
-static int build_index_buckets(musc_ctx* c, int32_t ww, int bits, int direct) {
+static int build_index_buckets(musc_ctx* c, int32_t ww, int bits, int direct, const IdxRange& R) {
   const uint64_t nb = 1ull << bits;
   c->ev_used = 0;
   hipEvent_t e0 = pool_event(c), e1 = pool_event(c), e2 = pool_event(c), e3 = pool_event(c);
@@ -884,10 +980,10 @@ static int build_index_buckets(musc_ctx* c, int32_t ww, int bits, int direct) {
   // the first time, and not repeated)
   HIPCHK(c, hipEventRecord(e0, c->stream));
   HIPCHK(c, hipMemsetAsync(T, 0, (nb + 1) * sizeof(BT), c->stream));
-  const unsigned blocks = (unsigned)std::min<uint64_t>((c->nbases + 255) / 256, 1u << 22);
-  if (c->nbases) {
+  const unsigned blocks = (unsigned)std::min<uint64_t>((R.b1 - R.b0 + 255) / 256, 1u << 22);
+  if (R.b1 > R.b0) {
     hipLaunchKernelGGL((k_index<false, BT>), dim3(blocks), dim3(256), 0, c->stream, c->db2, c->dbm2, c->seq_off, c->nseq,
-                       c->nbases, ww, bits, direct, c->wide, T, (uint4*)nullptr);
+                       R.b0, R.b1, ww, bits, direct, c->wide, T, (uint4*)nullptr);
     HIPCHK(c, hipGetLastError());
   }
   // overflow lists: sizes -> offsets (u64: a 10 Gbp database has billions of overflow entries)
@@ -915,9 +1011,9 @@ static int build_index_buckets(musc_ctx* c, int32_t ww, int bits, int direct) {
     c->idx_E_cap = novf + 16;
   }
   HIPCHK(c, hipEventRecord(e3, c->stream));
-  if (c->nbases) {
+  if (R.b1 > R.b0) {
     hipLaunchKernelGGL((k_index<true, BT>), dim3(blocks), dim3(256), 0, c->stream, c->db2, c->dbm2, c->seq_off, c->nseq,
-                       c->nbases, ww, bits, direct, c->wide, T, c->idx_E);
+                       R.b0, R.b1, ww, bits, direct, c->wide, T, c->idx_E);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(e1, c->stream));
@@ -930,86 +1026,62 @@ static int build_index_buckets(musc_ctx* c, int32_t ww, int bits, int direct) {
 }
 }  // extern "C++"
 
+// The window-start index over the targets of R.  lines: 1 / 0 = line / 64-byte buckets (a partitioned pass settles it
+// once), -1 = the usual choice (want_line_buckets).
+static int build_index_classic(musc_ctx* c, int32_t ww, const IdxRange& R, int lines_kind) {
+  c->wide = c->nbases >= 0xFFFFFFF0ull || c->env.force_wide;
+  if (c->wide && c->nseq >= (1u << 24))
+    return fail(c, 5, "a database of 2^32 bases or more may hold at most 2^24 targets (has %u)", c->nseq);
+  int bits, direct;
+  classic_table(c, ww, R.size, &bits, &direct);
+  // A resident window-start index for this width keeps its layout: the automatic choice looks at the free memory
+  // of the moment (want_line_buckets), which moves as the pass buffers grow, and a flip would mean dropping the
+  // sized state and rebuilding tens of gigabytes in the middle of a run.  Only an explicit MUSC_INDEX = lines |
+  // classic64 that contradicts the resident layout rebuilds.  (The targets covered are part of the key: a
+  // partition never reuses another one's table.)
+  if (c->idx_ww == ww && c->idx_kind == 0 && c->idx_T && c->idx_bits == bits && c->idx_direct == direct &&
+      c->idx_g0 == R.g0 && c->idx_g1 == R.g1 && (lines_kind < 0 || c->idx_lines == (lines_kind == 1)) &&
+      !(c->env.index == EnvKnobs::IDX_LINES && !c->idx_lines) && !(c->env.index == EnvKnobs::IDX_CLASSIC64 && c->idx_lines))
+    return 0;
+  const bool lines = lines_kind >= 0 ? lines_kind == 1 : want_line_buckets(c, ww, bits, direct, R.size) && bits <= 30;
+  free_index(c);
+  drop_ctx_index(c);  // one index kind is resident at a time
+  c->idx_kind = 0;
+  c->idx_lines = lines;
+  const int rc = lines ? build_index_buckets<LineBucket>(c, ww, bits, direct, R) : build_index_buckets<Bucket>(c, ww, bits, direct, R);
+  if (rc) return rc;
+  c->idx_ww = ww;
+  c->idx_bits = bits;
+  c->idx_direct = direct;
+  c->idx_g0 = R.g0;
+  c->idx_g1 = R.g1;
+  return 0;
+}
+
 int musc_db_build_index(musc_ctx* c, int32_t ww) {
   if (!c) return 1;
   if (!c->db2) return fail(c, 4, "no database loaded");
   if (ww < 1 || ww > 4096) return fail(c, 2, "bad window width %d", ww);
   HIPCHK(c, hipSetDevice(c->device));
-  c->wide = c->nbases >= 0xFFFFFFF0ull || c->env.force_wide;
-  if (c->wide && c->nseq >= (1u << 24))
-    return fail(c, 5, "a database of 2^32 bases or more may hold at most 2^24 targets (has %u)", c->nseq);
-  // Direct addressing (bucket = the 2*ww-bit key itself: exact, and bytewise-sorted reads walk
-  // the table front to back) when that table is at most 32x the database and at most 2^30
-  // buckets (64 GiB; line buckets: 128 GiB); otherwise a hashed table with about one bucket per base, at
-  // most 2^31 buckets (128 GiB; longer lists go to the overflow array).
-  int bits, direct = 0;
-  const uint64_t floor_bases = std::max<uint64_t>(c->nbases, 1ull << 19);
-  if (2 * ww <= 30 && (1ull << (2 * ww)) <= 32 * floor_bases) {
-    bits = 2 * ww;
-    direct = 1;
-  } else {
-    bits = 10;
-    while (bits < 31 && (1ull << bits) < c->nbases) bits++;
-  }
-  if (c->env.index_bits >= 8 && c->env.index_bits <= 31) { bits = c->env.index_bits; direct = 0; }  // experiments only: force a hashed table size
-  // A resident window-start index for this width keeps its layout: the automatic choice looks at the free memory
-  // of the moment (want_line_buckets), which moves as the pass buffers grow, and a flip would mean dropping the
-  // sized state and rebuilding tens of gigabytes in the middle of a run.  Only an explicit MUSC_INDEX = lines |
-  // classic64 that contradicts the resident layout rebuilds.
-  if (c->idx_ww == ww && c->idx_kind == 0 && c->idx_T && c->idx_bits == bits && c->idx_direct == direct &&
-      !(c->env.index == EnvKnobs::IDX_LINES && !c->idx_lines) && !(c->env.index == EnvKnobs::IDX_CLASSIC64 && c->idx_lines))
-    return 0;
-  const bool lines = want_line_buckets(c, ww, bits, direct) && bits <= 30;
-  free_index(c);
-  drop_ctx_index(c);  // one index kind is resident at a time
-  c->idx_kind = 0;
-  c->idx_lines = lines;
-  const int rc = lines ? build_index_buckets<LineBucket>(c, ww, bits, direct) : build_index_buckets<Bucket>(c, ww, bits, direct);
-  if (rc) return rc;
-  c->idx_ww = ww;
-  c->idx_bits = bits;
-  c->idx_direct = direct;
-  return 0;
+  return build_index_classic(c, ww, whole_db(c), -1);
 }
 
 // Context buckets for window width ww and CL bases of left context (kernels_match.hpp).
 // Returns 0 and leaves idx_kind == 1 on success; 100 when the table does not fit the device's
 // free memory (the caller then builds the classic index); anything else is an error.
-static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide) {
-  // 4^ww buckets with the key as the bucket (exact) when that is at most twice the database's
-  // window count; else about one bucket per base under a 64-bit mix (a colliding key fails the
-  // window comparison in k_match: the context includes the window bases)
-  int bits, direct = 0;
-  const uint64_t floor_bases = std::max<uint64_t>(c->nbases, 1ull << 9);
-  if (2 * ww <= 30 && ((1ull << (2 * ww)) <= 2 * floor_bases || c->env.ctx_direct)) {  // tests: MUSC_DEBUG_CTX_DIRECT
-    bits = 2 * ww;
-    direct = 1;
-  } else {
-    bits = 10;
-    while (bits < 30 && (1ull << bits) < c->nbases) bits++;
-  }
-  if (c->env.index_bits >= 8 && c->env.index_bits <= 30) { bits = c->env.index_bits; direct = 0; }  // experiments only: force a hashed table size
+static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide, const IdxRange& R) {
+  int bits, direct;
+  ctx_table(c, ww, R.size, &bits, &direct);
   // (the table kind is part of the comparison: a musc_reload_env that flips MUSC_DEBUG_CTX_DIRECT or
-  // MUSC_DEBUG_INDEX_BITS rebuilds the resident table on the next pass)
+  // MUSC_DEBUG_INDEX_BITS rebuilds the resident table on the next pass; so are the targets covered: a partition
+  // never reuses another one's table)
   if (c->idx_kind == 1 && c->idx_ww == ww && c->idx_CL == CL && c->idx_wide == wide && c->idx_bits == bits &&
-      c->idx_direct == direct && c->ctx_T)
+      c->idx_direct == direct && c->idx_g0 == R.g0 && c->idx_g1 == R.g1 && c->ctx_T)
     return 0;
-  // (ctx_E_cap counts 40-byte CtxEntry; a wide index asks for its 60-byte entries in those units)
-  const uint64_t esz = wide ? sizeof(CtxEntryW) : sizeof(CtxEntry);
   free_index(c);
   c->wide = 0;
   const uint64_t nb = 1ull << bits;
-  // memory: the table, 8 B + 4 B per bucket of build temporaries, and the overflow entries (their
-  // number is known only after the counting pass: assume a third of the windows for the estimate)
-  {
-    size_t mfree = 0, mtotal = 0;
-    HIPCHK(c, hipMemGetInfo(&mfree, &mtotal));
-    const uint64_t have = (uint64_t)mfree + (c->ctx_T ? c->ctx_T_cap * sizeof(CtxBucket) : 0) +
-                          (c->ctx_E ? c->ctx_E_cap * sizeof(CtxEntry) : 0) + c->idx_T_bytes +
-                          (c->idx_E ? c->idx_E_cap * sizeof(uint4) : 0);
-    const uint64_t need = (nb + 1) * (sizeof(CtxBucket) + 12) + c->nbases / (wide ? 2 : 3) * esz + (4ull << 30);
-    if (need > have) return 100;
-  }
+  if (ctx_need(bits, wide, R.size) > index_room(c, CTX_RESERVE)) return 100;
   // the classic tables go first (one index kind is resident at a time)
   if (c->idx_T) (void)hipFree(c->idx_T);
   if (c->idx_E) (void)hipFree(c->idx_E);
@@ -1041,14 +1113,14 @@ static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide) {
   HIPCHK(c, hipEventRecord(e0, c->stream));
   HIPCHK(c, hipMemsetAsync(c->ctx_T, 0, (nb + 1) * sizeof(CtxBucket), c->stream));
   HIPCHK(c, hipMemsetAsync(cursor, 0, (nb + 1) * 4, c->stream));
-  const unsigned blocks = (unsigned)std::min<uint64_t>((c->nbases + 255) / 256, 1u << 22);
+  const unsigned blocks = (unsigned)std::min<uint64_t>((R.b1 - R.b0 + 255) / 256, 1u << 22);
   // a database with X: its windows with an X stay out, entries whose context touches one are flagged
   const uint32_t* const xm2 = c->db_has_x ? c->dbm2 : nullptr;
   const uint32_t* const xbl = c->db_has_x ? c->dbx : nullptr;
-  if (c->nbases) {
+  if (R.b1 > R.b0) {
     // (the counting pass does not look at the entries: one instance serves both layouts)
     hipLaunchKernelGGL((k_index_ctx<false, false>), dim3(blocks), dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases,
-                       ww, bits, direct, CL, c->ctx_T, (void*)nullptr, cursor);
+                       R.b0, R.b1, ww, bits, direct, CL, c->ctx_T, (void*)nullptr, cursor);
     HIPCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k_ctx_ovf_count, dim3(nblk(nb + 1, 256)), dim3(256), 0, c->stream, c->ctx_T, nb,
@@ -1077,13 +1149,13 @@ static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide) {
     c->ctx_E_cap = ecap;
   }
   HIPCHK(c, hipEventRecord(e3, c->stream));
-  if (c->nbases) {
+  if (R.b1 > R.b0) {
     if (wide)
       hipLaunchKernelGGL((k_index_ctx<true, true>), dim3(blocks), dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases,
-                         ww, bits, direct, CL, c->ctx_T, (void*)c->ctx_E, cursor);
+                         R.b0, R.b1, ww, bits, direct, CL, c->ctx_T, (void*)c->ctx_E, cursor);
     else
       hipLaunchKernelGGL((k_index_ctx<true, false>), dim3(blocks), dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases,
-                         ww, bits, direct, CL, c->ctx_T, (void*)c->ctx_E, cursor);
+                         R.b0, R.b1, ww, bits, direct, CL, c->ctx_T, (void*)c->ctx_E, cursor);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(e1, c->stream));
@@ -1098,6 +1170,8 @@ static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide) {
   c->idx_CL = CL;
   c->idx_bits = bits;
   c->idx_direct = direct;
+  c->idx_g0 = R.g0;
+  c->idx_g1 = R.g1;
   return 0;
 }
 
@@ -1226,10 +1300,129 @@ static bool ctx_eligible(musc_ctx* c, const musc_params* P, uint32_t max_len, in
   return true;
 }
 
+// ---- partitions
+enum { PK_CTX = 1, PK_LINES = 2, PK_CLASSIC64 = 3 };
+static const uint32_t MAX_PARTITIONS = 4096;
+
+// The index kind the usual cascade (context -> line -> 64-byte buckets) builds over `bases` bases if it fits the
+// device memory (less each kind's reserve for the pass, and `extra`), 0 if none does.  fit = false: the kind
+// regardless of memory.
+static int index_kind_for(musc_ctx* c, int32_t ww, bool ctx_ok, int wide, uint64_t bases, bool fit, uint64_t extra) {
+  int bits, direct;
+  if (ctx_ok) {
+    ctx_table(c, ww, bases, &bits, &direct);
+    if (ctx_need(bits, wide, bases) <= index_room(c, CTX_RESERVE + extra)) return PK_CTX;
+  }
+  classic_table(c, ww, bases, &bits, &direct);
+  const uint64_t nb = 1ull << bits;
+  const bool lines = bits <= 30 && (c->env.index == EnvKnobs::IDX_LINES ||
+                                    (c->env.index != EnvKnobs::IDX_CLASSIC64 && direct && bases >= 4 * nb &&
+                                     lines_need(nb, bases) <= index_room(c, LINES_RESERVE + extra)));
+  if (lines) return !fit || lines_need(nb, bases) <= index_room(c, LINES_RESERVE + extra) ? PK_LINES : 0;
+  return !fit || classic64_need(nb, bases) <= index_room(c, CLASSIC_RESERVE + extra) ? PK_CLASSIC64 : 0;
+}
+
+// What a partitioned pass holds beside the index and the usual pass buffers (match_partitioned; all of it released
+// when the pass ends): 20 B per read (best, survivor count / cursor, run offset), the summed block counters, and the
+// accumulated tuple lists -- 20 B per tuple (the list and one scan word), estimated from the tuple buffer of the passes
+// so far and at least one tuple per read
+static uint64_t merge_reserve(const musc_ctx* c) {
+  const uint64_t tuples = std::max<uint64_t>(c->hits.cap, c->nreads);
+  return 20 * (c->nreads + 1) + (4ull << BLOCK_TABLE_BITS) + 20 * tuples;
+}
+
+// Cut the targets into ranges of at most `limit` bases (a target longer than that is a range of its own); returns
+// false beyond MAX_PARTITIONS ranges
+static bool cut_targets(const musc_ctx* c, uint64_t limit, std::vector<uint32_t>* first, uint64_t* largest) {
+  const std::vector<uint64_t>& off = c->h_seq_off;
+  limit = std::min(limit, c->nbases);
+  first->assign(1, 0u);
+  *largest = 0;
+  uint32_t g = 0;
+  while (g < c->nseq) {
+    // the last boundary within `limit` bases of target g's start
+    uint32_t g1 = (uint32_t)(std::upper_bound(off.begin() + g + 1, off.begin() + c->nseq + 1, off[g] + limit) - off.begin()) - 1;
+    if (g1 <= g) g1 = g + 1;
+    *largest = std::max<uint64_t>(*largest, off[g1] - off[g]);
+    first->push_back(g1);
+    if (first->size() > MAX_PARTITIONS + 1) return false;
+    g = g1;
+  }
+  return true;
+}
+
+// The partition plan of a pass with these parameters: one partition (the unpartitioned path) whenever the index fits,
+// or the limit of musc_db_set_partition_bases allows; otherwise the fewest ranges of about equal bases whose index
+// fits.  Every partition then builds the same index kind and table size, settled on the largest one.
+static int plan_partitions(musc_ctx* c, const musc_params* P, uint32_t max_len) {
+  const int32_t ww = P->window_width;
+  const std::vector<uint32_t> one = {0u, c->nseq};
+  // automatic, and an index of the whole database is resident: it fits (nothing to decide, nothing to query)
+  if (!c->part_bases && c->idx_ww == ww && c->idx_g0 == 0 && c->idx_g1 == c->nseq && c->nseq) {
+    c->part_first = one;
+    return 0;
+  }
+  int CL = 0, wide = 0;
+  const bool ctx_ok = ctx_eligible(c, P, max_len, &CL, &wide);
+  std::vector<uint32_t> first;
+  uint64_t largest = 0;
+  int kind = 0;
+  if (c->part_bases) {
+    if (!cut_targets(c, c->part_bases, &first, &largest))
+      return fail(c, 5, "DbPartitionBases %llu cuts the database into more than %u partitions",
+                  (unsigned long long)c->part_bases, MAX_PARTITIONS);
+    const uint64_t extra = first.size() > 2 ? merge_reserve(c) : 0;
+    kind = index_kind_for(c, ww, ctx_ok, wide, largest, true, extra);
+    if (!kind) kind = index_kind_for(c, ww, false, wide, largest, false, 0);  // (then the build reports what failed)
+  } else if (index_kind_for(c, ww, ctx_ok, wide, c->nbases, true, 0)) {
+    first = one;
+  } else {
+    // the fewest partitions whose largest index fits: a binary search over the number of equal shares
+    uint32_t lo = 2, hi = MAX_PARTITIONS;
+    bool found = false;
+    while (lo <= hi) {
+      const uint32_t n = lo + (hi - lo) / 2;
+      std::vector<uint32_t> f;
+      uint64_t lg = 0;
+      const bool ok = cut_targets(c, (c->nbases + n - 1) / n, &f, &lg);
+      const int k = ok ? index_kind_for(c, ww, ctx_ok, wide, lg, true, merge_reserve(c)) : 0;
+      if (k) {
+        first.swap(f);
+        largest = lg;
+        kind = k;
+        found = true;
+        hi = n - 1;
+      } else {
+        lo = n + 1;
+      }
+    }
+    if (!found)
+      return fail(c, 5, "the index of this database does not fit the device even in %u partitions", MAX_PARTITIONS);
+  }
+  c->part_first = first;
+  c->part_kind = first.size() > 2 ? kind : 0;
+  c->part_size = first.size() > 2 ? largest : c->nbases;
+  return 0;
+}
+
 static int ensure_index(musc_ctx* c, const musc_params* P, uint32_t max_len) {
   int CL = 0, wide = 0;
+  if (c->part_first.size() > 2) {  // one partition of a partitioned pass: the kind settled by plan_partitions
+    const uint32_t p = c->cur_part;
+    const uint32_t g0 = c->part_first[p], g1 = c->part_first[p + 1];
+    const IdxRange R{g0, g1, c->h_seq_off[g0], c->h_seq_off[g1], c->part_size};
+    if (c->part_kind == PK_CTX) {
+      if (!ctx_eligible(c, P, max_len, &CL, &wide)) return fail(c, 12, "internal: a partition lost context-bucket eligibility");
+      const int rc = build_index_ctx(c, P->window_width, CL, wide, R);
+      if (rc == 100)
+        return fail(c, 5, "the context index of partition %u (%llu bases) does not fit the device", p,
+                    (unsigned long long)(R.b1 - R.b0));
+      return rc;
+    }
+    return build_index_classic(c, P->window_width, R, c->part_kind == PK_LINES ? 1 : 0);
+  }
   if (ctx_eligible(c, P, max_len, &CL, &wide)) {
-    const int rc = build_index_ctx(c, P->window_width, CL, wide);
+    const int rc = build_index_ctx(c, P->window_width, CL, wide, whole_db(c));
     if (rc != 100) return rc;
     // (does not fit the free memory: the classic index is a quarter of the size)
   }
@@ -1244,7 +1437,25 @@ int musc_db_build_index_for(musc_ctx* c, const musc_params* P, int32_t max_read_
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t ml = max_read_len > 0 ? (uint32_t)max_read_len
                                        : (P->max_read_length > 0 ? (uint32_t)P->max_read_length : c->max_len);
+  if ((rc = plan_partitions(c, P, ml))) return rc;
+  c->cur_part = 0;  // (several partitions: the first one's index)
   return ensure_index(c, P, ml);
+}
+
+int musc_db_set_partition_bases(musc_ctx* c, uint64_t max_bases) {
+  if (!c) return 1;
+  c->part_bases = max_bases;
+  return 0;
+}
+
+int musc_db_partitions(musc_ctx* c, uint32_t* first_target, uint32_t cap, uint32_t* n) {
+  if (!c) return 1;
+  if (!n) return fail(c, 2, "musc_db_partitions: n is NULL");
+  *n = c->part_first.empty() ? 0u : (uint32_t)c->part_first.size() - 1;
+  if (!first_target || !*n) return 0;
+  if (cap < *n + 1) return fail(c, 2, "musc_db_partitions: room for %u boundaries < %u", cap, *n + 1);
+  memcpy(first_target, c->part_first.data(), (*n + 1) * sizeof(uint32_t));
+  return 0;
 }
 
 // ---------------------------------------------------------------- reads
@@ -1535,6 +1746,7 @@ static void launch_match(musc_ctx* c, match_kernel_t kern, uint64_t r0, uint32_t
 }  // extern "C++"
 
 static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits);
+static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits);
 
 // The geometry-specialised instance a pass may launch: SpecGeom<g> is taken only when EVERY quantity it turns into
 // a constant equals the run's -- window width, window starts, context offset, MinDinuc, the first-window sets, and
@@ -1634,7 +1846,7 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
         if (cap.begin(c->stream) != hipSuccess) {  // no capture on this stream: the plain sized pass
           (void)hipGetLastError();
           c->graph_failed = true;
-          return match_device_impl(c, P, nhits);
+          return match_index_pass(c, P, nhits);
         }
       } else {
         HIPCHK(c, hipEventRecord(ev0, c->stream));
@@ -1736,7 +1948,7 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
         (void)hipGetLastError();
         c->graph_exec = nullptr;
         c->graph_failed = true;
-        return match_device_impl(c, P, nhits);
+        return match_index_pass(c, P, nhits);
       }
       c->graph_epoch = c->data_epoch;
       c->graph_params = *P;
@@ -1756,7 +1968,7 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
       if (!sized) return fail(c, 12, "internal: a capacity guard fired although every batch was sized (flags %llu)",
                               (unsigned long long)c->h_pinned[3]);
       c->sized_epoch = 0;  // the pass did not fit after all: run it the careful way
-      return match_device_impl(c, P, nhits);
+      return match_index_pass(c, P, nhits);
     }
     if (sized) {
       n_windows = c->h_pinned[8 + 0];
@@ -1776,7 +1988,7 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
       c->force_exact_blocks = true;  // screening inconclusive: repeat with exact per-block counters
       c->exact_epoch = c->data_epoch;
       c->exact_params = *P;
-      rc = match_device_impl(c, P, nhits);
+      rc = match_index_pass(c, P, nhits);
       c->force_exact_blocks = false;
       return rc;
     }
@@ -1808,6 +2020,8 @@ int musc_match_device(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
   return rc;
 }
 
+static int match_partitioned(musc_ctx* c, const musc_params* P, uint64_t* nhits);
+
 static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
   Range rg_pass("musc_match_device");
   int rc = check_params(c, P);
@@ -1815,7 +2029,15 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
   if (!c->db2) return fail(c, 4, "no database loaded");
   if (!c->rd && c->nreads) return fail(c, 4, "no reads loaded");
   HIPCHK(c, hipSetDevice(c->device));
-  rc = ensure_index(c, P, c->max_len);
+  if ((rc = plan_partitions(c, P, c->max_len))) return rc;
+  c->cur_part = 0;
+  if (c->part_first.size() > 2) return match_partitioned(c, P, nhits);
+  return match_index_pass(c, P, nhits);
+}
+
+// One pass over the resident index (of the whole database, or of partition cur_part of a partitioned pass)
+static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
+  int rc = ensure_index(c, P, c->max_len);
   if (rc) return rc;
 
   const float keep_index_ms = c->stats.ms_index_build;
@@ -2053,7 +2275,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
     if (c->h_pinned[3]) {
       // a guard fired: the pass did not fit after all -- forget the sizing and run it the careful way
       c->sized_epoch = 0;
-      return match_device_impl(c, P, nhits);
+      return match_index_pass(c, P, nhits);
     }
     n_windows = c->h_pinned[8];  // the batch-local block accumulated over the whole pass
     n_cand = c->h_pinned[8 + 3];
@@ -2078,7 +2300,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
     c->force_exact_blocks = true;
     c->exact_epoch = c->data_epoch;
     c->exact_params = *P;
-    rc = match_device_impl(c, P, nhits);
+    rc = match_index_pass(c, P, nhits);
     c->force_exact_blocks = false;
     return rc;
   }
@@ -2106,6 +2328,155 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
   c->sized_exact_blocks = block_mode == 2;
   c->sized_bsz = bsz;
   return 0;
+}
+
+// A partitioned pass: for each partition in turn its index is built and the per-index pass runs over
+// every read, with exact MaxMatches block counters (summed over the partitions, so that a block whose accepted pairs
+// are split counts in full).  Each partition's read-major list is appended to `pacc` and folded into the per-read best;
+// after the last one, the survivors of the global best + MMTol selection go read-major into `hits`.  The index of each
+// partition is a new data epoch, so no sized-pass or hipGraph shortcut ever replays one partition's pass for another.
+static int match_partitions_run(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
+  const uint32_t np = (uint32_t)c->part_first.size() - 1;
+  const uint64_t nr = c->nreads;
+  const bool check_blocks = !P->skip_block_check;
+  const uint32_t BT = 1u << BLOCK_TABLE_BITS;
+  int rc = 0;
+  if ((rc = ensure(c, c->pbest, nr + 1))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->pbest.p, 0xFF, (nr + 1) * 4, c->stream));
+  if (check_blocks) {
+    if ((rc = ensure(c, c->block_acc, BT))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->block_acc.p, 0, (uint64_t)BT * 4, c->stream));
+  }
+  musc_stats sum;
+  memset(&sum, 0, sizeof sum);
+  std::vector<uint64_t> seg(np + 1, 0);
+  for (uint32_t p = 0; p < np && !rc; p++) {
+    c->cur_part = p;
+    uint64_t nh = 0;
+    if ((rc = ensure_index(c, P, c->max_len))) break;
+    const float build_ms = c->stats.ms_index_build;
+    if ((rc = match_index_pass(c, P, &nh))) break;
+    const musc_stats& s = c->stats;
+    sum.n_read_windows += s.n_read_windows;
+    sum.n_candidates += s.n_candidates;
+    sum.n_pairs += s.n_pairs;
+    sum.n_accepted += s.n_accepted;
+    sum.confirm_bytes += s.confirm_bytes;
+    sum.confirm_launches += s.confirm_launches;
+    sum.n_batches += s.n_batches;
+    sum.ms_screen += s.ms_screen;
+    sum.ms_scan += s.ms_scan;
+    sum.ms_confirm += s.ms_confirm;
+    sum.ms_select += s.ms_select;
+    sum.ms_total += s.ms_total;
+    sum.ms_index_build += build_ms;
+    sum.n_descriptors += s.n_descriptors;
+    sum.match_launches += s.match_launches;
+    sum.n_overflow_entries += s.n_overflow_entries;
+    sum.match_bytes += s.match_bytes;
+    sum.match_bytes_strict += s.match_bytes_strict;
+    sum.index_kind = s.index_kind;        // (equal for every partition: plan_partitions settles the kind)
+    sum.match_variant = s.match_variant;
+    sum.index_bytes = s.index_bytes;
+    if (nh) {
+      if ((rc = ensure(c, c->pacc, seg[p] + nh, true))) break;
+      HIPCHK(c, hipMemcpyAsync(c->pacc.p + seg[p], c->hits.p, nh * sizeof(musc_hit), hipMemcpyDeviceToDevice, c->stream));
+      hipLaunchKernelGGL(k_part_best, dim3(std::min(nblk(nh, 256), 4u * MAX_GRID)), dim3(256), 0, c->stream,
+                         reinterpret_cast<const uint4*>(c->pacc.p + seg[p]), nh, c->pbest.p);
+      HIPCHK(c, hipGetLastError());
+    }
+    if (check_blocks) {
+      hipLaunchKernelGGL(k_add_u32, dim3(nblk(BT, 256)), dim3(256), 0, c->stream, c->block_acc.p, c->block_table.p, (uint64_t)BT);
+      HIPCHK(c, hipGetLastError());
+    }
+    seg[p + 1] = seg[p] + nh;
+  }
+  if (rc) return rc;
+
+  // the merge: survivors per read -> output offsets -> each segment's survivors to their places, in partition order
+  Range rg("partition merge");
+  hipEvent_t ev0 = pool_event(c), ev1 = pool_event(c);
+  if (!ev0 || !ev1) return fail(c, 10, "hipEventCreate failed");
+  HIPCHK(c, hipEventRecord(ev0, c->stream));
+  const uint64_t total_in = seg[np];
+  const uint32_t mmtol = P->mmtol > 0xFFFF ? 0xFFFFu : (uint32_t)P->mmtol;
+  uint64_t max_seg = 0;
+  for (uint32_t p = 0; p < np; p++) max_seg = std::max(max_seg, seg[p + 1] - seg[p]);
+  if (max_seg >= 0xFFFFFFFFull) return fail(c, 6, "one partition returned %llu tuples (>= 2^32)", (unsigned long long)max_seg);
+  if ((rc = ensure(c, c->pcnt, nr + 1)) || (rc = ensure(c, c->padj, nr + 1)) ||
+      (rc = ensure(c, c->pflags, max_seg + 1)) || (rc = ensure(c, c->pflags_tmp, scan_tmp_elems(max_seg + 1))))
+    return rc;
+  if (scan_tmp_elems(nr + 1) * 2 > c->pflags_tmp.cap && (rc = ensure(c, c->pflags_tmp, scan_tmp_elems(nr + 1) * 2)))
+    return rc;  // (scan_u64 borrows it too, in u64 units)
+  HIPCHK(c, hipMemsetAsync(c->pcnt.p, 0, (nr + 1) * 8, c->stream));
+  if (total_in) {
+    hipLaunchKernelGGL(k_part_count, dim3(std::min(nblk(total_in, 256), 4u * MAX_GRID)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const uint4*>(c->pacc.p), total_in, c->pbest.p, mmtol, P->apply_mmtol,
+                       reinterpret_cast<unsigned long long*>(c->pcnt.p));
+    HIPCHK(c, hipGetLastError());
+  }
+  if ((rc = scan_u64(c, c->pcnt.p, c->pcnt.p, nr + 1, reinterpret_cast<uint64_t*>(c->pflags_tmp.p)))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->pcnt.p + nr, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t total = c->h_pinned[0];
+  if ((rc = ensure(c, c->hits, total ? total : 1))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
+  for (uint32_t p = 0; p < np; p++) {
+    const uint64_t n = seg[p + 1] - seg[p];
+    if (!n) continue;
+    const uint4* const h = reinterpret_cast<const uint4*>(c->pacc.p + seg[p]);
+    const dim3 grid(std::min(nblk(n + 1, 256), 4u * MAX_GRID));
+    hipLaunchKernelGGL(k_part_flags, grid, dim3(256), 0, c->stream, h, n, c->pbest.p, mmtol, P->apply_mmtol, c->pflags.p);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = scan_u32(c, c->pflags.p, c->pflags.p, n + 1, false, c->pflags_tmp.p, c->stream))) return rc;
+    hipLaunchKernelGGL(k_part_head, grid, dim3(256), 0, c->stream, h, n, c->pflags.p, c->pcnt.p, c->padj.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_part_scatter, grid, dim3(256), 0, c->stream, h, n, c->pflags.p, c->padj.p, c->pcnt.p,
+                       reinterpret_cast<uint4*>(c->hits.p), total, c->d_flag);
+    HIPCHK(c, hipGetLastError());
+  }
+  // the MaxMatches verdict of the whole database: the summed exact counters, then the usual count of full blocks
+  if (check_blocks) {
+    HIPCHK(c, hipMemcpyAsync(c->block_table.p, c->block_acc.p, (uint64_t)BT * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->counters + 5, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_block_overflow, dim3(1024), dim3(256), 0, c->stream, c->block_table.p, c->last_max_matches, c->counters);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipEventRecord(ev1, c->stream));
+  c->h_pinned[1] = 0;
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + 5, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->h_pinned[1]) return fail(c, 12, "internal: the partition merge overran its %llu tuples", (unsigned long long)total);
+  float merge_ms = 0;
+  (void)hipEventElapsedTime(&merge_ms, ev0, ev1);
+  sum.ms_select += merge_ms;
+  sum.ms_total += merge_ms;
+  sum.n_reads = nr;
+  sum.n_hits = c->nhits = total;
+  sum.n_overflow_blocks = check_blocks ? c->h_pinned[0] : ~0ull;
+  c->stats = sum;
+  c->last_exact_blocks = check_blocks;
+  if (nhits) *nhits = total;
+  return 0;
+}
+
+// Every partition runs with exact block counters; on every exit the context's own setting comes back and the merge's
+// buffers are released, so that the next plan sees the memory it reserved for them (merge_reserve)
+static int match_partitioned(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
+  const bool keep_force = c->force_exact_blocks;
+  c->force_exact_blocks = true;
+  const int rc = match_partitions_run(c, P, nhits);
+  c->force_exact_blocks = keep_force;
+  (void)hipStreamSynchronize(c->stream);  // (an error path may leave merge kernels queued)
+  c->pacc.release();
+  c->pbest.release();
+  c->pcnt.release();
+  c->padj.release();
+  c->pflags.release();
+  c->pflags_tmp.release();
+  c->block_acc.release();
+  return rc;
 }
 
 int musc_hits_copy(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_device) {
