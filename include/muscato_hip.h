@@ -254,6 +254,32 @@ void musc_free_hits(musc_hit* hits);
 
 int musc_get_stats(musc_ctx* ctx, musc_stats* out);
 
+/* Which kernel instances the last musc_match* launched (tests: a pass that silently took another instance than the
+ * one a test was written for is noticed).  The host resolves every kernel through a table whose entries hold the
+ * function pointer and its descriptor side by side; these words are the descriptors of the entries the last pass took.
+ *   out[0]  the fused kernel (0: the pass ran the two-kernel path)
+ *             MUSC_INST_MATCH_T  k_match_t<RW, W, XM, WIDE, SG>
+ *             MUSC_INST_MATCH_G  k_match_g<RW, SG>
+ *   out[1]  the screen kernel of the two-kernel path (0: a fused pass)
+ *             MUSC_INST_SCREEN   k_screen<RW, mask, one, lines>
+ *             MUSC_INST_SCREEN_T k_screen_t<RW>
+ *   out[2]  MUSC_INST_CONFIRM    k_confirm<RW, mask, w2>  (0: a fused pass, or no batch reached the confirm stage)
+ *   out[3]  bits 0-7 the MaxMatches block mode of the last pass (0 none, 1 screening, 2 exact counters); bit 8: that
+ *           pass was the exact repeat of a pass whose screening was inconclusive
+ * A descriptor: bits 0-7 the family, 8-15 RW (0: the runtime-stride instance), then one template argument per
+ * field, in the order written above: bits 16-19, 20-23, 24-27, 28-31 (k_match_g: SG in 28-31).
+ * After a partitioned pass: the instances of the last partition. */
+#define MUSC_INSTANCE_WORDS 4
+#define MUSC_INST_MATCH_T 1u
+#define MUSC_INST_MATCH_G 2u
+#define MUSC_INST_SCREEN 3u
+#define MUSC_INST_SCREEN_T 4u
+#define MUSC_INST_CONFIRM 5u
+int musc_last_instance(const musc_ctx* ctx, uint32_t* out);
+/* Every descriptor the library's resolvers can return (needs no device): *n their number, the first `capacity` of
+ * them in `out` (may be NULL with capacity 0). */
+int musc_instances(uint32_t* out, uint32_t capacity, uint32_t* n);
+
 /* When the last musc_match* left n_overflow_blocks > 0: the (read, window) probes whose
  * (window, key) block may hold more than MaxMatches accepted pairs -- the blocks for which
  * cmd/muscato_confirm/main.go:233-242, 424-448 keep an order-dependent subset.  The library

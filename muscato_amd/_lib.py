@@ -59,7 +59,7 @@ SYMBOLS = [
     "musc_db_set_partition_bases", "musc_db_partitions",
     "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique",
     "musc_match_device", "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_free_hits",
-    "musc_get_stats", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
+    "musc_get_stats", "musc_last_instance", "musc_instances", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
 ]
 
 _lib = None
@@ -118,6 +118,8 @@ def load() -> ctypes.CDLL:
     lib.musc_free_hits.argtypes = [vp]
     lib.musc_free_hits.restype = None
     lib.musc_get_stats.argtypes = [vp, ctypes.POINTER(MuscStats)]
+    lib.musc_last_instance.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
+    lib.musc_instances.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
     lib.musc_overflow_probes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(u64)]
     lib.musc_overflow_probes.restype = ctypes.c_int
     lib.musc_free_u32.argtypes = [vp]
@@ -129,7 +131,7 @@ def load() -> ctypes.CDLL:
     for name in ("musc_init", "musc_reload_env", "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for", "musc_db_build_index_for",
                  "musc_db_set_partition_bases", "musc_db_partitions",
                  "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique", "musc_match_device",
-                 "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_get_stats",
+                 "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_get_stats", "musc_last_instance", "musc_instances",
                  "musc_gather", "musc_gather_rccl", "musc_rccl_probe"):
         getattr(lib, name).restype = ctypes.c_int
     _lib = lib

@@ -363,10 +363,54 @@ class Engine:
         self._lib.musc_free_u32(pw)
         return out
 
+    def last_instance(self) -> dict:
+        """The kernel instances the last match launched, from the resolver that returned their function pointers:
+        {"path": "fused" | "two-kernel" | "none", "match": k_match_t / k_match_g descriptor or None, "screen": k_screen /
+        k_screen_t descriptor or None, "confirm": k_confirm descriptor or None, "block_mode": 0 | 1 | 2, "exact_rerun":
+        the pass repeated one whose MaxMatches screening was inconclusive}; a descriptor is decode_instance's dict."""
+        w = (ctypes.c_uint32 * 4)()
+        self._check(self._lib.musc_last_instance(self._h, w), "musc_last_instance")
+        return {"path": "fused" if w[0] else "two-kernel" if w[1] else "none",
+                "match": decode_instance(w[0]), "screen": decode_instance(w[1]), "confirm": decode_instance(w[2]),
+                "block_mode": w[3] & 0xFF, "exact_rerun": bool(w[3] & 0x100)}
+
     def stats(self) -> dict:
         s = _lib.MuscStats()
         self._check(self._lib.musc_get_stats(self._h, ctypes.byref(s)), "musc_get_stats")
         return {k: getattr(s, k) for k, _ in s._fields_}
+
+
+_INST_FIELDS = {1: ("k_match_t", ("W", "XM", "WIDE", "SG")), 2: ("k_match_g", (None, None, None, "SG")),
+                3: ("k_screen", ("mask", "one", "lines")), 4: ("k_screen_t", ()), 5: ("k_confirm", ("mask", "w2"))}
+
+
+def decode_instance(word: int) -> Optional[dict]:
+    """A descriptor word of musc_last_instance / musc_instances (include/muscato_hip.h) as
+    {"kernel": name, "RW": .., <template argument>: ..}; None for 0 (no such kernel in the pass)."""
+    if not word:
+        return None
+    name, fields = _INST_FIELDS[word & 0xFF]
+    d = {"kernel": name, "RW": (word >> 8) & 0xFF}
+    for i, f in enumerate(fields):
+        if f:
+            d[f] = (word >> (16 + 4 * i)) & 0xF
+    return d
+
+
+def instance_name(d: Optional[dict]) -> str:
+    """k_match_t<8, 2, 0, 0, 0> for a decoded descriptor, in the template's argument order."""
+    return "none" if d is None else "%s<%s>" % (d["kernel"], ", ".join(str(v) for k, v in d.items() if k != "kernel"))
+
+
+def instances() -> List[dict]:
+    """Every kernel instance the library's resolvers can return (no GPU needed)."""
+    lib = _lib.load()
+    n = ctypes.c_uint32()
+    if lib.musc_instances(None, 0, ctypes.byref(n)):
+        raise RuntimeError("musc_instances failed")
+    buf = (ctypes.c_uint32 * max(1, n.value))()
+    lib.musc_instances(buf, n.value, ctypes.byref(n))
+    return [decode_instance(w) for w in buf[:n.value]]
 
 
 def gather(engines: Sequence["Engine"], read_bases: Sequence[int], rccl: bool = False) -> np.ndarray:

@@ -319,6 +319,7 @@ struct musc_ctx {
   uint32_t cur_block_thr = 0;
   PathParams last_pp;          // of the last musc_match_device
   uint32_t last_max_matches = 0;
+  uint32_t last_inst[MUSC_INSTANCE_WORDS] = {0, 0, 0, 0};  // musc_last_instance: what the resolvers of the last pass returned
   bool last_exact_blocks = false;  // block_table holds exact counters of that pass
   unsigned long long* counters = nullptr;  // [0] valid windows [1] accepted [2] hit cursor
   uint64_t* h_pinned = nullptr;            // 16 x u64 pinned staging
@@ -576,37 +577,54 @@ auto by_rw(int rw, F&& f) {
 }
 
 // The instance of each two-kernel-path kernel a run launches: one resolver per kernel, which the launch
-// (and for k_screen_t the occupancy query of screen_grid) takes it from
+// (and for k_screen_t the occupancy query of screen_grid) takes it from.  A resolver returns the function pointer
+// TOGETHER with its descriptor (musc_last_instance, include/muscato_hip.h): both come from one table entry, written
+// by one macro from one list of template arguments, so what a pass reports is what it launched.
 typedef decltype(&k_screen_t<8>) screen_t_fn;
 typedef decltype(&k_screen<0, false, false, false>) screen_fn;
 typedef decltype(&k_confirm<0, false, false>) confirm_fn;
+template <class Fn>
+struct Inst {
+  Fn fn;
+  uint32_t id;  // MUSC_INST_* family and template arguments; 0 with fn == nullptr
+};
+constexpr uint32_t inst_id(uint32_t family, int rw, int a = 0, int b = 0, int c = 0, int d = 0) {
+  return family | (uint32_t)rw << 8 | (uint32_t)a << 16 | (uint32_t)b << 20 | (uint32_t)c << 24 | (uint32_t)d << 28;
+}
+#define INST_SCREEN_T(RW) Inst<screen_t_fn>{k_screen_t<RW>, inst_id(MUSC_INST_SCREEN_T, RW)}
+#define INST_SCREEN(RW, M, ONE, LN) Inst<screen_fn>{k_screen<RW, M, ONE, LN>, inst_id(MUSC_INST_SCREEN, RW, M, ONE, LN)}
+#define INST_CONFIRM(RW, M, W2) Inst<confirm_fn>{k_confirm<RW, M, W2>, inst_id(MUSC_INST_CONFIRM, RW, M, W2)}
 
-screen_t_fn screen_t_kernel(const musc_ctx* c) {  // (screen_lane: only the strides k_screen_t is built for)
-  return by_rw(c->rw, [](auto rw) -> screen_t_fn {
-    if constexpr (decltype(rw)::value != 0) return k_screen_t<decltype(rw)::value>;
-    else return nullptr;
+Inst<screen_t_fn> screen_t_instance(int rw) {  // (screen_lane: only the strides k_screen_t is built for)
+  return by_rw(rw, [](auto r) -> Inst<screen_t_fn> {
+    if constexpr (decltype(r)::value != 0) return INST_SCREEN_T(decltype(r)::value);
+    else return Inst<screen_t_fn>{nullptr, 0};
   });
 }
 
-screen_fn screen_kernel(const musc_ctx* c, int W) {
-  const int m = c->rdm != nullptr, one = W <= 2, ln = c->idx_lines;
-  return by_rw(c->rw, [&](auto rw) -> screen_fn {
-    constexpr int RW = decltype(rw)::value;
-    static const screen_fn k[2][2][2] = {
-        {{k_screen<RW, false, false, false>, k_screen<RW, false, false, true>}, {k_screen<RW, false, true, false>, k_screen<RW, false, true, true>}},
-        {{k_screen<RW, true, false, false>, k_screen<RW, true, false, true>}, {k_screen<RW, true, true, false>, k_screen<RW, true, true, true>}}};
+Inst<screen_fn> screen_instance(int rw, bool mask, int W, bool lines) {
+  const int m = mask, one = W <= 2, ln = lines;
+  return by_rw(rw, [&](auto r) -> Inst<screen_fn> {
+    constexpr int RW = decltype(r)::value;
+    static const Inst<screen_fn> k[2][2][2] = {
+        {{INST_SCREEN(RW, false, false, false), INST_SCREEN(RW, false, false, true)}, {INST_SCREEN(RW, false, true, false), INST_SCREEN(RW, false, true, true)}},
+        {{INST_SCREEN(RW, true, false, false), INST_SCREEN(RW, true, false, true)}, {INST_SCREEN(RW, true, true, false), INST_SCREEN(RW, true, true, true)}}};
     return k[m][one][ln];
   });
 }
 
-confirm_fn confirm_kernel(const musc_ctx* c, bool mask, int W) {
-  const int w2 = W <= 2;
-  return by_rw(c->rw, [&](auto rw) -> confirm_fn {
-    constexpr int RW = decltype(rw)::value;
-    static const confirm_fn k[2][2] = {{k_confirm<RW, false, false>, k_confirm<RW, false, true>}, {k_confirm<RW, true, false>, k_confirm<RW, true, true>}};
-    return k[mask][w2];
+Inst<confirm_fn> confirm_instance(int rw, bool mask, int W) {
+  const int m = mask, w2 = W <= 2;
+  return by_rw(rw, [&](auto r) -> Inst<confirm_fn> {
+    constexpr int RW = decltype(r)::value;
+    static const Inst<confirm_fn> k[2][2] = {{INST_CONFIRM(RW, false, false), INST_CONFIRM(RW, false, true)}, {INST_CONFIRM(RW, true, false), INST_CONFIRM(RW, true, true)}};
+    return k[m][w2];
   });
 }
+
+Inst<screen_t_fn> screen_t_kernel(const musc_ctx* c) { return screen_t_instance(c->rw); }
+Inst<screen_fn> screen_kernel(const musc_ctx* c, int W) { return screen_instance(c->rw, c->rdm != nullptr, W, c->idx_lines); }
+Inst<confirm_fn> confirm_kernel(const musc_ctx* c, bool mask, int W) { return confirm_instance(c->rw, mask, W); }
 
 // workgroups of the screen stage: the descriptor buffer is cut into that many regions.  k_screen_t's
 // workgroups are single waves that stay for the whole launch: as many as are resident at once (a
@@ -616,7 +634,7 @@ unsigned screen_grid(musc_ctx* c, uint32_t n, bool mask) {
   if (screen_lane(c, mask)) {
     if (!c->scrt_resident) {
       int per_cu = 0, ncu = 0;
-      const void* fn = reinterpret_cast<const void*>(screen_t_kernel(c));
+      const void* fn = reinterpret_cast<const void*>(screen_t_kernel(c).fn);
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 8; }
       if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu < 1) ncu = 256;
       c->scrt_resident = (unsigned)per_cu * (unsigned)ncu;
@@ -631,14 +649,19 @@ unsigned screen_grid(musc_ctx* c, uint32_t n, bool mask) {
 void launch_screen(musc_ctx* c, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
   const dim3 sgrid(screen_grid(c, n, mask));
   auto& b = c->bs[c->cur];
-  if (screen_lane(c, mask))
-    hipLaunchKernelGGL(screen_t_kernel(c), sgrid, dim3(64), 0, c->stream, c->rd, r0, n, c->d_pp, c->nmiss_tab.p,
+  if (screen_lane(c, mask)) {
+    const auto k = screen_t_kernel(c);
+    c->last_inst[1] = k.id;
+    hipLaunchKernelGGL(k.fn, sgrid, dim3(64), 0, c->stream, c->rd, r0, n, c->d_pp, c->nmiss_tab.p,
                        reinterpret_cast<const LineBucket*>(c->idx_T), c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p,
                        b.tbase.p, b.tcount.p, c->counters + 8, c->counters + 3);
-  else
-    hipLaunchKernelGGL(screen_kernel(c, pp.W), sgrid, dim3(TILE), 0, c->stream, c->rd, c->rdm, r0, n, c->rw, c->d_pp,
+  } else {
+    const auto k = screen_kernel(c, pp.W);
+    c->last_inst[1] = k.id;
+    hipLaunchKernelGGL(k.fn, sgrid, dim3(TILE), 0, c->stream, c->rd, c->rdm, r0, n, c->rw, c->d_pp,
                        c->nmiss_tab.p, c->idx_T, c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p, b.tbase.p, b.tcount.p,
                        c->counters + 8, c->counters + 3);
+  }
 }
 
 void launch_confirm(musc_ctx* c, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
@@ -647,7 +670,9 @@ void launch_confirm(musc_ctx* c, bool mask, uint64_t r0, uint32_t n, const PathP
   static_assert((1u << 24) / TILE / MAX_GRID <= CONF_TILES, "a k_confirm workgroup keeps its tile list in LDS");
   const size_t lds = c->cur_block_mode ? (size_t)TILE * pp.W * 4 : 0;
   auto& b = c->bs[c->cur];
-  hipLaunchKernelGGL(confirm_kernel(c, mask, pp.W), grid, dim3(TILE), lds, c->s_confirm, c->rd, c->rdm, c->db2, c->dbm2,
+  const auto k = confirm_kernel(c, mask, pp.W);
+  c->last_inst[2] = k.id;
+  hipLaunchKernelGGL(k.fn, grid, dim3(TILE), lds, c->s_confirm, c->rd, c->rdm, c->db2, c->dbm2,
                      c->dbx, r0, n, c->rw, c->d_pp, c->nmiss_tab.p, b.cdesc.p, b.rvalid.p, c->p_nx.p, b.tbase.p, b.tcount.p,
                      b.wb.p, c->cur_block_mode, c->cur_block_thr, c->block_table.p, c->seq_off, c->stage.p, c->tcount2.p,
                      c->counters);
@@ -1685,27 +1710,35 @@ static size_t match_dyn_lds(int kind, int W, int block_mode) {
 // both take it from here.  Instances (kernels_match_lane_inst.hpp): k_match_t on 120-base buckets for records of 4, 8,
 // 12 words and on wide ones for 4 to 16, each for 1-4 windows and three X modes; the geometry-specialised
 // k_match_t<8, 2, 0, false, 1>; k_match_g<8, 0 | 1>.
+typedef Inst<match_kernel_t> MatchInst;  // pointer and descriptor from one table entry, as on the two-kernel path
+#define INST_T(RW, W, XM, WD, SG) MatchInst{k_match_t<RW, W, XM, WD, SG>, inst_id(MUSC_INST_MATCH_T, RW, W, XM, WD, SG)}
+#define INST_G(RW, SG) MatchInst{k_match_g<RW, SG>, inst_id(MUSC_INST_MATCH_G, RW, 0, 0, 0, SG)}
 template <int RW, bool WD>
-static match_kernel_t lane_kernel(int W, int xm) {
-  static const match_kernel_t k[4][3] = {
-      {k_match_t<RW, 1, 0, WD, 0>, k_match_t<RW, 1, 1, WD, 0>, k_match_t<RW, 1, 2, WD, 0>},
-      {k_match_t<RW, 2, 0, WD, 0>, k_match_t<RW, 2, 1, WD, 0>, k_match_t<RW, 2, 2, WD, 0>},
-      {k_match_t<RW, 3, 0, WD, 0>, k_match_t<RW, 3, 1, WD, 0>, k_match_t<RW, 3, 2, WD, 0>},
-      {k_match_t<RW, 4, 0, WD, 0>, k_match_t<RW, 4, 1, WD, 0>, k_match_t<RW, 4, 2, WD, 0>}};
+static MatchInst lane_instance(int W, int xm) {
+  static const MatchInst k[4][3] = {
+      {INST_T(RW, 1, 0, WD, 0), INST_T(RW, 1, 1, WD, 0), INST_T(RW, 1, 2, WD, 0)},
+      {INST_T(RW, 2, 0, WD, 0), INST_T(RW, 2, 1, WD, 0), INST_T(RW, 2, 2, WD, 0)},
+      {INST_T(RW, 3, 0, WD, 0), INST_T(RW, 3, 1, WD, 0), INST_T(RW, 3, 2, WD, 0)},
+      {INST_T(RW, 4, 0, WD, 0), INST_T(RW, 4, 1, WD, 0), INST_T(RW, 4, 2, WD, 0)}};
   return k[(W >= 1 && W <= 3 ? W : 4) - 1][xm];
 }
 
-static match_kernel_t match_kernel(const musc_ctx* c, int W) {
-  if (match_kind(c, W) == MK_DMA) return c->spec_geom == 1 ? k_match_g<8, 1> : k_match_g<8, 0>;
-  if (c->spec_geom == 1) return k_match_t<8, 2, 0, false, 1>;  // (chosen by spec_geom_matches: every specialised quantity equals the run's)
-  const int xm = c->db_has_x ? 2 : c->reads_have_x ? 1 : 0;
-  return by_rw(c->rw, [&](auto rw) -> match_kernel_t {
-    constexpr int RW = decltype(rw)::value;
-    if constexpr (RW == 0) return nullptr;
-    else if (c->idx_wide) return lane_kernel<RW, true>(W, xm);
-    else if constexpr (RW <= 12) return lane_kernel<RW, false>(W, xm);
-    else return nullptr;
+// (kind, spec_geom: what match_kind and spec_geom_matches decided for the run)
+static MatchInst match_instance(int kind, int spec_geom, int rw, bool wide, int W, int xm) {
+  if (kind == MK_DMA) return spec_geom == 1 ? INST_G(8, 1) : INST_G(8, 0);
+  if (spec_geom == 1) return INST_T(8, 2, 0, false, 1);  // (chosen by spec_geom_matches: every specialised quantity equals the run's)
+  return by_rw(rw, [&](auto r) -> MatchInst {
+    constexpr int RW = decltype(r)::value;
+    if constexpr (RW == 0) return MatchInst{nullptr, 0};
+    else if (wide) return lane_instance<RW, true>(W, xm);
+    else if constexpr (RW <= 12) return lane_instance<RW, false>(W, xm);
+    else return MatchInst{nullptr, 0};
   });
+}
+
+static MatchInst match_kernel(const musc_ctx* c, int W) {
+  const int xm = c->db_has_x ? 2 : c->reads_have_x ? 1 : 0;
+  return match_instance(match_kind(c, W), c->spec_geom, c->rw, c->idx_wide != 0, W, xm);
 }
 
 // workgroups of the kernel that are resident at once on this device: the persistent grid
@@ -1802,11 +1835,14 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
   // which looks like a tail a dynamically dispatched grid would remove.  It does not: 2 / 4 / 8 / 16 times the resident
   // workgroups run the cfg3 launch in 1.03 / 1.04 / 1.06 / 1.11 ms against 0.98-0.99 (profiles/r04_ab_shape_spec_dma.txt).
   // The memory system is the shared resource: the waves that finish early leave their share to the slow ones.)
-  const match_kernel_t kern = match_kernel(c, pp.W);
+  const MatchInst inst = match_kernel(c, pp.W);
+  const match_kernel_t kern = inst.fn;
+  c->last_inst[0] = inst.id;
   if (!kern) return fail(c, 12, "internal: no fused kernel instance for record stride %d, %d windows", c->rw, pp.W);
   const unsigned resident = match_resident(c, kern, pp.W, block_mode);
   uint32_t block_thr = (uint32_t)std::min<uint64_t>(max_matches / (planned_batches * resident), 0x7FFFFFFFull);
   if (block_mode == 1 && block_thr < 2) block_mode = 2;
+  c->last_inst[3] = (uint32_t)block_mode | (c->force_exact_blocks ? 0x100u : 0u);
   if (block_mode == 2 && !c->block_table.p) {
     if ((rc = ensure(c, c->block_table, 1ull << BLOCK_TABLE_BITS))) return rc;
   }
@@ -2108,6 +2144,8 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
   }
   c->stats.index_kind = c->idx_kind == 1 ? (c->idx_wide ? 2u : 1u) : (c->idx_lines ? 3u : 0u);
   c->stats.match_variant = 0;  // (match_ctx_pass says which fused kernel it launches)
+  c->last_inst[0] = c->last_inst[1] = c->last_inst[2] = 0;  // (the resolvers of this pass fill them in)
+  c->last_inst[3] = (uint32_t)block_mode | (c->force_exact_blocks ? 0x100u : 0u);
   c->stats.index_bytes = c->idx_kind == 1
                              ? ((1ull << c->idx_bits) + 1) * sizeof(CtxBucket) + ctx_entries_bytes(c->idx_novf + 16, c->idx_wide)
                              : ((1ull << c->idx_bits) + 1) * (c->idx_lines ? sizeof(LineBucket) : sizeof(Bucket)) + (c->idx_novf + 16) * sizeof(uint4);
@@ -2686,6 +2724,40 @@ void musc_free_u32(uint32_t* p) { free(p); }
 int musc_get_stats(musc_ctx* c, musc_stats* out) {
   if (!c || !out) return 1;
   *out = c->stats;
+  return 0;
+}
+
+int musc_last_instance(const musc_ctx* c, uint32_t* out) {
+  if (!c || !out) return 1;
+  for (int i = 0; i < MUSC_INSTANCE_WORDS; i++) out[i] = c->last_inst[i];
+  return 0;
+}
+
+// Every descriptor the resolvers can return, read out of the resolvers themselves over every argument they take
+// (no GPU, no context): the tests compare their case lists with it, so an instance without a case is noticed.
+int musc_instances(uint32_t* out, uint32_t capacity, uint32_t* n) {
+  if (!n) return 1;
+  std::vector<uint32_t> ids;
+  auto add = [&](uint32_t id) {
+    if (id && std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
+  };
+  static const int strides[] = {4, 8, 12, 16, 20};  // (20: a stride without instances of its own, the runtime-stride ones)
+  for (int rw : strides) {
+    for (int kind : {MK_LANE, MK_DMA})
+      for (int sg = 0; sg <= MUSC_SPEC_GEOMS; sg++)
+        for (int wide = 0; wide < 2; wide++)
+          for (int W = 1; W <= CTX_MAX_W; W++)
+            for (int xm = 0; xm < 3; xm++) add(match_instance(kind, sg, rw, wide != 0, W, xm).id);
+    add(screen_t_instance(rw).id);
+    for (int mask = 0; mask < 2; mask++)
+      for (int W = 2; W <= 3; W++) {
+        for (int lines = 0; lines < 2; lines++) add(screen_instance(rw, mask != 0, W, lines != 0).id);
+        add(confirm_instance(rw, mask != 0, W).id);
+      }
+  }
+  *n = (uint32_t)ids.size();
+  if (out)
+    for (uint32_t i = 0; i < capacity && i < ids.size(); i++) out[i] = ids[i];
   return 0;
 }
 

@@ -1,8 +1,12 @@
 """Medium-scale fuzz of the GPU path against the literal C++ oracle (not collected by pytest):
 `python tests/fuzz_gpu_medium.py LO HI` draws one random configuration per seed -- 1-5 windows,
 WindowWidth 6-20 (direct and hashed index), PMatch 0.9-1, MinDinuc 0-6, MMTol 0-3, X rate 0 / 0.1 % /
-1 %, read length 40-150 -- over a few thousand reads and a few hundred targets, and compares all
-accepted tuples and the best+MMTol selection.  Round 1: seeds 0..85000, no mismatch (28 min on
+1 %, read length 40-200 (180 and 200: records of 16 words; half of the runs of 150 bases and more keep their windows
+within 200 bases of context, so that they stay on the fused path), MaxMatches 25 / 20 000 / 10^6 -- over a few thousand reads and a few hundred targets, and compares all
+accepted tuples (the oracle without truncation), the best+MMTol selection and the MaxMatches verdict (every probe of
+an overflowing oracle block named by overflow_probes(); a verdict without one is counted apart), and tallies
+Engine.last_instance() per run: the totals line lists the kernel instances that ran and those with no run
+(profiles/r06_fuzz_instance_totals.txt).  Round 1: seeds 0..85000, no mismatch (28 min on
 one MI355X); round 2 (both index kinds, as each configuration selects): seeds 0..56000 with k_match,
 0..80000 with k_match_d where a configuration has at most two windows, and 0..20000 with
 MUSC_FUZZ_READS_X=1 (X in the reads only): no mismatch; round 3 (k_match_t, wide and line buckets): seeds
@@ -25,6 +29,7 @@ import numpy as np
 from oracle import literal
 from oracle import muscato_oracle as orc
 from muscato_amd import Config, Engine, sorted_hits
+from muscato_amd.api import instance_name, instances
 from cases import hot_probes
 
 
@@ -42,20 +47,24 @@ SPEC = bool(os.environ.get("MUSC_FUZZ_SPEC"))
 SPEC_BLOCK = 100
 # MUSC_FUZZ_SECONDS=S: stop after the seed that ends past S seconds (the totals line names the seeds that ran)
 SECONDS = float(os.environ.get("MUSC_FUZZ_SECONDS", "0"))
-BLOCKS = {"overflow": 0, "extra verdict": 0}  # SPEC: configurations with an overflowing block / a verdict without one
-VARIANTS = {0: 0, 2: 0, 3: 0, 4: 0, 5: 0}  # musc_stats.match_variant: 0 two-kernel path, 2 / 3 k_match_t general / specialised, 4 / 5 k_match_g
+BLOCKS = {"overflow": 0, "extra verdict": 0}  # configurations with an overflowing block / a verdict without one
+INSTANCES = {}  # runs per kernel instance (Engine.last_instance(): a two-kernel pass counts for its screen and its confirm instance)
 
 
 def case(seed):
     rng = np.random.default_rng(seed)
-    L = int(rng.choice([40, 60, 100, 120, 150]))
+    L = int(rng.choice([40, 60, 100, 120, 150, 180, 200]))
     ww = int(rng.integers(6, 21))
     nwin = int(rng.integers(1, 6))
     wins = sorted(int(x) for x in rng.choice(np.arange(0, max(1, L - ww - 5)), size=nwin, replace=False))
     if rng.random() < 0.5:
         wins[0] = 0
+    if L >= 150 and rng.random() < 0.5:  # windows within 200 - L bases of each other: wide context buckets hold such a run
+        nwin = min(nwin, 201 - L)
+        w0 = int(rng.integers(0, L - ww - (200 - L)))
+        wins = sorted(int(x) for x in w0 + rng.choice(np.arange(0, 201 - L), size=nwin, replace=False))
     cfg = orc.Config(Windows=wins, WindowWidth=ww, PMatch=float(rng.choice([1.0, 0.97, 0.95, 0.92, 0.9])),
-                     MinDinuc=int(rng.integers(0, 7)), MaxReadLength=L, MaxMatches=1000000,
+                     MinDinuc=int(rng.integers(0, 7)), MaxReadLength=L, MaxMatches=int(rng.choice([25, 20000, 1000000])),
                      MMTol=int(rng.integers(0, 4)), MatchMode=str(rng.choice(["best", "first"])))
     nt, tlen, nr = int(rng.integers(50, 400)), int(rng.integers(L + 5, 800)), int(rng.integers(500, 6000))
     xrate = float(rng.choice([0.0, 0.001, 0.01]))
@@ -171,7 +180,7 @@ def main():
             c, reads, targets = case(seed)
         rbuf, roff = literal.concat(reads)
         gbuf, goff = literal.concat(targets)
-        oc = orc.Config(**dict(c.__dict__, MaxMatches=2 ** 31 - 1)) if SPEC else c  # (SPEC: every tuple, no truncation)
+        oc = orc.Config(**dict(c.__dict__, MaxMatches=2 ** 31 - 1))  # (every tuple, no truncation)
         exp, _, _ = literal.match_arrays(rbuf, roff, gbuf, goff, literal.make_params(oc, bloom_size=16_000_000, num_hash=6, nthreads=8))
         if targets is not loaded:  # (SPEC: one database, one table build, per block of seeds)
             e.load_targets(targets)
@@ -182,31 +191,34 @@ def main():
         got = sorted_hits(e.match(k, apply_mmtol=False))
         ok = got.shape == exp.shape and bool((got == exp).all())
         st = e.stats()
+        # n_overflow_blocks is an upper bound (hashed block counters): every probe of an overflowing block must be
+        # named; a verdict without an oracle overflow is counted apart
+        hot = hot_probes(reads, targets, c, exp)
+        probes = set(map(tuple, e.overflow_probes().tolist())) if st["n_overflow_blocks"] else set()
+        ok = ok and hot <= probes and (st["n_overflow_blocks"] >= 1 or not hot)
         if SPEC:
-            # n_overflow_blocks is an upper bound (hashed block counters): every probe of an overflowing block must be
-            # named; a verdict without an oracle overflow is counted apart
-            hot = hot_probes(reads, targets, c, exp)
-            probes = set(map(tuple, e.overflow_probes().tolist())) if st["n_overflow_blocks"] else set()
-            ok = ok and hot <= probes and st["match_variant"] == (5 if os.environ.get("MUSC_MATCH") == "dma" else 3)
-            BLOCKS["overflow"] += bool(hot)
-            BLOCKS["extra verdict"] += bool(probes) and not hot
+            ok = ok and st["match_variant"] == (5 if os.environ.get("MUSC_MATCH") == "dma" else 3)
+        BLOCKS["overflow"] += bool(hot)
+        BLOCKS["extra verdict"] += bool(probes) and not hot
         best = sorted_hits(e.match(k, apply_mmtol=True))
         eb = np.array(sorted(orc.best_filter([tuple(int(x) for x in r) for r in exp], c.MMTol)), dtype=np.uint32).reshape(-1, 4)
-        if SPEC:
-            ok = ok and best.shape == eb.shape and bool((best == eb).all())
-        else:
-            ok = ok and best.shape == eb.shape and bool((best == eb).all()) and e.stats()["n_overflow_blocks"] == 0
+        ok = ok and best.shape == eb.shape and bool((best == eb).all())
         KINDS[e.stats()["index_kind"]] += 1
-        VARIANTS[e.stats()["match_variant"]] = VARIANTS.get(e.stats()["match_variant"], 0) + 1
+        li = e.last_instance()
+        for d in (li["match"], li["screen"], li["confirm"]):
+            if d is not None:
+                INSTANCES[instance_name(d)] = INSTANCES.get(instance_name(d), 0) + 1
         if not ok:
             bad += 1
             print("MISMATCH seed", seed, c, len(reads), len(targets), len(got), len(exp), flush=True)
         if seed % 50 == 0:
             print("seed", seed, "hits", len(exp), "elapsed %.0fs" % (time.time() - t0), flush=True)
-    print("fuzz_medium", lo, hi, "bad", bad, "in %.0fs" % (time.time() - t0), "index kinds used", KINDS, "kernel variants", VARIANTS,
+    print("fuzz_medium", lo, hi, "bad", bad, "in %.0fs" % (time.time() - t0), "index kinds used", KINDS, "MaxMatches", BLOCKS,
           "(reads-only X)" if READS_X_ONLY else "(database X, mode %d)" % DB_X if DB_X else
-          "(SpecGeom<1> on a direct table%s; MaxMatches %s)" % (", MUSC_MATCH=dma" if os.environ.get("MUSC_MATCH") == "dma" else "", BLOCKS)
+          "(SpecGeom<1> on a direct table%s)" % (", MUSC_MATCH=dma" if os.environ.get("MUSC_MATCH") == "dma" else "")
           if SPEC else "")
+    print("instances run:", ", ".join("%s x %d" % kv for kv in sorted(INSTANCES.items())))
+    print("instances with no run:", ", ".join(sorted(set(map(instance_name, instances())) - set(INSTANCES))) or "none")
 
 
 if __name__ == "__main__":

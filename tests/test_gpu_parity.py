@@ -675,6 +675,14 @@ def test_index_selection(monkeypatch):
             eng.load_reads(reads)
             got = sorted_hits(eng.match(to_cfg(ocfg), apply_mmtol=False))
             assert eng.stats()["index_kind"] == kind, what
+            # the kernel the resolver handed out: k_match_t on context buckets (WIDE as the bucket width), k_screen ->
+            # k_confirm on the window-start buckets
+            li = eng.last_instance()
+            if kind:
+                assert li["path"] == "fused" and li["match"]["kernel"] == "k_match_t" and li["match"]["WIDE"] == kind - 1, (what, li)
+                assert li["match"]["W"] == len(wins) and li["match"]["XM"] == int(b"X" in alphabet) and li["match"]["SG"] == 0, (what, li)
+            else:
+                assert li["path"] == "two-kernel" and li["screen"]["kernel"] == "k_screen" and li["confirm"]["kernel"] == "k_confirm", (what, li)
             assert_same(got, as_arr(orc.match_direct(reads, targets, ocfg)))
         # a database with X keeps its context buckets (entries whose context touches an X are flagged and
         # compared through the mask plane); MUSC_NO_X_CONTEXT=1 sends it to the two-kernel path as before
