@@ -280,6 +280,16 @@ int musc_last_instance(const musc_ctx* ctx, uint32_t* out);
  * them in `out` (may be NULL with capacity 0). */
 int musc_instances(uint32_t* out, uint32_t capacity, uint32_t* n);
 
+/* The schedule of a streamed load (musc_reads_load_packed32 with async = 1) and of the pass that consumes it (needs no
+ * device): the upload is queued in *n pieces, piece i ending before read ends[i]; is_batch_end[i] != 0 where the pass
+ * launches a batch that ends with piece i.  Full batches of batch_reads (rounded up to 64) while two of them remain,
+ * then batches of half of what is left, down to a last batch of at most max(64, batch_reads / 16 rounded up to 64)
+ * reads; every end but the last is a multiple of 64.  *planned_batches: the batch count the MaxMatches screening
+ * threshold of that pass is divided by.  The first `capacity` entries are written (ends / is_batch_end may be NULL);
+ * 1 for fixed_len > 65535 or nreads >= 2^32 - 16.  batch_reads outside 1..2^24: the default, 2^24. */
+int musc_stream_plan(uint64_t nreads, uint32_t fixed_len, uint32_t batch_reads, uint64_t* ends, uint8_t* is_batch_end,
+                     uint64_t capacity, uint64_t* n, uint64_t* planned_batches);
+
 /* When the last musc_match* left n_overflow_blocks > 0: the (read, window) probes whose
  * (window, key) block may hold more than MaxMatches accepted pairs -- the blocks for which
  * cmd/muscato_confirm/main.go:233-242, 424-448 keep an order-dependent subset.  The library

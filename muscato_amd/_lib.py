@@ -59,7 +59,7 @@ SYMBOLS = [
     "musc_db_set_partition_bases", "musc_db_partitions",
     "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique",
     "musc_match_device", "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_free_hits",
-    "musc_get_stats", "musc_last_instance", "musc_instances", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
+    "musc_get_stats", "musc_last_instance", "musc_instances", "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
 ]
 
 _lib = None
@@ -120,6 +120,7 @@ def load() -> ctypes.CDLL:
     lib.musc_get_stats.argtypes = [vp, ctypes.POINTER(MuscStats)]
     lib.musc_last_instance.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
     lib.musc_instances.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    lib.musc_stream_plan.argtypes = [u64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.musc_overflow_probes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(u64)]
     lib.musc_overflow_probes.restype = ctypes.c_int
     lib.musc_free_u32.argtypes = [vp]
@@ -132,7 +133,7 @@ def load() -> ctypes.CDLL:
                  "musc_db_set_partition_bases", "musc_db_partitions",
                  "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique", "musc_match_device",
                  "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_get_stats", "musc_last_instance", "musc_instances",
-                 "musc_gather", "musc_gather_rccl", "musc_rccl_probe"):
+                 "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe"):
         getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

@@ -413,6 +413,22 @@ def instances() -> List[dict]:
     return [decode_instance(w) for w in buf[:n.value]]
 
 
+def stream_plan(nreads: int, fixed_len: int, batch_reads: int = 16 << 20) -> dict:
+    """The schedule of a streamed load of `nreads` reads of `fixed_len` bases (no GPU needed): {"piece_ends": read
+    index each piece of the upload ends before, "batch_ends": where the batches of the pass that consumes it end (a
+    subset of piece_ends), "planned_batches": the batch count the MaxMatches screening threshold is divided by}."""
+    lib = _lib.load()
+    n, planned = ctypes.c_uint64(), ctypes.c_uint64()
+    if lib.musc_stream_plan(nreads, fixed_len, batch_reads, None, None, 0, ctypes.byref(n), ctypes.byref(planned)):
+        raise ValueError("musc_stream_plan: %d reads of %d bases is not a read set the loader takes" % (nreads, fixed_len))
+    ends = np.zeros(max(1, n.value), dtype=np.uint64)
+    flags = np.zeros(max(1, n.value), dtype=np.uint8)
+    lib.musc_stream_plan(nreads, fixed_len, batch_reads, ends.ctypes.data, flags.ctypes.data, n.value, ctypes.byref(n),
+                         ctypes.byref(planned))
+    ends, flags = ends[:n.value], flags[:n.value]
+    return {"piece_ends": ends, "batch_ends": ends[flags != 0], "planned_batches": int(planned.value)}
+
+
 def gather(engines: Sequence["Engine"], read_bases: Sequence[int], rccl: bool = False) -> np.ndarray:
     """Concatenate the device-resident hits of several engines of ONE process in order, adding
     read_bases[i] to the read_idx of engine i (musc_gather: every GPU copies its own to the host;

@@ -454,3 +454,24 @@ MUSC_KERNEL __launch_bounds__(256) void k_pack_compact(const uint4* __restrict__
     }
   }
 }
+
+// The same for tuples [t0, t1) of the list (a download to the host packs and copies chunk by chunk): a tuple's
+// neighbours are taken from the whole list, so a run that crosses the edge of a chunk is counted once and in full, by
+// the launch that holds its head.  words[t0, t1) are final when the launch ends, counts when every chunk has run.
+MUSC_KERNEL __launch_bounds__(256) void k_pack_compact_range(const uint4* __restrict__ hits, uint64_t n, uint64_t t0, uint64_t t1,
+                                                            PackBits b, uint32_t* __restrict__ words, uint8_t* __restrict__ counts,
+                                                            uint32_t* __restrict__ bad) {
+  for (uint64_t i = t0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t1; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint4 h = hits[i];
+    if (((uint64_t)h.y >> b.gene) || ((uint64_t)h.z >> b.pos) || ((uint64_t)h.w >> b.nmiss)) atomicOr(bad, 1u);
+    words[i] = (((h.y << b.pos) | h.z) << b.nmiss) | h.w;
+    const uint32_t prev = i ? hits[i - 1].x : 0xFFFFFFFFu;
+    if (i && prev > h.x) atomicOr(bad, 4u);
+    if (i == 0 || prev != h.x) {
+      uint32_t cnt = 1;
+      while (i + cnt < n && cnt < 256 && hits[i + cnt].x == h.x) cnt++;
+      if (cnt > 255) atomicOr(bad, 2u);
+      counts[h.x] = (uint8_t)cnt;
+    }
+  }
+}

@@ -154,6 +154,40 @@ struct TmpBufs {
 
 }  // namespace
 
+// The read ranges of a streamed load (musc_reads_load_packed32 with async = 1) and of the pass that consumes it: the
+// pieces the upload is queued in, and the batches the pass launches, every batch a whole number of pieces.  The upload
+// is several times slower per read than the match, so the GPU idles through most of a streamed pass and what shows in
+// its wall time is the work left after the last byte has landed: the pack and the match of the LAST batch.  Hence full
+// batches (batch_reads, rounded up to whole wave-tiles) while at least two of them remain, then batches that take half
+// of what is left each, down to a last batch of at most batch_reads / 16.  No batch holds more than twice the reads of
+// the batch after it (give or take the rounding to 64), so the match of one batch ends well before the upload of the
+// next one does, whatever the two rates are as long as the match is the faster one per read.  Every end but the last is
+// a multiple of 64 reads: whole wave-tiles, and whole bytes of the 2-bit stream for any read length.
+struct StreamPlan {
+  std::vector<uint64_t> piece_end, batch_end;  // ascending; the last of each is the read count
+};
+static void stream_plan(uint64_t nreads, uint64_t batch_reads, StreamPlan* sp) {
+  auto up64 = [](uint64_t x) { return (x + 63) & ~63ull; };
+  sp->piece_end.clear();
+  sp->batch_end.clear();
+  const uint64_t full = std::max<uint64_t>(up64(batch_reads), 64);
+  const uint64_t last_max = std::max<uint64_t>(up64(batch_reads / 16), 64);
+  const uint64_t piece = up64(std::max<uint64_t>(batch_reads / 4, 64));  // a quarter of a full batch
+  for (uint64_t r0 = 0; r0 < nreads;) {
+    const uint64_t left = nreads - r0;
+    const uint64_t n = left >= 2 * full ? full : left <= last_max ? left : up64((left + 1) / 2);
+    for (uint64_t p = r0 + piece; p < r0 + n; p += piece) sp->piece_end.push_back(p);
+    r0 += n;
+    sp->piece_end.push_back(r0);
+    sp->batch_end.push_back(r0);
+  }
+}
+// reads of the batch that starts at r0 on that schedule
+static uint64_t stream_plan_batch(const StreamPlan& sp, uint64_t r0) {
+  const auto it = std::upper_bound(sp.batch_end.begin(), sp.batch_end.end(), r0);
+  return it == sp.batch_end.end() ? 0 : *it - r0;
+}
+
 // The MUSC_* environment knobs (tests, A/B runs, experiments), read ONCE per context at musc_init -- a pass
 // never calls getenv -- and again only on musc_reload_env (tests that flip a knob on a live context).
 struct EnvKnobs {
@@ -275,6 +309,7 @@ struct musc_ctx {
 
   // reads
   uint32_t* rd = nullptr;
+  uint64_t rd_cap = 0;      // bytes of rd when a fixed-length load made it (kept from load to load), 0: sized for the reads in hand
   uint32_t* rdm = nullptr;  // null when no read holds an X
   uint64_t nreads = 0;
   int rw = 0;
@@ -282,13 +317,15 @@ struct musc_ctx {
 
   // musc_reads_load_packed32(async): reads of one length on their way from the host -- the 2-bit
   // stream goes to `stage` in pieces on the copy stream s_up, an event per piece; a pass packs the
-  // records of a batch (k_pack_reads_fixed) when the batch's pieces have arrived
+  // records of a batch (k_pack_reads_fixed) when the batch's pieces have arrived.  stream_plan decides
+  // the pieces and the batches of the pass that consumes them.
   struct Upload {
     uint32_t* stage = nullptr;
     uint64_t stage_words = 0;
     hipStream_t s_up = nullptr;
     std::vector<hipEvent_t> ev;
-    uint64_t piece = 0, n_pieces = 0;  // reads per piece, pieces of this upload
+    StreamPlan plan;                   // piece ends and batch ends of this upload, in reads
+    uint64_t next_piece = 0;           // the first piece whose records are still missing
     uint64_t packed_upto = 0;          // reads whose records exist
     uint32_t L = 0;
     bool active = false;               // records are still missing
@@ -327,6 +364,7 @@ struct musc_ctx {
   DevBuf<musc_hit> hits;
   uint64_t nhits = 0;
   DevBuf<uint64_t> packed;      // staging of musc_hits_copy_packed / musc_hits_unpack for host pointers
+  std::vector<hipEvent_t> dl_ev;  // download_chunks: one event per chunk
   DevBuf<musc_hit> gathered;    // musc_gather_rccl: every context's tuples on this device
   uint32_t* d_flag = nullptr;   // one device word for kernels that report "does not fit"
 
@@ -487,19 +525,27 @@ void free_db(musc_ctx* c) {
   c->data_epoch++;
 }
 
-void free_reads(musc_ctx* c) {
+// Forget the reads in hand.  keep_rd: the record buffer stays allocated for the fixed-length load that follows
+// (reads_load_fixed: a hipFree waits for the device, and freeing and allocating 1.4 GB again before every load kept
+// the link idle at the start of each streamed step)
+void drop_reads(musc_ctx* c, bool keep_rd) {
   if (c->up.active) {  // an upload nobody matched: the caller's buffer is borrowed until it ends
     (void)hipStreamSynchronize(c->up.s_up);
     c->up.active = false;
   }
-  if (c->rd) (void)hipFree(c->rd);
+  if (c->rd && !(keep_rd && c->rd_cap)) {
+    (void)hipFree(c->rd);
+    c->rd = nullptr;
+    c->rd_cap = 0;
+  }
   if (c->rdm) (void)hipFree(c->rdm);
-  c->rd = c->rdm = nullptr;
+  c->rdm = nullptr;
   c->reads_have_x = false;
   c->nreads = 0;
   c->rw = 0;
   c->data_epoch++;
 }
+void free_reads(musc_ctx* c) { drop_reads(c, false); }
 
 struct EvPair {
   hipEvent_t a, b;
@@ -773,6 +819,7 @@ void musc_destroy(musc_ctx* c) {
   for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
   if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
   for (hipEvent_t ev : c->up.ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : c->dl_ev) (void)hipEventDestroy(ev);
   if (c->up.stage) (void)hipFree(c->up.stage);
   if (c->up.s_up) (void)hipStreamDestroy(c->up.s_up);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -1492,13 +1539,14 @@ static int upload_prepare(musc_ctx* c, uint64_t r0, uint64_t n, hipStream_t st) 
   musc_ctx::Upload& u = c->up;
   if (!u.active) return 0;
   const uint64_t want = std::min<uint64_t>(r0 + n, c->nreads);
-  while (u.packed_upto < want) {
-    const uint64_t i = u.packed_upto / u.piece;
-    const uint64_t first = i * u.piece, cnt = std::min<uint64_t>(u.piece, c->nreads - first);
+  while (u.packed_upto < want && u.next_piece < u.plan.piece_end.size()) {
+    const uint64_t i = u.next_piece;
+    const uint64_t first = u.packed_upto, cnt = u.plan.piece_end[i] - first;
     HIPCHK(c, hipStreamWaitEvent(st, u.ev[i], 0));
     hipLaunchKernelGGL(k_pack_reads_fixed, dim3(nblk(cnt * (uint64_t)c->rw, 256)), dim3(256), 0, st, u.stage, first, cnt, u.L, c->rw, c->rd);
     HIPCHK(c, hipGetLastError());
     u.packed_upto = first + cnt;
+    u.next_piece = i + 1;
   }
   if (u.packed_upto >= c->nreads) u.active = false;
   return 0;
@@ -1591,23 +1639,29 @@ static int reads_load(musc_ctx* c, const unsigned char* ascii, const uint8_t* ba
 // them (upload_prepare), so that upload and matching overlap.
 static int reads_load_fixed(musc_ctx* c, const uint8_t* bases2bit, uint32_t L, uint64_t nreads, int async) {
   HIPCHK(c, hipSetDevice(c->device));
-  free_reads(c);
-  if (nreads >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read_idx");
-  if (L > 65535) return fail(c, 2, "read of %u bases exceeds the 65535-base record limit", L);
+  // The reads in hand go, the record buffer stays: a streamed step is bound by the link, so the first bytes are queued
+  // before anything else that takes time, and in the steady state (a read set that fits the buffers of the last one)
+  // this call neither frees nor allocates.
+  drop_reads(c, true);
+  int rw = (int)((2ull * L + 31) / 32) + 1;
+  rw = (rw + 3) & ~3;
+  if (rw < 4) rw = 4;
+  const uint64_t words = nreads * (uint64_t)rw;
+  const char* refuse = nreads >= 0xFFFFFFF0ull ? "too many reads for 32-bit read_idx"
+                       : L > 65535             ? "read length exceeds the 65535-base record limit"
+                       : words >= (1ull << 32) ? "too many read words for one dispatch (reads x record words >= 2^32)"
+                                               : nullptr;
+  if (refuse) {
+    free_reads(c);
+    return fail(c, 2, "%s", refuse);
+  }
   c->nreads = nreads;
   if (nreads == 0) {
     c->rw = 4;
     return 0;
   }
   c->max_len = L;
-  int rw = (int)((2ull * L + 31) / 32) + 1;
-  rw = (rw + 3) & ~3;
-  if (rw < 4) rw = 4;
   c->rw = rw;
-  const uint64_t words = nreads * (uint64_t)rw;
-  if (words >= (1ull << 32)) return fail(c, 2, "too many read words for one dispatch (reads x record words >= 2^32)");
-  HIPCHK(c, hipMalloc((void**)&c->rd, words * 4 + 256));
-  HIPCHK(c, hipMemsetAsync(c->rd + words, 0, 256, c->stream));
   c->reads_have_x = false;
   musc_ctx::Upload& u = c->up;
   const uint64_t total_bytes = (nreads * (uint64_t)L + 3) / 4;
@@ -1620,28 +1674,37 @@ static int reads_load_fixed(musc_ctx* c, const uint8_t* bases2bit, uint32_t L, u
     u.stage_words = need_words;
   }
   if (!u.s_up) HIPCHK(c, hipStreamCreateWithFlags(&u.s_up, hipStreamNonBlocking));
-  // pieces of whole bytes of the stream (4 | piece) and whole wave-tiles (64 | piece), a quarter of a
-  // pass's batch each: the first batch can start when a quarter of it has arrived... no: a batch
-  // needs all its pieces, but the NEXT batch's pieces arrive while this one is matched
-  uint64_t piece = std::max<uint64_t>(c->batch_reads / 4, 64);
-  piece = (piece + 63) & ~63ull;
-  u.piece = piece;
-  u.n_pieces = (nreads + piece - 1) / piece;
+  // the pieces: whole bytes of the stream and whole wave-tiles (64 | every end but the last), each batch of the pass
+  // that consumes them a whole number of pieces -- a batch needs all of its pieces, and the next batch's pieces arrive
+  // while it is matched
+  stream_plan(nreads, c->batch_reads, &u.plan);
+  const std::vector<uint64_t>& ends = u.plan.piece_end;
   u.L = L;
   u.packed_upto = 0;
-  while (u.ev.size() < u.n_pieces) {
+  u.next_piece = 0;
+  while (u.ev.size() < ends.size()) {
     hipEvent_t e = nullptr;
     HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     u.ev.push_back(e);
   }
   HIPCHK(c, hipMemsetAsync(u.stage + (need_words - 4), 0, 16, u.s_up));
-  for (uint64_t i = 0; i < u.n_pieces; i++) {
-    const uint64_t b0 = i * piece * (uint64_t)L / 4;  // (64 | piece: a whole number of bytes)
-    const uint64_t b1 = std::min<uint64_t>(((i + 1) * piece * (uint64_t)L + 3) / 4, total_bytes);
+  for (size_t i = 0; i < ends.size(); i++) {
+    const uint64_t b0 = (i ? ends[i - 1] : 0) * (uint64_t)L / 4;  // (64 | end: a whole number of bytes)
+    const uint64_t b1 = std::min<uint64_t>((ends[i] * (uint64_t)L + 3) / 4, total_bytes);
     HIPCHK(c, hipMemcpyAsync(reinterpret_cast<uint8_t*>(u.stage) + b0, bases2bit + b0, b1 - b0, hipMemcpyHostToDevice, u.s_up));
     HIPCHK(c, hipEventRecord(u.ev[i], u.s_up));
   }
   u.active = true;
+  // the records (nothing reads them before the first piece has landed): the buffer of the last fixed-length load where
+  // it is large enough, its zeroed 256-byte tail at its new place
+  if (c->rd_cap < words * 4 + 256) {
+    if (c->rd) (void)hipFree(c->rd);
+    c->rd = nullptr;
+    c->rd_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&c->rd, words * 4 + 256));
+    c->rd_cap = words * 4 + 256;
+  }
+  HIPCHK(c, hipMemsetAsync(c->rd + words, 0, 256, c->stream));
   if (!async) {
     int rc = upload_prepare(c, 0, nreads, c->stream);
     if (rc) return rc;
@@ -1850,6 +1913,11 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
   const bool sized = c->sized_epoch == c->data_epoch && c->sized_exact_blocks == (block_mode == 2) &&
                      memcmp(&c->sized_params, P, sizeof *P) == 0 && !c->env.debug_sync;
   uint32_t bsz = sized ? c->sized_bsz : c->batch_reads;
+  // A pass that starts with an upload in flight takes its batches from the upload's schedule (stream_plan: whole pieces,
+  // tapered towards the end), every attempt of it.  Such a pass sizes itself (the reads are new) and leaves the context
+  // UNSIZED: a later pass over the same reads finds them resident, sizes itself on uniform batches and is the one later
+  // passes replay -- the tapered schedule is never replayed against resident reads, where small batches only cost.
+  bool streamed = c->up.active && !sized;
   const uint64_t L = c->max_len;
   // A sized pass can be replayed as a hipGraph (MUSC_GRAPH=1): its launches, the counter memsets
   // and the final readback are captured once per (reads, database, parameters) and then cost one
@@ -1897,7 +1965,7 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
       if (block_mode == 2) HIPCHK(c, hipMemsetAsync(c->block_table.p, 0, (1ull << BLOCK_TABLE_BITS) * 4, c->stream));
     }
     while (!replay && r0 < c->nreads) {
-      const uint32_t n = (uint32_t)std::min<uint64_t>(bsz, c->nreads - r0);
+      const uint32_t n = (uint32_t)(streamed ? stream_plan_batch(c->up.plan, r0) : std::min<uint64_t>(bsz, c->nreads - r0));
       const uint32_t ntiles = nblk(n, WT);  // wave-tiles of 64 reads
       const uint64_t sgrid = std::min<uint64_t>(nblk(n, TILE), resident);
       const uint64_t swaves = sgrid * (TILE / 64);  // regions of stage and spill are per wave
@@ -1928,6 +1996,7 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
         if (need_stage > (1ull << 31)) {  // u32 tuple offsets within a batch: retry with half the reads
           if (n == 1) return fail(c, 6, "one read has %llu tuples (> 2^31)", (unsigned long long)c->h_pinned[8 + 7]);
           bsz = n / 2;
+          streamed = false;  // (uniform batches of the halved size from here on)
           again = true;
           break;
         }
@@ -2037,7 +2106,7 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
     c->stats.match_bytes = c->nreads * rec_b + n_windows * sizeof(CtxBucket) + n_ovf * ent_b + 16 * c->stats.n_hits;
     c->stats.match_bytes_strict = c->nreads * rec_b + n_windows * 8 + n_cand * ent_b + 16 * c->stats.n_hits;
     if (nhits) *nhits = c->nhits;
-    c->sized_epoch = c->data_epoch;
+    c->sized_epoch = streamed ? 0 : c->data_epoch;  // (see `streamed` above)
     c->sized_params = *P;
     c->sized_exact_blocks = block_mode == 2;
     c->sized_bsz = bsz;
@@ -2123,7 +2192,9 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
 
   HIPCHK(c, hipMemsetAsync(c->counters, 0, 8 * sizeof(unsigned long long), c->stream));
   // MaxMatches accounting (see k_confirm): screening first, exact only if inconclusive
-  const uint64_t planned_batches = (c->nreads + c->batch_reads - 1) / c->batch_reads + 1;
+  // (a pass that starts with an upload in flight runs on the upload's schedule, stream_plan: its batch count)
+  const uint64_t planned_batches = c->up.active ? std::max<uint64_t>(c->up.plan.batch_end.size(), 1)
+                                                : (c->nreads + c->batch_reads - 1) / c->batch_reads + 1;
   uint64_t max_matches = P->max_matches > 0 ? (uint64_t)P->max_matches : 0x7FFFFFFFull;
   if (P->n_shards > 1) max_matches /= (uint64_t)P->n_shards;  // this context sees one shard of each block
   const uint32_t block_thr = (uint32_t)std::min<uint64_t>(max_matches / (planned_batches * MAX_GRID), 0x7FFFFFFFull);
@@ -2182,6 +2253,7 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
   const uint64_t PAIR_CAP = 1ull << 31;  // u32 descriptor offsets
   uint64_t r0 = 0;
   uint32_t bsz = sized ? c->sized_bsz : c->batch_reads;
+  bool streamed = c->up.active && !sized;  // batches from the upload's schedule, and no sized state left behind: as in match_ctx_pass
   if (sized) HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8 * sizeof(unsigned long long), c->stream));
   // MUSC_PIPELINE=1: a sized pass of several batches is pipelined over two streams, k_screen of
   // batch b+1 beside k_confirm + k_compact of batch b, alternating between the two batch sets.
@@ -2199,7 +2271,7 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
   }
   uint32_t batch_no = 0;
   while (r0 < c->nreads) {
-    const uint32_t n = (uint32_t)std::min<uint64_t>(bsz, c->nreads - r0);
+    const uint32_t n = (uint32_t)(streamed ? stream_plan_batch(c->up.plan, r0) : std::min<uint64_t>(bsz, c->nreads - r0));
     if (piped) {
       c->cur = (int)(batch_no & 1u);
       // the set is free once the batch before last has been compacted
@@ -2245,6 +2317,7 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
         // too many pairs for one launch: retry this range with half the reads
         if (n == 1) return fail(c, 6, "one read has %llu candidate pairs (> 2^31)", (unsigned long long)total);
         bsz = n / 2;
+        streamed = false;  // (uniform batches of the halved size from here on)
         HIPCHK(c, hipMemsetAsync(c->counters + 3, 0, 8, c->stream));
         continue;
       }
@@ -2361,7 +2434,7 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
         (rc = ensure(c, c->bs[1].cdesc, c->bs[0].cdesc.cap)))
       return rc;
   }
-  c->sized_epoch = c->data_epoch;
+  c->sized_epoch = streamed ? 0 : c->data_epoch;
   c->sized_params = *P;
   c->sized_exact_blocks = block_mode == 2;
   c->sized_bsz = bsz;
@@ -2530,6 +2603,57 @@ int musc_hits_copy(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_dev
   return 0;
 }
 
+// Tuples that are packed on the device on their way to the host (musc_hits_copy_compact, musc_hits_copy_packed): the
+// pack kernel runs at memory speed, the copy at link speed, so packing everything first keeps the link idle for the
+// whole kernel.  Instead the list goes in chunks: `pack(t0, t1)` launches the kernel for tuples [t0, t1) on the
+// context's stream, and the copy of those `elem`-byte words follows on the copy stream behind an event while the next
+// chunk is packed.  The first chunk is 1/32 of the list (what the link waits for), each later one four times the one
+// before: the pack of a chunk is over long before the copy of the previous one.  Queues only; download_end waits.
+extern "C++" {
+template <class Pack>
+static int download_chunks(musc_ctx* c, uint64_t n, size_t elem, const void* src, void* dst, Pack pack) {
+  if (!c->up.s_up) HIPCHK(c, hipStreamCreateWithFlags(&c->up.s_up, hipStreamNonBlocking));
+  const uint64_t smallest = std::min<uint64_t>(c->batch_reads, 1u << 18);  // (MUSC_BATCH_READS: several chunks of a test-sized list)
+  uint64_t sz = std::max<uint64_t>(n / 32, smallest);
+  size_t k = 0;
+  for (uint64_t t0 = 0; t0 < n; k++, sz *= 4) {
+    const uint64_t t1 = n - t0 <= sz + sz / 2 ? n : t0 + sz;
+    if (k == c->dl_ev.size()) {
+      hipEvent_t e = nullptr;
+      HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      c->dl_ev.push_back(e);
+    }
+    pack(t0, t1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->dl_ev[k], c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->up.s_up, c->dl_ev[k], 0));
+    HIPCHK(c, hipMemcpyAsync((char*)dst + t0 * elem, (const char*)src + t0 * elem, (t1 - t0) * elem, hipMemcpyDeviceToHost, c->up.s_up));
+    t0 = t1;
+  }
+  return 0;
+}
+}  // extern "C++"
+
+// The end of such a download: the kernels' verdict word to *h_bad (pinned), `tail_bytes` more bytes that are complete
+// only after the last chunk's kernel (the count bytes) behind the chunks on the copy stream, then both streams are
+// waited for -- on every path, so that nothing is still being written to the caller's buffers when the call returns.
+static int download_end(musc_ctx* c, uint32_t* h_bad, void* tail_dst, const void* tail_src, uint64_t tail_bytes) {
+  hipError_t e = hipMemcpyAsync(h_bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && tail_bytes) {
+    hipStream_t st = c->up.s_up ? c->up.s_up : c->stream;
+    if (st != c->stream && (e = hipEventRecord(c->ev_join, c->stream)) == hipSuccess) e = hipStreamWaitEvent(st, c->ev_join, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(tail_dst, tail_src, tail_bytes, hipMemcpyDeviceToHost, st);
+  }
+  const hipError_t e1 = hipStreamSynchronize(c->stream);
+  const hipError_t e2 = c->up.s_up ? hipStreamSynchronize(c->up.s_up) : hipSuccess;
+  if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e2;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, 10, "copying the tuples to the host failed: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+
 static int check_pack_bits(musc_ctx* c, const int32_t* bits, PackBits* b) {
   if (!bits) return fail(c, 2, "bits is NULL");
   int sum = 0;
@@ -2559,14 +2683,23 @@ int musc_hits_copy_packed(musc_ctx* c, uint64_t* dst, uint64_t capacity, int dst
     out = c->packed.p;
   }
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
-  hipLaunchKernelGGL(k_pack_hits, dim3(std::min(nblk(c->nhits, 256), MAX_GRID)), dim3(256), 0, c->stream,
-                     reinterpret_cast<const uint4*>(c->hits.p), c->nhits, read_base, b, out, c->d_flag);
-  HIPCHK(c, hipGetLastError());
-  uint32_t bad = 0;
-  HIPCHK(c, hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  if (!dst_on_device)
-    HIPCHK(c, hipMemcpyAsync(dst, out, c->nhits * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint4* const hits = reinterpret_cast<const uint4*>(c->hits.p);
+  auto pack = [&](uint64_t t0, uint64_t t1) {
+    hipLaunchKernelGGL(k_pack_hits, dim3(std::min(nblk(t1 - t0, 256), MAX_GRID)), dim3(256), 0, c->stream, hits + t0, t1 - t0,
+                       read_base, b, out + t0, c->d_flag);
+  };
+  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned);
+  if (dst_on_device) {
+    pack(0, c->nhits);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  } else {
+    rc = download_chunks(c, c->nhits, 8, out, dst, pack);
+    const int rc_end = download_end(c, h_bad, nullptr, nullptr, 0);
+    if (rc || rc_end) return rc ? rc : rc_end;
+  }
+  const uint32_t bad = *h_bad;
   if (bad) return fail(c, 8, "musc_hits_copy_packed: a tuple field does not fit its width (%d/%d/%d/%d bits)",
                        b.read, b.gene, b.pos, b.nmiss);
   return 0;
@@ -2599,18 +2732,27 @@ int musc_hits_copy_compact(musc_ctx* c, uint32_t* words, uint64_t words_cap, uin
   }
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
   if (c->nreads) HIPCHK(c, hipMemsetAsync(dc, 0, c->nreads, c->stream));
-  if (c->nhits) {
-    hipLaunchKernelGGL(k_pack_compact, dim3(std::min(nblk(c->nhits, 256), MAX_GRID)), dim3(256), 0, c->stream,
-                       reinterpret_cast<const uint4*>(c->hits.p), c->nhits, b, dw, dc, c->d_flag);
-    HIPCHK(c, hipGetLastError());
+  const uint4* const hits = reinterpret_cast<const uint4*>(c->hits.p);
+  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned);
+  if (dst_on_device) {
+    if (c->nhits) {
+      hipLaunchKernelGGL(k_pack_compact, dim3(std::min(nblk(c->nhits, 256), MAX_GRID)), dim3(256), 0, c->stream, hits, c->nhits,
+                         b, dw, dc, c->d_flag);
+      HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(h_bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  } else {
+    // the words chunk by chunk, then the count bytes: a count is final only when the chunk that holds the head of its
+    // read's run has been packed, and the counts are the smaller copy
+    int rc = download_chunks(c, c->nhits, 4, dw, words, [&](uint64_t t0, uint64_t t1) {
+      hipLaunchKernelGGL(k_pack_compact_range, dim3(std::min(nblk(t1 - t0, 256), MAX_GRID)), dim3(256), 0, c->stream, hits,
+                         c->nhits, t0, t1, b, dw, dc, c->d_flag);
+    });
+    const int rc_end = download_end(c, h_bad, counts, dc, c->nreads);
+    if (rc || rc_end) return rc ? rc : rc_end;
   }
-  uint32_t bad = 0;
-  HIPCHK(c, hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  if (!dst_on_device) {
-    if (c->nhits) HIPCHK(c, hipMemcpyAsync(words, dw, c->nhits * 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->nreads) HIPCHK(c, hipMemcpyAsync(counts, dc, c->nreads, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint32_t bad = *h_bad;
   if (bad & 4u) return fail(c, 12, "internal: the hit list is not read-major");
   if (bad) return fail(c, 8, "musc_hits_copy_compact: %s", (bad & 1u) ? "a tuple field does not fit its width"
                                                                       : "a read has more than 255 tuples");
@@ -2758,6 +2900,25 @@ int musc_instances(uint32_t* out, uint32_t capacity, uint32_t* n) {
   *n = (uint32_t)ids.size();
   if (out)
     for (uint32_t i = 0; i < capacity && i < ids.size(); i++) out[i] = ids[i];
+  return 0;
+}
+
+// stream_plan as the loader and the passes use it (no GPU, no context): the tests check its rules over read counts
+// no test could upload.
+int musc_stream_plan(uint64_t nreads, uint32_t fixed_len, uint32_t batch_reads, uint64_t* ends, uint8_t* is_batch_end,
+                     uint64_t capacity, uint64_t* n, uint64_t* planned_batches) {
+  if (!n || fixed_len > 65535 || nreads >= 0xFFFFFFF0ull) return 1;  // (no read index / record for these)
+  if (batch_reads < 1 || batch_reads > (16u << 20)) batch_reads = 16u << 20;  // (as musc_init reads MUSC_BATCH_READS)
+  StreamPlan sp;
+  stream_plan(nreads, batch_reads, &sp);
+  *n = sp.piece_end.size();
+  if (planned_batches) *planned_batches = std::max<uint64_t>(sp.batch_end.size(), 1);
+  size_t b = 0;
+  for (size_t i = 0; i < sp.piece_end.size() && i < capacity; i++) {
+    if (ends) ends[i] = sp.piece_end[i];
+    while (b < sp.batch_end.size() && sp.batch_end[b] < sp.piece_end[i]) b++;
+    if (is_batch_end) is_batch_end[i] = b < sp.batch_end.size() && sp.batch_end[b] == sp.piece_end[i];
+  }
   return 0;
 }
 
