@@ -79,25 +79,54 @@ typedef struct {
   int32_t reserved[2];
 } musc_params;
 
-/* Counters and device timings of the last musc_match* call on a context. */
+/* Counters and device timings of the last musc_match* call on a context.
+ *
+ * What each counter counts, per path (tests/stats_model.py recounts every one of them on the CPU from the oracle's
+ * window gate, k-mer index and fit rule; tests/test_gpu_stats.py holds each path to it).  "Fused" = context buckets
+ * (index_kind 1 and 2: k_match_t, k_match_g), "two-kernel" = k_screen / k_screen_t -> k_confirm (index_kind 0 and 3).
+ * Every counter is that of ONE pass over the reads: a batch that is repeated after its buffers grew, a pass that starts
+ * over on smaller batches, and the exact repeat of a pass whose MaxMatches screening was inconclusive are counted
+ * once, and a sized pass, a hipGraph replay and a streamed pass report what the first, careful pass reports.
+ *   a PROBE     a (read, window) pair with len >= Windows[k] + WindowWidth and CountDinuc(window) >= MinDinuc.  Fused: less
+ *               the read windows that hold an X (they never probe; a read with more X than its xpos word lists -- four,
+ *               wide buckets three -- has no probe at all).  Two-kernel: a window with an X does probe.
+ *   a CANDIDATE an index entry of the bucket a probe fetches.  On a direct table (bucket = key) these are the window
+ *               starts of the database with the probe's key -- a window that would cross its target's end is never
+ *               indexed, and context buckets do not index a window that holds an X; on a hashed table also the entries
+ *               of the keys that share the bucket.
+ *   FITS        p = jx - Windows[k] >= 0 and p + len <= target length, or, at jx == 0, len <= min(100 - WindowWidth, target
+ *               length) (cmd/muscato_screen/main.go:294-316, :347-353, cmd/muscato_confirm/main.go:201-203).
+ * With several partitions every counter but n_reads, n_hits and n_overflow_blocks is the SUM over the partitions'
+ * passes: each pass probes every read window again (n_read_windows = probes x partitions), finds the candidates of its
+ * own index, and writes its own tuples (with apply_mmtol the best + MMTol among that partition's targets: the bytes bill
+ * those, which may be more than n_hits). */
 typedef struct {
-  uint64_t n_reads;         /* unique reads processed                                  */
-  uint64_t n_read_windows;  /* (read, window) seeds that passed the length+entropy gate */
-  uint64_t n_candidates;    /* index entries probed (k-mer hits incl. chance hits)      */
-  uint64_t n_pairs;         /* (window, read, placement) candidate pairs that reached the
-                             * confirm kernel -- the reference's smatch/win join output,
-                             * minus what the flank filter already ruled out               */
-  uint64_t n_accepted;      /* pairs with nmiss <= budget, after the union over windows */
-  uint64_t n_hits;          /* tuples returned                                          */
+  uint64_t n_reads;         /* unique reads loaded (several partitions: once)                                   */
+  uint64_t n_read_windows;  /* probes                                                                           */
+  uint64_t n_candidates;    /* candidates: the sum over the probes of their bucket's entry count                */
+  uint64_t n_pairs;         /* fused: the candidates that fit -- every one of them is compared with the read.
+                             * two-kernel: the candidates that fit AND pass the flank filter (the min(Windows[k], 8) read
+                             * bases left of the window and the min(len - Windows[k] - WindowWidth, 8) right of it differ from
+                             * the target's in at most the read's mismatch budget), per (read, window, placement) -- the
+                             * reference's smatch/win join output minus what the flank filter rules out: what reaches
+                             * k_confirm, a two-window descriptor counting twice.  The screen never compares the key
+                             * itself, so on a hashed table an entry of a colliding key that fits and passes the flank
+                             * filter is a pair too (k_confirm rejects it)                                  */
+  uint64_t n_accepted;      /* distinct (read, target, position) with nmiss <= budget: the union over the windows, before
+                             * the best + MMTol selection, whatever apply_mmtol is                      */
+  uint64_t n_hits;          /* tuples returned (apply_mmtol = 0: n_accepted)                             */
   /* (window,key) blocks whose accepted pairs may exceed MaxMatches: 0 = proven none (the
    * reference's truncation, cmd/muscato_confirm/main.go:233-242, 424-448, never triggered and
    * the tuples are exact); > 0 = upper bound; ~0 = check skipped */
   uint64_t n_overflow_blocks;
-  uint64_t confirm_bytes;   /* algorithmic bytes of the confirm launches: 63 B per DESCRIPTOR
-                             * loaded at 100 bp (descriptor 12 + record 25 + target span 26,
-                             * SURVEY.md 8d) + 16 B per tuple written                       */
-  uint32_t confirm_launches;
-  uint32_t n_batches;
+  uint64_t confirm_bytes;   /* two-kernel: algorithmic bytes of the confirm launches: n_descriptors x (12 B descriptor +
+                             * ceil(2L/8) B record + ceil(2L/8) + 1 B target span; 63 B at L = 100) + 16 B per
+                             * tuple written, L = the longest loaded read.  Fused: 0                         */
+  uint32_t confirm_launches; /* two-kernel: k_confirm launches, <= n_batches and equal when every batch has a descriptor
+                             * (a careful pass skips the launch for a batch without one).  Fused: 0              */
+  uint32_t n_batches;       /* batches of the pass: ceil(n_reads / batch) uniform ones, or those of musc_stream_plan
+                             * when the pass consumes a streamed load (the exact repeat of such a pass finds the
+                             * reads resident and runs, and reports, uniform batches)                          */
   float ms_screen;          /* HIP-event time of each kernel family, summed over batches:  */
   float ms_scan;            /*   k_screen (index_kind 0) or k_match (1) | scan | (see match_variant) |
                              *   k_confirm (index_kind 0 only) | scan+k_compact            */
@@ -110,23 +139,33 @@ typedef struct {
   float ms_total;           /* first launch to last completion on the context's stream  */
   float ms_index_build;     /* last musc_db_build_index                                 */
   float ms_read_prep;       /* last musc_reads_sort_unique (device time)                   */
-  uint64_t n_descriptors;   /* descriptors k_screen wrote: one per placement of a read, also
-                             * when two windows of the read found it (then it is two pairs);
-                             * 0 with context buckets (no descriptors exist)               */
+  uint64_t n_descriptors;   /* two-kernel: descriptors k_screen wrote.  Line buckets (index_kind 3): one per pair,
+                             * n_descriptors = n_pairs.  64-byte buckets: one descriptor stands for windows 2j and 2j + 1
+                             * of a read when both found the placement among their buckets' inline entries (then it is two
+                             * pairs), so distinct (read, window pair, placement) <= n_descriptors <= n_pairs, and
+                             * n_pairs - n_descriptors = the two-window descriptors.  Fused: 0 (no descriptors exist) */
   /* ---- since ABI version 2 */
   uint32_t index_kind;      /* index the pass ran on: 0 = 64-byte window-start buckets + target
                              * gather (k_screen -> k_confirm), 3 = the same on 128-byte line
                              * buckets (dense databases; k_screen_t -> k_confirm), 1 = context
                              * buckets, 120 bases (k_match_t or k_match), 2 = wide context
                              * buckets, 200 bases (k_match_t)                                */
-  uint32_t match_launches;  /* launches of that kernel (index_kind 1)                       */
-  uint64_t n_overflow_entries; /* index entries beyond a bucket's inline ones that were walked */
-  uint64_t match_bytes;     /* algorithmic bytes of those launches: record (ceil(2L/8) B)
-                             * per read + one 128-B bucket line per probe + 40 B (wide: 60)
-                             * per overflow entry walked + 16 B per tuple staged                         */
-  uint64_t match_bytes_strict; /* the same with a probe billed for what it uses of its line:
-                             * 8 B header + 40 B per inline entry present                   */
-  uint64_t index_bytes;     /* device memory held by the index (table + overflow entries)  */
+  uint32_t match_launches;  /* fused: launches of the match kernel = n_batches.  Two-kernel: 0     */
+  uint64_t n_overflow_entries; /* fused: the sum over the probes of max(0, bucket count - 3) (wide buckets: - 2), the
+                             * entries beyond a bucket's inline ones, all of which are walked.  Two-kernel: 0 (not counted) */
+  uint64_t match_bytes;     /* fused: algorithmic bytes of the match launches: n_reads x ceil(2L/8) B of records (L = the
+                             * longest loaded read) + one 128-B bucket line per probe + 40 B (wide: 60) per overflow entry
+                             * + 16 B per tuple staged.  Two-kernel: 0                         */
+  uint64_t match_bytes_strict; /* the same with a probe billed for what it uses of its line: 8 B header + 40 B
+                             * (wide: 60) per entry, inline or not: n_reads x ceil(2L/8) + 8 x n_read_windows + 40 x
+                             * n_candidates + 16 per tuple staged                                  */
+  uint64_t index_bytes;     /* device memory the resident index holds: (buckets + 1) x the bucket size (context and line
+                             * buckets 128 B, window-start buckets 64 B; a direct table has 4^WindowWidth buckets) + the overflow
+                             * array as allocated -- context buckets: whole 128-B lines of three entries (wide: two) for the
+                             * overflow entries + 16; 64-byte buckets: 16 B x (overflow entries + 16); line buckets: 16 B x
+                             * (8 x the overflow lines of eight slots, used or not, + 16).  The build's temporaries,
+                             * released when the build ends, are not included.  Several partitions: the last partition's
+                             * index.  (tests/stats_model.py models the context tables only.)                       */
 } musc_stats;
 
 int musc_abi_version(void);

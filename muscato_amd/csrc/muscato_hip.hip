@@ -1974,6 +1974,8 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
         if ((rc = ensure(c, c->scan_tmp, scan_tmp_elems((uint64_t)ntiles + 1)))) return rc;
         if ((rc = ensure(c, c->tcount2, (uint64_t)ntiles + 1))) return rc;
         if ((rc = ensure(c, c->tpre, (uint64_t)ntiles + 1))) return rc;
+        // (a first pass provides for 2 n staged tuples; tests/test_stats_model.py: test_heavy_reads_outgrow_a_first_pass
+        // restates this figure so that the growing case of tests/test_gpu_stats.py does grow -- keep the two in step)
         if ((rc = ensure(c, c->stage, std::max<uint64_t>(2ull * n, swaves * 64)))) return rc;
         if ((rc = ensure(c, c->spill, swaves * 32))) return rc;
         HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8 * sizeof(unsigned long long), c->stream));
@@ -2288,6 +2290,8 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
       if ((rc = ensure(c, c->scan_tmp, scan_tmp_elems((uint64_t)ntiles + 1)))) return rc;
       if ((rc = ensure(c, c->tcount2, (uint64_t)ntiles + 1))) return rc;
       if ((rc = ensure(c, c->tpre, (uint64_t)ntiles + 1))) return rc;
+      // (a first pass provides for max(4 n, 1024) descriptors; tests/test_stats_model.py:
+      // test_heavy_reads_outgrow_a_first_pass restates this figure -- keep the two in step)
       if ((rc = ensure(c, c->bs[c->cur].cdesc, std::max<uint64_t>(4ull * n, 1024)))) return rc;
       // batch-local counters: [0] valid windows [3] candidates [4] pairs [7] descriptor cursor
       HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8 * sizeof(unsigned long long), c->stream));

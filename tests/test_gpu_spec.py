@@ -21,6 +21,7 @@ import pytest
 from oracle import literal
 from oracle import muscato_oracle as orc
 
+import stats_model
 from cases import hot_probes
 
 pytestmark = pytest.mark.gpu
@@ -175,9 +176,12 @@ class SpecEngine:
         got = sorted_hits(self.e.match(to_cfg(c), apply_mmtol=apply_mmtol))
         return got, self.e.stats()
 
-    def check(self, reads, c, variant="spec", general=True, exp=None, what=""):
+    def check(self, reads, c, variant="spec", general=True, exp=None, what="", model=False):
         """Full tuple set and best+MMTol selection against the oracle, the kernel variant on both passes, and (spec,
-        general=True) the general instance on the same table: identical tuples and counters.  -> (tuples, stats)."""
+        general=True) the general instance on the same table: identical tuples and counters.  model=True: the
+        counters and the algorithmic bytes also equal tests/stats_model.py's (the table is direct and the reads hold no
+        X: equalities), which ties the specialised instance to the oracle's own count and not only to the general
+        instance.  -> (tuples, stats)."""
         what = "%s %s %s" % (self.mode, what, c)
         full = oracle_full(reads, c, self.targets if self.targets is not TARGETS else None) if exp is None else exp
         want = (SPEC if variant == "spec" else GENERAL)[self.mode] if variant in ("spec", "general") else variant
@@ -185,6 +189,11 @@ class SpecEngine:
         assert st["index_kind"] == 1, what
         assert st["match_variant"] == want, (what, st["match_variant"])
         assert_same(got, full, what)
+        if model:
+            want_st = model_counters(reads, self.targets, c, full)
+            for k in COUNTERS + MODEL_BYTES:
+                assert st[k] == want_st[k], (what, "model", k, st[k], want_st[k])
+            assert st["n_descriptors"] == 0 and st["match_launches"] == st["n_batches"] == (len(reads) + BATCH - 1) // BATCH, what
         best, st2 = self.run(reads, c, True)
         assert st2["match_variant"] == want, (what, st2["match_variant"])
         assert_same(best, np.array(sorted(orc.best_filter(map(tuple, full.tolist()), c.MMTol)), dtype=np.uint32).reshape(-1, 4),
@@ -200,7 +209,22 @@ class SpecEngine:
             assert_same(got2, got, what + " general instance")
             for k in COUNTERS + ("n_overflow_blocks",):
                 assert gst[k] == st[k], (what, k, gst[k], st[k])
+            if model:
+                for k in COUNTERS + MODEL_BYTES:
+                    assert gst[k] == want_st[k], (what, "model, general instance", k, gst[k], want_st[k])
         return full, st
+
+
+MODEL_BYTES = ("match_bytes", "match_bytes_strict")
+_MODEL = {}
+
+
+def model_counters(reads, targets, c, full):
+    """tests/stats_model.py's counters for narrow context buckets, once per read set (both fused kernels ask)."""
+    key = (id(reads), id(targets), str(c))
+    if key not in _MODEL:
+        _MODEL[key] = (stats_model.expected(reads, targets, c, "ctx", full), reads, targets)
+    return _MODEL[key][0]
 
 
 _PROBES = {}  # mode -> (reads, config, the specialised instance's overflow probes): the classic path's check at the end
@@ -229,11 +253,21 @@ def se(request):
 
 
 def test_uniform_100_base_reads(se):
-    """(a) every read 100 bases: the constant-mask tiles.  Three full batches and a ragged fourth."""
-    reads = reads_of(1, [100] * 30000)
+    """(a) every read 100 bases: the constant-mask tiles.  Three full batches and a ragged fourth.  The counters and
+    bytes of the specialised and of the general instance equal the CPU model's."""
+    reads = _uniform_reads()
     assert len(reads) > 3 * BATCH
-    full, _ = se.check(reads, geom())
+    full, _ = se.check(reads, geom(), model=True)
     assert len(full) > 20000
+
+
+_UNIFORM = []
+
+
+def _uniform_reads():
+    if not _UNIFORM:
+        _UNIFORM.append(reads_of(1, [100] * 30000))
+    return _UNIFORM[0]
 
 
 @pytest.mark.parametrize("L", [80, 49, 99])
