@@ -185,7 +185,9 @@ int musc_reload_env(musc_ctx* ctx);
  * ASCII form: `seqs` holds nseq sequences back to back, sequence i = bytes
  * [offsets[i], offsets[i+1]).  'A','C','G','T' are bases, every other byte is the
  * reference's 'X' (cmd/muscato_prep_targets/main.go:68-80).  on_device != 0 means both
- * pointers are device pointers. */
+ * pointers are device pointers.  A target may have any length (an empty one included) on a database below 2^32
+ * bases; context buckets on a database with X take targets below 2^31 bases (longer ones run on the window-start
+ * buckets), and tuples report positions in 32 bits whatever the index kind. */
 int musc_db_load_ascii(musc_ctx* ctx, const char* seqs, const uint64_t* offsets, uint32_t nseq,
                        int on_device);
 /* Packed form: 2 bits per base (A=0 C=1 G=2 T=3), base j of the concatenated stream in bits

@@ -277,6 +277,79 @@ def test_cli_replays_maxmatches_truncation(tmp_path, mode, seed):
 
 
 @pytest.mark.gpu
+def test_cli_targets_longer_than_65535_bases(tmp_path):
+    """A 70 001-base and a 131 075-base target among short ones, reads around the places where the index entries' 16-bit
+    distances saturate (pos + q1 = 65 535, T - (pos + q1) = 65 535, straddling 65 536, flush with the end, position 0)
+    and a motif planted five times whose block MaxMatches 20 truncates: result.txt (column 3, the position, beyond
+    65 535) and the nonmatch file equal what the literal oracle and the reference's post-chain give."""
+    import json
+    import random
+    from oracle import literal
+    rng = random.Random(65536)
+    rnd = lambda n: bytes(rng.choice(b"ACGT") for _ in range(n))
+    lens = [300, 70001, 8, 131075, 700]
+    T = [bytearray(rnd(n)) for n in lens]
+    motif = rnd(120)
+    for g, p in ((1, 70001 - 120), (1, 65535 - 20), (3, 0), (3, 65536), (3, 100000)):
+        T[g][p:p + 120] = motif
+    targets = [bytes(t) for t in T]
+    wins, ww = [0, 20], 15
+    reads = set()
+
+    def place(g, p, L):
+        if 0 <= p and p + L <= lens[g]:
+            r = bytearray(targets[g][p:p + L])
+            if rng.random() < 0.3:
+                j = rng.randrange(L)
+                r[j] = b"ACGT"[(b"ACGT".index(r[j]) + 1) % 4]
+            reads.add(bytes(r))
+
+    for g in (1, 3):
+        for q1 in wins:
+            for j in (-1, 0, 1):
+                place(g, 65535 - q1 + j, rng.randint(q1 + ww, 100))
+                place(g, lens[g] - 65535 - q1 + j, rng.randint(q1 + ww, 100))
+        for L in (100, 61):
+            place(g, 65536 - L, L)
+            place(g, 65535, L)
+            place(g, lens[g] - L, L)
+        for L in (85, 86, 65, 66):  # both sides of 100 - ww and of 100 - (q1 + ww)
+            place(g, 0, L)
+        for _ in range(12):
+            L = rng.randint(30, 100)
+            place(g, rng.randint(65536, lens[g] - L), L)
+    for L in range(60, 100, 3):  # 14 reads from the motif's start: one block of 70 accepted pairs per window
+        reads.add(motif[:L])
+    reads |= {rnd(rng.randint(20, 100)) for _ in range(10)}
+    reads = sorted(reads)
+    rng.shuffle(reads)
+    ocfg = orc.Config(Windows=wins, WindowWidth=ww, PMatch=0.95, MinDinuc=2, MaxReadLength=100, MaxMatches=20, MMTol=1, MatchMode="best")
+    d = tmp_path
+    (d / "genes.txt").write_bytes(b"".join(b"g%d\t%s\n" % (i, t) for i, t in enumerate(targets)))
+    (d / "reads.fastq").write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"F" * len(r)) for i, r in enumerate(reads)))
+    r = run([os.path.join(BIN, "muscato_prep_targets"), "genes.txt"], d)
+    assert r.returncode == 0, r.stderr
+    cfg = {"ReadFileName": "reads.fastq", "GeneFileName": "musc_genes.txt.sz", "GeneIdFileName": "musc_ids_genes.txt.sz",
+           "ResultsFileName": "result.txt", "Windows": wins, "WindowWidth": ww, "PMatch": 0.95, "MinDinuc": 2,
+           "MaxReadLength": 100, "MaxMatches": 20, "MMTol": 1, "MatchMode": "best"}
+    (d / "config.json").write_text(json.dumps(cfg))
+    r = run([os.path.join(BIN, "muscato"), "-ConfigFileName=config.json"], d)
+    assert r.returncode == 0, r.stderr.decode()
+    assert b"replaying the reference's truncation" in r.stderr
+    seqs, ids = orc.prep_targets_file(str(d / "genes.txt"), False)
+    ureads = orc.uniqify(orc.prep_reads(orc.read_fastq((d / "reads.fastq").read_bytes()), ocfg))
+    hits = literal.match_literal([u.seq for u in ureads], seqs, ocfg, bloom_size=4000000, num_hash=20)
+    exp = orc.results_text(hits, ureads, seqs, ids, ocfg)
+    # the case is what it says: positions beyond 65 535 in both long targets, and a truncated block
+    far = {l.split(b"\t")[4] for l in exp.splitlines() if int(l.split(b"\t")[2]) > 65535}
+    assert far == {b"g1", b"g3"}, far
+    full = orc.results_text(orc.match_direct([u.seq for u in ureads], seqs, ocfg, check_overflow=False), ureads, seqs, ids, ocfg)
+    assert full != exp
+    assert (d / "result.txt").read_bytes() == exp
+    assert (d / "result.nonmatch.txt.fastq").read_bytes() == orc.nonmatch_text(exp, ureads)
+
+
+@pytest.mark.gpu
 def test_cli_read_prep_on_gpu_equals_oracle(tmp_path):
     """Duplicated reads with many names (the 1000-character cut), reads that are prefixes of
     others, non-ACGT letters, MinReadLength / MaxReadLength: the CLI's GPU sort + collapse
