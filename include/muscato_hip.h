@@ -295,6 +295,52 @@ void musc_free_hits(musc_hit* hits);
 
 int musc_get_stats(musc_ctx* ctx, musc_stats* out);
 
+/* ---- results.txt from the resident tuples: replaces the post-chain of cmd/muscato/main.go:422-676 (combine_windows,
+ * the gene-id join, `sort -k1`, the read join).  A line is
+ *     read \t targetsub \t pos \t nmiss \t name \t len \t count \t names \n
+ * with targetsub = target[pos : pos + len(read)] clipped at the target's end; the lines are ordered bytewise on
+ * their first six columns (cmd/muscato/main.go:657).  Reads, database and tuples are resident; the two texts below
+ * are what the device cannot know.  MUSC_ABI_VERSION is unchanged: these are additions.
+ * targetsub is rendered and ordered from the packed database (2 bits a base + the X plane): every target byte that is
+ * none of A C G T comes out as 'X', as musc_db_load_ascii reads it.  A host whose targets hold other letters (an 'N'
+ * that muscato_prep_targets left in the last FASTA record, cmd/muscato_prep_targets/main.go:204-212) and that must
+ * quote them literally keeps its own post-chain for that run, as the CLI does. */
+/* Gene g's `name\tlen` (what follows the gene number on its line of the id file, the join of
+ * cmd/muscato/main.go:524-611) = bytes [offsets[g], offsets[g + 1]) of text, nseq = the loaded targets.  absent (may be
+ * NULL): absent[g] != 0 = the id file has no line for gene g, and its tuples vanish as unpairable lines do in `join`.
+ * Uploads the text and ranks the genes' texts bytewise (equal texts share a rank).  A database load forgets it. */
+int musc_results_set_gene_text(musc_ctx* ctx, const char* text, const uint64_t* offsets, const uint8_t* absent, uint32_t nseq);
+/* Read r's `count\tnames` (columns 2 and 3 of reads_sorted.txt.sz, joined at cmd/muscato/main.go:659) = bytes
+ * [offsets[r], offsets[r + 1]); nreads = the loaded reads.  A read load forgets it.  Without it the lines end after
+ * the sixth column. */
+int musc_results_set_read_text(musc_ctx* ctx, const char* text, const uint64_t* offsets, uint64_t nreads);
+/* Order n tuples (hits == NULL: the list the last musc_match* left on the device, n ignored; on_device != 0: hits is
+ * a device pointer) as `sort -k1` orders their lines (cmd/muscato/main.go:657), without the tuples of absent genes,
+ * and compute every line's byte offset: *nlines lines, *nbytes bytes in all.  The tuples are expected to be the
+ * selection that reaches results.txt (matches.txt: apply_mmtol = 1).  A tuple with read_idx >= the loaded reads,
+ * gene_idx >= the loaded targets, pos > its target's length or nmiss > 65535 fails the call (code 2) before anything
+ * is loaded through it.  Needs the gene text; setting either text afterwards invalidates the order.
+ * A device list must be 16-byte aligned (it is read one tuple per 16-byte load; hipMalloc'ed memory is).  hits == NULL
+ * needs the list of a pass over the reads and the database in hand: after a read or database load the call fails
+ * (code 2) until the next musc_match*. */
+int musc_results_order(musc_ctx* ctx, const musc_hit* hits, uint64_t n, int on_device, uint64_t* nlines, uint64_t* nbytes);
+/* The ordered tuples (capacity in tuples): the lines of matches.txt (cmd/muscato_combine_windows/main.go:36-60) with
+ * their gene number still in place, in the order `sort -k1` gives their results lines (cmd/muscato/main.go:657). */
+int musc_results_hits(musc_ctx* ctx, musc_hit* dst, uint64_t capacity, int dst_on_device);
+/* The bytes of lines [line0, line0 + nlines) of the last order, clipped at its end (a range past it: 0 bytes), into
+ * dst -- a host buffer is filled through a bounded device staging buffer.  *nbytes = bytes of the range; dst == NULL
+ * only reports them.  The concatenation over consecutive ranges is ResultsFileName.  Code 11: a line no longer fits
+ * the data in hand (nothing of the range is to be used). */
+int musc_results_text(musc_ctx* ctx, uint64_t line0, uint64_t nlines, char* dst, uint64_t capacity, int dst_on_device,
+                      uint64_t* nbytes);
+/* HIP-event time of the last musc_results_order and of all musc_results_text calls since (the reference logs wall
+ * time per stage of this chain only: cmd/muscato/main.go:1041-1056). */
+int musc_results_last_ms(musc_ctx* ctx, float* ms_order, float* ms_text);
+/* "pos \t nmiss" of a line as one integer that compares as that text does under `sort` (cmd/muscato/main.go:657):
+ * each decimal digit is 4 bits (digit + 1), left-aligned and zero-padded, ten digits of pos above five of nmiss.
+ * Needs no device; 2 for nmiss > 99999. */
+int musc_results_number_key(uint32_t pos, uint32_t nmiss, uint64_t* key);
+
 /* Which kernel instances the last musc_match* launched (tests: a pass that silently took another instance than the
  * one a test was written for is noticed).  The host resolves every kernel through a table whose entries hold the
  * function pointer and its descriptor side by side; these words are the descriptors of the entries the last pass took.

@@ -60,6 +60,8 @@ SYMBOLS = [
     "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique",
     "musc_match_device", "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_free_hits",
     "musc_get_stats", "musc_last_instance", "musc_instances", "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
+    "musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits", "musc_results_text",
+    "musc_results_last_ms", "musc_results_number_key",
 ]
 
 _lib = None
@@ -129,6 +131,16 @@ def load() -> ctypes.CDLL:
                                 ctypes.POINTER(vp), ctypes.POINTER(u64)]
     lib.musc_gather_rccl.argtypes = lib.musc_gather.argtypes
     lib.musc_rccl_probe.argtypes = [ctypes.c_char_p, ctypes.c_uint64]
+    lib.musc_results_set_gene_text.argtypes = [vp, vp, vp, vp, ctypes.c_uint32]
+    lib.musc_results_set_read_text.argtypes = [vp, vp, vp, u64]
+    lib.musc_results_order.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.musc_results_hits.argtypes = [vp, vp, u64, ctypes.c_int]
+    lib.musc_results_text.argtypes = [vp, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
+    lib.musc_results_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    lib.musc_results_number_key.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(u64)]
+    for name in ("musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits",
+                 "musc_results_text", "musc_results_last_ms", "musc_results_number_key"):
+        getattr(lib, name).restype = ctypes.c_int
     for name in ("musc_init", "musc_reload_env", "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for", "musc_db_build_index_for",
                  "musc_db_set_partition_bases", "musc_db_partitions",
                  "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique", "musc_match_device",

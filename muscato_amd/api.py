@@ -160,6 +160,7 @@ class Engine:
         self.device = device
         self.n_targets = 0
         self.n_reads = 0
+        self._res_nlines = 0
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -374,6 +375,71 @@ class Engine:
                 "match": decode_instance(w[0]), "screen": decode_instance(w[1]), "confirm": decode_instance(w[2]),
                 "block_mode": w[3] & 0xFF, "exact_rerun": bool(w[3] & 0x100)}
 
+    # ---- results.txt from the resident tuples (cmd/muscato/main.go:422-676 on the device)
+    def set_gene_text(self, id_rests: Sequence[bytes], absent: Optional[Sequence[bool]] = None) -> None:
+        """Gene g's ``name\\tlen`` (what follows the gene number on its id line); absent[g] true = the id file has no
+        line for gene g: its tuples vanish from the results.  Forgotten by the next target load.
+        The device renders and orders targetsub from the packed targets (2 bits a base + an X plane): every target
+        byte that is none of A C G T comes out as ``X`` in the lines."""
+        buf, off = concat(list(id_rests))
+        ab = None
+        if absent is not None:
+            ab = np.ascontiguousarray(np.asarray(absent, dtype=bool).astype(np.uint8))
+            if len(ab) != len(id_rests):
+                raise MuscatoError("absent must have one entry per gene")
+        self._check(self._lib.musc_results_set_gene_text(self._h, buf.ctypes.data, off.ctypes.data,
+                                                         ab.ctypes.data if ab is not None else None, len(off) - 1),
+                    "musc_results_set_gene_text")
+
+    def set_read_text(self, tails: Sequence[bytes]) -> None:
+        """Read r's ``count\\tnames`` tail.  Without it a line ends after its sixth column.  Forgotten by the next
+        read load."""
+        buf, off = concat(list(tails))
+        self._check(self._lib.musc_results_set_read_text(self._h, buf.ctypes.data, off.ctypes.data, len(off) - 1),
+                    "musc_results_set_read_text")
+
+    def results_order(self, hits: Optional[np.ndarray] = None) -> Tuple[int, int]:
+        """Order tuples as the lines of results.txt are ordered and compute the line offsets -> (nlines, nbytes).
+        hits: uint32 [n, 4] of (read_idx, gene_idx, pos, nmiss) in any order, or None = the list the last match left
+        on the device.  Tuples of absent genes are dropped."""
+        nl, nb = ctypes.c_uint64(), ctypes.c_uint64()
+        self._res_nlines = 0
+        if hits is None:
+            rc = self._lib.musc_results_order(self._h, None, 0, 0, ctypes.byref(nl), ctypes.byref(nb))
+        else:
+            # (a NULL list means "the device list": an empty host list still passes a pointer)
+            a = np.ascontiguousarray(np.asarray(hits, dtype=np.uint32).reshape(-1, 4))
+            ptr = a.ctypes.data if len(a) else np.zeros((1, 4), dtype=np.uint32).ctypes.data
+            rc = self._lib.musc_results_order(self._h, ptr, len(a), 0, ctypes.byref(nl), ctypes.byref(nb))
+        self._check(rc, "musc_results_order")
+        self._res_nlines = int(nl.value)
+        return int(nl.value), int(nb.value)
+
+    def results_hits(self) -> np.ndarray:
+        """The tuples of the last results_order, in line order: uint32 [nlines, 4]."""
+        out = np.zeros((self._res_nlines, 4), dtype=np.uint32)
+        self._check(self._lib.musc_results_hits(self._h, out.ctypes.data, self._res_nlines, 0), "musc_results_hits")
+        return out
+
+    def results_text(self, line0: int = 0, nlines: Optional[int] = None) -> bytes:
+        """The bytes of lines [line0, line0 + nlines) of the last results_order (nlines None: to the end); the
+        concatenation over consecutive ranges is results.txt."""
+        count = (1 << 62) if nlines is None else int(nlines)
+        nb = ctypes.c_uint64()
+        self._check(self._lib.musc_results_text(self._h, int(line0), count, None, 0, 0, ctypes.byref(nb)), "musc_results_text")
+        if not nb.value:
+            return b""
+        buf = np.empty(nb.value, dtype=np.uint8)
+        self._check(self._lib.musc_results_text(self._h, int(line0), count, buf.ctypes.data, nb.value, 0, ctypes.byref(nb)),
+                    "musc_results_text")
+        return buf.tobytes()
+
+    def results_ms(self) -> Tuple[float, float]:
+        """HIP-event milliseconds of the last results_order and of the results_text calls since."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._check(self._lib.musc_results_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "musc_results_last_ms")
+        return float(a.value), float(b.value)
+
     def stats(self) -> dict:
         s = _lib.MuscStats()
         self._check(self._lib.musc_get_stats(self._h, ctypes.byref(s)), "musc_get_stats")
@@ -382,6 +448,15 @@ class Engine:
 
 _INST_FIELDS = {1: ("k_match_t", ("W", "XM", "WIDE", "SG")), 2: ("k_match_g", (None, None, None, "SG")),
                 3: ("k_screen", ("mask", "one", "lines")), 4: ("k_screen_t", ()), 5: ("k_confirm", ("mask", "w2"))}
+
+
+def number_key(pos: int, nmiss: int) -> int:
+    """``pos \\t nmiss`` of a results line as one integer that compares as that text does bytewise (no GPU needed):
+    4 bits a decimal digit (digit + 1), left-aligned, ten digits of pos above five of nmiss."""
+    k = ctypes.c_uint64()
+    if _lib.load().musc_results_number_key(int(pos), int(nmiss), ctypes.byref(k)):
+        raise ValueError("number_key: nmiss %d has more than five digits" % nmiss)
+    return int(k.value)
 
 
 def decode_instance(word: int) -> Optional[dict]:

@@ -505,6 +505,13 @@ inline std::vector<std::string> fields(const std::string& s) {
   return f;
 }
 
+// 1: with one GPU the CLI orders and renders results.txt on the device unless MUSC_RESULTS=host; 0: only with
+// MUSC_RESULTS=device.  Measured (profiles/results_render.py): the results.txt lap of a 2 M-read run is
+// 0.24 s on the device against 1.1 s on the host, the runs of either side within 0.25 s of each other.
+#ifndef MUSC_RESULTS_DEFAULT_DEVICE
+#define MUSC_RESULTS_DEFAULT_DEVICE 1
+#endif
+
 // hits must already be the per-read best+MMTol selection (matches.txt).  Produces the bytes
 // of ResultsFileName: sort -k5 + join with the id file + cut (:524-611) turns the gene number
 // into "name\tlen" (hits whose number is absent from the id file are unpairable and vanish);
@@ -541,6 +548,55 @@ inline std::string results_text(const musc_hit* hits, size_t nhits, const std::v
     out += reads[l.read].names;
     out += '\n';
   }
+  return out;
+}
+
+// The same bytes from the device (musc_results_*): `c` holds the database and every read; device_list =
+// the tuples are the list the last pass left on the device, else `hits`.  Throws Die on a library error.
+inline std::string results_text_device(musc_ctx* c, bool device_list, const std::vector<musc_hit>& hits, const std::vector<UniqueRead>& reads,
+                                       const std::vector<std::string>& targets, const std::map<uint64_t, std::string>& id_rest,
+                                       float* ms_order, float* ms_text) {
+  auto check = [&](int rc) { if (rc) throw Die(1, std::string("results on the device failed: ") + musc_last_error(c)); };
+  {
+    std::string text;
+    std::vector<uint64_t> off(targets.size() + 1, 0);
+    std::vector<uint8_t> absent(targets.size(), 1);
+    for (auto& kv : id_rest) {
+      if (kv.first >= targets.size()) continue;  // (no tuple names such a gene)
+      absent[kv.first] = 0;
+      off[kv.first + 1] = kv.second.size();
+    }
+    for (size_t g = 0; g < targets.size(); g++) off[g + 1] += off[g];
+    text.resize(off.back());
+    for (auto& kv : id_rest)
+      if (kv.first < targets.size()) memcpy(&text[off[kv.first]], kv.second.data(), kv.second.size());
+    check(musc_results_set_gene_text(c, text.data(), off.data(), absent.data(), (uint32_t)targets.size()));
+  }
+  {
+    std::string text;
+    std::vector<uint64_t> off;
+    off.reserve(reads.size() + 1);
+    off.push_back(0);
+    for (auto& u : reads) {
+      text += std::to_string(u.count);
+      text += '\t';
+      text += u.names;
+      off.push_back(text.size());
+    }
+    check(musc_results_set_read_text(c, text.data(), off.data(), reads.size()));
+  }
+  uint64_t nlines = 0, nbytes = 0;
+  static const musc_hit none = {0, 0, 0, 0};
+  check(musc_results_order(c, device_list ? nullptr : hits.empty() ? &none : hits.data(), hits.size(), 0, &nlines, &nbytes));
+  std::string out(nbytes, '\0');
+  uint64_t done = 0;
+  for (uint64_t l0 = 0; l0 < nlines; l0 += 1u << 20) {
+    uint64_t nb = 0;
+    check(musc_results_text(c, l0, 1u << 20, &out[done], nbytes - done, 0, &nb));
+    done += nb;
+  }
+  if (done != nbytes) throw Die(1, "results on the device: the rendered ranges do not add up to the whole");
+  musc_results_last_ms(c, ms_order, ms_text);
   return out;
 }
 
@@ -918,8 +974,12 @@ inline std::vector<musc_hit> best_filter(const std::vector<musc_hit>& all, size_
 
 // Load the targets, shard the unique reads over cfg.GPUs devices (one host thread + one
 // musc_ctx per device, as the ABI's threading rule asks), run the hot path, gather.
+// keep0 (one GPU only): the context stays alive and is handed to the caller, with every read and the database
+// loaded, for the results stage; *list_on_device = the returned tuples are the list the last pass left on the device
+// (false after the MaxMatches replay, whose selection exists on the host only).
 inline std::vector<musc_hit> run_hot_path(const Config& cfg, const std::vector<UniqueRead>& reads,
-                                          const std::vector<std::string>& targets, Logger& log, musc_stats* stats0) {
+                                          const std::vector<std::string>& targets, Logger& log, musc_stats* stats0,
+                                          musc_ctx** keep0 = nullptr, bool* list_on_device = nullptr) {
   const int G = cfg.GPUs;
   const Concat db = concat(targets.begin(), targets.end(), [](const std::string& s) -> const std::string& { return s; });
   if (targets.size() >= 0xFFFFFFFFull) throw Die(1, "too many targets");
@@ -1038,6 +1098,11 @@ inline std::vector<musc_hit> run_hot_path(const Config& cfg, const std::vector<U
     musc_free_u32(pr);
     musc_free_u32(pw);
   }
+  if (keep0 && G == 1 && err.empty()) {
+    *keep0 = ctxs[0];
+    ctxs[0] = nullptr;
+    if (list_on_device) *list_on_device = !overflow;
+  }
   for (auto c : ctxs) if (c) musc_destroy(c);
   if (!err.empty()) throw Die(1, "muscato hot path failed:\n" + err);
   return out;
@@ -1148,13 +1213,14 @@ inline int run_muscato(Config cfg) {
   // (cmd/muscato_screen/main.go:439-452); id file: "%011d\tname\tlen" (join field 1)
   std::vector<std::string> targets;
   for (auto& l : split_lines(read_maybe_sz(cfg.GeneFileName))) targets.push_back(l.substr(0, l.find('\t')));
+  size_t nodd = 0;  // target bytes that are none of ACGTX
   {
     // Targets are compared as 2-bit bases + an "X" plane: every byte that is not A, C, G or T is an
     // X here.  muscato_prep_targets writes nothing else (it leaves the LAST FASTA record un-substituted,
     // cmd/muscato_prep_targets/main.go:204-212), but a hand-made gene file may: the reference then
     // compares the raw byte, so an 'N' in a target would mismatch an 'X' in a read where this tool
     // counts a match.  Say so instead of differing silently.
-    size_t nodd = 0, first_t = 0;
+    size_t first_t = 0;
     for (size_t t = 0; t < targets.size(); t++)
       for (unsigned char ch : targets[t])
         if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T' && ch != 'X' && nodd++ == 0) first_t = t;
@@ -1175,14 +1241,40 @@ inline int run_muscato(Config cfg) {
   fputs("Screening...\nConfirming...\n", stderr);
   musc_stats st;
   memset(&st, 0, sizeof st);
-  std::vector<musc_hit> hits = run_hot_path(cfg, reads, targets, log, &st);
+  // MUSC_RESULTS=host|device: where results.txt is ordered and rendered.  The device needs one
+  // context that holds every read: with several GPUs the host path stays.
+  const char* res_env = getenv("MUSC_RESULTS");
+  const bool env_device = res_env && !strcmp(res_env, "device"), env_host = res_env && !strcmp(res_env, "host");
+  // The device renders and orders targetsub from the 2-bit planes, where every byte that is none of ACGT is an X;
+  // results.txt quotes the target's own bytes.  A gene file with other letters (the scan above) keeps the host path,
+  // whatever MUSC_RESULTS says: the bytes are the same on every path.
+  const bool res_device = cfg.GPUs == 1 && nodd == 0 && (env_device || (!env_host && MUSC_RESULTS_DEFAULT_DEVICE));
+  if (nodd && cfg.GPUs == 1 && !env_host)
+    log.printf("results on the host: the targets hold bytes that are none of ACGTX, which the device would render as X");
+  musc_ctx* ctx0 = nullptr;
+  bool list_on_device = false;
+  struct CtxGuard {
+    musc_ctx*& c;
+    ~CtxGuard() { if (c) musc_destroy(c); }
+  } ctx_guard{ctx0};
+  std::vector<musc_hit> hits = run_hot_path(cfg, reads, targets, log, &st, res_device ? &ctx0 : nullptr, &list_on_device);
   if (st.n_overflow_blocks)
     fprintf(stderr, "Warning: %llu window-key blocks may exceed MaxMatches; results keep all their matches\n",
             (unsigned long long)st.n_overflow_blocks);
 
   clk.lap("hot path (init, load, match)");
   fputs("Combining windows...\nJoining gene names...\nJoining read names...\n", stderr);
-  const std::string res = results_text(hits.data(), hits.size(), reads, targets, id_rest);
+  std::string res;
+  if (ctx0) {
+    float ms_order = 0, ms_text = 0;
+    res = results_text_device(ctx0, list_on_device, hits, reads, targets, id_rest, &ms_order, &ms_text);
+    log.printf("results on the device: %zu bytes, order %.3f ms, text %.3f ms", res.size(), ms_order, ms_text);
+    musc_destroy(ctx0);
+    ctx0 = nullptr;
+  } else {
+    res = results_text(hits.data(), hits.size(), reads, targets, id_rest);
+    log.printf("results on the host: %zu bytes", res.size());
+  }
   spit(cfg.ResultsFileName, res);
   clk.lap("results.txt");
 

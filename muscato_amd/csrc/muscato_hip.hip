@@ -44,6 +44,7 @@
 #include "kernels_match_lane_inst.hpp"  // k_match_t: declaration only (defined in match_lane_rw*.hip)
 #include "kernels_screen_lane.hpp"
 #include "kernels_partition.hpp"
+#include "kernels_results.hpp"
 MUSC_LANE_INSTANCES_4(extern)
 MUSC_LANE_INSTANCES_8(extern)
 MUSC_LANE_INSTANCES_12(extern)
@@ -368,6 +369,21 @@ struct musc_ctx {
   DevBuf<musc_hit> gathered;    // musc_gather_rccl: every context's tuples on this device
   uint32_t* d_flag = nullptr;   // one device word for kernels that report "does not fit"
 
+  // results.txt on the device: the texts the lines quote, and the ordered list of the last
+  // musc_results_order with its line offsets
+  char* res_gtext = nullptr;        // every gene's name\tlen (musc_results_set_gene_text); released with the database
+  uint64_t* res_goff = nullptr;     // nseq + 1 byte offsets into it
+  uint32_t* res_rank = nullptr;     // per gene: rank of its text among all genes' texts, RES_ABSENT without an id line
+  char* res_ttext = nullptr;        // every read's count\tnames (musc_results_set_read_text); released with the reads
+  uint64_t* res_toff = nullptr;     // nreads + 1 byte offsets into it
+  DevBuf<musc_hit> res_hits;        // the ordered tuples
+  DevBuf<uint64_t> res_off;         // res_n + 1 line offsets
+  DevBuf<unsigned char> res_stage;  // musc_results_text: the bytes on their way to a host buffer
+  uint64_t res_n = 0, res_bytes = 0;
+  bool res_valid = false;           // res_hits / res_off describe the reads, database and texts in hand
+  bool hits_current = false;        // `hits` is the list of a pass over the reads and the database in hand
+  float res_ms_order = 0, res_ms_text = 0;
+
   uint32_t batch_reads = 16u << 20;
   // A pass over the same reads, database and parameters as the last completed one needs no
   // sizing: its buffers are known to suffice, so it runs without host round trips.
@@ -509,8 +525,32 @@ void drop_ctx_index(musc_ctx* c) {
   c->ctx_T_cap = c->ctx_E_cap = 0;
 }
 
+// the gene text of the results stage belongs to a database, the read text to a read set
+void drop_gene_text(musc_ctx* c) {
+  if (c->res_gtext) (void)hipFree(c->res_gtext);
+  if (c->res_goff) (void)hipFree(c->res_goff);
+  if (c->res_rank) (void)hipFree(c->res_rank);
+  c->res_gtext = nullptr;
+  c->res_goff = nullptr;
+  c->res_rank = nullptr;
+  c->res_valid = false;
+  c->hits_current = false;  // (called when the database goes)
+}
+void drop_read_text(musc_ctx* c) {
+  if (c->res_ttext) (void)hipFree(c->res_ttext);
+  if (c->res_toff) (void)hipFree(c->res_toff);
+  c->res_ttext = nullptr;
+  c->res_toff = nullptr;
+  c->res_valid = false;
+}
+void forget_read_text(musc_ctx* c) {  // the reads go: so do their text and the standing of the resident tuple list
+  drop_read_text(c);
+  c->hits_current = false;
+}
+
 void free_db(musc_ctx* c) {
   free_index(c);
+  drop_gene_text(c);
   if (c->db2) (void)hipFree(c->db2);
   if (c->dbm2) (void)hipFree(c->dbm2);
   if (c->dbx) (void)hipFree(c->dbx);
@@ -540,6 +580,7 @@ void drop_reads(musc_ctx* c, bool keep_rd) {
   }
   if (c->rdm) (void)hipFree(c->rdm);
   c->rdm = nullptr;
+  forget_read_text(c);
   c->reads_have_x = false;
   c->nreads = 0;
   c->rw = 0;
@@ -811,6 +852,7 @@ void musc_destroy(musc_ctx* c) {
   c->hits.release();
   c->packed.release();
   c->gathered.release();
+  c->res_hits.release(); c->res_off.release(); c->res_stage.release();
   if (c->d_flag) (void)hipFree(c->d_flag);
   if (c->counters) (void)hipFree(c->counters);
   if (c->h_pinned) (void)hipHostFree(c->h_pinned);
@@ -2122,8 +2164,10 @@ static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& p
 // device, so a later pass packs and matches them.
 int musc_match_device(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
   if (!c) return 1;
+  c->hits_current = false;
   const int rc = match_device_impl(c, P, nhits);
   if (rc != 0 && c->up.active && c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);
+  c->hits_current = rc == 0;
   return rc;
 }
 
@@ -2604,6 +2648,382 @@ int musc_hits_copy(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_dev
   HIPCHK(c, hipMemcpyAsync(dst, c->hits.p, c->nhits * sizeof(musc_hit),
                            dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------- results.txt on the device
+// The post-chain of cmd/muscato/main.go:422-676 from the resident tuples: musc_results_order drops the tuples of genes
+// without an id line, orders the rest as `sort -k1` orders their six-column lines and computes every line's byte
+// offset; musc_results_text renders a range of lines (kernels_results.hpp).
+
+static ResData res_data(const musc_ctx* c) {
+  ResData D;
+  D.rd = c->rd;
+  D.rdm = c->reads_have_x ? c->rdm : nullptr;
+  D.db2 = c->db2;
+  D.dbm2 = c->db_has_x ? c->dbm2 : nullptr;
+  D.seq_off = c->seq_off;
+  D.gtext = c->res_gtext;
+  D.goff = c->res_goff;
+  D.ttext = c->res_ttext;
+  D.toff = c->res_toff;
+  D.nreads = c->nreads;
+  D.nseq = c->nseq;
+  D.rw = c->rw;
+  return D;
+}
+
+// text + offsets of n items to the device (the offsets must not decrease; item i = bytes [offsets[i], offsets[i + 1]))
+static int upload_text(musc_ctx* c, const char* what, const char* text, const uint64_t* offsets, uint64_t n, char** d_text, uint64_t** d_off) {
+  for (uint64_t i = 0; i < n; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(c, 2, "%s: offsets decrease at item %llu", what, (unsigned long long)i);
+  const uint64_t bytes = offsets[n];
+  HIPCHK(c, hipMalloc((void**)d_text, bytes + 16));
+  HIPCHK(c, hipMalloc((void**)d_off, (n + 1) * 8));
+  if (bytes) HIPCHK(c, hipMemcpyAsync(*d_text, text, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(*d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int musc_results_set_gene_text(musc_ctx* c, const char* text, const uint64_t* offsets, const uint8_t* absent, uint32_t nseq) {
+  if (!c) return 1;
+  if (!offsets || (!text && offsets[nseq] != 0)) return fail(c, 2, "musc_results_set_gene_text: NULL input");
+  if (!c->db2 || nseq != c->nseq)
+    return fail(c, 2, "musc_results_set_gene_text: text of %u genes for a database of %u targets", nseq, c->nseq);
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool list_ok = c->hits_current;  // (a new text leaves the tuple list as good as it was)
+  drop_gene_text(c);
+  c->hits_current = list_ok;
+  int rc = upload_text(c, "musc_results_set_gene_text", text, offsets, nseq, &c->res_gtext, &c->res_goff);
+  if (rc) {
+    drop_gene_text(c);
+    return rc;
+  }
+  // rank of each gene's text among all of them, bytewise; equal texts share a rank
+  std::vector<uint32_t> order;
+  order.reserve(nseq);
+  for (uint32_t g = 0; g < nseq; g++)
+    if (!absent || !absent[g]) order.push_back(g);
+  auto cmp = [&](uint32_t a, uint32_t b) {
+    const uint64_t la = offsets[a + 1] - offsets[a], lb = offsets[b + 1] - offsets[b];
+    const int d = memcmp(text + offsets[a], text + offsets[b], (size_t)std::min(la, lb));
+    return d ? d : la < lb ? -1 : la > lb ? 1 : 0;
+  };
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cmp(a, b) < 0; });
+  std::vector<uint32_t> rank(nseq, RES_ABSENT);
+  uint32_t rk = 0;
+  for (size_t i = 0; i < order.size(); i++) {
+    if (i && cmp(order[i - 1], order[i]) != 0) rk++;
+    rank[order[i]] = rk;
+  }
+  hipError_t e = hipMalloc((void**)&c->res_rank, (uint64_t)nseq * 4 + 16);
+  if (e == hipSuccess) e = hipMemcpy(c->res_rank, rank.data(), (uint64_t)nseq * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    drop_gene_text(c);
+    return fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+
+int musc_results_set_read_text(musc_ctx* c, const char* text, const uint64_t* offsets, uint64_t nreads) {
+  if (!c) return 1;
+  if (!offsets || (!text && offsets[nreads] != 0)) return fail(c, 2, "musc_results_set_read_text: NULL input");
+  if (nreads != c->nreads)
+    return fail(c, 2, "musc_results_set_read_text: text of %llu reads, %llu are loaded", (unsigned long long)nreads, (unsigned long long)c->nreads);
+  HIPCHK(c, hipSetDevice(c->device));
+  drop_read_text(c);
+  const int rc = upload_text(c, "musc_results_set_read_text", text, offsets, nreads, &c->res_ttext, &c->res_toff);
+  if (rc) drop_read_text(c);
+  return rc;
+}
+
+int musc_results_number_key(uint32_t pos, uint32_t nmiss, uint64_t* key) {
+  if (!key || nmiss > 99999u) return 2;
+  *key = res_number_key(pos, nmiss);
+  return 0;
+}
+
+static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_device) {
+  const dim3 B256(256);
+  auto grid = [](uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); };
+  const uint4* d_in = reinterpret_cast<const uint4*>(hits);
+  TmpBufs B;
+  if (!hits) {
+    if (!c->hits_current)
+      return fail(c, 2, "musc_results_order: the resident tuple list is not that of a pass over the reads and the database in hand");
+    d_in = reinterpret_cast<const uint4*>(c->hits.p);
+    n = c->nhits;
+  } else if (on_device && ((uintptr_t)hits & 15u)) {
+    return fail(c, 2, "musc_results_order: a device list must be 16-byte aligned");
+  } else if (!on_device && n) {
+    // a host list is checked here, before it is uploaded (a device list: k_results_flag)
+    for (uint64_t i = 0; i < n; i++) {
+      const musc_hit& h = hits[i];
+      if (h.read_idx >= c->nreads || h.gene_idx >= c->nseq || h.nmiss > RES_MAX_NMISS ||
+          h.pos > c->h_seq_off[(size_t)h.gene_idx + 1] - c->h_seq_off[h.gene_idx])
+        return fail(c, 2, "musc_results_order: tuple %llu (read %u, gene %u, pos %u, nmiss %u) is outside the loaded reads and targets",
+                    (unsigned long long)i, h.read_idx, h.gene_idx, h.pos, h.nmiss);
+    }
+    uint4* up = nullptr;
+    HIPCHK(c, B.alloc(&up, n * 16));
+    HIPCHK(c, hipMemcpyAsync(up, hits, n * 16, hipMemcpyHostToDevice, c->stream));
+    d_in = up;
+  }
+  if (n >= 0xFFFFFFF0ull) return fail(c, 2, "musc_results_order: too many tuples for 32-bit line numbers");
+  int rc;
+  if ((rc = ensure(c, c->res_off, n + 1))) return rc;
+  if (n == 0) {
+    HIPCHK(c, hipMemsetAsync(c->res_off.p, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+
+  // ---- validate, drop the tuples of absent genes
+  uint32_t *keep = nullptr, *excl = nullptr, *stmp = nullptr;
+  uint4* a = nullptr;
+  HIPCHK(c, B.alloc(&keep, n * 4));
+  HIPCHK(c, B.alloc(&excl, n * 4));
+  HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(n) * 4));
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
+  hipLaunchKernelGGL(k_results_flag, grid(n), B256, 0, c->stream, d_in, n, c->nreads, c->nseq, c->seq_off, c->res_rank, keep, c->d_flag);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, keep, excl, n, false, stmp))) return rc;
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  HIPCHK(c, hipMemcpyAsync(h32, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h32 + 1, excl + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h32 + 2, keep + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h32[0] & 1u)
+    return fail(c, 2, "musc_results_order: a tuple names a read, a target or a position outside the loaded reads and targets");
+  const bool read_major = !(h32[0] & 2u);
+  const uint64_t m = (uint64_t)h32[1] + h32[2];
+  if ((rc = ensure(c, c->res_hits, std::max<uint64_t>(m, 1)))) return rc;
+  uint4* const out = reinterpret_cast<uint4*>(c->res_hits.p);
+  if (m == 0) {
+    HIPCHK(c, hipMemsetAsync(c->res_off.p, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  HIPCHK(c, B.alloc(&a, m * 16));
+  hipLaunchKernelGGL(k_results_compact, grid(n), B256, 0, c->stream, d_in, keep, excl, n, a);
+  HIPCHK(c, hipGetLastError());
+
+  uint64_t *k0 = nullptr, *k1 = nullptr;
+  uint32_t *p0 = nullptr, *p1 = nullptr;
+  void* tmp = nullptr;
+  size_t tmp_bytes = 0;
+  auto sort_bufs = [&](TmpBufs& T, uint64_t k) -> int {
+    HIPCHK(c, T.alloc(&k0, k * 8));
+    HIPCHK(c, T.alloc(&k1, k * 8));
+    HIPCHK(c, T.alloc(&p0, k * 4));
+    HIPCHK(c, T.alloc(&p1, k * 4));
+    tmp_bytes = 0;
+    for (unsigned end : {32u, 33u, 60u, 63u}) {
+      size_t tb = 0;
+      HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tb, k0, k1, p0, p1, (size_t)k, 0u, end, c->stream));
+      tmp_bytes = std::max(tmp_bytes, tb);
+    }
+    HIPCHK(c, T.alloc(&tmp, tmp_bytes));
+    return 0;
+  };
+  // one stable LSD pass over (key word, permutation) pairs
+  auto sort_pass = [&](const uint32_t* idx, uint64_t k, uint32_t what, unsigned end_bit) -> int {
+    hipLaunchKernelGGL(k_results_keys, grid(k), B256, 0, c->stream, a, idx, p0, k, what, c->res_rank, c->rd, c->rw, c->db2,
+                       c->db_has_x ? c->dbm2 : (const uint32_t*)nullptr, c->seq_off, k0);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, rocprim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, p0, p1, (size_t)k, 0u, end_bit, c->stream));
+    std::swap(p0, p1);
+    return 0;
+  };
+
+  // ---- a list that is not read-major (a host list in any order): one sort on read_idx first
+  if (!read_major) {
+    TmpBufs T;
+    uint4* a2 = nullptr;
+    if ((rc = sort_bufs(T, m))) return rc;
+    HIPCHK(c, B.alloc(&a2, m * 16));
+    hipLaunchKernelGGL(k_results_iota, grid(m), B256, 0, c->stream, p0, m);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = sort_pass(nullptr, m, RES_KEY_READ, 32u))) return rc;
+    hipLaunchKernelGGL(k_results_gather, grid(m), B256, 0, c->stream, a, p0, m, a2);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (T is released at the end of this scope)
+    a = a2;
+  }
+
+  // ---- read segments: a read with one tuple is in place; the others are sorted
+  uint32_t *multi = nullptr, *incl = nullptr, *idx = nullptr;
+  HIPCHK(c, B.alloc(&multi, m * 4));
+  HIPCHK(c, B.alloc(&incl, m * 4));
+  HIPCHK(c, hipMemsetAsync(c->counters + 4, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_results_segments, grid(m), B256, 0, c->stream, a, m, c->rd, c->rw, multi, c->counters + 4);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, multi, incl, m, true, stmp))) return rc;  // (m <= n: stmp is large enough)
+  HIPCHK(c, hipMemcpyAsync(h32, incl + (m - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->counters + 4, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t k = h32[0], maxlen = c->h_pinned[1];
+  if (k == 0) {
+    HIPCHK(c, hipMemcpyAsync(out, a, m * 16, hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    TmpBufs T;
+    if ((rc = sort_bufs(T, k))) return rc;
+    HIPCHK(c, T.alloc(&idx, k * 4));
+    hipLaunchKernelGGL(k_results_idx, grid(m), B256, 0, c->stream, multi, incl, m, idx);
+    hipLaunchKernelGGL(k_results_iota, grid(k), B256, 0, c->stream, p0, k);
+    HIPCHK(c, hipGetLastError());
+    // least significant first: gene rank, the number word, the target words from last to first, the read
+    const uint32_t nw = (uint32_t)((maxlen + RES_BASES_PER_WORD - 1) / RES_BASES_PER_WORD);
+    if ((rc = sort_pass(idx, k, RES_KEY_RANK, 32u))) return rc;
+    if ((rc = sort_pass(idx, k, RES_KEY_NUMBER, 60u))) return rc;
+    for (uint32_t w = nw; w-- > 0;)
+      if ((rc = sort_pass(idx, k, RES_KEY_SPAN + w, 63u))) return rc;
+    if ((rc = sort_pass(idx, k, RES_KEY_READ, 32u))) return rc;
+    hipLaunchKernelGGL(k_results_place, grid(m), B256, 0, c->stream, a, multi, incl, idx, p0, m, out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+
+  // ---- line lengths -> offsets
+  uint64_t* stmp64 = nullptr;
+  HIPCHK(c, B.alloc(&stmp64, scan_tmp_elems(m + 1) * 8));
+  hipLaunchKernelGGL(k_results_len, grid(m + 1), B256, 0, c->stream, out, m, res_data(c), c->res_off.p);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u64(c, c->res_off.p, c->res_off.p, m + 1, stmp64))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->res_off.p + m, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->res_n = m;
+  c->res_bytes = c->h_pinned[0];
+  return 0;
+}
+
+int musc_results_order(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_device, uint64_t* nlines, uint64_t* nbytes) {
+  if (!c) return 1;
+  if (nlines) *nlines = 0;
+  if (nbytes) *nbytes = 0;
+  c->res_valid = false;
+  c->res_n = c->res_bytes = 0;
+  if (!c->db2 || !c->res_gtext || !c->res_rank) return fail(c, 2, "musc_results_order: no gene text (musc_results_set_gene_text)");
+  if (c->up.active) return fail(c, 2, "musc_results_order: a streamed read load has not been matched yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->ev_used = 0;
+  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  const int rc = results_order_impl(c, hits, n, on_device);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);  // (nothing of a failed call is still queued when its temporaries go)
+    return rc;
+  }
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->res_ms_order = 0;
+  (void)hipEventElapsedTime(&c->res_ms_order, e0, e1);
+  c->res_ms_text = 0;
+  c->res_valid = true;
+  if (nlines) *nlines = c->res_n;
+  if (nbytes) *nbytes = c->res_bytes;
+  return 0;
+}
+
+int musc_results_hits(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_device) {
+  if (!c) return 1;
+  if (!c->res_valid) return fail(c, 2, "musc_results_hits: no ordered list (musc_results_order)");
+  if (capacity < c->res_n) return fail(c, 2, "musc_results_hits: capacity %llu < %llu tuples", (unsigned long long)capacity, (unsigned long long)c->res_n);
+  if (c->res_n == 0) return 0;
+  if (!dst) return fail(c, 2, "musc_results_hits: dst is NULL");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(dst, c->res_hits.p, c->res_n * sizeof(musc_hit), dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+static const uint64_t RES_STAGE_BYTES = 64ull << 20;  // device staging of musc_results_text for a host destination
+static const uint64_t RES_STAGE_LINES = 1ull << 20;   // line offsets fetched to the host at a time
+
+static void launch_render(musc_ctx* c, uint64_t l0, uint64_t l1, unsigned char* out) {
+  const uint64_t nl = l1 - l0;
+  const unsigned blocks = (unsigned)std::min<uint64_t>((nl + 3) / 4, 4 * MAX_GRID);
+  hipLaunchKernelGGL(k_results_render, dim3(blocks), dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(c->res_hits.p), c->res_off.p, l0, l1,
+                     res_data(c), out, c->d_flag);
+}
+
+static int results_text_impl(musc_ctx* c, uint64_t l0, uint64_t l1, char* dst, uint64_t capacity, int dst_on_device, uint64_t* nbytes) {
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->res_off.p + l0, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->res_off.p + l1, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t o0 = c->h_pinned[0], bytes = c->h_pinned[1] - o0;
+  *nbytes = bytes;
+  if (!dst) return 0;  // the size of the range
+  if (capacity < bytes)
+    return fail(c, 2, "musc_results_text: capacity %llu < %llu bytes", (unsigned long long)capacity, (unsigned long long)bytes);
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));  // raised by a line the kernel refuses to render
+  if (dst_on_device) {
+    launch_render(c, l0, l1, reinterpret_cast<unsigned char*>(dst));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  std::vector<uint64_t> off;
+  for (uint64_t b0 = l0; b0 < l1;) {
+    const uint64_t b1 = std::min(l1, b0 + RES_STAGE_LINES);
+    off.resize(b1 - b0 + 1);
+    HIPCHK(c, hipMemcpyAsync(off.data(), c->res_off.p + b0, (b1 - b0 + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint64_t p0 = b0; p0 < b1;) {
+      // the most lines whose bytes fit the staging buffer, at least one
+      const uint64_t start = off[p0 - b0];
+      uint64_t p1 = std::upper_bound(off.begin() + (p0 - b0), off.end(), start + RES_STAGE_BYTES) - off.begin() - 1 + b0;
+      p1 = std::min(std::max(p1, p0 + 1), b1);
+      const uint64_t pb = off[p1 - b0] - start;
+      int rc = ensure(c, c->res_stage, std::max(pb, RES_STAGE_BYTES));
+      if (rc) return rc;
+      launch_render(c, p0, p1, c->res_stage.p);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(dst + (start - o0), c->res_stage.p, pb, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      p0 = p1;
+    }
+    b0 = b1;
+  }
+  return 0;
+}
+
+int musc_results_text(musc_ctx* c, uint64_t line0, uint64_t nlines, char* dst, uint64_t capacity, int dst_on_device, uint64_t* nbytes) {
+  if (!c) return 1;
+  if (!nbytes) return fail(c, 2, "musc_results_text: nbytes is NULL");
+  *nbytes = 0;
+  if (!c->res_valid) return fail(c, 2, "musc_results_text: no ordered list (musc_results_order)");
+  if (line0 >= c->res_n || nlines == 0) return 0;
+  const uint64_t l1 = nlines > c->res_n - line0 ? c->res_n : line0 + nlines;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->ev_used = 0;
+  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  const int rc = results_text_impl(c, line0, l1, dst, capacity, dst_on_device, nbytes);
+  const hipError_t er = hipEventRecord(e1, c->stream);
+  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned + 2);
+  *h_bad = 0;
+  const hipError_t ef = rc == 0 && dst ? hipMemcpyAsync(h_bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIPCHK(c, er);
+  HIPCHK(c, ef);
+  HIPCHK(c, es);
+  if (*h_bad) {
+    *nbytes = 0;
+    return fail(c, 11, "musc_results_text: a line of the ordered list no longer fits the reads, the database or the texts in hand");
+  }
+  float ms = 0;
+  if (dst && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->res_ms_text += ms;
+  return 0;
+}
+
+int musc_results_last_ms(musc_ctx* c, float* ms_order, float* ms_text) {
+  if (!c) return 1;
+  if (ms_order) *ms_order = c->res_ms_order;
+  if (ms_text) *ms_text = c->res_ms_text;
   return 0;
 }
 
