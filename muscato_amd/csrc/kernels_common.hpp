@@ -178,7 +178,7 @@ MUSC_KERNEL void k_max_len(const uint64_t* __restrict__ off, uint64_t n, unsigne
 }
 
 // one thread per (read, record word).  Record = rw u32 words: bases in words 0..rw-2
-// (2 bits each, zero filled past the read), word rw-1 = len | valid_windows << 16.
+// (2 bits each, zero filled past the read), word rw-1 = len | READ_HAS_X (bit 16: the read holds an X).
 template <bool PACKED>
 __global__ void k_pack_reads(const unsigned char* __restrict__ s, const uint32_t* __restrict__ in2,
                              const uint32_t* __restrict__ inm, const uint64_t* __restrict__ off,

@@ -83,3 +83,16 @@ def hot_probes(reads, targets, cfg, full):
             counts[k][key] = counts[k].get(key, 0) + 1
     hot = [{key for key, n in d.items() if n > cfg.MaxMatches} for d in counts]
     return {(ri, k) for ri, r in enumerate(reads) for k, q1 in enumerate(cfg.Windows) if valid[ri][k] and r[q1:q1 + ww] in hot[k]}
+
+
+def check_groups(reads, order, ustart):
+    """order/ustart describe exactly sorted(set(reads)) with stable groups."""
+    uniq = sorted(set(reads))
+    assert len(ustart) == len(uniq) + 1 and ustart[0] == 0 and ustart[-1] == len(reads)
+    assert sorted(order.tolist()) == list(range(len(reads)))
+    for g, u in enumerate(uniq):
+        grp = order[ustart[g]:ustart[g + 1]].tolist()
+        assert grp, "empty group"
+        assert all(reads[i] == u for i in grp)
+        assert grp == sorted(grp), "ties must keep input order"
+    return uniq

@@ -9,7 +9,7 @@ import pytest
 
 from oracle import muscato_oracle as orc
 
-from cases import make_case
+from cases import check_groups, make_case
 
 pytestmark = pytest.mark.gpu
 
@@ -20,19 +20,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def check_groups(reads, order, ustart):
-    """order/ustart describe exactly sorted(set(reads)) with stable groups."""
-    uniq = sorted(set(reads))
-    assert len(ustart) == len(uniq) + 1 and ustart[0] == 0 and ustart[-1] == len(reads)
-    assert sorted(order.tolist()) == list(range(len(reads)))
-    for g, u in enumerate(uniq):
-        grp = order[ustart[g]:ustart[g + 1]].tolist()
-        assert grp, "empty group"
-        assert all(reads[i] == u for i in grp)
-        assert grp == sorted(grp), "ties must keep input order"
-    return uniq
 
 
 def names_like_reference(reads, names, order, ustart):
