@@ -266,6 +266,38 @@ int musc_reads_load_packed32(musc_ctx* ctx, const uint8_t* bases2bit, const uint
 int musc_reads_sort_unique(musc_ctx* ctx, const char* seqs, const uint64_t* offsets, uint64_t nreads,
                            int on_device, uint32_t** order, uint32_t** ustart, uint64_t* nunique);
 
+/* FASTQ parsing on the GPU, in front of the sort above: replaces utils/fastq.go:35-61 (records of four lines under
+ * bufio.ScanLines: one trailing '\r' of a line is dropped, a last line without '\n' is a line, an incomplete last
+ * record of 1, 2 or 3 lines is dropped) and cmd/muscato_prep_reads/main.go:46-92 (a read whose raw length is below
+ * MinReadLength goes; every byte that is none of A C G T becomes X; the rest is cut at MaxReadLength).
+ * text = the nbytes raw bytes of the read file (on_device != 0: a device pointer, any alignment; bytes outside
+ * [text, text + nbytes) are never read).  min_read_len <= 0 keeps every record; max_read_len < 0 is an error (2).
+ * Afterwards the context's reads are the distinct PREPARED sequences in bytewise order, exactly what
+ * musc_reads_sort_unique leaves for the same prepared reads (a prepared read of more than 65535 bases fails as it does
+ * there), stats.ms_read_prep covers the whole device stage (parse + sort + collapse), and `out` describes the kept
+ * reads, numbered in file order: spans into the caller's text, and order / ustart as musc_reads_sort_unique returns
+ * them.  No complete record (nbytes == 0 included): zero reads, and arrays that are valid and empty.
+ * What stays with the caller: the 1000-byte rule for a read's name (cmd/muscato_prep_reads/main.go:76-79: name_len is
+ * the length before it), the cut of a name at its first tab and the 1000-byte rule of the joined names
+ * (cmd/muscato_uniqify/main.go:83-135), and the order of the names within a group (the bytewise order of the names).
+ * Not enforced: the reference's 1 MiB line limit (utils/fastq.go:25-27 gives its scanner a 1 MiB buffer and panics on a
+ * longer line; the host path of this project does not enforce it either).
+ * A device allocation that fails returns 10, the library's code for a failed HIP call ("out of memory" in the text);
+ * after that, as after every failed call here, the context holds no reads and `out` is all zero.
+ * The arrays are malloc'ed by the library: musc_fastq_prep_free (which zeroes the struct; a zeroed struct is fine).
+ * MUSC_ABI_VERSION is unchanged: these are additions. */
+typedef struct musc_fastq_prep {
+  uint64_t n_records, n_short, n_reads, n_unique;  /* n_reads = n_records - n_short */
+  uint32_t max_len, reserved;      /* max_len: the longest prepared read                        */
+  uint64_t *name_off, *seq_off;    /* [n_reads] byte offsets into the caller's text            */
+  uint32_t *name_len, *seq_len;    /* [n_reads] name: after the \r rule, before the 1000 rule; */
+                                   /*           seq: the prepared length                       */
+  uint32_t *order, *ustart;        /* as musc_reads_sort_unique, over the kept reads           */
+} musc_fastq_prep;
+int  musc_reads_prep_fastq(musc_ctx* ctx, const char* text, uint64_t nbytes, int on_device,
+                           int32_t min_read_len, int32_t max_read_len, musc_fastq_prep* out);
+void musc_fastq_prep_free(musc_fastq_prep* p);
+
 /* ---- the hot path: screen + confirm (+ per-read best filter) -------------------------
  * musc_match_device leaves the hits in device memory (count in *nhits);
  * musc_hits_copy copies them to `dst` (host, or device if dst_on_device) -- capacity in

@@ -52,12 +52,23 @@ class MuscStats(ctypes.Structure):
     ]
 
 
+class MuscFastqPrep(ctypes.Structure):
+    _fields_ = [
+        ("n_records", ctypes.c_uint64), ("n_short", ctypes.c_uint64), ("n_reads", ctypes.c_uint64), ("n_unique", ctypes.c_uint64),
+        ("max_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("name_off", ctypes.POINTER(ctypes.c_uint64)), ("seq_off", ctypes.POINTER(ctypes.c_uint64)),
+        ("name_len", ctypes.POINTER(ctypes.c_uint32)), ("seq_len", ctypes.POINTER(ctypes.c_uint32)),
+        ("order", ctypes.POINTER(ctypes.c_uint32)), ("ustart", ctypes.POINTER(ctypes.c_uint32)),
+    ]
+
+
 # every symbol include/muscato_hip.h declares
 SYMBOLS = [
     "musc_abi_version", "musc_init", "musc_destroy", "musc_last_error", "musc_reload_env",
     "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for",
     "musc_db_set_partition_bases", "musc_db_partitions",
     "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique",
+    "musc_reads_prep_fastq", "musc_fastq_prep_free",
     "musc_match_device", "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_free_hits",
     "musc_get_stats", "musc_last_instance", "musc_instances", "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
     "musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits", "musc_results_text",
@@ -111,6 +122,10 @@ def load() -> ctypes.CDLL:
     lib.musc_reads_load_packed32.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u64, ctypes.c_int]
     lib.musc_reads_sort_unique.argtypes = [vp, vp, vp, u64, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp),
                                            ctypes.POINTER(u64)]
+    lib.musc_reads_prep_fastq.argtypes = [vp, vp, u64, ctypes.c_int, i32, i32, ctypes.POINTER(MuscFastqPrep)]
+    lib.musc_reads_prep_fastq.restype = ctypes.c_int
+    lib.musc_fastq_prep_free.argtypes = [ctypes.POINTER(MuscFastqPrep)]
+    lib.musc_fastq_prep_free.restype = None
     lib.musc_match_device.argtypes = [vp, ctypes.POINTER(MuscParams), ctypes.POINTER(u64)]
     lib.musc_hits_copy.argtypes = [vp, vp, u64, ctypes.c_int]
     lib.musc_hits_copy_packed.argtypes = [vp, vp, u64, ctypes.c_int, u64, ctypes.POINTER(i32)]

@@ -282,6 +282,34 @@ class Engine:
         self.n_reads = int(nu.value)
         return order, ustart
 
+    def prep_fastq(self, raw: bytes, min_len: int, max_len: int) -> dict:
+        """FASTQ parsing and read prep on the GPU (musc_reads_prep_fastq): `raw` is the text of the read file.  Loads
+        the distinct prepared sequences in bytewise order as the context's reads and returns the counts (n_records,
+        n_short, n_reads, n_unique, max_len) and, as numpy arrays over the kept reads in file order, their spans in
+        `raw` (name_off, name_len, seq_off, seq_len) and order / ustart as sort_unique_reads returns them."""
+        buf = np.frombuffer(raw, dtype=np.uint8)
+        return self.prep_fastq_device(buf.ctypes.data if len(buf) else None, len(buf), min_len, max_len, on_device=False)
+
+    def prep_fastq_device(self, ptr: Optional[int], nbytes: int, min_len: int, max_len: int, on_device: bool = True) -> dict:
+        """The same for `nbytes` of text at `ptr`: a device pointer of any alignment (the spans are offsets from it)."""
+        fp = _lib.MuscFastqPrep()
+        self.n_reads = 0
+        self._check(self._lib.musc_reads_prep_fastq(self._h, ptr, int(nbytes), 1 if on_device else 0, int(min_len), int(max_len),
+                                                    ctypes.byref(fp)), "musc_reads_prep_fastq")
+        try:
+            n, nu = int(fp.n_reads), int(fp.n_unique)
+
+            def arr(p, count):
+                return np.ctypeslib.as_array(p, shape=(max(count, 1),))[:count].copy()
+            out = {"n_records": int(fp.n_records), "n_short": int(fp.n_short), "n_reads": n, "n_unique": nu,
+                   "max_len": int(fp.max_len), "name_off": arr(fp.name_off, n), "seq_off": arr(fp.seq_off, n),
+                   "name_len": arr(fp.name_len, n), "seq_len": arr(fp.seq_len, n), "order": arr(fp.order, n),
+                   "ustart": arr(fp.ustart, nu + 1)}
+        finally:
+            self._lib.musc_fastq_prep_free(ctypes.byref(fp))
+        self.n_reads = nu
+        return out
+
     def load_reads_packed(self, seqs: Sequence[bytes]) -> None:
         buf, off = concat(seqs)
         packed, mask = pack_2bit(buf, int(off[-1]))

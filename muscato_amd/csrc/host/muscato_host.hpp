@@ -1165,6 +1165,66 @@ inline std::vector<UniqueRead> prep_reads(const std::string& fastq, const Config
   return out;
 }
 
+// 1: the CLI parses the read file on the device unless MUSC_PREP=host; 0: only with MUSC_PREP=device.
+#ifndef MUSC_PREP_DEFAULT_DEVICE
+#define MUSC_PREP_DEFAULT_DEVICE 0
+#endif
+
+// The same with the parse on the device (musc_reads_prep_fastq: records, the \r rule, MinReadLength, subx,
+// MaxReadLength, sort and collapse); the host makes strings of the group heads' sequences and of the names only, and
+// keeps the name rules: 1000 bytes per name (cmd/muscato_prep_reads/main.go:76-79), the names of a group in bytewise
+// order, each cut at its first tab, 1000 bytes for the joined names (cmd/muscato_uniqify/main.go:83-135).
+// *fell_back: the device had no memory for the stage and the host path ran instead.
+inline std::vector<UniqueRead> prep_reads_device(const std::string& fastq, const Config& c, size_t* n_total, Logger& log,
+                                                 bool* fell_back) {
+  *fell_back = false;
+  musc_ctx* ctx = nullptr;
+  if (musc_init(c.Device, &ctx)) throw Die(1, std::string("read prep: ") + musc_last_error(nullptr));
+  musc_fastq_prep fp;
+  const int rc = musc_reads_prep_fastq(ctx, fastq.data(), fastq.size(), 0, c.MinReadLength, c.MaxReadLength, &fp);
+  if (rc) {
+    const std::string e = musc_last_error(ctx);
+    musc_destroy(ctx);
+    if (rc == 10 && e.find("out of memory") != std::string::npos) {
+      log.printf("read prep on the host: the device stage found no memory (%s)", e.c_str());
+      *fell_back = true;
+      return prep_reads(fastq, c, n_total);
+    }
+    throw Die(1, "read prep: " + e);
+  }
+  musc_stats st;
+  musc_get_stats(ctx, &st);
+  musc_destroy(ctx);
+  log.printf("read prep on the device: %llu records, %llu kept, %llu distinct, %.3f ms", (unsigned long long)fp.n_records,
+             (unsigned long long)fp.n_reads, (unsigned long long)fp.n_unique, st.ms_read_prep);
+  if (n_total) *n_total = fp.n_reads;
+  std::vector<UniqueRead> out;
+  out.reserve(fp.n_unique);
+  std::vector<std::string> grp;
+  for (uint64_t g = 0; g < fp.n_unique; g++) {
+    grp.clear();
+    for (uint32_t k = fp.ustart[g]; k < fp.ustart[g + 1]; k++) {
+      const uint32_t r = fp.order[k];
+      std::string rn = fastq.substr(fp.name_off[r], fp.name_len[r]);
+      if (rn.size() > 1000) rn = rn.substr(0, 995) + "...";
+      grp.push_back(std::move(rn));
+    }
+    std::sort(grp.begin(), grp.end());
+    std::string na;
+    for (size_t i = 0; i < grp.size(); i++) {
+      if (i) na += ';';
+      na += grp[i].substr(0, grp[i].find('\t'));
+    }
+    if (na.size() > 1000) na = na.substr(0, 996) + "...";
+    const uint32_t h = fp.order[fp.ustart[g]];
+    std::string seq = fastq.substr(fp.seq_off[h], fp.seq_len[h]);
+    subx(seq);
+    out.push_back(UniqueRead{std::move(seq), grp.size(), na});
+  }
+  musc_fastq_prep_free(&fp);
+  return out;
+}
+
 inline int run_muscato(Config cfg) {
   // setupEnvs/makeTemp/setupLog/saveConfig (cmd/muscato/main.go:906-967, 680-706)
   const std::string uid = make_uid();
@@ -1189,7 +1249,12 @@ inline int run_muscato(Config cfg) {
   StageClock clk(log);
   fputs("Preparing reads...\n", stderr);
   size_t n_total = 0;
-  std::vector<UniqueRead> reads = prep_reads(slurp(cfg.ReadFileName), cfg, &n_total);
+  // MUSC_PREP=host|device: where the read file is parsed
+  const char* prep_env = getenv("MUSC_PREP");
+  const bool prep_device = prep_env ? !strcmp(prep_env, "device") : MUSC_PREP_DEFAULT_DEVICE != 0;
+  bool prep_fell_back = false;
+  std::vector<UniqueRead> reads = prep_device ? prep_reads_device(slurp(cfg.ReadFileName), cfg, &n_total, log, &prep_fell_back)
+                                              : prep_reads(slurp(cfg.ReadFileName), cfg, &n_total);
   if (reads.empty()) throw Die(1, "muscato_uniqify: no input from -");
   fprintf(stderr, "Found %zu total sequences\nFound %zu unique sequences\n", n_total, reads.size());
   spit(join_path(cfg.LogDir, "seqinfo.json"),

@@ -3522,5 +3522,6 @@ int musc_gather_rccl(musc_ctx* const* ctxs, int n, const uint64_t* read_base, mu
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- read prep (sort + collapse)
+// ---------------------------------------------------------------- read prep (FASTQ parse, sort + collapse)
+#include "kernels_fastq.hpp"
 #include "muscato_prep.hpp"

@@ -133,43 +133,12 @@ MUSC_KERNEL void k_prep_pack(const unsigned char* __restrict__ s, const uint64_t
 
 typedef TmpBufs PrepBufs;  // temporaries of musc_reads_sort_unique, released on every exit path
 
-extern "C" int musc_reads_sort_unique(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads,
-                                      int on_device, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
-  if (!c) return 1;
-  if (!order || !ustart || !nunique) return fail(c, 2, "musc_reads_sort_unique: NULL output pointer");
-  *order = *ustart = nullptr;
-  *nunique = 0;
-  if ((!seqs || !offsets) && nreads) return fail(c, 2, "musc_reads_sort_unique: NULL input");
-  HIPCHK(c, hipSetDevice(c->device));
-  free_reads(c);
-  if (nreads >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read numbers");
-  if (nreads == 0) {
-    c->rw = 4;
-    *order = (uint32_t*)malloc(4);
-    *ustart = (uint32_t*)calloc(1, 4);
-    if (!*order || !*ustart) return fail(c, 7, "out of host memory");
-    return 0;
-  }
-  c->ev_used = 0;
-  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
-  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+// The device stage of musc_reads_sort_unique on n > 0 prepared reads that are already in device memory (d_s, d_off as
+// musc_reads_load_ascii takes them).  e0 has been recorded by the caller, in front of whatever device work of its own
+// the time is to cover; e1 is recorded here.
+static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const uint64_t* d_off, const uint64_t n,
+                                 hipEvent_t e0, hipEvent_t e1, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
   PrepBufs B;
-  const uint64_t n = nreads;
-  const unsigned char* d_s = (const unsigned char*)seqs;
-  const uint64_t* d_off = offsets;
-  uint64_t total = 0;
-  if (!on_device) {
-    total = offsets[n];
-    unsigned char* ds = nullptr;
-    uint64_t* doff = nullptr;
-    HIPCHK(c, B.alloc(&ds, total + 64));
-    HIPCHK(c, B.alloc(&doff, (n + 1) * 8));
-    HIPCHK(c, hipMemcpyAsync(ds, seqs, total, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(doff, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    d_s = ds;
-    d_off = doff;
-  }
-  HIPCHK(c, hipEventRecord(e0, c->stream));
   HIPCHK(c, hipMemsetAsync(c->counters + 4, 0, 8, c->stream));
   hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(n, 256), MAX_GRID)), dim3(256), 0, c->stream, d_off, n, c->counters + 4);
   HIPCHK(c, hipGetLastError());
@@ -271,4 +240,197 @@ extern "C" int musc_reads_sort_unique(musc_ctx* c, const char* seqs, const uint6
   *ustart = h_ustart;
   *nunique = nu;
   return 0;
+}
+
+extern "C" int musc_reads_sort_unique(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads,
+                                      int on_device, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
+  if (!c) return 1;
+  if (!order || !ustart || !nunique) return fail(c, 2, "musc_reads_sort_unique: NULL output pointer");
+  *order = *ustart = nullptr;
+  *nunique = 0;
+  if ((!seqs || !offsets) && nreads) return fail(c, 2, "musc_reads_sort_unique: NULL input");
+  HIPCHK(c, hipSetDevice(c->device));
+  free_reads(c);
+  if (nreads >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read numbers");
+  if (nreads == 0) {
+    c->rw = 4;
+    *order = (uint32_t*)malloc(4);
+    *ustart = (uint32_t*)calloc(1, 4);
+    if (!*order || !*ustart) return fail(c, 7, "out of host memory");
+    return 0;
+  }
+  c->ev_used = 0;
+  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+  PrepBufs B;  // the upload: released when the device stage has returned
+  const uint64_t n = nreads;
+  const unsigned char* d_s = (const unsigned char*)seqs;
+  const uint64_t* d_off = offsets;
+  if (!on_device) {
+    const uint64_t total = offsets[n];
+    unsigned char* ds = nullptr;
+    uint64_t* doff = nullptr;
+    HIPCHK(c, B.alloc(&ds, total + 64));
+    HIPCHK(c, B.alloc(&doff, (n + 1) * 8));
+    HIPCHK(c, hipMemcpyAsync(ds, seqs, total, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(doff, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    d_s = ds;
+    d_off = doff;
+  }
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  return reads_sort_unique_dev(c, d_s, d_off, n, e0, e1, order, ustart, nunique);
+}
+
+// ---------------------------------------------------------------- FASTQ text -> prepared reads (kernels_fastq.hpp)
+
+extern "C" void musc_fastq_prep_free(musc_fastq_prep* p) {
+  if (!p) return;
+  free(p->name_off);
+  free(p->seq_off);
+  free(p->name_len);
+  free(p->seq_len);
+  free(p->order);
+  free(p->ustart);
+  memset(p, 0, sizeof *p);
+}
+
+// a failed device allocation of the stage: the library's code for a failed HIP call, the text says which and why
+#define FQ_ALLOC(c, B, ptr, bytes)                                                                                   \
+  do {                                                                                                               \
+    const hipError_t e_ = (B).alloc((ptr), (bytes));                                                                 \
+    if (e_ != hipSuccess) {                                                                                          \
+      (void)hipGetLastError();                                                                                       \
+      return fail((c), 10, "musc_reads_prep_fastq: device allocation of %llu bytes failed: %s",                      \
+                  (unsigned long long)(bytes), hipGetErrorString(e_));                                               \
+    }                                                                                                                \
+  } while (0)
+
+static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on_device, int32_t min_len, uint32_t max_len,
+                          musc_fastq_prep* out) {
+  c->ev_used = 0;
+  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+  PrepBufs P;  // the text and the record tables: released before the sort takes its own temporaries
+  PrepBufs S;  // the prepared reads
+  const unsigned char* d_text = (const unsigned char*)text;
+  if (!on_device && nbytes) {
+    unsigned char* dt = nullptr;
+    FQ_ALLOC(c, P, &dt, nbytes + 16);
+    HIPCHK(c, hipMemcpyAsync(dt, text, nbytes, hipMemcpyHostToDevice, c->stream));
+    d_text = dt;
+  }
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+
+  // ---- lines: newlines per tile, tile bases
+  const uint64_t lo = (uint64_t)((uintptr_t)d_text & (FQ_LANE_BYTES - 1)), hi = lo + nbytes;
+  const unsigned char* base16 = d_text - lo;
+  const uint64_t ntiles = (hi + FQ_TILE_BYTES - 1) / FQ_TILE_BYTES;
+  const dim3 tgrid((unsigned)std::min<uint64_t>(std::max<uint64_t>(ntiles, 1), 4 * MAX_GRID));
+  uint64_t* cnt = nullptr;
+  uint64_t nrec = 0, newlines = 0;
+  uint32_t virt = 0;
+  if (nbytes) {
+    uint64_t* stmp = nullptr;
+    FQ_ALLOC(c, P, &cnt, (ntiles + 1) * 8);
+    FQ_ALLOC(c, P, &stmp, scan_tmp_elems(ntiles + 1) * 8);
+    HIPCHK(c, hipMemsetAsync(cnt + ntiles, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_fq_count, tgrid, dim3(FQ_BLOCK), 0, c->stream, base16, lo, hi, ntiles, cnt);
+    HIPCHK(c, hipGetLastError());
+    int rc = scan_u64(c, cnt, cnt, ntiles + 1, stmp);
+    if (rc) return rc;
+    c->h_pinned[1] = 0;
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned, cnt + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, d_text + (nbytes - 1), 1, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    newlines = c->h_pinned[0];
+    virt = *reinterpret_cast<const unsigned char*>(c->h_pinned + 1) != '\n';  // a last line without a newline is a line
+    nrec = (newlines + virt) / 4;                                              // an incomplete last record is dropped
+  }
+  if (nrec >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read numbers");
+
+  // ---- records: spans, the \r rule, the length rules; kept reads' numbers and offsets
+  uint64_t *lines = nullptr, *len = nullptr;
+  uint32_t *kidx = nullptr, *name_len = nullptr;
+  uint64_t nkept = 0, total = 0;
+  if (nrec) {
+    uint64_t* stmp64 = nullptr;
+    uint32_t* stmp32 = nullptr;
+    FQ_ALLOC(c, P, &lines, (3 * (nrec + 1) + 2) * 8);  // three tables and the two counters of k_fq_records
+    FQ_ALLOC(c, P, &len, (nrec + 1) * 8);
+    FQ_ALLOC(c, P, &kidx, (nrec + 1) * 4);
+    FQ_ALLOC(c, P, &name_len, (nrec + 1) * 4);
+    FQ_ALLOC(c, P, &stmp64, scan_tmp_elems(nrec + 1) * 8);
+    FQ_ALLOC(c, P, &stmp32, scan_tmp_elems(nrec + 1) * 4);
+    uint64_t *name_begin = lines, *name_end = lines + (nrec + 1), *seq_end = lines + 2 * (nrec + 1);
+    unsigned long long* st = reinterpret_cast<unsigned long long*>(lines + 3 * (nrec + 1));
+    hipLaunchKernelGGL(k_fq_lines, tgrid, dim3(FQ_BLOCK), 0, c->stream, base16, lo, hi, ntiles, cnt, nrec, virt, newlines,
+                       name_begin, name_end, seq_end);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemsetAsync(st, 0, 16, c->stream));
+    hipLaunchKernelGGL(k_fq_records, dim3(std::min(nblk(nrec + 1, 256), MAX_GRID)), dim3(256), 0, c->stream, d_text, nrec,
+                       name_begin, name_end, seq_end, min_len, max_len, kidx, len, name_len, st);
+    HIPCHK(c, hipGetLastError());
+    int rc = scan_u32(c, kidx, kidx, nrec + 1, false, stmp32);
+    if (rc) return rc;
+    if ((rc = scan_u64(c, len, len, nrec + 1, stmp64))) return rc;
+    uint32_t nk32 = 0;
+    HIPCHK(c, hipMemcpyAsync(&nk32, kidx + nrec, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned, len + nrec, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2, st, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    nkept = nk32;
+    total = c->h_pinned[0];
+    out->max_len = (uint32_t)c->h_pinned[2];
+    out->n_short = c->h_pinned[3];
+  }
+  out->n_records = nrec;
+  out->n_reads = nkept;
+  out->name_off = (uint64_t*)malloc(std::max<uint64_t>(nkept, 1) * 8);
+  out->seq_off = (uint64_t*)malloc(std::max<uint64_t>(nkept, 1) * 8);
+  out->name_len = (uint32_t*)malloc(std::max<uint64_t>(nkept, 1) * 4);
+  out->seq_len = (uint32_t*)malloc(std::max<uint64_t>(nkept, 1) * 4);
+  if (!out->name_off || !out->seq_off || !out->name_len || !out->seq_len) return fail(c, 7, "out of host memory for the read spans");
+  if (nkept == 0) {  // as musc_reads_sort_unique of no reads
+    c->rw = 4;
+    out->order = (uint32_t*)malloc(4);
+    out->ustart = (uint32_t*)calloc(1, 4);
+    if (!out->order || !out->ustart) return fail(c, 7, "out of host memory");
+    return 0;
+  }
+
+  // ---- the prepared reads, and the kept reads' spans for the host
+  unsigned char* prep = nullptr;
+  uint64_t *prep_off = nullptr, *o64 = nullptr;
+  uint32_t* o32 = nullptr;
+  FQ_ALLOC(c, S, &prep, total + 64);
+  FQ_ALLOC(c, S, &prep_off, (nkept + 1) * 8);
+  FQ_ALLOC(c, P, &o64, 2 * nkept * 8);
+  FQ_ALLOC(c, P, &o32, 2 * nkept * 4);
+  hipLaunchKernelGGL(k_fq_gather, dim3(std::min(nblk(nrec, 256 / FQ_GROUP), 4 * MAX_GRID)), dim3(256), 0, c->stream, d_text, nbytes,
+                     nrec, lines, lines + (nrec + 1), kidx, len, name_len, prep, prep_off, o64, o64 + nkept, o32, o32 + nkept);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out->name_off, o64, nkept * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->seq_off, o64 + nkept, nkept * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->name_len, o32, nkept * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out->seq_len, o32 + nkept, nkept * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  P.release();
+  return reads_sort_unique_dev(c, prep, prep_off, nkept, e0, e1, &out->order, &out->ustart, &out->n_unique);
+}
+
+extern "C" int musc_reads_prep_fastq(musc_ctx* c, const char* text, uint64_t nbytes, int on_device, int32_t min_read_len,
+                                     int32_t max_read_len, musc_fastq_prep* out) {
+  if (!c) return 1;
+  if (!out) return fail(c, 2, "musc_reads_prep_fastq: NULL output pointer");
+  memset(out, 0, sizeof *out);
+  if (!text && nbytes) return fail(c, 2, "musc_reads_prep_fastq: NULL input");
+  HIPCHK(c, hipSetDevice(c->device));
+  free_reads(c);
+  if (max_read_len < 0) return fail(c, 2, "musc_reads_prep_fastq: max_read_len %d is negative", max_read_len);
+  const int rc = fastq_prep_run(c, text, nbytes, on_device, min_read_len, (uint32_t)max_read_len, out);
+  if (rc) {  // nothing stale: no reads, no arrays
+    musc_fastq_prep_free(out);
+    free_reads(c);
+  }
+  return rc;
 }
