@@ -92,6 +92,60 @@ DEV void block_add_u64(unsigned long long v, unsigned long long* dst) {
 #endif
 
 // ------------------------------------------------------------------------------------
+// The counters of a pass: CNT_WORDS u64 on the device (musc_ctx::counters), read back into the
+// pinned mirror (musc_ctx::h_pinned) with the same indices.
+//
+//   counters[0 .. 7]   the PASS block, cleared when a pass starts:
+//     CNT_ACCEPTED     accepted (read, target, position) pairs, before the per-read selection
+//     CNT_HITS         the hit cursor: tuples in `hits` so far (k_compact* read it, k_advance moves it)
+//     CNT_FLAGS        the flag word, FLAG_* below: a guard fired
+//     CNT_SCRATCH      not the pass's: one word for whoever needs a device scalar between passes (borrowers below)
+//     CNT_OVF_BLOCKS   (window, key) blocks above MaxMatches (k_block_overflow, block mode 2)
+//     CNT_HOT          block mode 1: a sketch cell reached the threshold -- the screening is inconclusive
+//     (slots 0 and 7 are unused)
+//   counters[CNT_BATCH .. CNT_BATCH + 7]   the BATCH block: cleared before every batch of a careful pass, once per
+//   sized pass (over which it then accumulates).  Its slots mean one thing on the fused path (k_match_t, k_match_g:
+//   counters[CNT_BATCH + MB_*]) and another on the two-kernel path (SB_*).  k_screen and k_screen_t are handed
+//   `counters + CNT_BATCH` and `counters + CNT_FLAGS`: they index the first with the bare SB_* names and OR into
+//   the second.
+//
+// Borrowers: the loaders (muscato_prep.hpp, the database and read loads), the results stage (CNT_SCRATCH: longest
+// sequence / segment); the partition merge (CNT_OVF_BLOCKS: k_block_overflow over the summed table); k_hot_probes
+// (the first word of the batch block as its output cursor).  All of them run between passes.
+// ------------------------------------------------------------------------------------
+enum : int {
+  CNT_ACCEPTED = 1,
+  CNT_HITS = 2,
+  CNT_FLAGS = 3,
+  CNT_SCRATCH = 4,
+  CNT_OVF_BLOCKS = 5,
+  CNT_HOT = 6,
+  CNT_PASS_WORDS = 8,
+  CNT_BATCH = 8,
+  CNT_BATCH_WORDS = 8,
+  CNT_WORDS = 16,
+  // batch block, fused path
+  MB_WINDOWS = 0,    // read windows probed
+  MB_CMP = 1,        // entries compared
+  MB_CAND = 3,       // index entries met
+  MB_OVF = 4,        // overflow entries walked
+  MB_SPILL_MAX = 5,  // largest spill of a wave and wave-tile parity
+  MB_TUPLES = 6,     // tuples staged
+  MB_STAGE_MAX = 7,  // largest staged region of a wave
+  // batch block, two-kernel path
+  SB_WINDOWS = 0,   // valid read windows
+  SB_CAND = 3,      // index entries met
+  SB_PAIRS = 4,     // descriptors written
+  SB_TWO = 5,       // of them, descriptors that stand for two windows
+  SB_DESC_MAX = 7,  // largest descriptor region of a workgroup
+};
+// CNT_FLAGS
+constexpr unsigned long long FLAG_STAGE_OVERRUN = 1;  // a staging region (fused) or descriptor region (two-kernel) ran out
+constexpr unsigned long long FLAG_HITS_OVERRUN = 2;   // `hits` ran out (k_compact, k_compact_w)
+constexpr unsigned long long FLAG_SPILL_OVERRUN = 4;  // a spill region ran out
+constexpr unsigned long long FLAG_SPEC_REFUSED = 8;   // a geometry-specialised instance met other parameters than its own
+
+// ------------------------------------------------------------------------------------
 // packing kernels (ASCII / 2-bit stream -> device layout)
 // ------------------------------------------------------------------------------------
 

@@ -175,7 +175,7 @@ DEV uint32_t confirm_pair(const uint4 ds, const uint32_t* __restrict__ rd, const
 // block_mode 1: screening -- each workgroup keeps a count-min sketch of (window, key) -> accepted
 //   pairs in LDS across all its tiles; if no sketch cell of any workgroup of any launch reaches
 //   `block_thr` = floor(MaxMatches / number of workgroup-launches), then by pigeonhole no block can
-//   hold more than MaxMatches pairs (cells only over-estimate).  Otherwise counters[6] is raised
+//   hold more than MaxMatches pairs (cells only over-estimate).  Otherwise counters[CNT_HOT] is raised
 //   and the host repeats the pass in mode 2.
 // block_mode 2: exact -- one global atomic per (read, window) into a 2^22-cell table.
 // (Eight waves per SIMD where the record fits 64 registers without spilling: measured 1.82 ms
@@ -324,25 +324,25 @@ __global__ __launch_bounds__(TILE, (RW <= 8 && !(RW == 8 && MASK)) ? 8 : 4) void
       emit(w, tj, ds.w, ds.z);
     }
   }
-  block_add_u64(acc, &counters[1]);
+  block_add_u64(acc, &counters[CNT_ACCEPTED]);
   if (block_mode == 1) {
     lds_barrier();
     uint32_t hot = 0;
     for (uint32_t t = threadIdx.x; t < (1u << BLOCK_LDS_BITS); t += TILE) hot |= s_sketch[t] >= block_thr;
-    if (__any(hot) && (threadIdx.x & 63) == 0) atomicOr(&counters[6], 1ull);
+    if (__any(hot) && (threadIdx.x & 63) == 0) atomicOr(&counters[CNT_HOT], 1ull);
   }
 }
 
-// k_compact -- hits[counters[2] + tpre[tile] ...] = the tile's staged tuples (tpre = scan of
+// k_compact -- hits[counters[CNT_HITS] + tpre[tile] ...] = the tile's staged tuples (tpre = scan of
 // tcount2): plain 16-byte copies, a tile's run is contiguous on both sides.
 MUSC_KERNEL __launch_bounds__(256) void k_compact(uint32_t ntiles, const uint32_t* __restrict__ tbase,
                                                  const uint32_t* __restrict__ tcount2,
                                                  const uint32_t* __restrict__ tpre,
                                                  const uint4* __restrict__ stage, uint4* __restrict__ hits,
                                                  uint64_t hits_cap, unsigned long long* __restrict__ counters) {
-  const unsigned long long base = counters[2];
+  const unsigned long long base = counters[CNT_HITS];
   if (base + tpre[ntiles] > hits_cap) {  // cannot happen on a sized pass; a sync-free pass re-runs sized
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&counters[3], 2ull);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&counters[CNT_FLAGS], FLAG_HITS_OVERRUN);
     return;
   }
   for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -385,9 +385,9 @@ __global__ __launch_bounds__(256) void k_hot_probes(const uint32_t* __restrict__
   }
 }
 
-// counters[2] (hits so far) += tpre[ntiles] (hits of this batch)
+// counters[CNT_HITS] (hits so far) += tpre[ntiles] (hits of this batch)
 MUSC_KERNEL void k_advance(const uint32_t* __restrict__ tpre, uint32_t ntiles, unsigned long long* counters) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) counters[2] += tpre[ntiles];
+  if (threadIdx.x == 0 && blockIdx.x == 0) counters[CNT_HITS] += tpre[ntiles];
 }
 
 // number of block counters above MaxMatches (hash collisions only inflate counters, so 0 is
@@ -397,7 +397,7 @@ MUSC_KERNEL void k_block_overflow(const uint32_t* __restrict__ block_table, uint
   unsigned long long c = 0;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < (1u << BLOCK_TABLE_BITS); i += gridDim.x * blockDim.x)
     c += block_table[i] > max_matches;
-  block_add_u64(c, &counters[5]);
+  block_add_u64(c, &counters[CNT_OVF_BLOCKS]);
 }
 
 // Tuples as one u64 each for the wire (RCCL gather to rank 0): read index (+ the shard's base)

@@ -480,16 +480,16 @@ __global__ void k_xpos_check_db(const uint32_t* __restrict__ xpos, uint64_t nrea
   if (b) atomicOr(bad, 1u);
 }
 
-// k_compact_w -- hits[counters[2] + tpre[wt] ...] = the wave-tile's staged tuples (tpre = scan of
+// k_compact_w -- hits[counters[CNT_HITS] + tpre[wt] ...] = the wave-tile's staged tuples (tpre = scan of
 // tcount2), a wave per wave-tile: plain 16-byte copies, contiguous on both sides.
 MUSC_KERNEL __launch_bounds__(256) void k_compact_w(uint32_t nwt, const uint32_t* __restrict__ tbase,
                                                    const uint32_t* __restrict__ tcount2,
                                                    const uint32_t* __restrict__ tpre, const uint4* __restrict__ stage,
                                                    uint4* __restrict__ hits, uint64_t hits_cap,
                                                    unsigned long long* __restrict__ counters) {
-  const unsigned long long base = counters[2];
+  const unsigned long long base = counters[CNT_HITS];
   if (base + tpre[nwt] > hits_cap) {  // cannot happen on a sized pass; a sync-free pass re-runs sized
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&counters[3], 2ull);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&counters[CNT_FLAGS], FLAG_HITS_OVERRUN);
     return;
   }
   const uint32_t lane = threadIdx.x & 63;

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
 #pragma unroll
     for (int k = 0; k < W; k++) same = same && mp->win[k] == S_WIN[k] && mp->need[k] == (1u << k) - 1u;
     if (!same) {
-      if (threadIdx.x == 0) atomicOr(&counters[3], 8ull);
+      if (threadIdx.x == 0) atomicOr(&counters[CNT_FLAGS], FLAG_SPEC_REFUSED);
       return;
     }
   }
@@ -745,22 +745,22 @@ __global__ __launch_bounds__(TILE, MATCHG_WAVES_OF(SG)) void k_match_g(const uin
         mx_spill = sp > mx_spill ? sp : mx_spill;
         over |= s_red[w][7] >> 32;
       }
-      if (t[0]) atomicAdd(&counters[8 + 0], t[0]);
-      if (t[1]) atomicAdd(&counters[8 + 1], t[1]);
-      if (t[2]) atomicAdd(&counters[8 + 3], t[2]);
-      if (t[3]) atomicAdd(&counters[8 + 4], t[3]);
-      if (t[4]) atomicAdd(&counters[1], t[4]);
-      if (t[5]) atomicAdd(&counters[8 + 6], t[5]);
-      atomicMax(&counters[8 + 7], mx_used);
-      if (mx_spill) atomicMax(&counters[8 + 5], mx_spill);
-      if (over) atomicOr(&counters[3], 1ull);
-      if (mx_spill > sregion) atomicOr(&counters[3], 4ull);
+      if (t[0]) atomicAdd(&counters[CNT_BATCH + MB_WINDOWS], t[0]);
+      if (t[1]) atomicAdd(&counters[CNT_BATCH + MB_CMP], t[1]);
+      if (t[2]) atomicAdd(&counters[CNT_BATCH + MB_CAND], t[2]);
+      if (t[3]) atomicAdd(&counters[CNT_BATCH + MB_OVF], t[3]);
+      if (t[4]) atomicAdd(&counters[CNT_ACCEPTED], t[4]);
+      if (t[5]) atomicAdd(&counters[CNT_BATCH + MB_TUPLES], t[5]);
+      atomicMax(&counters[CNT_BATCH + MB_STAGE_MAX], mx_used);
+      if (mx_spill) atomicMax(&counters[CNT_BATCH + MB_SPILL_MAX], mx_spill);
+      if (over) atomicOr(&counters[CNT_FLAGS], FLAG_STAGE_OVERRUN);
+      if (mx_spill > sregion) atomicOr(&counters[CNT_FLAGS], FLAG_SPILL_OVERRUN);
     }
   }
   if (block_mode == 1) {
     __syncthreads();
     uint32_t hot = 0;
     for (uint32_t t = threadIdx.x; t < (1u << MATCHG_SKETCH_BITS); t += TILE) hot |= s_sketch[t] >= block_thr;
-    if (__any(hot) && (threadIdx.x & 63) == 0) atomicOr(&counters[6], 1ull);
+    if (__any(hot) && (threadIdx.x & 63) == 0) atomicOr(&counters[CNT_HOT], 1ull);
   }
 }

@@ -12,8 +12,8 @@
 // MinDinuc and the table kind become compile-time constants -- the mask tables turn into immediates, the image
 // shift into a constant, a third of the scalar instructions and nine tenths of the spilled scalars go away
 // (profiles/r03_spec_variant.txt: 3-4 % of the launch).  SpecGeom<SG> names the geometry; the host launches such an
-// instance ONLY after comparing every one of these quantities with the run's (spec_geom_matches, muscato_hip.hip),
-// and the kernel checks them again at entry and refuses to touch the table on a mismatch (flag 8 of counters[3]).
+// instance ONLY after comparing every one of these quantities with the run's (spec_geom_matches, muscato_pass.hpp),
+// and the kernel checks them again at entry and refuses to touch the table on a mismatch (FLAG_SPEC_REFUSED of counters[CNT_FLAGS]).
 template <int SG>
 struct SpecGeom {  // SG = 0: the general kernel, everything from MatchParams
   static constexpr bool on = false;

@@ -211,10 +211,10 @@ DEV int rec_count_dinuc(const R& r, const R& m, bool has_m, uint32_t q1, int ww)
 // global offset << 24, y = its low 32 bits, z = window k | z-flag << 4 | pos_ok << 5 | position
 // in the target << 6 (when it fits 16 bits exactly) | DESC_TWO (windows k and k+1 both found
 // the placement), w = gene.
-// counters (batch-local block = pass-level block + 8): [0] valid windows, [3] candidates (index
-//           entries walked), [4] descriptors, [5] descriptors that stand for two windows, [7] the
-//           largest number of descriptors any workgroup needed (region size to retry with);
-//           pass-level [3] is raised when a region ran out.
+// counters = the batch block (kernels_common.hpp: counters + CNT_BATCH): SB_WINDOWS valid windows, SB_CAND
+//           candidates (index entries walked), SB_PAIRS descriptors, SB_TWO descriptors that stand for two
+//           windows, SB_DESC_MAX the largest number of descriptors any workgroup needed (region size to retry
+//           with); pass_flags = counters + CNT_FLAGS: FLAG_STAGE_OVERRUN is raised when a region ran out.
 #define SCR_OWN 2048  // overflow items per chunk whose owner is looked up directly
 #define SCR_PROBES (2 * TILE)  // probes per chunk: two windows of every read of the tile
 
@@ -579,13 +579,13 @@ __global__ __launch_bounds__(TILE, (ONE && !MASK) ? 8 : SCR_WAVES) void k_screen
     }
     lds_barrier();  // before the next tile resets s_tilecnt
   }
-  block_add_u64(nvalid, &counters[0]);
-  block_add_u64(ncand, &counters[3]);
-  block_add_u64(ntwo, &counters[5]);
+  block_add_u64(nvalid, &counters[SB_WINDOWS]);
+  block_add_u64(ncand, &counters[SB_CAND]);
+  block_add_u64(ntwo, &counters[SB_TWO]);
   if (threadIdx.x == 0) {
-    atomicAdd(&counters[4], (unsigned long long)used);
-    atomicMax(&counters[7], (unsigned long long)used);
-    if (used > region) atomicOr(pass_flags, 1ull);  // pass-level flag: descriptor space ran out
+    atomicAdd(&counters[SB_PAIRS], (unsigned long long)used);
+    atomicMax(&counters[SB_DESC_MAX], (unsigned long long)used);
+    if (used > region) atomicOr(pass_flags, FLAG_STAGE_OVERRUN);  // pass-level flag: descriptor space ran out
   }
 }
 

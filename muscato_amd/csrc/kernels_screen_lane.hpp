@@ -303,10 +303,10 @@ __global__ __launch_bounds__(64, SCRT_WAVES) void k_screen_t(const uint32_t* __r
   // (a wave is a workgroup here: one reduction per wave and a handful of atomics from its first lane)
   const unsigned long long v0 = nvalid, v1 = ncand;
   if (lane == 0) {
-    if (v0) atomicAdd(&counters[0], v0);
-    if (v1) atomicAdd(&counters[3], v1);
-    atomicAdd(&counters[4], (unsigned long long)used);
-    atomicMax(&counters[7], (unsigned long long)used);
-    if (used > region) atomicOr(pass_flags, 1ull);  // pass-level flag: descriptor space ran out
+    if (v0) atomicAdd(&counters[SB_WINDOWS], v0);
+    if (v1) atomicAdd(&counters[SB_CAND], v1);
+    atomicAdd(&counters[SB_PAIRS], (unsigned long long)used);
+    atomicMax(&counters[SB_DESC_MAX], (unsigned long long)used);
+    if (used > region) atomicOr(pass_flags, FLAG_STAGE_OVERRUN);  // pass-level flag: descriptor space ran out
   }
 }

@@ -353,14 +353,12 @@ struct musc_ctx {
   // combination start with the exact per-block counters instead of screening, failing and repeating
   uint64_t exact_epoch = 0;
   musc_params exact_params;
-  int cur_block_mode = 0;          // of the pass in flight
-  uint32_t cur_block_thr = 0;
   PathParams last_pp;          // of the last musc_match_device
   uint32_t last_max_matches = 0;
   uint32_t last_inst[MUSC_INSTANCE_WORDS] = {0, 0, 0, 0};  // musc_last_instance: what the resolvers of the last pass returned
   bool last_exact_blocks = false;  // block_table holds exact counters of that pass
-  unsigned long long* counters = nullptr;  // [0] valid windows [1] accepted [2] hit cursor
-  uint64_t* h_pinned = nullptr;            // 16 x u64 pinned staging
+  unsigned long long* counters = nullptr;  // CNT_WORDS u64: the pass block and the batch block (kernels_common.hpp)
+  uint64_t* h_pinned = nullptr;            // their pinned mirror (and 16 x u64 of staging for whoever reads a scalar back)
 
   DevBuf<musc_hit> hits;
   uint64_t nhits = 0;
@@ -645,126 +643,6 @@ int check_params(musc_ctx* c, const musc_params* P) {
   return 0;
 }
 
-// line buckets without X anywhere, record strides k_screen_t is built for: the wave-autonomous screen
-// (kernels_screen_lane.hpp); MUSC_SCREEN=wg keeps k_screen (A/B runs)
-bool screen_lane(const musc_ctx* c, bool mask) {
-  return c->idx_lines && !mask && !c->rdm && (c->rw == 4 || c->rw == 8 || c->rw == 12 || c->rw == 16) && !c->env.screen_wg;
-}
-
-// f(std::integral_constant<int, RW>{}) for the record strides that have kernel instances of their own (RW = 0: any other)
-template <class F>
-auto by_rw(int rw, F&& f) {
-  switch (rw) {
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 12: return f(std::integral_constant<int, 12>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    default: return f(std::integral_constant<int, 0>{});
-  }
-}
-
-// The instance of each two-kernel-path kernel a run launches: one resolver per kernel, which the launch
-// (and for k_screen_t the occupancy query of screen_grid) takes it from.  A resolver returns the function pointer
-// TOGETHER with its descriptor (musc_last_instance, include/muscato_hip.h): both come from one table entry, written
-// by one macro from one list of template arguments, so what a pass reports is what it launched.
-typedef decltype(&k_screen_t<8>) screen_t_fn;
-typedef decltype(&k_screen<0, false, false, false>) screen_fn;
-typedef decltype(&k_confirm<0, false, false>) confirm_fn;
-template <class Fn>
-struct Inst {
-  Fn fn;
-  uint32_t id;  // MUSC_INST_* family and template arguments; 0 with fn == nullptr
-};
-constexpr uint32_t inst_id(uint32_t family, int rw, int a = 0, int b = 0, int c = 0, int d = 0) {
-  return family | (uint32_t)rw << 8 | (uint32_t)a << 16 | (uint32_t)b << 20 | (uint32_t)c << 24 | (uint32_t)d << 28;
-}
-#define INST_SCREEN_T(RW) Inst<screen_t_fn>{k_screen_t<RW>, inst_id(MUSC_INST_SCREEN_T, RW)}
-#define INST_SCREEN(RW, M, ONE, LN) Inst<screen_fn>{k_screen<RW, M, ONE, LN>, inst_id(MUSC_INST_SCREEN, RW, M, ONE, LN)}
-#define INST_CONFIRM(RW, M, W2) Inst<confirm_fn>{k_confirm<RW, M, W2>, inst_id(MUSC_INST_CONFIRM, RW, M, W2)}
-
-Inst<screen_t_fn> screen_t_instance(int rw) {  // (screen_lane: only the strides k_screen_t is built for)
-  return by_rw(rw, [](auto r) -> Inst<screen_t_fn> {
-    if constexpr (decltype(r)::value != 0) return INST_SCREEN_T(decltype(r)::value);
-    else return Inst<screen_t_fn>{nullptr, 0};
-  });
-}
-
-Inst<screen_fn> screen_instance(int rw, bool mask, int W, bool lines) {
-  const int m = mask, one = W <= 2, ln = lines;
-  return by_rw(rw, [&](auto r) -> Inst<screen_fn> {
-    constexpr int RW = decltype(r)::value;
-    static const Inst<screen_fn> k[2][2][2] = {
-        {{INST_SCREEN(RW, false, false, false), INST_SCREEN(RW, false, false, true)}, {INST_SCREEN(RW, false, true, false), INST_SCREEN(RW, false, true, true)}},
-        {{INST_SCREEN(RW, true, false, false), INST_SCREEN(RW, true, false, true)}, {INST_SCREEN(RW, true, true, false), INST_SCREEN(RW, true, true, true)}}};
-    return k[m][one][ln];
-  });
-}
-
-Inst<confirm_fn> confirm_instance(int rw, bool mask, int W) {
-  const int m = mask, w2 = W <= 2;
-  return by_rw(rw, [&](auto r) -> Inst<confirm_fn> {
-    constexpr int RW = decltype(r)::value;
-    static const Inst<confirm_fn> k[2][2] = {{INST_CONFIRM(RW, false, false), INST_CONFIRM(RW, false, true)}, {INST_CONFIRM(RW, true, false), INST_CONFIRM(RW, true, true)}};
-    return k[m][w2];
-  });
-}
-
-Inst<screen_t_fn> screen_t_kernel(const musc_ctx* c) { return screen_t_instance(c->rw); }
-Inst<screen_fn> screen_kernel(const musc_ctx* c, int W) { return screen_instance(c->rw, c->rdm != nullptr, W, c->idx_lines); }
-Inst<confirm_fn> confirm_kernel(const musc_ctx* c, bool mask, int W) { return confirm_instance(c->rw, mask, W); }
-
-// workgroups of the screen stage: the descriptor buffer is cut into that many regions.  k_screen_t's
-// workgroups are single waves that stay for the whole launch: as many as are resident at once (a
-// second, thinner round of them would cost what a full one does).
-unsigned screen_grid(musc_ctx* c, uint32_t n, bool mask) {
-  unsigned g = std::min(nblk(n, TILE), MAX_GRID);
-  if (screen_lane(c, mask)) {
-    if (!c->scrt_resident) {
-      int per_cu = 0, ncu = 0;
-      const void* fn = reinterpret_cast<const void*>(screen_t_kernel(c).fn);
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 8; }
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu < 1) ncu = 256;
-      c->scrt_resident = (unsigned)per_cu * (unsigned)ncu;
-      c->scrt_rw = c->rw;
-    }
-    if (c->scrt_rw != c->rw) { c->scrt_resident = 0; return screen_grid(c, n, mask); }
-    g = std::min(g, std::min(c->scrt_resident, MAX_GRID));
-  }
-  return g;
-}
-
-void launch_screen(musc_ctx* c, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
-  const dim3 sgrid(screen_grid(c, n, mask));
-  auto& b = c->bs[c->cur];
-  if (screen_lane(c, mask)) {
-    const auto k = screen_t_kernel(c);
-    c->last_inst[1] = k.id;
-    hipLaunchKernelGGL(k.fn, sgrid, dim3(64), 0, c->stream, c->rd, r0, n, c->d_pp, c->nmiss_tab.p,
-                       reinterpret_cast<const LineBucket*>(c->idx_T), c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p,
-                       b.tbase.p, b.tcount.p, c->counters + 8, c->counters + 3);
-  } else {
-    const auto k = screen_kernel(c, pp.W);
-    c->last_inst[1] = k.id;
-    hipLaunchKernelGGL(k.fn, sgrid, dim3(TILE), 0, c->stream, c->rd, c->rdm, r0, n, c->rw, c->d_pp,
-                       c->nmiss_tab.p, c->idx_T, c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p, b.tbase.p, b.tcount.p,
-                       c->counters + 8, c->counters + 3);
-  }
-}
-
-void launch_confirm(musc_ctx* c, bool mask, uint64_t r0, uint32_t n, const PathParams& pp) {
-  // persistent over tiles; the MaxMatches screening threshold assumes at most MAX_GRID workgroups
-  const dim3 grid(std::min(nblk(n, TILE), MAX_GRID));
-  static_assert((1u << 24) / TILE / MAX_GRID <= CONF_TILES, "a k_confirm workgroup keeps its tile list in LDS");
-  const size_t lds = c->cur_block_mode ? (size_t)TILE * pp.W * 4 : 0;
-  auto& b = c->bs[c->cur];
-  const auto k = confirm_kernel(c, mask, pp.W);
-  c->last_inst[2] = k.id;
-  hipLaunchKernelGGL(k.fn, grid, dim3(TILE), lds, c->s_confirm, c->rd, c->rdm, c->db2, c->dbm2,
-                     c->dbx, r0, n, c->rw, c->d_pp, c->nmiss_tab.p, b.cdesc.p, b.rvalid.p, c->p_nx.p, b.tbase.p, b.tcount.p,
-                     b.wb.p, c->cur_block_mode, c->cur_block_thr, c->block_table.p, c->seq_off, c->stage.p, c->tcount2.p,
-                     c->counters);
-}
-
 }  // namespace
 
 extern "C" {
@@ -801,11 +679,11 @@ int musc_init(int device_ordinal, musc_ctx** out) {
       (e = hipEventCreateWithFlags(&c->ev_free[0], hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&c->ev_free[1], hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipMalloc((void**)&c->counters, 16 * sizeof(unsigned long long))) != hipSuccess ||
+      (e = hipMalloc((void**)&c->counters, CNT_WORDS * sizeof(unsigned long long))) != hipSuccess ||
       (e = hipMalloc((void**)&c->d_flag, 4)) != hipSuccess ||
       (e = hipMalloc((void**)&c->d_mp, sizeof(MatchParams))) != hipSuccess ||
       (e = hipMalloc((void**)&c->d_pp, sizeof(PathParams))) != hipSuccess ||
-      (e = hipHostMalloc((void**)&c->h_pinned, 16 * sizeof(uint64_t))) != hipSuccess) {
+      (e = hipHostMalloc((void**)&c->h_pinned, CNT_WORDS * sizeof(uint64_t))) != hipSuccess) {
     fail(nullptr, 3, "musc_init: %s", hipGetErrorString(e));
     musc_destroy(c);
     return 3;
@@ -890,10 +768,10 @@ static int db_finish(musc_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(&hasx, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
   // the longest target
   unsigned long long tl = 0;
-  HIPCHK(c, hipMemsetAsync(c->counters + 4, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(c->nseq, 256), MAX_GRID)), dim3(256), 0, c->stream, c->seq_off, (uint64_t)c->nseq, c->counters + 4);
+  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(c->nseq, 256), MAX_GRID)), dim3(256), 0, c->stream, c->seq_off, (uint64_t)c->nseq, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(&tl, c->counters + 4, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&tl, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->max_tlen = tl;
   c->db_has_x = hasx != 0;
@@ -1612,10 +1490,10 @@ static int reads_load(musc_ctx* c, const unsigned char* ascii, const uint8_t* ba
     HIPCHK(c, hipMemcpyAsync(d_off, offsets, (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
     offp = d_off;
   }
-  HIPCHK(c, hipMemsetAsync(c->counters + 4, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(nreads, 256), MAX_GRID)), dim3(256), 0, c->stream, offp, nreads, c->counters + 4);
+  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(nreads, 256), MAX_GRID)), dim3(256), 0, c->stream, offp, nreads, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + 4, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
   uint64_t first = 0, total = 0;
   HIPCHK(c, hipMemcpyAsync(&first, offp, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&total, offp + nreads, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1797,697 +1675,14 @@ int musc_reads_load_packed(musc_ctx* c, const uint8_t* bases2bit, const uint8_t*
 
 // ---------------------------------------------------------------- hot path
 
-// One pass on context buckets: per batch k_match (screen + confirm + select, tuples staged per
-// workgroup) -> scan of the per-tile tuple counts -> k_compact.  The only data-dependent
-// capacities are the staging region and the spill region of a workgroup; the first pass over a
-// (reads, database, parameters) combination sizes them (a batch that does not fit makes the pass
-// start over with larger buffers), later passes run without host round trips and check the
-// guards once at the end -- the same protocol as the two-kernel path below.
-extern "C++" {
-static size_t match_dyn_lds(int kind, int W, int block_mode) {
-  // per-(window, read) counters of the wave-tile in hand (k_match_t: of two wave-tiles), then (mode 1) the sketch
-  if (kind == MK_DMA) return block_mode == 1 ? (size_t)(4u << MATCHG_SKETCH_BITS) : 0u;  // (its per-(window, read) counters are registers)
-  const size_t wcnt = (size_t)TILE * W * 4 * (kind == MK_LANE ? 2 : 1);  // TILE = 4 waves x 64
-  return block_mode ? wcnt + (block_mode == 1 ? (4u << MATCH_SKETCH_BITS) : 0u) : 0u;
-}
-
-// The fused-kernel instance a pass launches (nullptr: none is built for the run); the occupancy query and the launch
-// both take it from here.  Instances (kernels_match_lane_inst.hpp): k_match_t on 120-base buckets for records of 4, 8,
-// 12 words and on wide ones for 4 to 16, each for 1-4 windows and three X modes; the geometry-specialised
-// k_match_t<8, 2, 0, false, 1>; k_match_g<8, 0 | 1>.
-typedef Inst<match_kernel_t> MatchInst;  // pointer and descriptor from one table entry, as on the two-kernel path
-#define INST_T(RW, W, XM, WD, SG) MatchInst{k_match_t<RW, W, XM, WD, SG>, inst_id(MUSC_INST_MATCH_T, RW, W, XM, WD, SG)}
-#define INST_G(RW, SG) MatchInst{k_match_g<RW, SG>, inst_id(MUSC_INST_MATCH_G, RW, 0, 0, 0, SG)}
-template <int RW, bool WD>
-static MatchInst lane_instance(int W, int xm) {
-  static const MatchInst k[4][3] = {
-      {INST_T(RW, 1, 0, WD, 0), INST_T(RW, 1, 1, WD, 0), INST_T(RW, 1, 2, WD, 0)},
-      {INST_T(RW, 2, 0, WD, 0), INST_T(RW, 2, 1, WD, 0), INST_T(RW, 2, 2, WD, 0)},
-      {INST_T(RW, 3, 0, WD, 0), INST_T(RW, 3, 1, WD, 0), INST_T(RW, 3, 2, WD, 0)},
-      {INST_T(RW, 4, 0, WD, 0), INST_T(RW, 4, 1, WD, 0), INST_T(RW, 4, 2, WD, 0)}};
-  return k[(W >= 1 && W <= 3 ? W : 4) - 1][xm];
-}
-
-// (kind, spec_geom: what match_kind and spec_geom_matches decided for the run)
-static MatchInst match_instance(int kind, int spec_geom, int rw, bool wide, int W, int xm) {
-  if (kind == MK_DMA) return spec_geom == 1 ? INST_G(8, 1) : INST_G(8, 0);
-  if (spec_geom == 1) return INST_T(8, 2, 0, false, 1);  // (chosen by spec_geom_matches: every specialised quantity equals the run's)
-  return by_rw(rw, [&](auto r) -> MatchInst {
-    constexpr int RW = decltype(r)::value;
-    if constexpr (RW == 0) return MatchInst{nullptr, 0};
-    else if (wide) return lane_instance<RW, true>(W, xm);
-    else if constexpr (RW <= 12) return lane_instance<RW, false>(W, xm);
-    else return MatchInst{nullptr, 0};
-  });
-}
-
-static MatchInst match_kernel(const musc_ctx* c, int W) {
-  const int xm = c->db_has_x ? 2 : c->reads_have_x ? 1 : 0;
-  return match_instance(match_kind(c, W), c->spec_geom, c->rw, c->idx_wide != 0, W, xm);
-}
-
-// workgroups of the kernel that are resident at once on this device: the persistent grid
-static unsigned match_resident(musc_ctx* c, match_kernel_t kern, int W, int block_mode) {
-  int per_cu = 0, ncu = 0;
-  const size_t lds = match_dyn_lds(match_kind(c, W), W, block_mode);
-  const void* fn = reinterpret_cast<const void*>(kern);
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, TILE, lds);
-  if (e != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; }
-  // The occupancy query counts LDS to the byte; the hardware hands it out in larger pieces
-  // (measured on gfx950: 3 x 54 208 B did not fit a CU's 160 KB, 3 x 52 160 B did), and a grid one
-  // workgroup per CU too large runs its last third as a second round (+45 % on cfg3).  Bound the
-  // count with 2 KB pieces.
-  {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, fn) == hipSuccess) {
-      const size_t total = ((size_t)fa.sharedSizeBytes + lds + 2047) / 2048 * 2048;
-      const int fit = total ? (int)((160u << 10) / total) : per_cu;
-      if (fit >= 1 && fit < per_cu) per_cu = fit;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu < 1) ncu = 256;
-  unsigned resident = (unsigned)per_cu * (unsigned)ncu;
-  if (c->env.debug_grid >= 1 && (unsigned)c->env.debug_grid < resident) resident = (unsigned)c->env.debug_grid;  // tests: a small grid makes every wave walk many wave-tiles of a small input
-  return resident;
-}
-
-static void launch_match(musc_ctx* c, match_kernel_t kern, uint64_t r0, uint32_t n, int W, int block_mode, uint32_t block_thr,
-                         unsigned ngrid) {
-  const size_t lds = match_dyn_lds(match_kind(c, W), W, block_mode);
-  const uint32_t* const rdx = c->reads_have_x ? (const uint32_t*)c->rdx.p : (const uint32_t*)nullptr;
-  hipLaunchKernelGGL(kern, dim3(ngrid), dim3(TILE), lds, c->stream, c->rd, r0, n, c->d_mp, c->nmiss_tab.p, c->ctx_T,
-                     c->ctx_E, c->stage.p, c->stage.cap, c->spill.p, c->spill.cap, c->bs[0].tbase.p, c->tcount2.p,
-                     block_mode, block_thr, c->block_table.p, c->counters, rdx);
-}
-}  // extern "C++"
-
-static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits);
-static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits);
-
-// The geometry-specialised instance a pass may launch: SpecGeom<g> is taken only when EVERY quantity it turns into
-// a constant equals the run's -- window width, window starts, context offset, MinDinuc, the first-window sets, and
-// the TABLE: a direct table of 2 * ww bits (cfg2's 10^8-base database gets a hashed 2^27-bucket table for the same
-// ww: the general instance) -- and the instance exists for this record stride / bucket width / X mode.  Reads of
-// other lengths than the geometry's are fine: the instance falls back to per-lane length masks for such a tile.
-// MUSC_NO_SPEC=1 keeps every pass on the general instances (A/B runs, tests).
-extern "C++" {
-template <int SG>
-static bool spec_geom_equals(const MatchParams& mp) {
-  typedef SpecGeom<SG> G;
-  if (mp.W != G::nwin || mp.ww != G::ww || mp.CL != G::CL || mp.min_dinuc != G::min_dinuc || mp.direct != 1 || mp.bits != 2 * G::ww) return false;
-  for (int k = 0; k < G::nwin; k++)
-    if (mp.win[k] != G::win[k] || mp.need[k] != (1u << k) - 1u) return false;
-  return true;
-}
-}  // extern "C++"
-static int spec_geom_matches(const musc_ctx* c, const MatchParams& mp) {
-  if (c->env.no_spec) return 0;
-  if (c->rw != 8 || c->idx_wide || c->db_has_x || c->reads_have_x) return 0;  // the instances that exist: <8, 2, 0, false, g>
-  if (spec_geom_equals<1>(mp)) return 1;
-  return 0;
-}
-
-static int match_ctx_pass(musc_ctx* c, const musc_params* P, const PathParams& pp, int block_mode, uint64_t max_matches, uint64_t planned_batches, uint64_t* nhits) {
-  int rc = 0;
-  if (c->rw != 4 && c->rw != 8 && c->rw != 12 && !(c->rw == 16 && c->idx_wide))
-    return fail(c, 12, "internal: record stride %d on the context path", c->rw);
-  // the run's parameter block (and with it the kernel instance: match_kernel looks at c->spec_geom)
-  {
-    static thread_local MatchParams mp;  // 16 KB with its mask tables: not on the stack
-    memset(&mp, 0, sizeof mp);
-    mp.W = pp.W; mp.ww = pp.ww; mp.min_dinuc = pp.min_dinuc; mp.bits = pp.bits; mp.direct = pp.direct;
-    mp.mmtol = pp.mmtol; mp.apply_mmtol = pp.apply_mmtol; mp.max_len = pp.max_len; mp.CL = c->idx_CL;
-    mp.q1zero_mask = pp.q1zero_mask;
-    mp.seq_off = c->db_has_x ? c->seq_off : nullptr;
-    mp.dbm2 = c->db_has_x ? c->dbm2 : nullptr;
-    for (int k = 0; k < pp.W && k < CTX_MAX_W; k++) mp.win[k] = pp.win[k];
-    match_tables(mp);
-    c->spec_geom = spec_geom_matches(c, mp);
-    c->stats.match_variant = (match_kind(c, pp.W) == MK_DMA ? 4u : 2u) + (c->spec_geom ? 1u : 0u);
-    if (!c->h_mp_valid || memcmp(&mp, &c->h_mp, sizeof mp) != 0) {
-      c->h_mp = mp;
-      HIPCHK(c, hipMemcpyAsync(c->d_mp, &c->h_mp, sizeof mp, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      c->h_mp_valid = true;
-    }
-  }
-  // the persistent grid = the workgroups that are resident at once (every wave then sees many
-  // wave-tiles and the end-of-kernel atomics stay few); the MaxMatches screening threshold is per
-  // workgroup-launch, so it follows the grid
-  // (The waves of a launch do not run at one speed -- r04: the slowest wave of a cfg3 launch takes 1.2-1.3 x the mean --
-  // which looks like a tail a dynamically dispatched grid would remove.  It does not: 2 / 4 / 8 / 16 times the resident
-  // workgroups run the cfg3 launch in 1.03 / 1.04 / 1.06 / 1.11 ms against 0.98-0.99 (profiles/r04_ab_shape_spec_dma.txt).
-  // The memory system is the shared resource: the waves that finish early leave their share to the slow ones.)
-  const MatchInst inst = match_kernel(c, pp.W);
-  const match_kernel_t kern = inst.fn;
-  c->last_inst[0] = inst.id;
-  if (!kern) return fail(c, 12, "internal: no fused kernel instance for record stride %d, %d windows", c->rw, pp.W);
-  const unsigned resident = match_resident(c, kern, pp.W, block_mode);
-  uint32_t block_thr = (uint32_t)std::min<uint64_t>(max_matches / (planned_batches * resident), 0x7FFFFFFFull);
-  if (block_mode == 1 && block_thr < 2) block_mode = 2;
-  c->last_inst[3] = (uint32_t)block_mode | (c->force_exact_blocks ? 0x100u : 0u);
-  if (block_mode == 2 && !c->block_table.p) {
-    if ((rc = ensure(c, c->block_table, 1ull << BLOCK_TABLE_BITS))) return rc;
-  }
-  const bool check_blocks = block_mode != 0;
-  const bool sized = c->sized_epoch == c->data_epoch && c->sized_exact_blocks == (block_mode == 2) &&
-                     memcmp(&c->sized_params, P, sizeof *P) == 0 && !c->env.debug_sync;
-  uint32_t bsz = sized ? c->sized_bsz : c->batch_reads;
-  // A pass that starts with an upload in flight takes its batches from the upload's schedule (stream_plan: whole pieces,
-  // tapered towards the end), every attempt of it.  Such a pass sizes itself (the reads are new) and leaves the context
-  // UNSIZED: a later pass over the same reads finds them resident, sizes itself on uniform batches and is the one later
-  // passes replay -- the tapered schedule is never replayed against resident reads, where small batches only cost.
-  bool streamed = c->up.active && !sized;
-  const uint64_t L = c->max_len;
-  // A sized pass can be replayed as a hipGraph (MUSC_GRAPH=1): its launches, the counter memsets
-  // and the final readback are captured once per (reads, database, parameters) and then cost one
-  // launch per pass.  Every buffer of a sized pass is fixed, so the captured arguments stay valid;
-  // any pass that sizes drops the graph.
-  const bool use_graph = sized && c->env.graph > 0 && !c->graph_failed;
-  if (!sized && c->graph_exec) {
-    (void)hipGraphExecDestroy(c->graph_exec);
-    c->graph_exec = nullptr;
-  }
-  // A batch's staged tuples go to their place in `hits` by a k_compact_w of their own.  (r02 / r03 moved them from inside
-  // the NEXT batch's match launch instead; r04's A/B on cfg3 / the cfg4 shard, profiles/r04_ab_shape_spec_dma.txt: the pass
-  // takes the same time either way, but the match launch grows by work its algorithmic bytes do not bill.)
-  for (int attempt = 0;; attempt++) {
-    if (attempt > 40) return fail(c, 12, "internal: the context pass did not converge on buffer sizes");
-    Timer tm(c);
-    hipEvent_t ev0 = pool_event(c), ev1 = pool_event(c);
-    if (!ev0 || !ev1) return fail(c, 10, "hipEventCreate failed");
-    const bool replay = use_graph && c->graph_exec && c->graph_epoch == c->data_epoch && c->graph_block_mode == block_mode &&
-                        memcmp(&c->graph_params, P, sizeof *P) == 0;
-    const bool capture = use_graph && !replay;
-    if (capture && c->graph_exec) {
-      (void)hipGraphExecDestroy(c->graph_exec);
-      c->graph_exec = nullptr;
-    }
-    tm.off = capture || replay;
-    CaptureGuard cap;  // (ends the capture if this attempt leaves early)
-    if (!replay) {
-      if (capture) {
-        if (cap.begin(c->stream) != hipSuccess) {  // no capture on this stream: the plain sized pass
-          (void)hipGetLastError();
-          c->graph_failed = true;
-          return match_index_pass(c, P, nhits);
-        }
-      } else {
-        HIPCHK(c, hipEventRecord(ev0, c->stream));
-      }
-    }
-    uint64_t n_cand = 0, n_cmp = 0, n_windows = 0, n_ovf = 0, r0 = 0;
-    c->stats.n_batches = 0;
-    c->stats.match_launches = 0;
-    bool again = false;
-    if (!replay) {
-      HIPCHK(c, hipMemsetAsync(c->counters, 0, 16 * sizeof(unsigned long long), c->stream));
-      if (block_mode == 2) HIPCHK(c, hipMemsetAsync(c->block_table.p, 0, (1ull << BLOCK_TABLE_BITS) * 4, c->stream));
-    }
-    while (!replay && r0 < c->nreads) {
-      const uint32_t n = (uint32_t)(streamed ? stream_plan_batch(c->up.plan, r0) : std::min<uint64_t>(bsz, c->nreads - r0));
-      const uint32_t ntiles = nblk(n, WT);  // wave-tiles of 64 reads
-      const uint64_t sgrid = std::min<uint64_t>(nblk(n, TILE), resident);
-      const uint64_t swaves = sgrid * (TILE / 64);  // regions of stage and spill are per wave
-      if (!sized) {
-        if ((rc = ensure(c, c->bs[0].tbase, (uint64_t)ntiles + 1))) return rc;
-        if ((rc = ensure(c, c->scan_tmp, scan_tmp_elems((uint64_t)ntiles + 1)))) return rc;
-        if ((rc = ensure(c, c->tcount2, (uint64_t)ntiles + 1))) return rc;
-        if ((rc = ensure(c, c->tpre, (uint64_t)ntiles + 1))) return rc;
-        // (a first pass provides for 2 n staged tuples; tests/test_stats_model.py: test_heavy_reads_outgrow_a_first_pass
-        // restates this figure so that the growing case of tests/test_gpu_stats.py does grow -- keep the two in step)
-        if ((rc = ensure(c, c->stage, std::max<uint64_t>(2ull * n, swaves * 64)))) return rc;
-        if ((rc = ensure(c, c->spill, swaves * 32))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8 * sizeof(unsigned long long), c->stream));
-      }
-      if ((rc = upload_prepare(c, r0, n, c->stream))) return rc;  // (reads still on their way from the host)
-      tm.begin(0);
-      {
-        Range rg("k_match");
-        launch_match(c, kern, r0, n, pp.W, block_mode, block_thr, (unsigned)sgrid);
-      }
-      HIPCHK(c, hipGetLastError());
-      tm.end(0);
-      c->stats.match_launches++;
-      c->stats.n_batches++;
-      if (!sized) {
-        HIPCHK(c, hipMemcpyAsync(&c->h_pinned[0], c->counters, 16 * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        // (k_match_t keeps a spill region per wave and wave-tile parity)
-        const uint64_t need_stage = c->h_pinned[8 + 7] * swaves, need_spill = 2 * c->h_pinned[8 + 5] * swaves;
-        if (need_stage > (1ull << 31)) {  // u32 tuple offsets within a batch: retry with half the reads
-          if (n == 1) return fail(c, 6, "one read has %llu tuples (> 2^31)", (unsigned long long)c->h_pinned[8 + 7]);
-          bsz = n / 2;
-          streamed = false;  // (uniform batches of the halved size from here on)
-          again = true;
-          break;
-        }
-        if (c->h_pinned[3] & 8ull)
-          return fail(c, 12, "internal: the kernel instance specialised for geometry %d refused this run's parameters", c->spec_geom);
-        if (c->h_pinned[3] || need_stage > c->stage.cap || need_spill > c->spill.cap) {
-          // room for every workgroup's tuples / spilled candidates, then the pass starts over
-          // (k_match has already added this batch to the pass-level counters)
-          if (need_stage > c->stage.cap && (rc = ensure(c, c->stage, need_stage + need_stage / 4 + swaves))) return rc;
-          if (need_spill > c->spill.cap && (rc = ensure(c, c->spill, need_spill + need_spill / 4 + swaves))) return rc;
-          again = true;
-          break;
-        }
-        n_windows += c->h_pinned[8 + 0];
-        n_cmp += c->h_pinned[8 + 1];
-        n_cand += c->h_pinned[8 + 3];
-        n_ovf += c->h_pinned[8 + 4];
-        if ((rc = ensure(c, c->hits, c->h_pinned[2] + c->h_pinned[8 + 6], true))) return rc;
-      }
-      Range rgc("scan + k_compact_w");
-      tm.begin(4);
-      tm.begin(1);
-      rc = scan_u32(c, c->tcount2.p, c->tpre.p, (uint64_t)ntiles + 1, false, c->scan_tmp.p, c->stream);
-      if (rc) return rc;
-      tm.end(1);
-      hipLaunchKernelGGL(k_compact_w, dim3(std::min(nblk(ntiles, 4), 4u * MAX_GRID)), dim3(256), 0, c->stream, ntiles,
-                         c->bs[0].tbase.p, c->tcount2.p, c->tpre.p, c->stage.p, reinterpret_cast<uint4*>(c->hits.p),
-                         c->hits.cap, c->counters);
-      HIPCHK(c, hipGetLastError());
-      hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, c->stream, c->tpre.p, ntiles, c->counters);
-      HIPCHK(c, hipGetLastError());
-      tm.end(4);
-      r0 += n;
-    }
-    if (again) continue;
-    c->last_pp = pp;
-    c->last_max_matches = (uint32_t)max_matches;
-    c->last_exact_blocks = block_mode == 2;
-    if (!replay) {
-      if (block_mode == 2) {
-        hipLaunchKernelGGL(k_block_overflow, dim3(1024), dim3(256), 0, c->stream, c->block_table.p, (uint32_t)max_matches,
-                           c->counters);
-        HIPCHK(c, hipGetLastError());
-      }
-      if (!capture) HIPCHK(c, hipEventRecord(ev1, c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters, 16 * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (capture) {
-      hipGraph_t g = nullptr;
-      hipError_t ge = cap.end(&g);
-      if (ge == hipSuccess) ge = hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0);
-      if (g) (void)hipGraphDestroy(g);
-      if (ge != hipSuccess) {  // the graph is an optimisation: without it the pass runs launch by launch
-        (void)hipGetLastError();
-        c->graph_exec = nullptr;
-        c->graph_failed = true;
-        return match_index_pass(c, P, nhits);
-      }
-      c->graph_epoch = c->data_epoch;
-      c->graph_params = *P;
-      c->graph_block_mode = block_mode;
-      c->graph_batches = c->stats.n_batches;
-    }
-    if (capture || replay) {
-      c->stats.n_batches = c->stats.match_launches = c->graph_batches;
-      HIPCHK(c, hipEventRecord(ev0, c->stream));
-      HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
-      HIPCHK(c, hipEventRecord(ev1, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_pinned[3] & 8ull)
-      return fail(c, 12, "internal: the kernel instance specialised for geometry %d refused this run's parameters", c->spec_geom);
-    if (c->h_pinned[3]) {
-      if (!sized) return fail(c, 12, "internal: a capacity guard fired although every batch was sized (flags %llu)",
-                              (unsigned long long)c->h_pinned[3]);
-      c->sized_epoch = 0;  // the pass did not fit after all: run it the careful way
-      return match_index_pass(c, P, nhits);
-    }
-    if (sized) {
-      n_windows = c->h_pinned[8 + 0];
-      n_cmp = c->h_pinned[8 + 1];
-      n_cand = c->h_pinned[8 + 3];
-      n_ovf = c->h_pinned[8 + 4];
-    }
-    c->stats.n_read_windows = n_windows;
-    c->stats.n_candidates = n_cand;
-    c->stats.n_pairs = n_cmp;
-    c->stats.n_descriptors = 0;
-    c->stats.n_overflow_entries = n_ovf;
-    c->stats.n_accepted = c->h_pinned[1];
-    c->stats.n_hits = c->nhits = c->h_pinned[2];
-    c->stats.n_overflow_blocks = check_blocks ? c->h_pinned[5] : ~0ull;
-    if (block_mode == 1 && (c->h_pinned[6] || c->stats.n_batches > planned_batches)) {
-      c->force_exact_blocks = true;  // screening inconclusive: repeat with exact per-block counters
-      c->exact_epoch = c->data_epoch;
-      c->exact_params = *P;
-      rc = match_index_pass(c, P, nhits);
-      c->force_exact_blocks = false;
-      return rc;
-    }
-    c->stats.ms_screen = tm.total(0);
-    c->stats.ms_scan = tm.total(1);
-    c->stats.ms_select = tm.total(4);
-    (void)hipEventElapsedTime(&c->stats.ms_total, ev0, ev1);
-    const uint64_t rec_b = (2 * L + 7) / 8;
-    const uint64_t ent_b = c->idx_wide ? sizeof(CtxEntryW) : sizeof(CtxEntry);
-    c->stats.match_bytes = c->nreads * rec_b + n_windows * sizeof(CtxBucket) + n_ovf * ent_b + 16 * c->stats.n_hits;
-    c->stats.match_bytes_strict = c->nreads * rec_b + n_windows * 8 + n_cand * ent_b + 16 * c->stats.n_hits;
-    if (nhits) *nhits = c->nhits;
-    c->sized_epoch = streamed ? 0 : c->data_epoch;  // (see `streamed` above)
-    c->sized_params = *P;
-    c->sized_exact_blocks = block_mode == 2;
-    c->sized_bsz = bsz;
-    return 0;
-  }
-}
-
-// musc_reads_load_packed32(async = 1) borrows the caller's host buffer "until the next musc_match* returns": that holds
-// on every exit -- a pass that fails early (parameters, no database, an index that cannot be built, a HIP error in a
-// batch) waits for the copies still queued on the upload stream before it returns.  The pieces stay valid on the
-// device, so a later pass packs and matches them.
-int musc_match_device(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
-  if (!c) return 1;
-  c->hits_current = false;
-  const int rc = match_device_impl(c, P, nhits);
-  if (rc != 0 && c->up.active && c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);
-  c->hits_current = rc == 0;
-  return rc;
-}
-
 static int match_partitioned(musc_ctx* c, const musc_params* P, uint64_t* nhits);
 
-static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
-  Range rg_pass("musc_match_device");
-  int rc = check_params(c, P);
-  if (rc) return rc;
-  if (!c->db2) return fail(c, 4, "no database loaded");
-  if (!c->rd && c->nreads) return fail(c, 4, "no reads loaded");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = plan_partitions(c, P, c->max_len))) return rc;
-  c->cur_part = 0;
-  if (c->part_first.size() > 2) return match_partitioned(c, P, nhits);
-  return match_index_pass(c, P, nhits);
-}
+}  // extern "C"
 
-// One pass over the resident index (of the whole database, or of partition cur_part of a partitioned pass)
-static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
-  int rc = ensure_index(c, P, c->max_len);
-  if (rc) return rc;
+// the pass driver and musc_match_device (C++: templates of kernel instances)
+#include "muscato_pass.hpp"
 
-  const float keep_index_ms = c->stats.ms_index_build;
-  memset(&c->stats, 0, sizeof c->stats);
-  c->stats.ms_index_build = keep_index_ms;
-  c->stats.n_reads = c->nreads;
-  c->nhits = 0;
-  if (nhits) *nhits = 0;
-
-  PathParams pp;
-  memset(&pp, 0, sizeof pp);
-  pp.W = P->n_windows;
-  pp.ww = P->window_width;
-  pp.min_dinuc = P->min_dinuc;
-  pp.bits = c->idx_bits;
-  pp.direct = c->idx_direct;
-  pp.mmtol = P->mmtol > 0xFFFF ? 0xFFFF : P->mmtol;
-  pp.apply_mmtol = P->apply_mmtol;
-  pp.wide = c->wide;
-  pp.max_len = (int32_t)c->max_len;
-  for (int k = 0; k < pp.W; k++) {
-    pp.win[k] = P->windows[k];
-    if (P->windows[k] == 0) pp.q1zero_mask |= 1u << k;
-  }
-
-  // nmiss budget per read length: int((1-PMatch)*float64(len)), IEEE double, truncation
-  // (cmd/muscato_confirm/main.go:198) -- evaluated on the host exactly as Go does.
-  if (c->nm_pmatch != P->pmatch || c->nm_mmp1 != P->max_mismatch_p1 || c->nm_maxlen != c->max_len || !c->nmiss_tab.p) {
-    std::vector<uint16_t> tab((size_t)c->max_len + 2);
-    for (uint32_t L = 0; L < tab.size(); L++) {
-      volatile double a = 1.0 - P->pmatch;
-      volatile double b = a * (double)L;
-      long long v = (long long)b;
-      if (P->max_mismatch_p1 > 0) v = P->max_mismatch_p1 - 1;  // --MaxMismatch addition
-      if (v < 0) v = 0;
-      if (v > 0xFFFE) v = 0xFFFE;
-      tab[L] = (uint16_t)v;
-    }
-    rc = ensure(c, c->nmiss_tab, tab.size());
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->nmiss_tab.p, tab.data(), tab.size() * 2, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // tab goes out of scope
-    c->nm_pmatch = P->pmatch;
-    c->nm_mmp1 = P->max_mismatch_p1;
-    c->nm_maxlen = c->max_len;
-  }
-
-  HIPCHK(c, hipMemsetAsync(c->counters, 0, 8 * sizeof(unsigned long long), c->stream));
-  // MaxMatches accounting (see k_confirm): screening first, exact only if inconclusive
-  // (a pass that starts with an upload in flight runs on the upload's schedule, stream_plan: its batch count)
-  const uint64_t planned_batches = c->up.active ? std::max<uint64_t>(c->up.plan.batch_end.size(), 1)
-                                                : (c->nreads + c->batch_reads - 1) / c->batch_reads + 1;
-  uint64_t max_matches = P->max_matches > 0 ? (uint64_t)P->max_matches : 0x7FFFFFFFull;
-  if (P->n_shards > 1) max_matches /= (uint64_t)P->n_shards;  // this context sees one shard of each block
-  const uint32_t block_thr = (uint32_t)std::min<uint64_t>(max_matches / (planned_batches * MAX_GRID), 0x7FFFFFFFull);
-  const bool known_exact = c->exact_epoch == c->data_epoch && memcmp(&c->exact_params, P, sizeof *P) == 0;
-  int block_mode = P->skip_block_check ? 0 : (c->force_exact_blocks || known_exact || block_thr < 2 ? 2 : 1);
-  const bool check_blocks = block_mode != 0;
-  c->cur_block_mode = block_mode;
-  c->cur_block_thr = block_thr;
-  if (block_mode == 2) {
-    if ((rc = ensure(c, c->block_table, 1ull << BLOCK_TABLE_BITS))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->block_table.p, 0, (1ull << BLOCK_TABLE_BITS) * 4, c->stream));
-  }
-  if (!c->h_pp_valid || memcmp(&pp, &c->h_pp, sizeof pp) != 0) {
-    c->h_pp = pp;
-    HIPCHK(c, hipMemcpyAsync(c->d_pp, &c->h_pp, sizeof pp, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->h_pp_valid = true;
-  }
-  c->stats.index_kind = c->idx_kind == 1 ? (c->idx_wide ? 2u : 1u) : (c->idx_lines ? 3u : 0u);
-  c->stats.match_variant = 0;  // (match_ctx_pass says which fused kernel it launches)
-  c->last_inst[0] = c->last_inst[1] = c->last_inst[2] = 0;  // (the resolvers of this pass fill them in)
-  c->last_inst[3] = (uint32_t)block_mode | (c->force_exact_blocks ? 0x100u : 0u);
-  c->stats.index_bytes = c->idx_kind == 1
-                             ? ((1ull << c->idx_bits) + 1) * sizeof(CtxBucket) + ctx_entries_bytes(c->idx_novf + 16, c->idx_wide)
-                             : ((1ull << c->idx_bits) + 1) * (c->idx_lines ? sizeof(LineBucket) : sizeof(Bucket)) + (c->idx_novf + 16) * sizeof(uint4);
-  if (c->idx_kind == 1)
-    return match_ctx_pass(c, P, pp, block_mode, max_matches, planned_batches, nhits);
-
-  Timer tm(c);
-  hipEvent_t ev0 = pool_event(c), ev1 = pool_event(c);
-  if (!ev0 || !ev1) return fail(c, 10, "hipEventCreate failed");
-  HIPCHK(c, hipEventRecord(ev0, c->stream));
-
-  const bool mask = c->reads_have_x || c->db_has_x;  // (a stale all-zero plane of an earlier batch does not count)
-  // a mask plane on only one side: allocate the missing all-zero plane once
-  if (mask && !c->rdm && c->nreads) {
-    const uint64_t words = c->nreads * (uint64_t)c->rw;
-    HIPCHK(c, hipMalloc((void**)&c->rdm, words * 4 + 256));
-    HIPCHK(c, hipMemsetAsync(c->rdm, 0, words * 4 + 256, c->stream));
-  }
-  if (mask && !c->dbm2) {
-    HIPCHK(c, hipMalloc((void**)&c->dbm2, (c->db_words + 64) * 4));
-    // (the index stays valid: bucket_of treats a null and an all-zero mask plane alike)
-    HIPCHK(c, hipMemsetAsync(c->dbm2, 0, (c->db_words + 64) * 4, c->stream));
-    if ((rc = db_xblocks(c))) return rc;
-  }
-
-  // Per batch: k_screen claims descriptor space as it goes; if a batch needs more than the
-  // buffer holds it reports how much and is repeated after growing the buffer (the first pass
-  // of a workload sizes it).  A pass over the same reads, database and parameters as the last
-  // completed one ("sized") is known to fit and runs without any host round trip; every kernel
-  // still guards its writes, and the flags are checked once at the end.
-  const bool sized = c->sized_epoch == c->data_epoch && c->sized_exact_blocks == (block_mode == 2) &&
-                     memcmp(&c->sized_params, P, sizeof *P) == 0 && !c->env.debug_sync;
-  uint64_t n_cand = 0, n_pairs = 0, n_windows = 0, n_two = 0;
-  const uint64_t PAIR_CAP = 1ull << 31;  // u32 descriptor offsets
-  uint64_t r0 = 0;
-  uint32_t bsz = sized ? c->sized_bsz : c->batch_reads;
-  bool streamed = c->up.active && !sized;  // batches from the upload's schedule, and no sized state left behind: as in match_ctx_pass
-  if (sized) HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8 * sizeof(unsigned long long), c->stream));
-  // MUSC_PIPELINE=1: a sized pass of several batches is pipelined over two streams, k_screen of
-  // batch b+1 beside k_confirm + k_compact of batch b, alternating between the two batch sets.
-  // Off by default: measured on cfg3 / cfg4 / cfg5 shards the pass moves ~5.6 TB/s of cache lines
-  // through HBM either way (both kernels are bound by the lines they fetch), so overlapping them
-  // gains nothing (5.66 vs 5.44 ms on cfg3) and the second set costs memory.
-  const bool want_pipe = c->env.pipeline;
-  const bool piped = sized && want_pipe && c->nreads > bsz && c->bs[1].cdesc.cap >= c->bs[0].cdesc.cap;
-  hipStream_t sA = c->stream, sB = piped ? c->stream2 : c->stream;
-  c->s_confirm = sB;
-  c->cur = 0;
-  if (piped) {  // the confirm stream starts after the memsets above
-    HIPCHK(c, hipEventRecord(c->ev_join, sA));
-    HIPCHK(c, hipStreamWaitEvent(sB, c->ev_join, 0));
-  }
-  uint32_t batch_no = 0;
-  while (r0 < c->nreads) {
-    const uint32_t n = (uint32_t)(streamed ? stream_plan_batch(c->up.plan, r0) : std::min<uint64_t>(bsz, c->nreads - r0));
-    if (piped) {
-      c->cur = (int)(batch_no & 1u);
-      // the set is free once the batch before last has been compacted
-      if (batch_no >= 2) HIPCHK(c, hipStreamWaitEvent(sA, c->ev_free[c->cur], 0));
-    }
-    const int W = pp.W;
-    const uint32_t ntiles = nblk(n, TILE);
-    uint64_t total = 1;  // pairs of this batch (unknown on a sized pass)
-    if (!sized) {
-      if ((rc = ensure(c, c->bs[c->cur].wb, (uint64_t)n * W))) return rc;
-      if ((rc = ensure(c, c->bs[c->cur].rvalid, (uint64_t)n + 1))) return rc;
-      if ((rc = ensure(c, c->bs[c->cur].tbase, (uint64_t)ntiles + 1))) return rc;
-      if ((rc = ensure(c, c->bs[c->cur].tcount, (uint64_t)ntiles + 1))) return rc;
-      if ((rc = ensure(c, c->scan_tmp, scan_tmp_elems((uint64_t)ntiles + 1)))) return rc;
-      if ((rc = ensure(c, c->tcount2, (uint64_t)ntiles + 1))) return rc;
-      if ((rc = ensure(c, c->tpre, (uint64_t)ntiles + 1))) return rc;
-      // (a first pass provides for max(4 n, 1024) descriptors; tests/test_stats_model.py:
-      // test_heavy_reads_outgrow_a_first_pass restates this figure -- keep the two in step)
-      if ((rc = ensure(c, c->bs[c->cur].cdesc, std::max<uint64_t>(4ull * n, 1024)))) return rc;
-      // batch-local counters: [0] valid windows [3] candidates [4] pairs [7] descriptor cursor
-      HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8 * sizeof(unsigned long long), c->stream));
-    }
-
-    if ((rc = upload_prepare(c, r0, n, c->stream))) return rc;  // (reads still on their way from the host)
-    tm.begin(0);
-    {
-      Range rg("k_screen");
-      launch_screen(c, mask, r0, n, pp);
-    }
-    HIPCHK(c, hipGetLastError());
-    tm.end(0);
-    if (piped) {
-      HIPCHK(c, hipEventRecord(c->ev_ready[c->cur], sA));
-      HIPCHK(c, hipStreamWaitEvent(sB, c->ev_ready[c->cur], 0));
-    }
-    if (!sized) {
-      HIPCHK(c, hipMemcpyAsync(&c->h_pinned[0], c->counters + 8, 8 * 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(&c->h_pinned[8], c->counters + 2, 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      total = c->h_pinned[4];
-      const uint64_t hits_so_far = c->h_pinned[8];
-      const uint64_t sgrid = screen_grid(c, n, mask);
-      const uint64_t need = c->h_pinned[7] * sgrid;  // every workgroup region as large as the fullest
-      if (need > PAIR_CAP) {
-        // too many pairs for one launch: retry this range with half the reads
-        if (n == 1) return fail(c, 6, "one read has %llu candidate pairs (> 2^31)", (unsigned long long)total);
-        bsz = n / 2;
-        streamed = false;  // (uniform batches of the halved size from here on)
-        HIPCHK(c, hipMemsetAsync(c->counters + 3, 0, 8, c->stream));
-        continue;
-      }
-      if (c->h_pinned[7] > c->bs[c->cur].cdesc.cap / sgrid) {
-        if ((rc = ensure(c, c->bs[c->cur].cdesc, need + need / 8 + sgrid))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->counters + 3, 0, 8, c->stream));
-        continue;  // repeat the batch with room for every workgroup's pairs
-      }
-      n_windows += c->h_pinned[0];
-      n_cand += c->h_pinned[3];
-      n_pairs += c->h_pinned[4];
-      n_two += c->h_pinned[5];
-      if ((rc = ensure(c, c->p_nx, c->bs[c->cur].cdesc.cap))) return rc;
-      if ((rc = ensure(c, c->stage, c->bs[c->cur].cdesc.cap))) return rc;
-      if ((rc = ensure(c, c->hits, hits_so_far + total, true))) return rc;
-    }
-    c->stats.n_batches++;
-
-    if (total) {
-      const dim3 sg(std::min(nblk(n, TILE), MAX_GRID));
-
-      tm.begin(3, sB);
-      {
-        Range rg("k_confirm");
-        launch_confirm(c, mask, r0, n, pp);
-      }
-      HIPCHK(c, hipGetLastError());
-      tm.end(3, sB);
-      c->stats.confirm_launches++;
-
-      Range rgc("scan + k_compact");
-      tm.begin(4, sB);
-      tm.begin(1, sB);
-      rc = scan_u32(c, c->tcount2.p, c->tpre.p, (uint64_t)ntiles + 1, false, c->scan_tmp.p, sB);
-      if (rc) return rc;
-      tm.end(1, sB);
-      hipLaunchKernelGGL(k_compact, sg, dim3(256), 0, sB, ntiles, c->bs[c->cur].tbase.p, c->tcount2.p, c->tpre.p,
-                         c->stage.p, reinterpret_cast<uint4*>(c->hits.p), c->hits.cap, c->counters);
-      HIPCHK(c, hipGetLastError());
-      hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, sB, c->tpre.p, ntiles, c->counters);
-      HIPCHK(c, hipGetLastError());
-      tm.end(4, sB);
-    }
-    if (piped) HIPCHK(c, hipEventRecord(c->ev_free[c->cur], sB));
-    r0 += n;
-    batch_no++;
-  }
-  if (piped) {  // join: everything below is ordered after both streams
-    HIPCHK(c, hipEventRecord(c->ev_join, sB));
-    HIPCHK(c, hipStreamWaitEvent(sA, c->ev_join, 0));
-  }
-  c->cur = 0;
-  c->s_confirm = c->stream;
-  c->last_pp = pp;
-  c->last_max_matches = (uint32_t)max_matches;
-  c->last_exact_blocks = block_mode == 2;
-  if (block_mode == 2) {
-    hipLaunchKernelGGL(k_block_overflow, dim3(1024), dim3(256), 0, c->stream, c->block_table.p,
-                       (uint32_t)max_matches, c->counters);
-    HIPCHK(c, hipGetLastError());
-  }
-  HIPCHK(c, hipEventRecord(ev1, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters, 16 * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (sized) {
-    if (c->h_pinned[3]) {
-      // a guard fired: the pass did not fit after all -- forget the sizing and run it the careful way
-      c->sized_epoch = 0;
-      return match_index_pass(c, P, nhits);
-    }
-    n_windows = c->h_pinned[8];  // the batch-local block accumulated over the whole pass
-    n_cand = c->h_pinned[8 + 3];
-    n_pairs = c->h_pinned[8 + 4];
-    n_two = c->h_pinned[8 + 5];
-  } else if (c->h_pinned[3]) {
-    return fail(c, 12, "internal: a capacity guard fired although every batch was sized (flags %llu)",
-                (unsigned long long)c->h_pinned[3]);
-  }
-  c->stats.n_read_windows = n_windows;
-  c->stats.n_accepted = c->h_pinned[1];
-  c->stats.n_hits = c->nhits = c->h_pinned[2];
-  c->stats.n_descriptors = n_pairs;
-  c->stats.n_pairs = n_pairs + n_two;  // a two-window descriptor is two of the reference's candidate pairs
-  c->stats.n_candidates = n_cand;
-  // 0 = proven: no (window,key) block exceeded MaxMatches, the tuples equal the reference's;
-  // otherwise an upper bound on the number of such blocks (or ~0ull when the check was skipped)
-  c->stats.n_overflow_blocks = check_blocks ? c->h_pinned[5] : ~0ull;
-  if (block_mode == 1 && (c->h_pinned[6] || c->stats.n_batches > planned_batches)) {
-    // screening inconclusive (a hot sketch cell, or more launches than the threshold assumed):
-    // repeat the pass with exact per-block counters
-    c->force_exact_blocks = true;
-    c->exact_epoch = c->data_epoch;
-    c->exact_params = *P;
-    rc = match_index_pass(c, P, nhits);
-    c->force_exact_blocks = false;
-    return rc;
-  }
-  c->stats.ms_screen = tm.total(0);
-  c->stats.ms_scan = tm.total(1);
-  c->stats.ms_confirm = tm.total(3);
-  c->stats.ms_select = tm.total(4);
-  (void)hipEventElapsedTime(&c->stats.ms_total, ev0, ev1);
-  // 12 B descriptor + ceil(2L/8) B read + ceil(2L/8)+1 B target span per pair the
-  // launch loads, + 16 B per tuple written.  A launch loads one descriptor, one record and one
-  // span per DESCRIPTOR; a descriptor that stands for two windows is two of the reference's
-  // candidate pairs but is fetched once, so the bytes are billed per descriptor (the r01 figure
-  // billed them per pair and over-credited the kernel).
-  const uint64_t L = c->max_len;
-  c->stats.confirm_bytes = c->stats.n_descriptors * (12 + (2 * L + 7) / 8 + (2 * L + 7) / 8 + 1) + 16 * c->stats.n_hits;
-  if (nhits) *nhits = c->nhits;
-  if (!sized && want_pipe) {  // the second batch set gets the capacities the first one ended up with
-    if ((rc = ensure(c, c->bs[1].wb, c->bs[0].wb.cap)) || (rc = ensure(c, c->bs[1].rvalid, c->bs[0].rvalid.cap)) ||
-        (rc = ensure(c, c->bs[1].tbase, c->bs[0].tbase.cap)) || (rc = ensure(c, c->bs[1].tcount, c->bs[0].tcount.cap)) ||
-        (rc = ensure(c, c->bs[1].cdesc, c->bs[0].cdesc.cap)))
-      return rc;
-  }
-  c->sized_epoch = streamed ? 0 : c->data_epoch;
-  c->sized_params = *P;
-  c->sized_exact_blocks = block_mode == 2;
-  c->sized_bsz = bsz;
-  return 0;
-}
+extern "C" {
 
 // A partitioned pass: for each partition in turn its index is built and the per-index pass runs over
 // every read, with exact MaxMatches block counters (summed over the partitions, so that a block whose accepted pairs
@@ -2597,13 +1792,13 @@ static int match_partitions_run(musc_ctx* c, const musc_params* P, uint64_t* nhi
   // the MaxMatches verdict of the whole database: the summed exact counters, then the usual count of full blocks
   if (check_blocks) {
     HIPCHK(c, hipMemcpyAsync(c->block_table.p, c->block_acc.p, (uint64_t)BT * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->counters + 5, 0, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->counters + CNT_OVF_BLOCKS, 0, 8, c->stream));
     hipLaunchKernelGGL(k_block_overflow, dim3(1024), dim3(256), 0, c->stream, c->block_table.p, c->last_max_matches, c->counters);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(ev1, c->stream));
   c->h_pinned[1] = 0;
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + 5, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_OVF_BLOCKS, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->h_pinned[1]) return fail(c, 12, "internal: the partition merge overran its %llu tuples", (unsigned long long)total);
@@ -2856,12 +2051,12 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   uint32_t *multi = nullptr, *incl = nullptr, *idx = nullptr;
   HIPCHK(c, B.alloc(&multi, m * 4));
   HIPCHK(c, B.alloc(&incl, m * 4));
-  HIPCHK(c, hipMemsetAsync(c->counters + 4, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_results_segments, grid(m), B256, 0, c->stream, a, m, c->rd, c->rw, multi, c->counters + 4);
+  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_results_segments, grid(m), B256, 0, c->stream, a, m, c->rd, c->rw, multi, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, multi, incl, m, true, stmp))) return rc;  // (m <= n: stmp is large enough)
   HIPCHK(c, hipMemcpyAsync(h32, incl + (m - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->counters + 4, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint64_t k = h32[0], maxlen = c->h_pinned[1];
   if (k == 0) {
@@ -3246,17 +2441,17 @@ int musc_overflow_probes(musc_ctx* c, uint32_t** read_idx, uint32_t** window, ui
     TmpBufs B;  // released at the end of every iteration and on every return
     uint2* d_out = nullptr;
     HIPCHK(c, B.alloc(&d_out, cap * sizeof(uint2)));
-    HIPCHK(c, hipMemsetAsync(c->counters + 8, 0, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->counters + CNT_BATCH, 0, 8, c->stream));
     const dim3 grid(std::min(nblk(c->nreads, 256), MAX_GRID)), block(256);
     switch (c->rw) {
-      case 4: hipLaunchKernelGGL((k_hot_probes<4>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + 8); break;
-      case 8: hipLaunchKernelGGL((k_hot_probes<8>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + 8); break;
-      case 12: hipLaunchKernelGGL((k_hot_probes<12>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + 8); break;
-      case 16: hipLaunchKernelGGL((k_hot_probes<16>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + 8); break;
-      default: hipLaunchKernelGGL((k_hot_probes<0>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + 8); break;
+      case 4: hipLaunchKernelGGL((k_hot_probes<4>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+      case 8: hipLaunchKernelGGL((k_hot_probes<8>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+      case 12: hipLaunchKernelGGL((k_hot_probes<12>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+      case 16: hipLaunchKernelGGL((k_hot_probes<16>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+      default: hipLaunchKernelGGL((k_hot_probes<0>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
     }
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(c->h_pinned, c->counters + 8, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->h_pinned, c->counters + CNT_BATCH, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, 10, "musc_overflow_probes: %s", hipGetErrorString(e));
     const uint64_t found = c->h_pinned[0];

@@ -139,10 +139,10 @@ typedef TmpBufs PrepBufs;  // temporaries of musc_reads_sort_unique, released on
 static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const uint64_t* d_off, const uint64_t n,
                                  hipEvent_t e0, hipEvent_t e1, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
   PrepBufs B;
-  HIPCHK(c, hipMemsetAsync(c->counters + 4, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(n, 256), MAX_GRID)), dim3(256), 0, c->stream, d_off, n, c->counters + 4);
+  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(n, 256), MAX_GRID)), dim3(256), 0, c->stream, d_off, n, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + 4, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
   uint64_t first = 0;
   HIPCHK(c, hipMemcpyAsync(&first, d_off, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

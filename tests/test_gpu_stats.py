@@ -5,8 +5,8 @@ oracle's own window gate, k-mer index and fit rule, recounted on the CPU -- on e
 four windows and on wide buckets, k_match_g, 64-byte buckets with one and two windows, line buckets through k_screen_t
 and k_screen) and in every way a pass can run: the first, careful pass of a fresh context, the sized pass after it,
 hipGraph capture and replay, one batch and several with a ragged last one, a streamed load, a first pass that must
-grow its buffers and repeat a batch, the exact repeat of a pass whose MaxMatches screening was inconclusive, the
-selection on and off, partitions, X on either side, and a hashed table (bounds).
+grow its buffers and repeat a batch, the exact repeat of a pass whose MaxMatches screening was inconclusive (and the
+capture and replay that follow it with MUSC_GRAPH=1), the selection on and off, partitions, X on either side, and a hashed table (bounds).
 
 The database (tests/stats_cases.py) is 25 kbase with WindowWidth 6: every table is direct by the documented rules, so
 the comparisons are equalities.  last_instance() is asserted before any counter: a case that ran on another path than
@@ -258,6 +258,26 @@ def test_exact_rerun_reports_one_pass(path, batch):
     check(path, st, inst, exp, nb, path + " exact rerun")
     same(got, full, path)
     assert st["n_overflow_blocks"] == 0
+
+
+@pytest.mark.parametrize("batch", [None, BATCH], ids=["one-batch", "batch-1024"])
+@pytest.mark.parametrize("path", FUSED)
+def test_exact_rerun_then_graph(path, batch):
+    """The exact repeat and the hipGraph together (MUSC_GRAPH=1, fused paths): pass 1 of a fresh context trips the
+    screening and is repeated with exact block counters, as in test_exact_rerun_reports_one_pass.  Passes 2 and 3, over
+    the same reads and parameters, remember that: they start with exact counters (no repeat), find the context sized
+    by the repeat, and run as a hipGraph -- the capture, then the replay (ms_screen is 0)."""
+    e = engine(path, batch=batch, graph=True)
+    c, reads, full, exp = sc.expected_for(path, "ragged", MaxMatches=40000)
+    e.load_reads(reads)
+    nb = sm.uniform_batches(len(reads), batch) if batch else 1
+    for i, form in enumerate(("exact rerun", "capture", "replay")):
+        got, st, inst = run(e, c, False)
+        what = "%s %s %s" % (path, batch, form)
+        assert inst["block_mode"] == 2 and bool(inst["exact_rerun"]) == (i == 0), (what, inst)
+        check(path, st, inst, exp, nb, what, graph_pass=i > 0)
+        same(got, full, what)
+        assert st["n_overflow_blocks"] == 0, what
 
 
 @pytest.mark.parametrize("path", list(sc.PATHS))
