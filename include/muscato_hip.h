@@ -373,6 +373,35 @@ int musc_results_last_ms(musc_ctx* ctx, float* ms_order, float* ms_text);
  * Needs no device; 2 for nmiss > 99999. */
 int musc_results_number_key(uint32_t pos, uint32_t nmiss, uint64_t* key);
 
+/* ---- the three side outputs from the resident tuples.  They replace what the reference reads back
+ * from results.txt: the nonmatch FASTQ of cmd/muscato_nonmatch/main.go:95-114 (an exact set for its Bloom filter),
+ * `*_genestats` of cmd/muscato/main.go:94-150 + cmd/muscato_genestats/main.go, and `*_readstats` of
+ * cmd/muscato_readstats/main.go (the gene set of a line in bytewise order).  Whitespace is C isspace.  The token of
+ * a read is the second field of its text `count\tnames` (the first name), its count the first field.
+ *   nonmatch:  the loaded reads in order, without those that have a kept tuple or an empty token:
+ *              token#count \n SEQ \n + \n !(len times) \n
+ *   genestats: name \t N \t \n per distinct gene NAME with a kept tuple, N = the kept tuples of all genes of that
+ *              name, in bytewise name order
+ *   readstats: the matched reads that have a token, in read order; consecutive ones with equal tokens are a run;
+ *              token \t then name; per distinct gene name among the run's kept tuples, bytewise, then \n
+ * MUSC_ABI_VERSION is unchanged: these are additions. */
+enum { MUSC_SIDE_NONMATCH = 0, MUSC_SIDE_GENESTATS = 1, MUSC_SIDE_READSTATS = 2 };
+/* Build the record lists of the three texts from the last successful musc_results_order of this context:
+ * nrecords[3] and nbytes[3] (either may be NULL) per text.  Code 2: no such order, no read text, or anything since
+ * that invalidates the order (a read or database load, a new gene or read text, a musc_match*).  Code 12: the gene
+ * text is not in the simple form the device needs -- every present gene's text exactly `name\tlen` with one tab, both
+ * sides non-empty and every other byte above 0x20 (what muscato_prep_targets writes; checked when the text is set).
+ * Code 12 is a refusal, not a fault: the context stays as it was, and the caller keeps its host path. */
+int musc_side_prepare(musc_ctx* ctx, uint64_t* nrecords, uint64_t* nbytes);
+/* The bytes of records [rec0, rec0 + nrec) of text `which`, clipped at its end (a range past it: 0 bytes), into dst
+ * -- a host buffer is filled through a bounded device staging buffer, a device buffer may have any alignment.
+ * *nbytes = bytes of the range; dst == NULL only reports them.  capacity < the range: code 2, nothing is written.
+ * The concatenation over consecutive ranges is the file.  Code 11: a record no longer fits the data in hand. */
+int musc_side_text(musc_ctx* ctx, int which, uint64_t rec0, uint64_t nrec, char* dst, uint64_t capacity, int dst_on_device,
+                   uint64_t* nbytes);
+/* HIP-event time of the last musc_side_prepare and of all musc_side_text calls since. */
+int musc_side_last_ms(musc_ctx* ctx, float* ms_prepare, float* ms_text);
+
 /* Which kernel instances the last musc_match* launched (tests: a pass that silently took another instance than the
  * one a test was written for is noticed).  The host resolves every kernel through a table whose entries hold the
  * function pointer and its descriptor side by side; these words are the descriptors of the entries the last pass took.

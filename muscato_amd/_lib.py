@@ -73,7 +73,11 @@ SYMBOLS = [
     "musc_get_stats", "musc_last_instance", "musc_instances", "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
     "musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits", "musc_results_text",
     "musc_results_last_ms", "musc_results_number_key",
+    "musc_side_prepare", "musc_side_text", "musc_side_last_ms",
 ]
+
+# `which` of musc_side_text (include/muscato_hip.h)
+SIDE_NONMATCH, SIDE_GENESTATS, SIDE_READSTATS = 0, 1, 2
 
 _lib = None
 
@@ -153,8 +157,12 @@ def load() -> ctypes.CDLL:
     lib.musc_results_text.argtypes = [vp, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
     lib.musc_results_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     lib.musc_results_number_key.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(u64)]
+    lib.musc_side_prepare.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.musc_side_text.argtypes = [vp, ctypes.c_int, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
+    lib.musc_side_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     for name in ("musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits",
-                 "musc_results_text", "musc_results_last_ms", "musc_results_number_key"):
+                 "musc_results_text", "musc_results_last_ms", "musc_results_number_key",
+                 "musc_side_prepare", "musc_side_text", "musc_side_last_ms"):
         getattr(lib, name).restype = ctypes.c_int
     for name in ("musc_init", "musc_reload_env", "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for", "musc_db_build_index_for",
                  "musc_db_set_partition_bases", "musc_db_partitions",

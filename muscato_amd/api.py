@@ -468,6 +468,44 @@ class Engine:
         self._check(self._lib.musc_results_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "musc_results_last_ms")
         return float(a.value), float(b.value)
 
+    # ---- the side outputs of a pass from the resident tuples
+    def side_prepare(self) -> dict:
+        """Build the nonmatch FASTQ, genestats and readstats of the last results_order on the device ->
+        {"nonmatch": (nrecords, nbytes), "genestats": ..., "readstats": ...}.  Needs the read text, and a gene text
+        whose entries are all ``name\\tlen`` without blanks (MuscatoError with code 12 otherwise)."""
+        nr, nb = (ctypes.c_uint64 * 3)(), (ctypes.c_uint64 * 3)()
+        self._check(self._lib.musc_side_prepare(self._h, nr, nb), "musc_side_prepare")
+        return {k: (int(nr[w]), int(nb[w])) for w, k in enumerate(("nonmatch", "genestats", "readstats"))}
+
+    def _side_text(self, which: int, rec0: int, nrec: Optional[int]) -> bytes:
+        count = (1 << 62) if nrec is None else int(nrec)
+        nb = ctypes.c_uint64()
+        self._check(self._lib.musc_side_text(self._h, which, int(rec0), count, None, 0, 0, ctypes.byref(nb)), "musc_side_text")
+        if not nb.value:
+            return b""
+        buf = np.empty(nb.value, dtype=np.uint8)
+        self._check(self._lib.musc_side_text(self._h, which, int(rec0), count, buf.ctypes.data, nb.value, 0, ctypes.byref(nb)),
+                    "musc_side_text")
+        return buf.tobytes()
+
+    def nonmatch_text(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
+        """FASTQ records [rec0, rec0 + nrec) of the reads without a results line (nrec None: to the end)."""
+        return self._side_text(_lib.SIDE_NONMATCH, rec0, nrec)
+
+    def genestats_text(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
+        """Lines [rec0, rec0 + nrec) of ``name\\tN\\t``: the kept tuples per gene name, in name order."""
+        return self._side_text(_lib.SIDE_GENESTATS, rec0, nrec)
+
+    def readstats_text(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
+        """Lines [rec0, rec0 + nrec) of ``token\\tname;name;``: per run of matched reads with one first name, its genes."""
+        return self._side_text(_lib.SIDE_READSTATS, rec0, nrec)
+
+    def side_ms(self) -> Tuple[float, float]:
+        """HIP-event milliseconds of the last side_prepare and of the text calls since."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._check(self._lib.musc_side_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "musc_side_last_ms")
+        return float(a.value), float(b.value)
+
     def stats(self) -> dict:
         s = _lib.MuscStats()
         self._check(self._lib.musc_get_stats(self._h, ctypes.byref(s)), "musc_get_stats")

@@ -600,6 +600,36 @@ inline std::string results_text_device(musc_ctx* c, bool device_list, const std:
   return out;
 }
 
+// 1: when results.txt came from the device the CLI also takes the three side outputs from it unless MUSC_SIDE=host;
+// 0: only with MUSC_SIDE=device.  Measured (profiles/side_outputs.py): the `nonmatch + stats files` lap
+// of a 2 M-read run is 0.10 s on the device against 1.41 s on the host, the runs of either side within 0.23 s of each other.
+#ifndef MUSC_SIDE_DEFAULT_DEVICE
+#define MUSC_SIDE_DEFAULT_DEVICE 1
+#endif
+
+// The nonmatch FASTQ, genestats and readstats (out[MUSC_SIDE_*]) from the device (musc_side_*): `c` has
+// just ordered and rendered results.txt.  false: the library refuses the gene text (code 12: a name with a blank, as
+// a hand-made id file can hold) and the host functions below are to run.  Throws Die on a library error.
+inline bool side_texts_device(musc_ctx* c, std::string out[3], float* ms_prepare, float* ms_text) {
+  uint64_t nrec[3], nbytes[3];
+  const int rc = musc_side_prepare(c, nrec, nbytes);
+  if (rc == 12) return false;
+  auto check = [&](int r) { if (r) throw Die(1, std::string("side outputs on the device failed: ") + musc_last_error(c)); };
+  check(rc);
+  for (int w = 0; w < 3; w++) {
+    out[w].assign(nbytes[w], '\0');
+    uint64_t done = 0;
+    for (uint64_t r0 = 0; r0 < nrec[w]; r0 += 1u << 20) {
+      uint64_t nb = 0;
+      check(musc_side_text(c, w, r0, 1u << 20, &out[w][done], nbytes[w] - done, 0, &nb));
+      done += nb;
+    }
+    if (done != nbytes[w]) throw Die(1, "side outputs on the device: the rendered ranges do not add up to the whole");
+  }
+  musc_side_last_ms(c, ms_prepare, ms_text);
+  return true;
+}
+
 inline std::string nonmatch_name(const std::string& results) {  // cmd/muscato_nonmatch/main.go:67-73
   size_t slash = results.rfind('/');
   std::string a = slash == std::string::npos ? "" : results.substr(0, slash + 1);
@@ -1329,13 +1359,20 @@ inline int run_muscato(Config cfg) {
 
   clk.lap("hot path (init, load, match)");
   fputs("Combining windows...\nJoining gene names...\nJoining read names...\n", stderr);
+  // MUSC_SIDE=host|device: where the nonmatch FASTQ and the two stats files are made.  The device
+  // takes them from the ordered list behind results.txt, so it can only when results.txt itself came from there.
+  const char* side_env = getenv("MUSC_SIDE");
+  const bool side_env_device = side_env && !strcmp(side_env, "device"), side_env_host = side_env && !strcmp(side_env, "host");
+  const bool side_device = ctx0 && (side_env_device || (!side_env_host && MUSC_SIDE_DEFAULT_DEVICE));
   std::string res;
   if (ctx0) {
     float ms_order = 0, ms_text = 0;
     res = results_text_device(ctx0, list_on_device, hits, reads, targets, id_rest, &ms_order, &ms_text);
     log.printf("results on the device: %zu bytes, order %.3f ms, text %.3f ms", res.size(), ms_order, ms_text);
-    musc_destroy(ctx0);
-    ctx0 = nullptr;
+    if (!side_device) {  // (else the context lives until the side outputs are written)
+      musc_destroy(ctx0);
+      ctx0 = nullptr;
+    }
   } else {
     res = results_text(hits.data(), hits.size(), reads, targets, id_rest);
     log.printf("results on the host: %zu bytes", res.size());
@@ -1352,9 +1389,25 @@ inline int run_muscato(Config cfg) {
         try { fn(); } catch (const std::exception& e) { err_side[i] = e.what(); } catch (...) { err_side[i] = "failed"; }
       });
     };
-    std::thread t0 = guarded(0, [&] { spit(nonmatch_name(cfg.ResultsFileName), nonmatch_text(res, reads)); });
-    std::thread t1 = guarded(1, [&] { spit(stats_name(cfg.ResultsFileName, "_readstats"), readstats_text(res)); });
-    std::thread t2 = guarded(2, [&] { spit(stats_name(cfg.ResultsFileName, "_genestats"), genestats_text(res)); });
+    std::string side[3];
+    bool from_device = false;
+    if (ctx0) {
+      float ms_prepare = 0, ms_text = 0;
+      from_device = side_texts_device(ctx0, side, &ms_prepare, &ms_text);
+      if (from_device) log.printf("side outputs on the device: prepare %.3f ms, text %.3f ms", ms_prepare, ms_text);
+      else log.printf("side outputs on the host: the gene text is not name\\tlen without blanks, which the device needs");
+      musc_destroy(ctx0);
+      ctx0 = nullptr;
+    }
+    std::thread t0 = guarded(0, [&] {
+      spit(nonmatch_name(cfg.ResultsFileName), from_device ? side[MUSC_SIDE_NONMATCH] : nonmatch_text(res, reads));
+    });
+    std::thread t1 = guarded(1, [&] {
+      spit(stats_name(cfg.ResultsFileName, "_readstats"), from_device ? side[MUSC_SIDE_READSTATS] : readstats_text(res));
+    });
+    std::thread t2 = guarded(2, [&] {
+      spit(stats_name(cfg.ResultsFileName, "_genestats"), from_device ? side[MUSC_SIDE_GENESTATS] : genestats_text(res));
+    });
     t0.join(); t1.join(); t2.join();
     for (auto& e : err_side) if (!e.empty()) throw Die(1, "side output: " + e);
   }

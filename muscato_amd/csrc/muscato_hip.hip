@@ -45,6 +45,8 @@
 #include "kernels_screen_lane.hpp"
 #include "kernels_partition.hpp"
 #include "kernels_results.hpp"
+#include "side_names.hpp"
+#include "kernels_side.hpp"
 MUSC_LANE_INSTANCES_4(extern)
 MUSC_LANE_INSTANCES_8(extern)
 MUSC_LANE_INSTANCES_12(extern)
@@ -382,6 +384,25 @@ struct musc_ctx {
   bool hits_current = false;        // `hits` is the list of a pass over the reads and the database in hand
   float res_ms_order = 0, res_ms_text = 0;
 
+  // the side outputs on the device: what musc_side_prepare leaves for musc_side_text
+  uint32_t* side_nrank = nullptr;   // per gene: rank of its name among all names, RES_ABSENT without an id line
+  uint2* side_names = nullptr;      // per name rank: a gene with that name, the name's bytes
+  uint32_t side_nnames = 0;
+  bool side_form_ok = false;        // every present gene's text is name\tlen in the simple form
+  uint32_t side_bad_gene = 0;       // the first gene whose text is not
+  bool side_after_match = false;    // a pass ran since the last musc_results_order: its list is not that order's
+  bool side_tok_valid = false;      // side_tok describes the read text in hand
+  bool side_valid = false;          // the tables below describe the last musc_results_order
+  DevBuf<uint4> side_tok;           // per read: count span and token span of its tail
+  DevBuf<uint32_t> side_cnt;        // per name rank: kept tuples
+  DevBuf<uint32_t> side_idx[2];     // nonmatch: the reads of the records; genestats: the name ranks of the lines
+  DevBuf<uint64_t> side_off[3];     // per text: nrec + 1 byte offsets
+  DevBuf<uint64_t> side_el, side_eloff;       // readstats: run << 32 | name rank per element, nel + 1 byte offsets
+  DevBuf<uint32_t> side_first, side_runread;  // readstats: per run its first element, its first read
+  uint64_t side_nel = 0;
+  uint64_t side_nrec[3] = {0, 0, 0}, side_nbytes[3] = {0, 0, 0};
+  float side_ms_prepare = 0, side_ms_text = 0;
+
   uint32_t batch_reads = 16u << 20;
   // A pass over the same reads, database and parameters as the last completed one needs no
   // sizing: its buffers are known to suffice, so it runs without host round trips.
@@ -528,6 +549,13 @@ void drop_gene_text(musc_ctx* c) {
   if (c->res_gtext) (void)hipFree(c->res_gtext);
   if (c->res_goff) (void)hipFree(c->res_goff);
   if (c->res_rank) (void)hipFree(c->res_rank);
+  if (c->side_nrank) (void)hipFree(c->side_nrank);
+  if (c->side_names) (void)hipFree(c->side_names);
+  c->side_nrank = nullptr;
+  c->side_names = nullptr;
+  c->side_nnames = 0;
+  c->side_form_ok = false;
+  c->side_valid = false;
   c->res_gtext = nullptr;
   c->res_goff = nullptr;
   c->res_rank = nullptr;
@@ -540,6 +568,8 @@ void drop_read_text(musc_ctx* c) {
   c->res_ttext = nullptr;
   c->res_toff = nullptr;
   c->res_valid = false;
+  c->side_tok_valid = false;
+  c->side_valid = false;
 }
 void forget_read_text(musc_ctx* c) {  // the reads go: so do their text and the standing of the resident tuple list
   drop_read_text(c);
@@ -731,6 +761,10 @@ void musc_destroy(musc_ctx* c) {
   c->packed.release();
   c->gathered.release();
   c->res_hits.release(); c->res_off.release(); c->res_stage.release();
+  c->side_tok.release(); c->side_cnt.release(); c->side_el.release(); c->side_eloff.release();
+  c->side_first.release(); c->side_runread.release();
+  for (auto& b : c->side_idx) b.release();
+  for (auto& b : c->side_off) b.release();
   if (c->d_flag) (void)hipFree(c->d_flag);
   if (c->counters) (void)hipFree(c->counters);
   if (c->h_pinned) (void)hipHostFree(c->h_pinned);
@@ -1918,6 +1952,23 @@ int musc_results_set_gene_text(musc_ctx* c, const char* text, const uint64_t* of
     drop_gene_text(c);
     return fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e));
   }
+  // for the side outputs: the form of the texts, and the rank of each gene's name alone
+  c->side_bad_gene = musc_side::first_bad_form(text, offsets, absent, nseq);
+  c->side_form_ok = c->side_bad_gene == nseq;
+  if (c->side_form_ok) {
+    const musc_side::NameRanks R = musc_side::name_ranks(text, offsets, absent, nseq);
+    std::vector<uint2> names(R.rep.size());
+    for (size_t k = 0; k < names.size(); k++) names[k] = make_uint2(R.rep[k], R.len[k]);
+    e = hipMalloc((void**)&c->side_nrank, (uint64_t)nseq * 4 + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->side_names, names.size() * 8 + 16);
+    if (e == hipSuccess) e = hipMemcpy(c->side_nrank, R.rank.data(), (uint64_t)nseq * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !names.empty()) e = hipMemcpy(c->side_names, names.data(), names.size() * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      drop_gene_text(c);
+      return fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e));
+    }
+    c->side_nnames = (uint32_t)names.size();
+  }
   return 0;
 }
 
@@ -2098,6 +2149,7 @@ int musc_results_order(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_dev
   if (nlines) *nlines = 0;
   if (nbytes) *nbytes = 0;
   c->res_valid = false;
+  c->side_valid = false;
   c->res_n = c->res_bytes = 0;
   if (!c->db2 || !c->res_gtext || !c->res_rank) return fail(c, 2, "musc_results_order: no gene text (musc_results_set_gene_text)");
   if (c->up.active) return fail(c, 2, "musc_results_order: a streamed read load has not been matched yet");
@@ -2117,6 +2169,7 @@ int musc_results_order(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_dev
   (void)hipEventElapsedTime(&c->res_ms_order, e0, e1);
   c->res_ms_text = 0;
   c->res_valid = true;
+  c->side_after_match = false;
   if (nlines) *nlines = c->res_n;
   if (nbytes) *nbytes = c->res_bytes;
   return 0;
@@ -2219,6 +2272,304 @@ int musc_results_last_ms(musc_ctx* c, float* ms_order, float* ms_text) {
   if (!c) return 1;
   if (ms_order) *ms_order = c->res_ms_order;
   if (ms_text) *ms_text = c->res_ms_text;
+  return 0;
+}
+
+// ---------------------------------------------------------------- the side outputs on the device
+// The nonmatch FASTQ (cmd/muscato_nonmatch/main.go:95-114, an exact set for the Bloom filter), `*_genestats`
+// (cmd/muscato/main.go:94-150 + cmd/muscato_genestats/main.go) and `*_readstats` (cmd/muscato_readstats/main.go, the
+// gene set sorted) from the ordered list of the last musc_results_order: musc_side_prepare builds the record lists
+// and their byte offsets, musc_side_text renders a range of records (kernels_side.hpp).
+
+static const int MUSC_SIDE_ERR_FORM = 12;  // the gene text is not in the simple form: the caller's cue for its host path
+
+static SideData side_data(const musc_ctx* c) {
+  SideData D;
+  D.rd = c->rd;
+  D.rdm = c->reads_have_x ? c->rdm : nullptr;
+  D.ttext = c->res_ttext;
+  D.toff = c->res_toff;
+  D.tok = c->side_tok.p;
+  D.gtext = c->res_gtext;
+  D.goff = c->res_goff;
+  D.names = c->side_names;
+  D.nreads = c->nreads;
+  D.nseq = c->nseq;
+  D.nnames = c->side_nnames;
+  D.rw = c->rw;
+  return D;
+}
+
+// flag / len over n + 1 items (the last one empty) -> the record list of text `which`: idx (when the text has one),
+// offsets, counts.  excl and stmp are scratch for n + 1 items; len is scanned in place.
+static int side_records(musc_ctx* c, int which, const uint32_t* flag, uint32_t* excl, uint64_t* len, uint64_t n, uint32_t* stmp,
+                        uint64_t* stmp64) {
+  auto grid = [](uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); };
+  int rc;
+  if ((rc = scan_u32(c, flag, excl, n + 1, false, stmp))) return rc;
+  if ((rc = scan_u64(c, len, len, n + 1, stmp64))) return rc;
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  HIPCHK(c, hipMemcpyAsync(h32, excl + n, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, len + n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t nrec = h32[0], nbytes = c->h_pinned[1];
+  if ((rc = ensure(c, c->side_idx[which], std::max<uint64_t>(nrec, 1)))) return rc;
+  if ((rc = ensure(c, c->side_off[which], nrec + 1))) return rc;
+  hipLaunchKernelGGL(k_side_compact, grid(n + 1), dim3(256), 0, c->stream, flag, excl, len, n, c->side_idx[which].p, c->side_off[which].p);
+  HIPCHK(c, hipGetLastError());
+  c->side_nrec[which] = nrec;
+  c->side_nbytes[which] = nbytes;
+  return 0;
+}
+
+static int side_prepare_impl(musc_ctx* c) {
+  const dim3 B256(256);
+  auto grid = [](uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); };
+  const uint64_t nreads = c->nreads, m = c->res_n, nnames = c->side_nnames;
+  const uint4* const hits = reinterpret_cast<const uint4*>(c->res_hits.p);
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  int rc;
+  TmpBufs B;
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
+
+  // ---- tokens: once per read text
+  if (!c->side_tok_valid) {
+    if ((rc = ensure(c, c->side_tok, std::max<uint64_t>(nreads, 1)))) return rc;
+    hipLaunchKernelGGL(k_side_tokens, grid(nreads), B256, 0, c->stream, c->res_ttext, c->res_toff, nreads, c->side_tok.p, c->d_flag);
+    HIPCHK(c, hipGetLastError());
+  }
+
+  // ---- mark the matched reads, count the tuples of every name
+  const uint64_t nmax = std::max(std::max(nreads, nnames), m) + 1;  // items of the largest scan below
+  uint32_t *matched = nullptr, *flag = nullptr, *excl = nullptr, *stmp = nullptr;
+  uint64_t *len = nullptr, *stmp64 = nullptr;
+  HIPCHK(c, B.alloc(&matched, (nreads + 1) * 4));
+  HIPCHK(c, B.alloc(&flag, nmax * 4));
+  HIPCHK(c, B.alloc(&excl, nmax * 4));
+  HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(nmax) * 4));
+  HIPCHK(c, B.alloc(&len, nmax * 8));
+  HIPCHK(c, B.alloc(&stmp64, scan_tmp_elems(nmax) * 8));
+  if ((rc = ensure(c, c->side_cnt, std::max<uint64_t>(nnames, 1)))) return rc;
+  HIPCHK(c, hipMemsetAsync(matched, 0, (nreads + 1) * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->side_cnt.p, 0, std::max<uint64_t>(nnames, 1) * 4, c->stream));
+  if (m) {
+    hipLaunchKernelGGL(k_side_mark, grid(m), B256, 0, c->stream, hits, m, c->side_nrank, nreads, c->nseq, (uint32_t)nnames, matched,
+                       c->side_cnt.p, c->d_flag);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemcpyAsync(h32 + 4, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h32[4]) return fail(c, 11, "musc_side_prepare: a read's text is longer than 4 GiB, or the ordered list no longer fits the reads and the gene text in hand");
+  c->side_tok_valid = true;
+  const SideData D = side_data(c);
+
+  // ---- nonmatch: the unmatched reads that have a token
+  hipLaunchKernelGGL(k_side_nm_len, grid(nreads + 1), B256, 0, c->stream, D, matched, flag, len);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = side_records(c, MUSC_SIDE_NONMATCH, flag, excl, len, nreads, stmp, stmp64))) return rc;
+
+  // ---- genestats: the names with a tuple
+  hipLaunchKernelGGL(k_side_gs_len, grid(nnames + 1), B256, 0, c->stream, D, c->side_cnt.p, flag, len);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = side_records(c, MUSC_SIDE_GENESTATS, flag, excl, len, nnames, stmp, stmp64))) return rc;
+
+  // ---- readstats: runs of equal tokens over the matched reads that have one
+  c->side_nel = 0;
+  c->side_nrec[MUSC_SIDE_READSTATS] = c->side_nbytes[MUSC_SIDE_READSTATS] = 0;
+  if ((rc = ensure(c, c->side_off[MUSC_SIDE_READSTATS], 1))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->side_off[MUSC_SIDE_READSTATS].p, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_side_rs_flag, grid(nreads + 1), B256, 0, c->stream, matched, c->side_tok.p, nreads, flag);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, flag, excl, nreads + 1, false, stmp))) return rc;
+  HIPCHK(c, hipMemcpyAsync(h32, excl + nreads, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t ncr = h32[0];
+  if (ncr == 0 || m == 0) return 0;
+  uint32_t *cr = nullptr, *head = nullptr, *incl = nullptr, *runof = nullptr;
+  HIPCHK(c, B.alloc(&cr, ncr * 4));
+  HIPCHK(c, B.alloc(&head, ncr * 4));
+  HIPCHK(c, B.alloc(&incl, ncr * 4));
+  HIPCHK(c, B.alloc(&runof, nreads * 4));
+  hipLaunchKernelGGL(k_side_compact, grid(nreads + 1), B256, 0, c->stream, flag, excl, (const uint64_t*)nullptr, nreads, cr, (uint64_t*)nullptr);
+  hipLaunchKernelGGL(k_side_rs_heads, grid(ncr), B256, 0, c->stream, cr, ncr, D, head);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, head, incl, ncr, true, stmp))) return rc;
+  HIPCHK(c, hipMemcpyAsync(h32, incl + (ncr - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t nruns = h32[0];
+  if ((rc = ensure(c, c->side_runread, nruns))) return rc;
+  if ((rc = ensure(c, c->side_first, nruns + 1))) return rc;
+  if ((rc = ensure(c, c->side_off[MUSC_SIDE_READSTATS], nruns + 1))) return rc;
+  HIPCHK(c, hipMemsetAsync(runof, 0xFF, nreads * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->side_first.p, 0, (nruns + 1) * 4, c->stream));  // (every run has an element; were one without, it reads element 0)
+  hipLaunchKernelGGL(k_side_rs_runs, grid(ncr), B256, 0, c->stream, cr, head, incl, ncr, runof, c->side_runread.p);
+  HIPCHK(c, hipGetLastError());
+
+  // one key per kept tuple, sorted; the distinct keys are the elements of the lines
+  uint64_t *k0 = nullptr, *k1 = nullptr;
+  void* tmp = nullptr;
+  size_t tmp_bytes = 0;
+  HIPCHK(c, B.alloc(&k0, m * 8));
+  HIPCHK(c, B.alloc(&k1, m * 8));
+  HIPCHK(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, k0, k1, (size_t)m, 0u, 64u, c->stream));
+  HIPCHK(c, B.alloc(&tmp, tmp_bytes));
+  hipLaunchKernelGGL(k_side_rs_keys, grid(m), B256, 0, c->stream, hits, m, runof, c->side_nrank, k0);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, rocprim::radix_sort_keys(tmp, tmp_bytes, k0, k1, (size_t)m, 0u, 64u, c->stream));
+  hipLaunchKernelGGL(k_side_rs_uniq, grid(m + 1), B256, 0, c->stream, k1, m, flag);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, flag, excl, m + 1, false, stmp))) return rc;
+  HIPCHK(c, hipMemcpyAsync(h32, excl + m, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t nel = h32[0];
+  if (nel < nruns) return fail(c, 11, "musc_side_prepare: a run of reads without an element");
+  if ((rc = ensure(c, c->side_el, nel))) return rc;
+  if ((rc = ensure(c, c->side_eloff, nel + 1))) return rc;
+  hipLaunchKernelGGL(k_side_rs_elems, grid(m), B256, 0, c->stream, k1, flag, excl, m, c->side_el.p);
+  hipLaunchKernelGGL(k_side_rs_len, grid(nel + 1), B256, 0, c->stream, c->side_el.p, nel, (uint32_t)nruns, D, c->side_runread.p,
+                     c->side_eloff.p, c->side_first.p);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u64(c, c->side_eloff.p, c->side_eloff.p, nel + 1, stmp64))) return rc;  // (nel <= m: stmp64 is large enough)
+  hipLaunchKernelGGL(k_side_rs_lines, grid(nruns + 1), B256, 0, c->stream, c->side_first.p, c->side_eloff.p, nruns,
+                     c->side_off[MUSC_SIDE_READSTATS].p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->side_eloff.p + nel, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->side_nel = nel;
+  c->side_nrec[MUSC_SIDE_READSTATS] = nruns;
+  c->side_nbytes[MUSC_SIDE_READSTATS] = c->h_pinned[0];
+  return 0;
+}
+
+int musc_side_prepare(musc_ctx* c, uint64_t* nrecords, uint64_t* nbytes) {
+  if (!c) return 1;
+  for (int w = 0; w < 3; w++) {
+    if (nrecords) nrecords[w] = 0;
+    if (nbytes) nbytes[w] = 0;
+  }
+  c->side_valid = false;
+  if (!c->res_valid) return fail(c, 2, "musc_side_prepare: no ordered list (musc_results_order) of the reads, the database and the texts in hand");
+  if (c->side_after_match) return fail(c, 2, "musc_side_prepare: a pass ran after the last musc_results_order: order its list first");
+  if (!c->res_ttext) return fail(c, 2, "musc_side_prepare: no read text (musc_results_set_read_text)");
+  if (!c->side_form_ok)
+    return fail(c, MUSC_SIDE_ERR_FORM, "musc_side_prepare: gene text not in the simple form (gene %u is not name\\tlen without blanks)", c->side_bad_gene);
+  if (c->nreads >= 0xFFFFFFF0ull) return fail(c, 2, "musc_side_prepare: too many reads for 32-bit record numbers");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->ev_used = 0;
+  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  const int rc = side_prepare_impl(c);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);  // (nothing of a failed call is still queued when its temporaries go)
+    return rc;
+  }
+  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->side_ms_prepare = 0;
+  (void)hipEventElapsedTime(&c->side_ms_prepare, e0, e1);
+  c->side_ms_text = 0;
+  c->side_valid = true;
+  for (int w = 0; w < 3; w++) {
+    if (nrecords) nrecords[w] = c->side_nrec[w];
+    if (nbytes) nbytes[w] = c->side_nbytes[w];
+  }
+  return 0;
+}
+
+static void launch_side(musc_ctx* c, int which, uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) {
+  const unsigned blocks = (unsigned)std::min<uint64_t>(bytes / 256 + 1, 4 * MAX_GRID);
+  const SideData D = side_data(c);
+  if (which == MUSC_SIDE_NONMATCH)
+    hipLaunchKernelGGL(k_side_nm_render, dim3(blocks), dim3(256), 0, c->stream, c->side_idx[0].p, c->side_off[0].p, r0, r1, D, out, c->d_flag);
+  else if (which == MUSC_SIDE_GENESTATS)
+    hipLaunchKernelGGL(k_side_gs_render, dim3(blocks), dim3(256), 0, c->stream, c->side_idx[1].p, c->side_off[1].p, r0, r1, D, c->side_cnt.p, out,
+                       c->d_flag);
+  else
+    hipLaunchKernelGGL(k_side_rs_render, dim3(blocks), dim3(256), 0, c->stream, c->side_el.p, c->side_nel, c->side_eloff.p, c->side_first.p,
+                       (uint32_t)c->side_nrec[2], r0, r1, D, c->side_runread.p, out, c->d_flag);
+}
+
+static int side_text_impl(musc_ctx* c, int which, uint64_t r0, uint64_t r1, char* dst, uint64_t capacity, int dst_on_device, uint64_t* nbytes) {
+  const uint64_t* const d_off = c->side_off[which].p;
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, d_off + r0, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, d_off + r1, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t o0 = c->h_pinned[0], bytes = c->h_pinned[1] - o0;
+  *nbytes = bytes;
+  if (!dst) return 0;  // the size of the range
+  if (capacity < bytes) {
+    *nbytes = 0;
+    return fail(c, 2, "musc_side_text: capacity %llu < %llu bytes", (unsigned long long)capacity, (unsigned long long)bytes);
+  }
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));  // raised by a record the kernel refuses to render
+  if (dst_on_device) {
+    launch_side(c, which, r0, r1, bytes, reinterpret_cast<unsigned char*>(dst));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  std::vector<uint64_t> off;
+  for (uint64_t b0 = r0; b0 < r1;) {
+    const uint64_t b1 = std::min(r1, b0 + RES_STAGE_LINES);
+    off.resize(b1 - b0 + 1);
+    HIPCHK(c, hipMemcpyAsync(off.data(), d_off + b0, (b1 - b0 + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint64_t p0 = b0; p0 < b1;) {
+      // the most records whose bytes fit the staging buffer, at least one
+      const uint64_t start = off[p0 - b0];
+      uint64_t p1 = std::upper_bound(off.begin() + (p0 - b0), off.end(), start + RES_STAGE_BYTES) - off.begin() - 1 + b0;
+      p1 = std::min(std::max(p1, p0 + 1), b1);
+      const uint64_t pb = off[p1 - b0] - start;
+      int rc = ensure(c, c->res_stage, std::max(pb, RES_STAGE_BYTES));
+      if (rc) return rc;
+      launch_side(c, which, p0, p1, pb, c->res_stage.p);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(dst + (start - o0), c->res_stage.p, pb, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      p0 = p1;
+    }
+    b0 = b1;
+  }
+  return 0;
+}
+
+int musc_side_text(musc_ctx* c, int which, uint64_t rec0, uint64_t nrec, char* dst, uint64_t capacity, int dst_on_device, uint64_t* nbytes) {
+  if (!c) return 1;
+  if (!nbytes) return fail(c, 2, "musc_side_text: nbytes is NULL");
+  *nbytes = 0;
+  if (which < 0 || which > 2) return fail(c, 2, "musc_side_text: no such text (%d)", which);
+  if (!c->side_valid || !c->res_valid || c->side_after_match) return fail(c, 2, "musc_side_text: nothing prepared (musc_side_prepare)");
+  const uint64_t n = c->side_nrec[which];
+  if (rec0 >= n || nrec == 0) return 0;
+  const uint64_t r1 = nrec > n - rec0 ? n : rec0 + nrec;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->ev_used = 0;
+  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  const int rc = side_text_impl(c, which, rec0, r1, dst, capacity, dst_on_device, nbytes);
+  const hipError_t er = hipEventRecord(e1, c->stream);
+  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned + 2);
+  *h_bad = 0;
+  const hipError_t ef = rc == 0 && dst ? hipMemcpyAsync(h_bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIPCHK(c, er);
+  HIPCHK(c, ef);
+  HIPCHK(c, es);
+  if (*h_bad) {
+    *nbytes = 0;
+    return fail(c, 11, "musc_side_text: a record no longer fits the reads or the texts in hand");
+  }
+  float ms = 0;
+  if (dst && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->side_ms_text += ms;
+  return 0;
+}
+
+int musc_side_last_ms(musc_ctx* c, float* ms_prepare, float* ms_text) {
+  if (!c) return 1;
+  if (ms_prepare) *ms_prepare = c->side_ms_prepare;
+  if (ms_text) *ms_text = c->side_ms_text;
   return 0;
 }
 

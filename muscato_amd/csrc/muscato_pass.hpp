@@ -807,6 +807,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
 extern "C" int musc_match_device(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
   if (!c) return 1;
   c->hits_current = false;
+  c->side_after_match = true;  // (musc_side_prepare: the ordered list is no longer that of the last pass)
   const int rc = match_device_impl(c, P, nhits);
   if (rc != 0 && c->up.active && c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);
   c->hits_current = rc == 0;
