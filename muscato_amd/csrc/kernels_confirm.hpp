@@ -131,7 +131,12 @@ DEV uint32_t confirm_pair(const uint4 ds, const uint32_t* __restrict__ rd, const
     const int len2 = 2 * (int)len;
     const uint32_t* __restrict__ recm = MASK ? rdm + (r0 + ri) * (uint64_t)rw : nullptr;
     uint32_t tlo = db2[widx], tmlo = MASK ? dbm2[widx] : 0u;
-    for (int j = 0; j < rw - 1; j++) {
+    // Only the words THIS read has: rw is the stride of the longest read loaded, and a step reads target word
+    // widx + j + 1.  The read ends inside its target, so the farthest word is one past the word of the read's last
+    // base (the funnel shift's high half): inside the planes' slack for any read length (db_alloc).  Every window
+    // that takes part lies inside len -- rvalid has no bit for any other -- so the words left out decide nothing.
+    const int nw = min(rw - 1, ((int)len + 15) >> 4);
+    for (int j = 0; j < nw; j++) {
       const uint32_t thi = db2[widx + j + 1];
       const uint32_t x = rec[j] ^ __funnelshift_r(tlo, thi, sh);
       tlo = thi;

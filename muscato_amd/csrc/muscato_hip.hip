@@ -837,7 +837,22 @@ static int db_alloc(musc_ctx* c, const uint64_t* offsets, uint32_t nseq, int on_
   c->h_seq_off.resize((size_t)nseq + 1);
   if (on_device) HIPCHK(c, hipMemcpy(c->h_seq_off.data(), offsets, ((uint64_t)nseq + 1) * 8, hipMemcpyDeviceToHost));
   else memcpy(c->h_seq_off.data(), offsets, ((uint64_t)nseq + 1) * 8);
-  const uint64_t alloc_words = c->db_words + 64;  // slack: k_confirm reads a whole span past the last base
+  // 64 words of zeroed slack behind both planes (pass_two_kernel allocates a missing mask plane the same way, and
+  // db_xblocks sizes dbx for db_words + 64).  What reads into it, and what bounds each access:
+  //   - k_confirm<RW != 0> (pair_issue): RW <= 16 words from the word of the placement's first base, whatever the
+  //     read's length -- at most 15 words past the last one.  db_span_has_x looks at the same RW * 16 bases.
+  //   - k_confirm<0> (confirm_pair, runtime stride): ceil(len / 16) steps, each reading one word ahead -- at most ONE
+  //     word past the word of the read's last base, and a read ends inside its target.  The bound is the read's own
+  //     length: bounded by the stride of the longest read loaded it walked up to 4 099 words past the last base.
+  //   - ext64 on a plane (bucket_of in the index build, res_span_word): two words past the word of its first bit,
+  //     and that bit belongs to a base of the database.  ctx_words (the context index build) takes the words of a
+  //     context of at most 200 bases around a window that starts inside the database.
+  //   - k_results_render / the side kernels read single words of bases inside [0, nbases).
+  // k_screen<0>, k_screen_t and k_hot_probes<0> never touch the planes: they read the index and the read records
+  // (Rec<0>::ext = ext64 on the record: a window that takes part ends inside len, so at most two words past the
+  // record's last base word -- the record's own length word, then the next record or the 256 spare bytes behind rd
+  // and rdm).  The results and side kernels take c->rw only to find a record and its length word.
+  const uint64_t alloc_words = c->db_words + 64;
   HIPCHK(c, hipMalloc((void**)&c->db2, alloc_words * 4));
   HIPCHK(c, hipMalloc((void**)&c->dbm2, alloc_words * 4));
   HIPCHK(c, hipMemsetAsync(c->db2, 0, alloc_words * 4, c->stream));
