@@ -361,8 +361,9 @@ int musc_results_order(musc_ctx* ctx, const musc_hit* hits, uint64_t n, int on_d
 int musc_results_hits(musc_ctx* ctx, musc_hit* dst, uint64_t capacity, int dst_on_device);
 /* The bytes of lines [line0, line0 + nlines) of the last order, clipped at its end (a range past it: 0 bytes), into
  * dst -- a host buffer is filled through a bounded device staging buffer.  *nbytes = bytes of the range; dst == NULL
- * only reports them.  The concatenation over consecutive ranges is ResultsFileName.  Code 11: a line no longer fits
- * the data in hand (nothing of the range is to be used). */
+ * only reports them.  capacity < the range: code 2, nothing is written, *nbytes = 0.  The concatenation over
+ * consecutive ranges is ResultsFileName.  Code 11: a line no longer fits the data in hand (nothing of the range is to
+ * be used). */
 int musc_results_text(musc_ctx* ctx, uint64_t line0, uint64_t nlines, char* dst, uint64_t capacity, int dst_on_device,
                       uint64_t* nbytes);
 /* HIP-event time of the last musc_results_order and of all musc_results_text calls since (the reference logs wall

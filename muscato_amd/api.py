@@ -449,18 +449,22 @@ class Engine:
         self._check(self._lib.musc_results_hits(self._h, out.ctypes.data, self._res_nlines, 0), "musc_results_hits")
         return out
 
-    def results_text(self, line0: int = 0, nlines: Optional[int] = None) -> bytes:
-        """The bytes of lines [line0, line0 + nlines) of the last results_order (nlines None: to the end); the
-        concatenation over consecutive ranges is results.txt."""
-        count = (1 << 62) if nlines is None else int(nlines)
+    def _text_range(self, name: str, fn, head: tuple, rec0: int, nrec: Optional[int]) -> bytes:
+        """Records [rec0, rec0 + nrec) of a text call `fn(*head, rec0, nrec, dst, capacity, on_device, &nbytes)`: one
+        call for the size, one that fills a host buffer of that size."""
+        count = (1 << 62) if nrec is None else int(nrec)
         nb = ctypes.c_uint64()
-        self._check(self._lib.musc_results_text(self._h, int(line0), count, None, 0, 0, ctypes.byref(nb)), "musc_results_text")
+        self._check(fn(*head, int(rec0), count, None, 0, 0, ctypes.byref(nb)), name)
         if not nb.value:
             return b""
         buf = np.empty(nb.value, dtype=np.uint8)
-        self._check(self._lib.musc_results_text(self._h, int(line0), count, buf.ctypes.data, nb.value, 0, ctypes.byref(nb)),
-                    "musc_results_text")
+        self._check(fn(*head, int(rec0), count, buf.ctypes.data, nb.value, 0, ctypes.byref(nb)), name)
         return buf.tobytes()
+
+    def results_text(self, line0: int = 0, nlines: Optional[int] = None) -> bytes:
+        """The bytes of lines [line0, line0 + nlines) of the last results_order (nlines None: to the end); the
+        concatenation over consecutive ranges is results.txt."""
+        return self._text_range("musc_results_text", self._lib.musc_results_text, (self._h,), line0, nlines)
 
     def results_ms(self) -> Tuple[float, float]:
         """HIP-event milliseconds of the last results_order and of the results_text calls since."""
@@ -478,15 +482,7 @@ class Engine:
         return {k: (int(nr[w]), int(nb[w])) for w, k in enumerate(("nonmatch", "genestats", "readstats"))}
 
     def _side_text(self, which: int, rec0: int, nrec: Optional[int]) -> bytes:
-        count = (1 << 62) if nrec is None else int(nrec)
-        nb = ctypes.c_uint64()
-        self._check(self._lib.musc_side_text(self._h, which, int(rec0), count, None, 0, 0, ctypes.byref(nb)), "musc_side_text")
-        if not nb.value:
-            return b""
-        buf = np.empty(nb.value, dtype=np.uint8)
-        self._check(self._lib.musc_side_text(self._h, which, int(rec0), count, buf.ctypes.data, nb.value, 0, ctypes.byref(nb)),
-                    "musc_side_text")
-        return buf.tobytes()
+        return self._text_range("musc_side_text", self._lib.musc_side_text, (self._h, which), rec0, nrec)
 
     def nonmatch_text(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
         """FASTQ records [rec0, rec0 + nrec) of the reads without a results line (nrec None: to the end)."""

@@ -551,6 +551,22 @@ inline std::string results_text(const musc_hit* hits, size_t nhits, const std::v
   return out;
 }
 
+// A whole text of `nrec` records and `nbytes` bytes from the device, in ranges of 2^20 records: `fetch(rec0, n, dst,
+// capacity, &nb)` renders records [rec0, rec0 + n), clipped at the end, into dst and reports their bytes (it throws on
+// a library error).
+template <class Fetch>
+inline std::string device_text(const char* what, uint64_t nrec, uint64_t nbytes, Fetch fetch) {
+  std::string out(nbytes, '\0');
+  uint64_t done = 0;
+  for (uint64_t r0 = 0; r0 < nrec; r0 += 1u << 20) {
+    uint64_t nb = 0;
+    fetch(r0, (uint64_t)1 << 20, &out[done], nbytes - done, &nb);
+    done += nb;
+  }
+  if (done != nbytes) throw Die(1, std::string(what) + ": the rendered ranges do not add up to the whole");
+  return out;
+}
+
 // The same bytes from the device (musc_results_*): `c` holds the database and every read; device_list =
 // the tuples are the list the last pass left on the device, else `hits`.  Throws Die on a library error.
 inline std::string results_text_device(musc_ctx* c, bool device_list, const std::vector<musc_hit>& hits, const std::vector<UniqueRead>& reads,
@@ -588,14 +604,9 @@ inline std::string results_text_device(musc_ctx* c, bool device_list, const std:
   uint64_t nlines = 0, nbytes = 0;
   static const musc_hit none = {0, 0, 0, 0};
   check(musc_results_order(c, device_list ? nullptr : hits.empty() ? &none : hits.data(), hits.size(), 0, &nlines, &nbytes));
-  std::string out(nbytes, '\0');
-  uint64_t done = 0;
-  for (uint64_t l0 = 0; l0 < nlines; l0 += 1u << 20) {
-    uint64_t nb = 0;
-    check(musc_results_text(c, l0, 1u << 20, &out[done], nbytes - done, 0, &nb));
-    done += nb;
-  }
-  if (done != nbytes) throw Die(1, "results on the device: the rendered ranges do not add up to the whole");
+  std::string out = device_text("results on the device", nlines, nbytes, [&](uint64_t l0, uint64_t n, char* dst, uint64_t cap, uint64_t* nb) {
+    check(musc_results_text(c, l0, n, dst, cap, 0, nb));
+  });
   musc_results_last_ms(c, ms_order, ms_text);
   return out;
 }
@@ -616,16 +627,10 @@ inline bool side_texts_device(musc_ctx* c, std::string out[3], float* ms_prepare
   if (rc == 12) return false;
   auto check = [&](int r) { if (r) throw Die(1, std::string("side outputs on the device failed: ") + musc_last_error(c)); };
   check(rc);
-  for (int w = 0; w < 3; w++) {
-    out[w].assign(nbytes[w], '\0');
-    uint64_t done = 0;
-    for (uint64_t r0 = 0; r0 < nrec[w]; r0 += 1u << 20) {
-      uint64_t nb = 0;
-      check(musc_side_text(c, w, r0, 1u << 20, &out[w][done], nbytes[w] - done, 0, &nb));
-      done += nb;
-    }
-    if (done != nbytes[w]) throw Die(1, "side outputs on the device: the rendered ranges do not add up to the whole");
-  }
+  for (int w = 0; w < 3; w++)
+    out[w] = device_text("side outputs on the device", nrec[w], nbytes[w], [&](uint64_t r0, uint64_t n, char* dst, uint64_t cap, uint64_t* nb) {
+      check(musc_side_text(c, w, r0, n, dst, cap, 0, nb));
+    });
   musc_side_last_ms(c, ms_prepare, ms_text);
   return true;
 }

@@ -259,49 +259,66 @@ MUSC_KERNEL __launch_bounds__(256) void k_results_len(const uint4* __restrict__ 
     len[i] = i < m ? res_line(D, hits[i]).total() : 0ull;
 }
 
+// Where a thread of a render kernel sits: one wave per record, the waves of the whole grid striding over the records.
+// The kernel hands in threadIdx.x, blockIdx.x, blockDim.x and gridDim.x: read in the kernel's own body blockDim.x is one
+// scalar load of a kernel argument and nwaves stays in SGPRs; read in here it came through a vector load and took two
+// VGPRs in every render kernel.
+struct WaveId {
+  uint32_t lane;
+  uint64_t wave, nwaves;
+};
+DEV WaveId wave_id(uint32_t tid, uint32_t bid, uint32_t bdim, uint32_t gdim) {
+  WaveId w;
+  w.lane = tid & 63u;
+  w.wave = (uint64_t)bid * (bdim >> 6) + (tid >> 6);
+  w.nwaves = (uint64_t)gdim * (bdim >> 6);
+  return w;
+}
+
+// `total` bytes at `p`, byte k = at(k), by one wave: each lane assembles whole dwords at the alignment the destination
+// ADDRESS has and stores them with one 4-byte store; only the bytes before the first aligned dword (lanes 0..2) and
+// after the last one (lanes 8..10) are byte stores
+template <class F>
+DEV void wave_store(unsigned char* p, uint64_t total, uint32_t lane, F at) {
+  const uint64_t mis = (uint64_t)(4u - ((uint32_t)(uintptr_t)p & 3u)) & 3u;
+  const uint64_t head = mis < total ? mis : total;
+  const uint64_t nd = (total - head) >> 2;
+  for (uint64_t d = lane; d < nd; d += 64) {
+    const uint64_t k = head + 4 * d;
+    *reinterpret_cast<uint32_t*>(p + k) = at(k) | (at(k + 1) << 8) | (at(k + 2) << 16) | (at(k + 3) << 24);
+  }
+  const uint64_t tail0 = head + 4 * nd;
+  if (lane < head) p[lane] = (unsigned char)at(lane);
+  else if (lane >= 8 && tail0 + (lane - 8) < total) p[tail0 + (lane - 8)] = (unsigned char)at(tail0 + (lane - 8));
+}
+
 // Lines [line0, line1) of the ordered list into `out`, line i at byte off[i] - off[line0].  One wave per line: the
-// line's descriptor is wave-uniform (scalar loads), each lane assembles whole dwords of the output at the alignment
-// the destination ADDRESS has and stores them with one 4-byte store; only the bytes before the first aligned dword
-// and after the last one are byte stores.  No LDS, no atomics; offsets are 64-bit.  Targets are rendered from the
-// 2-bit planes: a target byte that is none of A C G T comes out as X.
+// line's descriptor is wave-uniform (scalar loads) and wave_store writes its bytes.  No LDS, no atomics; offsets are
+// 64-bit.  Targets are rendered from the 2-bit planes: a target byte that is none of A C G T comes out as X.
 // An ordered list was checked before any load and its offsets were made from the same data, so neither test below
 // fails unless the context's bookkeeping is wrong; a line that does fail is not rendered and fails the call through
 // *flag (a plain store: every writer stores the same word).
 MUSC_KERNEL __launch_bounds__(256) void k_results_render(const uint4* __restrict__ hits, const uint64_t* __restrict__ off, uint64_t line0,
                                                         uint64_t line1, ResData D, unsigned char* __restrict__ out,
                                                         uint32_t* __restrict__ flag) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const WaveId w = wave_id(threadIdx.x, blockIdx.x, blockDim.x, gridDim.x);
   const uint64_t base = off[line0];
-  for (uint64_t i = line0 + wave; i < line1; i += nwaves) {
+  for (uint64_t i = line0 + w.wave; i < line1; i += w.nwaves) {
     uint4 h = hits[i];
     h.x = __builtin_amdgcn_readfirstlane(h.x);
     h.y = __builtin_amdgcn_readfirstlane(h.y);
     h.z = __builtin_amdgcn_readfirstlane(h.z);
     h.w = __builtin_amdgcn_readfirstlane(h.w);
     if ((uint64_t)h.x >= D.nreads || h.y >= D.nseq) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
     const ResLine l = res_line(D, h);
     const uint64_t total = off[i + 1] - off[i];
     if (total != l.total()) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
-    unsigned char* const p = out + (off[i] - base);
-    const uint64_t mis = (uint64_t)(4u - ((uint32_t)(uintptr_t)p & 3u)) & 3u;
-    const uint64_t head = mis < total ? mis : total;
-    const uint64_t nd = (total - head) >> 2;
-    for (uint64_t d = lane; d < nd; d += 64) {
-      const uint64_t k = head + 4 * d;
-      const uint32_t v = res_line_byte(D, l, k) | (res_line_byte(D, l, k + 1) << 8) | (res_line_byte(D, l, k + 2) << 16) |
-                         (res_line_byte(D, l, k + 3) << 24);
-      *reinterpret_cast<uint32_t*>(p + k) = v;
-    }
-    const uint64_t tail0 = head + 4 * nd;
-    if (lane < head) p[lane] = (unsigned char)res_line_byte(D, l, lane);
-    else if (lane >= 8 && tail0 + (lane - 8) < total) p[tail0 + (lane - 8)] = (unsigned char)res_line_byte(D, l, tail0 + (lane - 8));
+    wave_store(out + (off[i] - base), total, w.lane, [&](uint64_t k) { return res_line_byte(D, l, k); });
   }
 }

@@ -8,28 +8,13 @@
 // the sequences, the gene text the names and the read text count and names.
 //
 // Every text is a list of records with 64-bit byte offsets, rendered one wave per record (per element for readstats)
-// the way k_results_render renders a line.  No LDS, no atomics but the per-name tuple counter, nothing waits on
-// another workgroup.
+// the way k_results_render renders a line (wave_id, wave_store: kernels_results.hpp).  No LDS, no atomics but the
+// per-name tuple counter, nothing waits on another workgroup.
 #pragma once
 
 #define SIDE_NONE 0xFFFFFFFFu  // a read that belongs to no readstats run
 
 DEV bool side_isspace(uint32_t b) { return b == 0x20u || b - 9u <= 4u; }  // C isspace in the C locale
-
-// `total` bytes at `p`, byte k = at(k): whole dwords at the alignment the destination has, byte stores at the ends
-template <class F>
-DEV void side_store(unsigned char* p, uint64_t total, uint32_t lane, F at) {
-  const uint64_t mis = (uint64_t)(4u - ((uint32_t)(uintptr_t)p & 3u)) & 3u;
-  const uint64_t head = mis < total ? mis : total;
-  const uint64_t nd = (total - head) >> 2;
-  for (uint64_t d = lane; d < nd; d += 64) {
-    const uint64_t k = head + 4 * d;
-    *reinterpret_cast<uint32_t*>(p + k) = at(k) | (at(k + 1) << 8) | (at(k + 2) << 16) | (at(k + 3) << 24);
-  }
-  const uint64_t tail0 = head + 4 * nd;
-  if (lane < head) p[lane] = (unsigned char)at(lane);
-  else if (lane >= 8 && tail0 + (lane - 8) < total) p[tail0 + (lane - 8)] = (unsigned char)at(tail0 + (lane - 8));
-}
 
 struct SideData {
   const uint32_t* rd;
@@ -166,23 +151,21 @@ MUSC_KERNEL __launch_bounds__(256) void k_side_nm_len(SideData D, const uint32_t
 MUSC_KERNEL __launch_bounds__(256) void k_side_nm_render(const uint32_t* __restrict__ idx, const uint64_t* __restrict__ off, uint64_t r0,
                                                         uint64_t r1, SideData D, unsigned char* __restrict__ out,
                                                         uint32_t* __restrict__ flag) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const WaveId w = wave_id(threadIdx.x, blockIdx.x, blockDim.x, gridDim.x);
   const uint64_t base = off[r0];
-  for (uint64_t j = r0 + wave; j < r1; j += nwaves) {
+  for (uint64_t j = r0 + w.wave; j < r1; j += w.nwaves) {
     const uint32_t r = __builtin_amdgcn_readfirstlane(idx[j]);
     if ((uint64_t)r >= D.nreads) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
     const SideNm s = side_nm(D, r);
     const uint64_t total = off[j + 1] - off[j];
     if (total != s.total() || s.TL == 0u) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
-    side_store(out + (off[j] - base), total, lane, [&](uint64_t k) { return side_nm_byte(D, s, k); });
+    wave_store(out + (off[j] - base), total, w.lane, [&](uint64_t k) { return side_nm_byte(D, s, k); });
   }
 }
 
@@ -200,14 +183,12 @@ MUSC_KERNEL __launch_bounds__(256) void k_side_gs_len(SideData D, const uint32_t
 MUSC_KERNEL __launch_bounds__(256) void k_side_gs_render(const uint32_t* __restrict__ idx, const uint64_t* __restrict__ off, uint64_t r0,
                                                         uint64_t r1, SideData D, const uint32_t* __restrict__ cnt,
                                                         unsigned char* __restrict__ out, uint32_t* __restrict__ flag) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const WaveId w = wave_id(threadIdx.x, blockIdx.x, blockDim.x, gridDim.x);
   const uint64_t base = off[r0];
-  for (uint64_t j = r0 + wave; j < r1; j += nwaves) {
+  for (uint64_t j = r0 + w.wave; j < r1; j += w.nwaves) {
     const uint32_t k = __builtin_amdgcn_readfirstlane(idx[j]);
     if (k >= D.nnames || D.names[k].x >= D.nseq) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
     const uint2 nm = D.names[k];
@@ -215,11 +196,11 @@ MUSC_KERNEL __launch_bounds__(256) void k_side_gs_render(const uint32_t* __restr
     const uint64_t g0 = D.goff[nm.x], G = D.goff[nm.x + 1] - g0;
     const uint64_t total = off[j + 1] - off[j], NL = nm.y;
     if (total != NL + 1 + nd + 2 || NL >= G || c == 0u) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
     const char* const name = D.gtext + g0;
-    side_store(out + (off[j] - base), total, lane, [&](uint64_t q) -> uint32_t {
+    wave_store(out + (off[j] - base), total, w.lane, [&](uint64_t q) -> uint32_t {
       const bool in_name = q < NL, in_num = q > NL && q - NL - 1 < nd;
       const uint32_t tb = (unsigned char)name[in_name ? q : 0ull];
       const uint32_t dg = res_digit_char(c, nd, in_num ? (uint32_t)(q - NL - 1) : 0u);
@@ -335,21 +316,19 @@ MUSC_KERNEL __launch_bounds__(256) void k_side_rs_render(const uint64_t* __restr
                                                         const uint32_t* __restrict__ first, uint32_t nruns, uint64_t r0, uint64_t r1,
                                                         SideData D, const uint32_t* __restrict__ runread, unsigned char* __restrict__ out,
                                                         uint32_t* __restrict__ flag) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  const WaveId w = wave_id(threadIdx.x, blockIdx.x, blockDim.x, gridDim.x);
   const uint64_t e0 = first[r0], e1 = first[r1];
   if (e0 > e1 || e1 > nel) {
     if (threadIdx.x == 0) *flag = 1u;
     return;
   }
   const uint64_t base = eloff[e0];
-  for (uint64_t k = e0 + wave; k < e1; k += nwaves) {
+  for (uint64_t k = e0 + w.wave; k < e1; k += w.nwaves) {
     SideEl e = side_el(el, nel, k);
     e.run = __builtin_amdgcn_readfirstlane(e.run);
     e.rank = __builtin_amdgcn_readfirstlane(e.rank);
     if (e.run >= nruns || e.rank >= D.nnames || D.names[e.rank].x >= D.nseq || (uint64_t)runread[e.run] >= D.nreads) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
     const uint2 nm = D.names[e.rank];
@@ -358,12 +337,12 @@ MUSC_KERNEL __launch_bounds__(256) void k_side_rs_render(const uint64_t* __restr
     const uint64_t g0 = D.goff[nm.x], G = D.goff[nm.x + 1] - g0;
     const uint64_t total = eloff[k + 1] - eloff[k];
     if (total != TL + NL + 1 + e.tail || NL >= G) {
-      if (lane == 0) *flag = 1u;
+      if (w.lane == 0) *flag = 1u;
       continue;
     }
     const char* const name = D.gtext + g0;
     const char* const tokp = D.ttext + D.toff[r] + D.tok[r].z;
-    side_store(out + (eloff[k] - base), total, lane, [&](uint64_t q) -> uint32_t {
+    wave_store(out + (eloff[k] - base), total, w.lane, [&](uint64_t q) -> uint32_t {
       const bool in_tok = q + 1 < TL, in_name = q >= TL && q - TL < NL;
       const uint32_t tb = (unsigned char)(in_tok ? tokp[q] : name[in_name ? q - TL : 0ull]);
       if (in_tok || in_name) return tb;

@@ -1,0 +1,644 @@
+// muscato_text.hpp -- the host side of the texts rendered on the device: results.txt (musc_results_*) and
+// the nonmatch FASTQ, genestats and readstats (musc_side_*).  Part of libmuscato_hip.so: included by
+// muscato_hip.hip after the context, the scans and the loaders (drop_gene_text, drop_read_text).  Both families build
+// record lists with 64-bit byte offsets and render ranges of them through one driver, text_range.
+#pragma once
+
+#include "text_stage.hpp"
+
+// the grid of a grid-stride kernel over k items
+static dim3 grid(uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); }
+
+// `body()` between two events of the context's pool on its stream: *ms = the time between them.  The stream is waited
+// for on every path, so nothing of a failed body is still queued when its temporaries go; *ms is written on success only.
+template <class Body>
+static int timed(musc_ctx* c, float* ms, Body body) {
+  c->ev_used = 0;
+  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
+  HIPCHK(c, hipEventRecord(e0, c->stream));
+  const int rc = body();
+  const hipError_t er = hipEventRecord(e1, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIPCHK(c, er);
+  HIPCHK(c, es);
+  *ms = 0;
+  (void)hipEventElapsedTime(ms, e0, e1);
+  return 0;
+}
+
+// A text as musc_results_text and musc_side_text see it: n records, record i = bytes [off[i], off[i + 1]) of the text.
+struct TextDesc {
+  const uint64_t* off;  // device, n + 1 offsets
+  uint64_t n;
+  const char* name;     // of the public call, for messages
+  const char* unfit;    // the code-11 message: a record the kernel refused to render
+  float* ms_text;       // accumulates the event time of the calls that render
+};
+
+// Records [rec0, rec0 + nrec) of a text, clipped at its end, into dst; `launch(r0, r1, bytes, out)` queues the kernel
+// that renders records [r0, r1), `bytes` in all, at `out` on the device.  dst == NULL only reports the size.  A device
+// destination takes one launch.  A host destination is filled through res_stage: the offsets come to the host in
+// windows of MUSC_DEBUG_STAGE_LINES records, and each window goes in pieces of the most records that fit
+// MUSC_DEBUG_STAGE_BYTES (text_stage.hpp), rendered, copied and waited for one after the other.
+// *nbytes = the bytes of the range on success and 0 on every failure.
+template <class Launch>
+static int text_range(musc_ctx* c, const TextDesc& t, uint64_t rec0, uint64_t nrec, char* dst, uint64_t capacity, int dst_on_device,
+                      uint64_t* nbytes, Launch launch) {
+  *nbytes = 0;
+  if (rec0 >= t.n || nrec == 0) return 0;
+  const uint64_t r0 = rec0, r1 = nrec > t.n - rec0 ? t.n : rec0 + nrec;
+  HIPCHK(c, hipSetDevice(c->device));
+  uint64_t bytes = 0;
+  float ms = 0;
+  int rc = timed(c, &ms, [&]() -> int {
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned, t.off + r0, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, t.off + r1, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint64_t o0 = c->h_pinned[0];
+    bytes = c->h_pinned[1] - o0;
+    if (!dst) return 0;
+    if (capacity < bytes)
+      return fail(c, 2, "%s: capacity %llu < %llu bytes", t.name, (unsigned long long)capacity, (unsigned long long)bytes);
+    HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));  // raised by a record the kernel refuses to render
+    if (dst_on_device) {
+      launch(r0, r1, bytes, reinterpret_cast<unsigned char*>(dst));
+      HIPCHK(c, hipGetLastError());
+      return 0;
+    }
+    const uint64_t stage = c->env.stage_bytes;
+    std::vector<uint64_t> off;
+    for (uint64_t b0 = r0; b0 < r1;) {
+      const uint64_t nw = std::min(r1 - b0, c->env.stage_lines);  // this window: records [b0, b0 + nw)
+      off.resize(nw + 1);
+      HIPCHK(c, hipMemcpyAsync(off.data(), t.off + b0, (nw + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (uint64_t p0 = 0; p0 < nw;) {
+        const uint64_t p1 = musc_text::stage_piece_end(off.data(), nw, p0, stage);
+        const uint64_t pb = off[p1] - off[p0];
+        const int re = ensure(c, c->res_stage, std::max(pb, stage));
+        if (re) return re;
+        launch(b0 + p0, b0 + p1, pb, c->res_stage.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(dst + (off[p0] - o0), c->res_stage.p, pb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        p0 = p1;
+      }
+      b0 += nw;
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  if (dst) {
+    uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned + 2);
+    *h_bad = 0;
+    HIPCHK(c, hipMemcpyAsync(h_bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (*h_bad) return fail(c, 11, "%s: %s", t.name, t.unfit);
+    *t.ms_text += ms;
+  }
+  *nbytes = bytes;
+  return 0;
+}
+
+// ---------------------------------------------------------------- results.txt on the device
+// The post-chain of cmd/muscato/main.go:422-676 from the resident tuples: musc_results_order drops the tuples of genes
+// without an id line, orders the rest as `sort -k1` orders their six-column lines and computes every line's byte
+// offset; musc_results_text renders a range of lines (kernels_results.hpp).
+
+static ResData res_data(const musc_ctx* c) {
+  ResData D;
+  D.rd = c->rd;
+  D.rdm = c->reads_have_x ? c->rdm : nullptr;
+  D.db2 = c->db2;
+  D.dbm2 = c->db_has_x ? c->dbm2 : nullptr;
+  D.seq_off = c->seq_off;
+  D.gtext = c->res_gtext;
+  D.goff = c->res_goff;
+  D.ttext = c->res_ttext;
+  D.toff = c->res_toff;
+  D.nreads = c->nreads;
+  D.nseq = c->nseq;
+  D.rw = c->rw;
+  return D;
+}
+
+// text + offsets of n items to the device (the offsets must not decrease; item i = bytes [offsets[i], offsets[i + 1]))
+static int upload_text(musc_ctx* c, const char* what, const char* text, const uint64_t* offsets, uint64_t n, char** d_text, uint64_t** d_off) {
+  for (uint64_t i = 0; i < n; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(c, 2, "%s: offsets decrease at item %llu", what, (unsigned long long)i);
+  const uint64_t bytes = offsets[n];
+  HIPCHK(c, hipMalloc((void**)d_text, bytes + 16));
+  HIPCHK(c, hipMalloc((void**)d_off, (n + 1) * 8));
+  if (bytes) HIPCHK(c, hipMemcpyAsync(*d_text, text, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(*d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int musc_results_set_gene_text(musc_ctx* c, const char* text, const uint64_t* offsets, const uint8_t* absent, uint32_t nseq) {
+  if (!c) return 1;
+  if (!offsets || (!text && offsets[nseq] != 0)) return fail(c, 2, "musc_results_set_gene_text: NULL input");
+  if (!c->db2 || nseq != c->nseq)
+    return fail(c, 2, "musc_results_set_gene_text: text of %u genes for a database of %u targets", nseq, c->nseq);
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool list_ok = c->hits_current;  // (a new text leaves the tuple list as good as it was)
+  drop_gene_text(c);
+  c->hits_current = list_ok;
+  int rc = upload_text(c, "musc_results_set_gene_text", text, offsets, nseq, &c->res_gtext, &c->res_goff);
+  if (rc) {
+    drop_gene_text(c);
+    return rc;
+  }
+  // rank of each gene's text among all of them, bytewise; equal texts share a rank
+  std::vector<uint32_t> order;
+  order.reserve(nseq);
+  for (uint32_t g = 0; g < nseq; g++)
+    if (!absent || !absent[g]) order.push_back(g);
+  auto cmp = [&](uint32_t a, uint32_t b) {
+    const uint64_t la = offsets[a + 1] - offsets[a], lb = offsets[b + 1] - offsets[b];
+    const int d = memcmp(text + offsets[a], text + offsets[b], (size_t)std::min(la, lb));
+    return d ? d : la < lb ? -1 : la > lb ? 1 : 0;
+  };
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cmp(a, b) < 0; });
+  std::vector<uint32_t> rank(nseq, RES_ABSENT);
+  uint32_t rk = 0;
+  for (size_t i = 0; i < order.size(); i++) {
+    if (i && cmp(order[i - 1], order[i]) != 0) rk++;
+    rank[order[i]] = rk;
+  }
+  hipError_t e = hipMalloc((void**)&c->res_rank, (uint64_t)nseq * 4 + 16);
+  if (e == hipSuccess) e = hipMemcpy(c->res_rank, rank.data(), (uint64_t)nseq * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    drop_gene_text(c);
+    return fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e));
+  }
+  // for the side outputs: the form of the texts, and the rank of each gene's name alone
+  c->side_bad_gene = musc_side::first_bad_form(text, offsets, absent, nseq);
+  c->side_form_ok = c->side_bad_gene == nseq;
+  if (c->side_form_ok) {
+    const musc_side::NameRanks R = musc_side::name_ranks(text, offsets, absent, nseq);
+    std::vector<uint2> names(R.rep.size());
+    for (size_t k = 0; k < names.size(); k++) names[k] = make_uint2(R.rep[k], R.len[k]);
+    e = hipMalloc((void**)&c->side_nrank, (uint64_t)nseq * 4 + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->side_names, names.size() * 8 + 16);
+    if (e == hipSuccess) e = hipMemcpy(c->side_nrank, R.rank.data(), (uint64_t)nseq * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !names.empty()) e = hipMemcpy(c->side_names, names.data(), names.size() * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      drop_gene_text(c);
+      return fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e));
+    }
+    c->side_nnames = (uint32_t)names.size();
+  }
+  return 0;
+}
+
+int musc_results_set_read_text(musc_ctx* c, const char* text, const uint64_t* offsets, uint64_t nreads) {
+  if (!c) return 1;
+  if (!offsets || (!text && offsets[nreads] != 0)) return fail(c, 2, "musc_results_set_read_text: NULL input");
+  if (nreads != c->nreads)
+    return fail(c, 2, "musc_results_set_read_text: text of %llu reads, %llu are loaded", (unsigned long long)nreads, (unsigned long long)c->nreads);
+  HIPCHK(c, hipSetDevice(c->device));
+  drop_read_text(c);
+  const int rc = upload_text(c, "musc_results_set_read_text", text, offsets, nreads, &c->res_ttext, &c->res_toff);
+  if (rc) drop_read_text(c);
+  return rc;
+}
+
+int musc_results_number_key(uint32_t pos, uint32_t nmiss, uint64_t* key) {
+  if (!key || nmiss > 99999u) return 2;
+  *key = res_number_key(pos, nmiss);
+  return 0;
+}
+
+static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_device) {
+  const dim3 B256(256);
+  const uint4* d_in = reinterpret_cast<const uint4*>(hits);
+  TmpBufs B;
+  if (!hits) {
+    if (!c->hits_current)
+      return fail(c, 2, "musc_results_order: the resident tuple list is not that of a pass over the reads and the database in hand");
+    d_in = reinterpret_cast<const uint4*>(c->hits.p);
+    n = c->nhits;
+  } else if (on_device && ((uintptr_t)hits & 15u)) {
+    return fail(c, 2, "musc_results_order: a device list must be 16-byte aligned");
+  } else if (!on_device && n) {
+    // a host list is checked here, before it is uploaded (a device list: k_results_flag)
+    for (uint64_t i = 0; i < n; i++) {
+      const musc_hit& h = hits[i];
+      if (h.read_idx >= c->nreads || h.gene_idx >= c->nseq || h.nmiss > RES_MAX_NMISS ||
+          h.pos > c->h_seq_off[(size_t)h.gene_idx + 1] - c->h_seq_off[h.gene_idx])
+        return fail(c, 2, "musc_results_order: tuple %llu (read %u, gene %u, pos %u, nmiss %u) is outside the loaded reads and targets",
+                    (unsigned long long)i, h.read_idx, h.gene_idx, h.pos, h.nmiss);
+    }
+    uint4* up = nullptr;
+    HIPCHK(c, B.alloc(&up, n * 16));
+    HIPCHK(c, hipMemcpyAsync(up, hits, n * 16, hipMemcpyHostToDevice, c->stream));
+    d_in = up;
+  }
+  if (n >= 0xFFFFFFF0ull) return fail(c, 2, "musc_results_order: too many tuples for 32-bit line numbers");
+  int rc;
+  if ((rc = ensure(c, c->res_off, n + 1))) return rc;
+  if (n == 0) {
+    HIPCHK(c, hipMemsetAsync(c->res_off.p, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+
+  // ---- validate, drop the tuples of absent genes
+  uint32_t *keep = nullptr, *excl = nullptr, *stmp = nullptr;
+  uint4* a = nullptr;
+  HIPCHK(c, B.alloc(&keep, n * 4));
+  HIPCHK(c, B.alloc(&excl, n * 4));
+  HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(n) * 4));
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
+  hipLaunchKernelGGL(k_results_flag, grid(n), B256, 0, c->stream, d_in, n, c->nreads, c->nseq, c->seq_off, c->res_rank, keep, c->d_flag);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, keep, excl, n, false, stmp))) return rc;
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  HIPCHK(c, hipMemcpyAsync(h32, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h32 + 1, excl + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h32 + 2, keep + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h32[0] & 1u)
+    return fail(c, 2, "musc_results_order: a tuple names a read, a target or a position outside the loaded reads and targets");
+  const bool read_major = !(h32[0] & 2u);
+  const uint64_t m = (uint64_t)h32[1] + h32[2];
+  if ((rc = ensure(c, c->res_hits, std::max<uint64_t>(m, 1)))) return rc;
+  uint4* const out = reinterpret_cast<uint4*>(c->res_hits.p);
+  if (m == 0) {
+    HIPCHK(c, hipMemsetAsync(c->res_off.p, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  HIPCHK(c, B.alloc(&a, m * 16));
+  hipLaunchKernelGGL(k_results_compact, grid(n), B256, 0, c->stream, d_in, keep, excl, n, a);
+  HIPCHK(c, hipGetLastError());
+
+  uint64_t *k0 = nullptr, *k1 = nullptr;
+  uint32_t *p0 = nullptr, *p1 = nullptr;
+  void* tmp = nullptr;
+  size_t tmp_bytes = 0;
+  auto sort_bufs = [&](TmpBufs& T, uint64_t k) -> int {
+    HIPCHK(c, T.alloc(&k0, k * 8));
+    HIPCHK(c, T.alloc(&k1, k * 8));
+    HIPCHK(c, T.alloc(&p0, k * 4));
+    HIPCHK(c, T.alloc(&p1, k * 4));
+    tmp_bytes = 0;
+    for (unsigned end : {32u, 33u, 60u, 63u}) {
+      size_t tb = 0;
+      HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tb, k0, k1, p0, p1, (size_t)k, 0u, end, c->stream));
+      tmp_bytes = std::max(tmp_bytes, tb);
+    }
+    HIPCHK(c, T.alloc(&tmp, tmp_bytes));
+    return 0;
+  };
+  // one stable LSD pass over (key word, permutation) pairs
+  auto sort_pass = [&](const uint32_t* idx, uint64_t k, uint32_t what, unsigned end_bit) -> int {
+    hipLaunchKernelGGL(k_results_keys, grid(k), B256, 0, c->stream, a, idx, p0, k, what, c->res_rank, c->rd, c->rw, c->db2,
+                       c->db_has_x ? c->dbm2 : (const uint32_t*)nullptr, c->seq_off, k0);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, rocprim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, p0, p1, (size_t)k, 0u, end_bit, c->stream));
+    std::swap(p0, p1);
+    return 0;
+  };
+
+  // ---- a list that is not read-major (a host list in any order): one sort on read_idx first
+  if (!read_major) {
+    TmpBufs T;
+    uint4* a2 = nullptr;
+    if ((rc = sort_bufs(T, m))) return rc;
+    HIPCHK(c, B.alloc(&a2, m * 16));
+    hipLaunchKernelGGL(k_results_iota, grid(m), B256, 0, c->stream, p0, m);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = sort_pass(nullptr, m, RES_KEY_READ, 32u))) return rc;
+    hipLaunchKernelGGL(k_results_gather, grid(m), B256, 0, c->stream, a, p0, m, a2);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (T is released at the end of this scope)
+    a = a2;
+  }
+
+  // ---- read segments: a read with one tuple is in place; the others are sorted
+  uint32_t *multi = nullptr, *incl = nullptr, *idx = nullptr;
+  HIPCHK(c, B.alloc(&multi, m * 4));
+  HIPCHK(c, B.alloc(&incl, m * 4));
+  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_results_segments, grid(m), B256, 0, c->stream, a, m, c->rd, c->rw, multi, c->counters + CNT_SCRATCH);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, multi, incl, m, true, stmp))) return rc;  // (m <= n: stmp is large enough)
+  HIPCHK(c, hipMemcpyAsync(h32, incl + (m - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t k = h32[0], maxlen = c->h_pinned[1];
+  if (k == 0) {
+    HIPCHK(c, hipMemcpyAsync(out, a, m * 16, hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    TmpBufs T;
+    if ((rc = sort_bufs(T, k))) return rc;
+    HIPCHK(c, T.alloc(&idx, k * 4));
+    hipLaunchKernelGGL(k_results_idx, grid(m), B256, 0, c->stream, multi, incl, m, idx);
+    hipLaunchKernelGGL(k_results_iota, grid(k), B256, 0, c->stream, p0, k);
+    HIPCHK(c, hipGetLastError());
+    // least significant first: gene rank, the number word, the target words from last to first, the read
+    const uint32_t nw = (uint32_t)((maxlen + RES_BASES_PER_WORD - 1) / RES_BASES_PER_WORD);
+    if ((rc = sort_pass(idx, k, RES_KEY_RANK, 32u))) return rc;
+    if ((rc = sort_pass(idx, k, RES_KEY_NUMBER, 60u))) return rc;
+    for (uint32_t w = nw; w-- > 0;)
+      if ((rc = sort_pass(idx, k, RES_KEY_SPAN + w, 63u))) return rc;
+    if ((rc = sort_pass(idx, k, RES_KEY_READ, 32u))) return rc;
+    hipLaunchKernelGGL(k_results_place, grid(m), B256, 0, c->stream, a, multi, incl, idx, p0, m, out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+
+  // ---- line lengths -> offsets
+  uint64_t* stmp64 = nullptr;
+  HIPCHK(c, B.alloc(&stmp64, scan_tmp_elems(m + 1) * 8));
+  hipLaunchKernelGGL(k_results_len, grid(m + 1), B256, 0, c->stream, out, m, res_data(c), c->res_off.p);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u64(c, c->res_off.p, c->res_off.p, m + 1, stmp64))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->res_off.p + m, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->res_n = m;
+  c->res_bytes = c->h_pinned[0];
+  return 0;
+}
+
+int musc_results_order(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_device, uint64_t* nlines, uint64_t* nbytes) {
+  if (!c) return 1;
+  if (nlines) *nlines = 0;
+  if (nbytes) *nbytes = 0;
+  c->res_valid = false;
+  c->side_valid = false;
+  c->res_n = c->res_bytes = 0;
+  if (!c->db2 || !c->res_gtext || !c->res_rank) return fail(c, 2, "musc_results_order: no gene text (musc_results_set_gene_text)");
+  if (c->up.active) return fail(c, 2, "musc_results_order: a streamed read load has not been matched yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = timed(c, &c->res_ms_order, [&] { return results_order_impl(c, hits, n, on_device); });
+  if (rc) return rc;
+  c->res_ms_text = 0;
+  c->res_valid = true;
+  c->side_after_match = false;
+  if (nlines) *nlines = c->res_n;
+  if (nbytes) *nbytes = c->res_bytes;
+  return 0;
+}
+
+int musc_results_hits(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_device) {
+  if (!c) return 1;
+  if (!c->res_valid) return fail(c, 2, "musc_results_hits: no ordered list (musc_results_order)");
+  if (capacity < c->res_n) return fail(c, 2, "musc_results_hits: capacity %llu < %llu tuples", (unsigned long long)capacity, (unsigned long long)c->res_n);
+  if (c->res_n == 0) return 0;
+  if (!dst) return fail(c, 2, "musc_results_hits: dst is NULL");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(dst, c->res_hits.p, c->res_n * sizeof(musc_hit), dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+static void launch_render(musc_ctx* c, uint64_t l0, uint64_t l1, unsigned char* out) {
+  const uint64_t nl = l1 - l0;
+  const unsigned blocks = (unsigned)std::min<uint64_t>((nl + 3) / 4, 4 * MAX_GRID);
+  hipLaunchKernelGGL(k_results_render, dim3(blocks), dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(c->res_hits.p), c->res_off.p, l0, l1,
+                     res_data(c), out, c->d_flag);
+}
+
+int musc_results_text(musc_ctx* c, uint64_t line0, uint64_t nlines, char* dst, uint64_t capacity, int dst_on_device, uint64_t* nbytes) {
+  if (!c) return 1;
+  if (!nbytes) return fail(c, 2, "musc_results_text: nbytes is NULL");
+  *nbytes = 0;
+  if (!c->res_valid) return fail(c, 2, "musc_results_text: no ordered list (musc_results_order)");
+  const TextDesc t = {c->res_off.p, c->res_n, "musc_results_text",
+                      "a line of the ordered list no longer fits the reads, the database or the texts in hand", &c->res_ms_text};
+  return text_range(c, t, line0, nlines, dst, capacity, dst_on_device, nbytes,
+                    [&](uint64_t l0, uint64_t l1, uint64_t, unsigned char* out) { launch_render(c, l0, l1, out); });
+}
+
+int musc_results_last_ms(musc_ctx* c, float* ms_order, float* ms_text) {
+  if (!c) return 1;
+  if (ms_order) *ms_order = c->res_ms_order;
+  if (ms_text) *ms_text = c->res_ms_text;
+  return 0;
+}
+
+// ---------------------------------------------------------------- the side outputs on the device
+// The nonmatch FASTQ (cmd/muscato_nonmatch/main.go:95-114, an exact set for the Bloom filter), `*_genestats`
+// (cmd/muscato/main.go:94-150 + cmd/muscato_genestats/main.go) and `*_readstats` (cmd/muscato_readstats/main.go, the
+// gene set sorted) from the ordered list of the last musc_results_order: musc_side_prepare builds the record lists
+// and their byte offsets, musc_side_text renders a range of records (kernels_side.hpp).
+
+static const int MUSC_SIDE_ERR_FORM = 12;  // the gene text is not in the simple form: the caller's cue for its host path
+
+static SideData side_data(const musc_ctx* c) {
+  SideData D;
+  D.rd = c->rd;
+  D.rdm = c->reads_have_x ? c->rdm : nullptr;
+  D.ttext = c->res_ttext;
+  D.toff = c->res_toff;
+  D.tok = c->side_tok.p;
+  D.gtext = c->res_gtext;
+  D.goff = c->res_goff;
+  D.names = c->side_names;
+  D.nreads = c->nreads;
+  D.nseq = c->nseq;
+  D.nnames = c->side_nnames;
+  D.rw = c->rw;
+  return D;
+}
+
+// flag / len over n + 1 items (the last one empty) -> the record list of text `which`: idx (when the text has one),
+// offsets, counts.  excl and stmp are scratch for n + 1 items; len is scanned in place.
+static int side_records(musc_ctx* c, int which, const uint32_t* flag, uint32_t* excl, uint64_t* len, uint64_t n, uint32_t* stmp,
+                        uint64_t* stmp64) {
+  int rc;
+  if ((rc = scan_u32(c, flag, excl, n + 1, false, stmp))) return rc;
+  if ((rc = scan_u64(c, len, len, n + 1, stmp64))) return rc;
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  HIPCHK(c, hipMemcpyAsync(h32, excl + n, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, len + n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t nrec = h32[0], nbytes = c->h_pinned[1];
+  if ((rc = ensure(c, c->side_idx[which], std::max<uint64_t>(nrec, 1)))) return rc;
+  if ((rc = ensure(c, c->side_off[which], nrec + 1))) return rc;
+  hipLaunchKernelGGL(k_side_compact, grid(n + 1), dim3(256), 0, c->stream, flag, excl, len, n, c->side_idx[which].p, c->side_off[which].p);
+  HIPCHK(c, hipGetLastError());
+  c->side_nrec[which] = nrec;
+  c->side_nbytes[which] = nbytes;
+  return 0;
+}
+
+static int side_prepare_impl(musc_ctx* c) {
+  const dim3 B256(256);
+  const uint64_t nreads = c->nreads, m = c->res_n, nnames = c->side_nnames;
+  const uint4* const hits = reinterpret_cast<const uint4*>(c->res_hits.p);
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  int rc;
+  TmpBufs B;
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
+
+  // ---- tokens: once per read text
+  if (!c->side_tok_valid) {
+    if ((rc = ensure(c, c->side_tok, std::max<uint64_t>(nreads, 1)))) return rc;
+    hipLaunchKernelGGL(k_side_tokens, grid(nreads), B256, 0, c->stream, c->res_ttext, c->res_toff, nreads, c->side_tok.p, c->d_flag);
+    HIPCHK(c, hipGetLastError());
+  }
+
+  // ---- mark the matched reads, count the tuples of every name
+  const uint64_t nmax = std::max(std::max(nreads, nnames), m) + 1;  // items of the largest scan below
+  uint32_t *matched = nullptr, *flag = nullptr, *excl = nullptr, *stmp = nullptr;
+  uint64_t *len = nullptr, *stmp64 = nullptr;
+  HIPCHK(c, B.alloc(&matched, (nreads + 1) * 4));
+  HIPCHK(c, B.alloc(&flag, nmax * 4));
+  HIPCHK(c, B.alloc(&excl, nmax * 4));
+  HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(nmax) * 4));
+  HIPCHK(c, B.alloc(&len, nmax * 8));
+  HIPCHK(c, B.alloc(&stmp64, scan_tmp_elems(nmax) * 8));
+  if ((rc = ensure(c, c->side_cnt, std::max<uint64_t>(nnames, 1)))) return rc;
+  HIPCHK(c, hipMemsetAsync(matched, 0, (nreads + 1) * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->side_cnt.p, 0, std::max<uint64_t>(nnames, 1) * 4, c->stream));
+  if (m) {
+    hipLaunchKernelGGL(k_side_mark, grid(m), B256, 0, c->stream, hits, m, c->side_nrank, nreads, c->nseq, (uint32_t)nnames, matched,
+                       c->side_cnt.p, c->d_flag);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemcpyAsync(h32 + 4, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h32[4]) return fail(c, 11, "musc_side_prepare: a read's text is longer than 4 GiB, or the ordered list no longer fits the reads and the gene text in hand");
+  c->side_tok_valid = true;
+  const SideData D = side_data(c);
+
+  // ---- nonmatch: the unmatched reads that have a token
+  hipLaunchKernelGGL(k_side_nm_len, grid(nreads + 1), B256, 0, c->stream, D, matched, flag, len);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = side_records(c, MUSC_SIDE_NONMATCH, flag, excl, len, nreads, stmp, stmp64))) return rc;
+
+  // ---- genestats: the names with a tuple
+  hipLaunchKernelGGL(k_side_gs_len, grid(nnames + 1), B256, 0, c->stream, D, c->side_cnt.p, flag, len);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = side_records(c, MUSC_SIDE_GENESTATS, flag, excl, len, nnames, stmp, stmp64))) return rc;
+
+  // ---- readstats: runs of equal tokens over the matched reads that have one
+  c->side_nel = 0;
+  c->side_nrec[MUSC_SIDE_READSTATS] = c->side_nbytes[MUSC_SIDE_READSTATS] = 0;
+  if ((rc = ensure(c, c->side_off[MUSC_SIDE_READSTATS], 1))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->side_off[MUSC_SIDE_READSTATS].p, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_side_rs_flag, grid(nreads + 1), B256, 0, c->stream, matched, c->side_tok.p, nreads, flag);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, flag, excl, nreads + 1, false, stmp))) return rc;
+  HIPCHK(c, hipMemcpyAsync(h32, excl + nreads, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t ncr = h32[0];
+  if (ncr == 0 || m == 0) return 0;
+  uint32_t *cr = nullptr, *head = nullptr, *incl = nullptr, *runof = nullptr;
+  HIPCHK(c, B.alloc(&cr, ncr * 4));
+  HIPCHK(c, B.alloc(&head, ncr * 4));
+  HIPCHK(c, B.alloc(&incl, ncr * 4));
+  HIPCHK(c, B.alloc(&runof, nreads * 4));
+  hipLaunchKernelGGL(k_side_compact, grid(nreads + 1), B256, 0, c->stream, flag, excl, (const uint64_t*)nullptr, nreads, cr, (uint64_t*)nullptr);
+  hipLaunchKernelGGL(k_side_rs_heads, grid(ncr), B256, 0, c->stream, cr, ncr, D, head);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, head, incl, ncr, true, stmp))) return rc;
+  HIPCHK(c, hipMemcpyAsync(h32, incl + (ncr - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t nruns = h32[0];
+  if ((rc = ensure(c, c->side_runread, nruns))) return rc;
+  if ((rc = ensure(c, c->side_first, nruns + 1))) return rc;
+  if ((rc = ensure(c, c->side_off[MUSC_SIDE_READSTATS], nruns + 1))) return rc;
+  HIPCHK(c, hipMemsetAsync(runof, 0xFF, nreads * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->side_first.p, 0, (nruns + 1) * 4, c->stream));  // (every run has an element; were one without, it reads element 0)
+  hipLaunchKernelGGL(k_side_rs_runs, grid(ncr), B256, 0, c->stream, cr, head, incl, ncr, runof, c->side_runread.p);
+  HIPCHK(c, hipGetLastError());
+
+  // one key per kept tuple, sorted; the distinct keys are the elements of the lines
+  uint64_t *k0 = nullptr, *k1 = nullptr;
+  void* tmp = nullptr;
+  size_t tmp_bytes = 0;
+  HIPCHK(c, B.alloc(&k0, m * 8));
+  HIPCHK(c, B.alloc(&k1, m * 8));
+  HIPCHK(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, k0, k1, (size_t)m, 0u, 64u, c->stream));
+  HIPCHK(c, B.alloc(&tmp, tmp_bytes));
+  hipLaunchKernelGGL(k_side_rs_keys, grid(m), B256, 0, c->stream, hits, m, runof, c->side_nrank, k0);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, rocprim::radix_sort_keys(tmp, tmp_bytes, k0, k1, (size_t)m, 0u, 64u, c->stream));
+  hipLaunchKernelGGL(k_side_rs_uniq, grid(m + 1), B256, 0, c->stream, k1, m, flag);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u32(c, flag, excl, m + 1, false, stmp))) return rc;
+  HIPCHK(c, hipMemcpyAsync(h32, excl + m, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t nel = h32[0];
+  if (nel < nruns) return fail(c, 11, "musc_side_prepare: a run of reads without an element");
+  if ((rc = ensure(c, c->side_el, nel))) return rc;
+  if ((rc = ensure(c, c->side_eloff, nel + 1))) return rc;
+  hipLaunchKernelGGL(k_side_rs_elems, grid(m), B256, 0, c->stream, k1, flag, excl, m, c->side_el.p);
+  hipLaunchKernelGGL(k_side_rs_len, grid(nel + 1), B256, 0, c->stream, c->side_el.p, nel, (uint32_t)nruns, D, c->side_runread.p,
+                     c->side_eloff.p, c->side_first.p);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u64(c, c->side_eloff.p, c->side_eloff.p, nel + 1, stmp64))) return rc;  // (nel <= m: stmp64 is large enough)
+  hipLaunchKernelGGL(k_side_rs_lines, grid(nruns + 1), B256, 0, c->stream, c->side_first.p, c->side_eloff.p, nruns,
+                     c->side_off[MUSC_SIDE_READSTATS].p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->side_eloff.p + nel, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->side_nel = nel;
+  c->side_nrec[MUSC_SIDE_READSTATS] = nruns;
+  c->side_nbytes[MUSC_SIDE_READSTATS] = c->h_pinned[0];
+  return 0;
+}
+
+int musc_side_prepare(musc_ctx* c, uint64_t* nrecords, uint64_t* nbytes) {
+  if (!c) return 1;
+  for (int w = 0; w < 3; w++) {
+    if (nrecords) nrecords[w] = 0;
+    if (nbytes) nbytes[w] = 0;
+  }
+  c->side_valid = false;
+  if (!c->res_valid) return fail(c, 2, "musc_side_prepare: no ordered list (musc_results_order) of the reads, the database and the texts in hand");
+  if (c->side_after_match) return fail(c, 2, "musc_side_prepare: a pass ran after the last musc_results_order: order its list first");
+  if (!c->res_ttext) return fail(c, 2, "musc_side_prepare: no read text (musc_results_set_read_text)");
+  if (!c->side_form_ok)
+    return fail(c, MUSC_SIDE_ERR_FORM, "musc_side_prepare: gene text not in the simple form (gene %u is not name\\tlen without blanks)", c->side_bad_gene);
+  if (c->nreads >= 0xFFFFFFF0ull) return fail(c, 2, "musc_side_prepare: too many reads for 32-bit record numbers");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = timed(c, &c->side_ms_prepare, [&] { return side_prepare_impl(c); });
+  if (rc) return rc;
+  c->side_ms_text = 0;
+  c->side_valid = true;
+  for (int w = 0; w < 3; w++) {
+    if (nrecords) nrecords[w] = c->side_nrec[w];
+    if (nbytes) nbytes[w] = c->side_nbytes[w];
+  }
+  return 0;
+}
+
+static void launch_side(musc_ctx* c, int which, uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) {
+  const unsigned blocks = (unsigned)std::min<uint64_t>(bytes / 256 + 1, 4 * MAX_GRID);
+  const SideData D = side_data(c);
+  if (which == MUSC_SIDE_NONMATCH)
+    hipLaunchKernelGGL(k_side_nm_render, dim3(blocks), dim3(256), 0, c->stream, c->side_idx[0].p, c->side_off[0].p, r0, r1, D, out, c->d_flag);
+  else if (which == MUSC_SIDE_GENESTATS)
+    hipLaunchKernelGGL(k_side_gs_render, dim3(blocks), dim3(256), 0, c->stream, c->side_idx[1].p, c->side_off[1].p, r0, r1, D, c->side_cnt.p, out,
+                       c->d_flag);
+  else
+    hipLaunchKernelGGL(k_side_rs_render, dim3(blocks), dim3(256), 0, c->stream, c->side_el.p, c->side_nel, c->side_eloff.p, c->side_first.p,
+                       (uint32_t)c->side_nrec[2], r0, r1, D, c->side_runread.p, out, c->d_flag);
+}
+
+int musc_side_text(musc_ctx* c, int which, uint64_t rec0, uint64_t nrec, char* dst, uint64_t capacity, int dst_on_device, uint64_t* nbytes) {
+  if (!c) return 1;
+  if (!nbytes) return fail(c, 2, "musc_side_text: nbytes is NULL");
+  *nbytes = 0;
+  if (which < 0 || which > 2) return fail(c, 2, "musc_side_text: no such text (%d)", which);
+  if (!c->side_valid || !c->res_valid || c->side_after_match) return fail(c, 2, "musc_side_text: nothing prepared (musc_side_prepare)");
+  const TextDesc t = {c->side_off[which].p, c->side_nrec[which], "musc_side_text", "a record no longer fits the reads or the texts in hand",
+                      &c->side_ms_text};
+  return text_range(c, t, rec0, nrec, dst, capacity, dst_on_device, nbytes,
+                    [&](uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) { launch_side(c, which, r0, r1, bytes, out); });
+}
+
+int musc_side_last_ms(musc_ctx* c, float* ms_prepare, float* ms_text) {
+  if (!c) return 1;
+  if (ms_prepare) *ms_prepare = c->side_ms_prepare;
+  if (ms_text) *ms_text = c->side_ms_text;
+  return 0;
+}

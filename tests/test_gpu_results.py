@@ -4,6 +4,7 @@ The expected bytes are always oracle.muscato_oracle.results_text over the fed tu
 every one of them; the tail of a line (count and names) is whatever text the test gave the read, so the oracle's own
 two last columns are replaced by it.  The tuple lists are fed by hand, so no matching workload is needed -- but for the
 last test, which orders the list a real pass left on the device."""
+import contextlib
 import ctypes
 import os
 import random
@@ -211,6 +212,86 @@ def test_text_in_chunks(eng, segments):
         assert b"".join(parts) == exp, step
     assert eng.results_text(nl, 5) == b"" and eng.results_text(nl + 1000) == b"" and eng.results_text(3, 0) == b""
     assert eng.results_text(nl - 2, 100) == b"".join(exp.splitlines(True)[-2:])
+
+
+STAGE_KNOBS = ("MUSC_DEBUG_STAGE_BYTES", "MUSC_DEBUG_STAGE_LINES")
+
+
+@contextlib.contextmanager
+def staged(eng, stage_bytes, stage_lines):
+    """The text calls of `eng` with a staging buffer of `stage_bytes` and offset windows of `stage_lines` records, so
+    that a small range passes through the host path in many pieces; the defaults are back afterwards."""
+    old = {k: os.environ.pop(k, None) for k in STAGE_KNOBS}
+    os.environ.update(MUSC_DEBUG_STAGE_BYTES=str(stage_bytes), MUSC_DEBUG_STAGE_LINES=str(stage_lines))
+    try:
+        eng.reload_env()
+        yield
+    finally:
+        for k in STAGE_KNOBS:
+            os.environ.pop(k, None)
+            if old[k] is not None:
+                os.environ[k] = old[k]
+        eng.reload_env()
+
+
+def test_staged_host_path_in_many_pieces(eng, segments):
+    """A stage of 256 bytes and windows of 7 lines: the 1 695 lines reach the host in hundreds of pieces.  The fixture's
+    own lines are under 100 bytes, so two reads (2 and 64 tuples) get a 300-byte tail here: their lines are larger than
+    the stage and go one to a piece, through a staging buffer that grows for them."""
+    reads, targets, rests, hits, tails = segments
+    tails = list(tails)
+    for r in (2, 4):
+        tails[r] = b"%d\t" % (r + 1) + b"n" * 300
+    load(eng, reads, targets, rests, tails)
+    exp = oracle_text(reads, targets, rests, hits, tails)
+    lines = exp.splitlines(True)
+    assert len(lines) == 1695 and max(len(ln) for ln in lines) > 256 > min(len(ln) for ln in lines)
+    nl, nb = eng.results_order(np.array(hits, dtype=np.uint32))
+    assert (nl, nb) == (len(lines), len(exp))
+    with staged(eng, 256, 7):
+        assert eng.results_text() == exp
+        for l0, cnt in ((0, 1), (3, 11), (nl - 1, 1)):
+            assert eng.results_text(l0, cnt) == b"".join(lines[l0:l0 + cnt]), l0
+    assert eng.results_text() == exp  # the knobs unset: the defaults are back
+
+
+def test_device_destinations_at_every_alignment(eng, segments):
+    import torch
+    reads, targets, rests, hits, tails = segments
+    load(eng, reads, targets, rests, tails)
+    exp = oracle_text(reads, targets, rests, hits, tails)
+    nl, _ = eng.results_order(np.array(hits, dtype=np.uint32))
+    nb = ctypes.c_uint64()
+    for a in range(4):
+        for l0, cnt in ((0, nl), (3, 11), (nl - 1, 1)):
+            want = eng.results_text(l0, cnt)  # (compared with the oracle's bytes by test_text_in_chunks)
+            assert want in exp and len(want) > 0
+            d = torch.full((len(want) + 16,), 0xEE, dtype=torch.uint8, device="cuda")
+            rc = eng._lib.musc_results_text(eng._h, l0, cnt, d.data_ptr() + 4 + a, len(want), 1, ctypes.byref(nb))
+            assert rc == 0, eng._lib.musc_last_error(eng._h)
+            torch.cuda.synchronize()
+            h = d.cpu().numpy().tobytes()
+            assert nb.value == len(want) and h[4 + a:4 + a + len(want)] == want, (a, l0)
+            assert set(h[:4 + a]) == {0xEE} and set(h[4 + a + len(want):]) == {0xEE}, (a, l0)
+
+
+def test_text_refusals(eng, segments):
+    """Capacity one byte short: code 2, nothing written, *nbytes = 0.  dst = NULL: the size of the range."""
+    reads, targets, rests, hits, tails = segments
+    load(eng, reads, targets, rests, tails)
+    exp = oracle_text(reads, targets, rests, hits, tails)
+    eng.results_order(np.array(hits, dtype=np.uint32))
+    nb = ctypes.c_uint64(77)
+    buf = np.full(len(exp) + 8, 0xEE, dtype=np.uint8)
+    rc = eng._lib.musc_results_text(eng._h, 0, 1 << 62, buf.ctypes.data, len(exp) - 1, 0, ctypes.byref(nb))
+    assert rc == 2 and b"capacity" in eng._lib.musc_last_error(eng._h) and nb.value == 0
+    assert set(buf.tolist()) == {0xEE}
+    nb.value = 77
+    rc = eng._lib.musc_results_text(eng._h, 0, 1 << 62, None, 0, 0, ctypes.byref(nb))
+    assert rc == 0 and nb.value == len(exp)
+    assert set(buf.tolist()) == {0xEE}
+    rc = eng._lib.musc_results_text(eng._h, 0, 1 << 62, buf.ctypes.data, len(exp), 0, ctypes.byref(nb))
+    assert rc == 0 and nb.value == len(exp) and buf[:nb.value].tobytes() == exp
 
 
 def test_offsets_beyond_four_gib(eng):

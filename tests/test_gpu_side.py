@@ -22,7 +22,7 @@ from oracle import muscato_oracle as orc
 
 from cases import make_case, rand_seq
 from test_cli import expected_genestats, expected_readstats
-from test_gpu_results import load, oracle_text, plain_case, rests_of
+from test_gpu_results import load, oracle_text, plain_case, rests_of, staged
 
 pytestmark = pytest.mark.gpu
 
@@ -235,6 +235,28 @@ def mixed():
 def test_ranges(eng, mixed):
     R, targets, rests, hits = mixed
     check(eng, R, targets, rests, hits, steps=(1, 7, 64))
+
+
+@pytest.mark.parametrize("stage_bytes,stage_lines", [(256, 7), (1, 1)])
+def test_staged_host_path_in_many_pieces(eng, mixed, stage_bytes, stage_lines):
+    """A stage of 256 bytes with windows of 7 records, and a stage of one byte with windows of one (every piece is then
+    one record, each larger than the stage): the three texts, whole and in three ranges, through the host path."""
+    R, targets, rests, hits = mixed
+    exp = dict(zip(TEXTS, expected(R, targets, rests, hits)))
+    load(eng, [r for r, _, _ in R], targets, rests, tails_of(R))
+    eng.results_order(np.array(hits, dtype=np.uint32))
+    got = eng.side_prepare()
+    with staged(eng, stage_bytes, stage_lines):
+        for which in TEXTS:
+            assert text_fn(eng, which)() == exp[which], which
+            per = 4 if which == "nonmatch" else 1
+            lines = exp[which].splitlines(True)
+            n = got[which][0]
+            assert n == len(lines) // per > 3
+            for r0, cnt in ((0, 1), (3, 11), (n - 1, 1)):
+                assert text_fn(eng, which)(r0, cnt) == b"".join(lines[per * r0:per * (r0 + cnt)]), (which, r0)
+    for which in TEXTS:
+        assert text_fn(eng, which)() == exp[which], which  # the knobs unset
 
 
 def test_device_destinations_at_every_alignment(eng, mixed):
