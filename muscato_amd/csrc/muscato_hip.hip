@@ -36,6 +36,8 @@
 
 #include "../../include/muscato_hip.h"
 
+#include "index_plan.hpp"
+
 #include "kernels_common.hpp"
 #include "kernels_index.hpp"
 #include "kernels_screen.hpp"
@@ -72,6 +74,25 @@ struct DevBuf {
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
+  }
+};
+
+// A table of the index: grown to what a build asks for and never shrunk (hipMalloc / hipFree of tens of GiB take
+// seconds), at exact sizes (DevBuf's growth by half is wrong for a 64 GiB table)
+struct DevTable {
+  void* p = nullptr;
+  uint64_t bytes = 0;
+  hipError_t grow(uint64_t n) {
+    if (p && bytes >= n) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc(&p, n);
+    if (e == hipSuccess) bytes = n; else p = nullptr;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
   }
 };
 
@@ -193,30 +214,27 @@ static uint64_t stream_plan_batch(const StreamPlan& sp, uint64_t r0) {
 
 // The MUSC_* environment knobs (tests, A/B runs, experiments), read ONCE per context at musc_init -- a pass
 // never calls getenv -- and again only on musc_reload_env (tests that flip a knob on a live context).
-struct EnvKnobs {
-  enum { IDX_AUTO = 0, IDX_CLASSIC, IDX_LINES, IDX_CLASSIC64 };
-  int index = IDX_AUTO;       // MUSC_INDEX = classic | lines | classic64: the two-kernel path (on that bucket layout)
+// (MUSC_INDEX, MUSC_DEBUG_INDEX_BITS, MUSC_DEBUG_CTX_DIRECT and MUSC_DEBUG_INDEX_BUDGET_MB are musc_index::Knobs: what the
+// index decisions of index_plan.hpp read)
+struct EnvKnobs : musc_index::Knobs {
   bool match_dma = false;     // MUSC_MATCH = dma: k_match_g (kernels_match_dma.hpp) where it is built for the run, k_match_t elsewhere
   bool screen_wg = false;     // MUSC_SCREEN = wg: k_screen on line buckets instead of k_screen_t
   int context = 0;            // MUSC_CONTEXT = narrow (1) | wide (2)
   bool no_x_context = false;  // MUSC_NO_X_CONTEXT
   bool force_wide = false;    // MUSC_DEBUG_FORCE_WIDE
-  int index_bits = 0;         // MUSC_DEBUG_INDEX_BITS (0: not set)
-  bool ctx_direct = false;    // MUSC_DEBUG_CTX_DIRECT: a direct context table whatever the database size (tests)
   int debug_grid = 0;         // MUSC_DEBUG_GRID (0: not set)
   bool debug_sync = false;    // MUSC_DEBUG_SYNC
   int graph = -1;             // MUSC_GRAPH: -1 not set, else its value
   bool pipeline = false;      // MUSC_PIPELINE > 0
   bool no_spec = false;       // MUSC_NO_SPEC: never pick a geometry-specialised kernel instance
   long batch_reads = 0;       // MUSC_BATCH_READS (0: not set)
-  long index_budget_mb = 0;   // MUSC_DEBUG_INDEX_BUDGET_MB: caps the memory the index fit checks and the partition planner see (tests)
   uint64_t stage_bytes = 64ull << 20;  // MUSC_DEBUG_STAGE_BYTES: device staging of a text call for a host destination (tests)
   uint64_t stage_lines = 1ull << 20;   // MUSC_DEBUG_STAGE_LINES: record offsets such a call fetches to the host at a time (tests)
   void read() {
     *this = EnvKnobs();
     auto is = [](const char* v, const char* w) { return v && !strcmp(v, w); };
     const char* e = getenv("MUSC_INDEX");
-    index = is(e, "classic") ? IDX_CLASSIC : is(e, "lines") ? IDX_LINES : is(e, "classic64") ? IDX_CLASSIC64 : IDX_AUTO;
+    index = is(e, "classic") ? musc_index::IDX_CLASSIC : is(e, "lines") ? musc_index::IDX_LINES : is(e, "classic64") ? musc_index::IDX_CLASSIC64 : musc_index::IDX_AUTO;
     e = getenv("MUSC_MATCH");
     match_dma = is(e, "dma");
     screen_wg = is(getenv("MUSC_SCREEN"), "wg");
@@ -275,7 +293,7 @@ struct musc_ctx {
   // the packed database stays resident, each range's index is built in turn and the tuples are merged on the device
   uint64_t part_bases = 0;           // musc_db_set_partition_bases: most bases per partition, 0 = automatic
   std::vector<uint32_t> part_first;  // the plan of the last pass: partition p = targets [part_first[p], part_first[p + 1])
-  int part_kind = 0;                 // several partitions: the index kind all of them build (PK_*), settled on the largest
+  musc_index::Kind part_kind = musc_index::K_CLASSIC64;  // several partitions: the index kind all of them build, settled on the largest
   uint64_t part_size = 0;            // bases of the largest partition: the size-dependent choices are made on it
   uint32_t cur_part = 0;             // the partition ensure_index builds
   // (the buffers of the merge below live for one partitioned pass: match_partitioned releases them)
@@ -285,26 +303,15 @@ struct musc_ctx {
   DevBuf<uint32_t> pflags, pflags_tmp;  // one segment's survivor flags and their scan
   DevBuf<uint32_t> block_acc;        // the exact MaxMatches block counters summed over the partitions
 
-  // index
-  int idx_ww = 0, idx_bits = 0, idx_direct = 0;
-  uint32_t idx_g0 = 0, idx_g1 = 0;  // the targets the resident index covers (the whole database or one partition)
+  // index (muscato_index.hpp)
+  musc_index::Resident idx;  // the index in hand: kind, width, table shape and the targets it covers; ww == 0: none
   int wide = 0;  // database >= 2^32 bases: 40-bit positions, gene numbers < 2^24
-  Bucket* idx_T = nullptr;  // 2^idx_bits buckets: 64-byte Bucket, or (idx_lines) 128-byte LineBucket
-  uint4* idx_E = nullptr;   // overflow entries
-  bool idx_lines = false;   // the table holds line buckets (kernels_index.hpp)
+  // only one kind is resident at a time: the window-start index (2^bits + 1 Bucket or LineBucket, uint4 overflow
+  // entries) or context buckets (CtxBucket, CtxEntry / CtxEntryW: kernels_match.hpp)
+  DevTable idx_T, idx_E, ctx_T, ctx_E;
   unsigned scrt_resident = 0;  // k_screen_t: waves resident at once (queried once per record stride)
   int scrt_rw = 0;
-  uint64_t idx_T_bytes = 0, idx_E_cap = 0;  // allocated table bytes / entries (kept across rebuilds:
-                                            // hipMalloc / hipFree of tens of GiB take seconds)
-  uint64_t idx_n = 0;       // indexed window starts
-  uint64_t idx_novf = 0;
-  // index kind 1: context buckets (kernels_match.hpp); only one kind is resident at a time
-  int idx_kind = 0;         // of the index idx_ww describes: 0 = Bucket table, 1 = CtxBucket table
-  int idx_wide = 0;         // idx_kind 1: the buckets are CtxBucketW (200 bases of context, two inline entries)
-  int idx_CL = 0;           // context buckets: bases of left context (the largest window start)
-  CtxBucket* ctx_T = nullptr;
-  CtxEntry* ctx_E = nullptr;
-  uint64_t ctx_T_cap = 0, ctx_E_cap = 0;
+  uint64_t idx_novf = 0;    // overflow entries of the index in hand
   PathParams* d_pp = nullptr;   // k_screen / k_confirm / k_hot_probes: the run's parameters
   PathParams h_pp;              // what d_pp holds
   bool h_pp_valid = false;
@@ -532,21 +539,7 @@ int scan_u64(musc_ctx* c, const uint64_t* in, uint64_t* out, uint64_t n, uint64_
   return 0;
 }
 
-void free_index(musc_ctx* c) {
-  // (the allocations stay for the next build; musc_destroy releases them)
-  c->idx_ww = 0;
-  c->idx_n = 0;
-  c->data_epoch++;
-}
-
-// release the context-bucket tables (the classic index is being built, or the database changes)
-void drop_ctx_index(musc_ctx* c) {
-  if (c->ctx_T) (void)hipFree(c->ctx_T);
-  if (c->ctx_E) (void)hipFree(c->ctx_E);
-  c->ctx_T = nullptr;
-  c->ctx_E = nullptr;
-  c->ctx_T_cap = c->ctx_E_cap = 0;
-}
+void free_index(musc_ctx* c);  // muscato_index.hpp
 
 // the gene text of the results stage belongs to a database, the read text to a read set
 void drop_gene_text(musc_ctx* c) {
@@ -744,10 +737,7 @@ void musc_destroy(musc_ctx* c) {
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
   free_db(c);
   free_reads(c);
-  if (c->idx_T) (void)hipFree(c->idx_T);
-  if (c->idx_E) (void)hipFree(c->idx_E);
-  if (c->ctx_T) (void)hipFree(c->ctx_T);
-  if (c->ctx_E) (void)hipFree(c->ctx_E);
+  for (DevTable* t : {&c->idx_T, &c->idx_E, &c->ctx_T, &c->ctx_E}) t->release();
   if (c->d_mp) (void)hipFree(c->d_mp);
   if (c->d_pp) (void)hipFree(c->d_pp);
   c->spill.release();
@@ -915,593 +905,12 @@ int musc_db_load_packed(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nm
   return db_finish(c);
 }
 
-extern "C++" {
-// The targets (and their bases) an index build covers, and the base count its size-dependent choices are made on:
-// the whole database, or one partition of a pass (then `size` is the largest partition's, so that every partition
-// builds the same kind and size of table)
-struct IdxRange {
-  uint32_t g0, g1;
-  uint64_t b0, b1, size;
-};
-static IdxRange whole_db(const musc_ctx* c) { return IdxRange{0, c->nseq, 0, c->nbases, c->nbases}; }
+}  // extern "C"
 
-// Device memory an index may take: what is free plus what the resident tables hold, less `reserve` (the pass's
-// buffers).  MUSC_DEBUG_INDEX_BUDGET_MB caps it (tests of the partition planner on small databases).
-static uint64_t index_room(musc_ctx* c, uint64_t reserve) {
-  size_t mfree = 0, mtotal = 0;
-  if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  const uint64_t have = (uint64_t)mfree + c->idx_T_bytes + c->idx_E_cap * sizeof(uint4) +
-                        (c->ctx_T ? c->ctx_T_cap * sizeof(CtxBucket) : 0) + (c->ctx_E ? c->ctx_E_cap * sizeof(CtxEntry) : 0);
-  uint64_t room = have > reserve ? have - reserve : 0;
-  if (c->env.index_budget_mb > 0) room = std::min<uint64_t>(room, (uint64_t)c->env.index_budget_mb << 20);
-  return room;
-}
+// the index layer: the build driver, eligibility, the partition planner, ensure_index, musc_db_build_index*
+#include "muscato_index.hpp"
 
-// What each bucket layout takes for a table of nb buckets over `bases` bases (the fit checks and the planner):
-// line buckets -- the table, the entries beyond the seventh in runs of eight (assume every bucket wastes half a run),
-// 8 B per bucket of build temporaries -- with 12 GiB for the pass's buffers; 64-byte buckets -- the table, its build
-// temporaries and at most one overflow entry per base -- with 4 GiB
-static uint64_t lines_need(uint64_t nb, uint64_t bases) {
-  return (nb + 1) * (sizeof(LineBucket) + 8) + (bases > 7 * nb ? (bases - 7 * nb) * 16 : 0) + nb * 64;
-}
-static uint64_t classic64_need(uint64_t nb, uint64_t bases) { return (nb + 1) * (sizeof(Bucket) + 16) + bases * sizeof(uint4); }
-static const uint64_t LINES_RESERVE = 12ull << 30, CLASSIC_RESERVE = 4ull << 30, CTX_RESERVE = 4ull << 30;
-
-// Which bucket layout the two-kernel index uses for this database and window width: line buckets
-// (LineBucket: a 128-byte line of seven entries + aligned overflow runs) when the direct table has
-// four or more window starts per key on average and the table fits, 64-byte buckets otherwise.
-// MUSC_INDEX=lines / classic64 force one or the other.
-static bool want_line_buckets(musc_ctx* c, int32_t ww, int bits, int direct, uint64_t bases) {
-  if (c->env.index == EnvKnobs::IDX_LINES) return true;
-  if (c->env.index == EnvKnobs::IDX_CLASSIC64) return false;
-  if (!direct) return false;
-  (void)ww;
-  const uint64_t nb = 1ull << bits;
-  if (bases < 4 * nb) return false;
-  return lines_need(nb, bases) <= index_room(c, LINES_RESERVE);
-}
-
-// The window-start table for width ww over `bases` bases: direct addressing (bucket = the 2*ww-bit key itself: exact,
-// and bytewise-sorted reads walk the table front to back) when that table is at most 32x the database and at most
-// 2^30 buckets (64 GiB; line buckets: 128 GiB); otherwise a hashed table with about one bucket per base, at most 2^31
-// buckets (128 GiB; longer lists go to the overflow array).
-static void classic_table(const musc_ctx* c, int32_t ww, uint64_t bases, int* bits, int* direct) {
-  *direct = 0;
-  const uint64_t floor_bases = std::max<uint64_t>(bases, 1ull << 19);
-  if (2 * ww <= 30 && (1ull << (2 * ww)) <= 32 * floor_bases) {
-    *bits = 2 * ww;
-    *direct = 1;
-  } else {
-    *bits = 10;
-    while (*bits < 31 && (1ull << *bits) < bases) (*bits)++;
-  }
-  if (c->env.index_bits >= 8 && c->env.index_bits <= 31) { *bits = c->env.index_bits; *direct = 0; }  // experiments only: force a hashed table size
-}
-
-// The context-bucket table for width ww over `bases` bases: 4^ww buckets with the key as the bucket (exact) when that
-// is at most twice the database's window count; else about one bucket per base under a 64-bit mix (a colliding key
-// fails the window comparison in k_match: the context includes the window bases)
-static void ctx_table(const musc_ctx* c, int32_t ww, uint64_t bases, int* bits, int* direct) {
-  *direct = 0;
-  const uint64_t floor_bases = std::max<uint64_t>(bases, 1ull << 9);
-  if (2 * ww <= 30 && ((1ull << (2 * ww)) <= 2 * floor_bases || c->env.ctx_direct)) {  // tests: MUSC_DEBUG_CTX_DIRECT
-    *bits = 2 * ww;
-    *direct = 1;
-  } else {
-    *bits = 10;
-    while (*bits < 30 && (1ull << *bits) < bases) (*bits)++;
-  }
-  if (c->env.index_bits >= 8 && c->env.index_bits <= 30) { *bits = c->env.index_bits; *direct = 0; }  // experiments only: force a hashed table size
-}
-// memory: the table, 8 B + 4 B per bucket of build temporaries, and the overflow entries (their number is known only
-// after the counting pass: assume a third of the windows for the estimate)
-static uint64_t ctx_need(int bits, int wide, uint64_t bases) {
-  const uint64_t esz = wide ? sizeof(CtxEntryW) : sizeof(CtxEntry);
-  return ((1ull << bits) + 1) * (sizeof(CtxBucket) + 12) + bases / (wide ? 2 : 3) * esz;
-}
-
-template <class BT>
-static int build_index_buckets(musc_ctx* c, int32_t ww, int bits, int direct, const IdxRange& R) {
-  const uint64_t nb = 1ull << bits;
-  c->ev_used = 0;
-  hipEvent_t e0 = pool_event(c), e1 = pool_event(c), e2 = pool_event(c), e3 = pool_event(c);
-  if (!e0 || !e1 || !e2 || !e3) return fail(c, 10, "hipEventCreate failed");
-  if (c->idx_T_bytes < (nb + 1) * sizeof(BT)) {
-    if (c->idx_T) (void)hipFree(c->idx_T);
-    c->idx_T = nullptr;
-    c->idx_T_bytes = 0;
-    HIPCHK(c, hipMalloc((void**)&c->idx_T, (nb + 1) * sizeof(BT)));
-    c->idx_T_bytes = (nb + 1) * sizeof(BT);
-  }
-  BT* const T = reinterpret_cast<BT*>(c->idx_T);
-  TmpBufs B;
-  uint64_t *tmp = nullptr, *stmp = nullptr;
-  HIPCHK(c, B.alloc(&tmp, (nb + 1 + 16) * 8));
-  HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(nb + 1) * 8));
-  // timed: the device work (allocation above and below is host time, seconds for a 64 GiB table
-  // the first time, and not repeated)
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  HIPCHK(c, hipMemsetAsync(T, 0, (nb + 1) * sizeof(BT), c->stream));
-  const unsigned blocks = (unsigned)std::min<uint64_t>((R.b1 - R.b0 + 255) / 256, 1u << 22);
-  if (R.b1 > R.b0) {
-    hipLaunchKernelGGL((k_index<false, BT>), dim3(blocks), dim3(256), 0, c->stream, c->db2, c->dbm2, c->seq_off, c->nseq,
-                       R.b0, R.b1, ww, bits, direct, c->wide, T, (uint4*)nullptr);
-    HIPCHK(c, hipGetLastError());
-  }
-  // overflow lists: sizes -> offsets (u64: a 10 Gbp database has billions of overflow entries)
-  hipLaunchKernelGGL((k_index_ovf_count<BT>), dim3(nblk(nb + 1, 256)), dim3(256), 0, c->stream, T, nb, tmp);
-  HIPCHK(c, hipGetLastError());
-  int rc = scan_u64(c, tmp, tmp, nb + 1, stmp);
-  if (rc) return rc;
-  uint64_t novf = 0;  // entries (64-byte buckets) or lines of eight entries (line buckets)
-  HIPCHK(c, hipMemcpyAsync(&novf, tmp + nb, 8, hipMemcpyDeviceToHost, c->stream));
-  hipLaunchKernelGGL((k_index_ovf_set<BT>), dim3(nblk(nb, 256)), dim3(256), 0, c->stream, T, nb, tmp);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(e2, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  B.release();  // 8 bytes per bucket: returned before the overflow array is allocated
-  if (std::is_same<BT, LineBucket>::value) {
-    if (novf >= 0xFFFFFFF0ull) return fail(c, 5, "internal: %llu overflow lines do not fit 32-bit numbers", (unsigned long long)novf);
-    novf *= 8;
-  }
-  c->idx_novf = novf;
-  if (c->idx_E_cap < novf + 16) {
-    if (c->idx_E) (void)hipFree(c->idx_E);
-    c->idx_E = nullptr;
-    c->idx_E_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->idx_E, ((uint64_t)novf + 16) * sizeof(uint4)));
-    c->idx_E_cap = novf + 16;
-  }
-  HIPCHK(c, hipEventRecord(e3, c->stream));
-  if (R.b1 > R.b0) {
-    hipLaunchKernelGGL((k_index<true, BT>), dim3(blocks), dim3(256), 0, c->stream, c->db2, c->dbm2, c->seq_off, c->nseq,
-                       R.b0, R.b1, ww, bits, direct, c->wide, T, c->idx_E);
-    HIPCHK(c, hipGetLastError());
-  }
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0, ms2 = 0;
-  (void)hipEventElapsedTime(&ms, e0, e2);
-  (void)hipEventElapsedTime(&ms2, e3, e1);
-  c->stats.ms_index_build = ms + ms2;
-  return 0;
-}
-}  // extern "C++"
-
-// The window-start index over the targets of R.  lines: 1 / 0 = line / 64-byte buckets (a partitioned pass settles it
-// once), -1 = the usual choice (want_line_buckets).
-static int build_index_classic(musc_ctx* c, int32_t ww, const IdxRange& R, int lines_kind) {
-  c->wide = c->nbases >= 0xFFFFFFF0ull || c->env.force_wide;
-  if (c->wide && c->nseq >= (1u << 24))
-    return fail(c, 5, "a database of 2^32 bases or more may hold at most 2^24 targets (has %u)", c->nseq);
-  int bits, direct;
-  classic_table(c, ww, R.size, &bits, &direct);
-  // A resident window-start index for this width keeps its layout: the automatic choice looks at the free memory
-  // of the moment (want_line_buckets), which moves as the pass buffers grow, and a flip would mean dropping the
-  // sized state and rebuilding tens of gigabytes in the middle of a run.  Only an explicit MUSC_INDEX = lines |
-  // classic64 that contradicts the resident layout rebuilds.  (The targets covered are part of the key: a
-  // partition never reuses another one's table.)
-  if (c->idx_ww == ww && c->idx_kind == 0 && c->idx_T && c->idx_bits == bits && c->idx_direct == direct &&
-      c->idx_g0 == R.g0 && c->idx_g1 == R.g1 && (lines_kind < 0 || c->idx_lines == (lines_kind == 1)) &&
-      !(c->env.index == EnvKnobs::IDX_LINES && !c->idx_lines) && !(c->env.index == EnvKnobs::IDX_CLASSIC64 && c->idx_lines))
-    return 0;
-  const bool lines = lines_kind >= 0 ? lines_kind == 1 : want_line_buckets(c, ww, bits, direct, R.size) && bits <= 30;
-  free_index(c);
-  drop_ctx_index(c);  // one index kind is resident at a time
-  c->idx_kind = 0;
-  c->idx_lines = lines;
-  const int rc = lines ? build_index_buckets<LineBucket>(c, ww, bits, direct, R) : build_index_buckets<Bucket>(c, ww, bits, direct, R);
-  if (rc) return rc;
-  c->idx_ww = ww;
-  c->idx_bits = bits;
-  c->idx_direct = direct;
-  c->idx_g0 = R.g0;
-  c->idx_g1 = R.g1;
-  return 0;
-}
-
-int musc_db_build_index(musc_ctx* c, int32_t ww) {
-  if (!c) return 1;
-  if (!c->db2) return fail(c, 4, "no database loaded");
-  if (ww < 1 || ww > 4096) return fail(c, 2, "bad window width %d", ww);
-  HIPCHK(c, hipSetDevice(c->device));
-  return build_index_classic(c, ww, whole_db(c), -1);
-}
-
-// Context buckets for window width ww and CL bases of left context (kernels_match.hpp).
-// Returns 0 and leaves idx_kind == 1 on success; 100 when the table does not fit the device's
-// free memory (the caller then builds the classic index); anything else is an error.
-static int build_index_ctx(musc_ctx* c, int32_t ww, int32_t CL, int wide, const IdxRange& R) {
-  int bits, direct;
-  ctx_table(c, ww, R.size, &bits, &direct);
-  // (the table kind is part of the comparison: a musc_reload_env that flips MUSC_DEBUG_CTX_DIRECT or
-  // MUSC_DEBUG_INDEX_BITS rebuilds the resident table on the next pass; so are the targets covered: a partition
-  // never reuses another one's table)
-  if (c->idx_kind == 1 && c->idx_ww == ww && c->idx_CL == CL && c->idx_wide == wide && c->idx_bits == bits &&
-      c->idx_direct == direct && c->idx_g0 == R.g0 && c->idx_g1 == R.g1 && c->ctx_T)
-    return 0;
-  free_index(c);
-  c->wide = 0;
-  const uint64_t nb = 1ull << bits;
-  if (ctx_need(bits, wide, R.size) > index_room(c, CTX_RESERVE)) return 100;
-  // the classic tables go first (one index kind is resident at a time)
-  if (c->idx_T) (void)hipFree(c->idx_T);
-  if (c->idx_E) (void)hipFree(c->idx_E);
-  c->idx_T = nullptr;
-  c->idx_E = nullptr;
-  c->idx_T_bytes = c->idx_E_cap = 0;
-  c->ev_used = 0;
-  hipEvent_t e0 = pool_event(c), e1 = pool_event(c), e2 = pool_event(c), e3 = pool_event(c);
-  if (!e0 || !e1 || !e2 || !e3) return fail(c, 10, "hipEventCreate failed");
-  if (c->ctx_T_cap < nb + 1) {
-    if (c->ctx_T) (void)hipFree(c->ctx_T);
-    c->ctx_T = nullptr;
-    c->ctx_T_cap = 0;
-    if (hipMalloc((void**)&c->ctx_T, (nb + 1) * sizeof(CtxBucket)) != hipSuccess) {
-      (void)hipGetLastError();
-      c->ctx_T = nullptr;
-      return 100;
-    }
-    c->ctx_T_cap = nb + 1;
-  }
-  TmpBufs B;
-  uint64_t *tmp = nullptr, *stmp = nullptr;
-  uint32_t* cursor = nullptr;
-  if (B.alloc(&tmp, (nb + 1 + 16) * 8) != hipSuccess || B.alloc(&stmp, scan_tmp_elems(nb + 1) * 8) != hipSuccess ||
-      B.alloc(&cursor, (nb + 1) * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    return 100;
-  }
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->ctx_T, 0, (nb + 1) * sizeof(CtxBucket), c->stream));
-  HIPCHK(c, hipMemsetAsync(cursor, 0, (nb + 1) * 4, c->stream));
-  const unsigned blocks = (unsigned)std::min<uint64_t>((R.b1 - R.b0 + 255) / 256, 1u << 22);
-  // a database with X: its windows with an X stay out, entries whose context touches one are flagged
-  const uint32_t* const xm2 = c->db_has_x ? c->dbm2 : nullptr;
-  const uint32_t* const xbl = c->db_has_x ? c->dbx : nullptr;
-  if (R.b1 > R.b0) {
-    // (the counting pass does not look at the entries: one instance serves both layouts)
-    hipLaunchKernelGGL((k_index_ctx<false, false>), dim3(blocks), dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases,
-                       R.b0, R.b1, ww, bits, direct, CL, c->ctx_T, (void*)nullptr, cursor);
-    HIPCHK(c, hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_ctx_ovf_count, dim3(nblk(nb + 1, 256)), dim3(256), 0, c->stream, c->ctx_T, nb,
-                     (uint32_t)(wide ? CTXW_INLINE : CTX_INLINE), tmp);
-  HIPCHK(c, hipGetLastError());
-  int rc = scan_u64(c, tmp, tmp, nb + 1, stmp);
-  if (rc) return rc;
-  uint64_t novf = 0;
-  HIPCHK(c, hipMemcpyAsync(&novf, tmp + nb, 8, hipMemcpyDeviceToHost, c->stream));
-  hipLaunchKernelGGL(k_ctx_ovf_set, dim3(nblk(nb, 256)), dim3(256), 0, c->stream, c->ctx_T, nb, tmp);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(e2, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (novf >= 0xFFFFFFF0ull) return fail(c, 5, "internal: %llu overflow entries do not fit 32-bit offsets", (unsigned long long)novf);
-  c->idx_novf = novf;
-  const uint64_t ecap = (ctx_entries_bytes(novf + 16, wide) + sizeof(CtxEntry) - 1) / sizeof(CtxEntry);  // (entries sit line-aligned: ctx_entry_word)
-  if (c->ctx_E_cap < ecap) {
-    if (c->ctx_E) (void)hipFree(c->ctx_E);
-    c->ctx_E = nullptr;
-    c->ctx_E_cap = 0;
-    if (hipMalloc((void**)&c->ctx_E, ecap * sizeof(CtxEntry)) != hipSuccess) {
-      (void)hipGetLastError();
-      c->ctx_E = nullptr;
-      return 100;
-    }
-    c->ctx_E_cap = ecap;
-  }
-  HIPCHK(c, hipEventRecord(e3, c->stream));
-  if (R.b1 > R.b0) {
-    if (wide)
-      hipLaunchKernelGGL((k_index_ctx<true, true>), dim3(blocks), dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases,
-                         R.b0, R.b1, ww, bits, direct, CL, c->ctx_T, (void*)c->ctx_E, cursor);
-    else
-      hipLaunchKernelGGL((k_index_ctx<true, false>), dim3(blocks), dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases,
-                         R.b0, R.b1, ww, bits, direct, CL, c->ctx_T, (void*)c->ctx_E, cursor);
-    HIPCHK(c, hipGetLastError());
-  }
-  HIPCHK(c, hipEventRecord(e1, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  float ms = 0, ms2 = 0;
-  (void)hipEventElapsedTime(&ms, e0, e2);
-  (void)hipEventElapsedTime(&ms2, e3, e1);
-  c->stats.ms_index_build = ms + ms2;
-  c->idx_kind = 1;
-  c->idx_wide = wide;
-  c->idx_ww = ww;
-  c->idx_CL = CL;
-  c->idx_bits = bits;
-  c->idx_direct = direct;
-  c->idx_g0 = R.g0;
-  c->idx_g1 = R.g1;
-  return 0;
-}
-
-// Which of the two fused kernels on context buckets runs
-enum MatchKind { MK_LANE = 2, MK_DMA = 3 };
-// MK_LANE = k_match_t (kernels_match_lane.hpp): every run on context buckets.  MK_DMA = k_match_g
-// (kernels_match_dma.hpp): the same comparisons at three to four waves per SIMD, everything from memory by LDS-DMA --
-// built for two windows on 120-base buckets, records of 8 words, no X on either side (BASELINE configs 2-4).  It is
-// the second implementation (MUSC_MATCH=dma; the parity tests run both): on cfg3 its launch takes as long as
-// k_match_t's.
-static int match_kind(const musc_ctx* c, int W) {
-  if (c->env.match_dma && W == 2 && c->rw == 8 && c->idx_kind == 1 && !c->idx_wide && !c->db_has_x && !c->reads_have_x) return MK_DMA;
-  return MK_LANE;
-}
-
-// The xpos words of the reads in hand, in the format of the bucket width
-static bool reads_xpos(musc_ctx* c, int wide) {
-  if (c->rdx_epoch == c->data_epoch && c->rdx_wide == wide) return true;
-  if (ensure(c, c->rdx, c->nreads)) return false;
-  if (wide)
-    hipLaunchKernelGGL(k_read_xpos<true>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->rdx.p);
-  else
-    hipLaunchKernelGGL(k_read_xpos<false>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->rdx.p);
-  if (hipGetLastError() != hipSuccess) return false;
-  c->rdx_epoch = c->data_epoch;
-  c->rdx_wide = wide;
-  c->xok_epoch = ~0ull;
-  c->xokdb_epoch = ~0ull;
-  return true;
-}
-
-// Reads with X fit the context path if every read that holds more of them than its xpos word lists
-// (XPos<wide>: four on 120-base buckets, three on wide ones) could not match anyway (that many
-// mismatches exceed its budget int((1 - PMatch) * len)).  One small kernel and a 4-byte readback
-// per (read set, bucket width, PMatch, MaxMismatch).
-static bool reads_x_fit(musc_ctx* c, const musc_params* P, uint32_t max_len, int wide) {
-  if (!c->rdm || !c->rd || !c->nreads) return false;
-  if (c->env.no_x_context) return false;
-  if (!reads_xpos(c, wide)) return false;
-  // (the budget table covers the reads in hand whatever length the caller planned the index for)
-  max_len = std::max(max_len, c->max_len);
-  if (c->xok_epoch == c->data_epoch && c->xok_pmatch == P->pmatch && c->xok_mmp1 == P->max_mismatch_p1) return c->xok;
-  std::vector<uint16_t> tab((size_t)max_len + 2);
-  for (uint32_t L = 0; L < tab.size(); L++) {  // the budget exactly as musc_match_device builds it
-    volatile double a = 1.0 - P->pmatch;
-    volatile double b = a * (double)L;
-    long long v = (long long)b;
-    if (P->max_mismatch_p1 > 0) v = P->max_mismatch_p1 - 1;
-    if (v < 0) v = 0;
-    if (v > 0xFFFE) v = 0xFFFE;
-    tab[L] = (uint16_t)v;
-  }
-  TmpBufs B;
-  uint16_t* d_tab = nullptr;
-  uint32_t bad = 1;
-  if (B.alloc(&d_tab, tab.size() * 2) != hipSuccess) return false;
-  if (hipMemcpyAsync(d_tab, tab.data(), tab.size() * 2, hipMemcpyHostToDevice, c->stream) != hipSuccess) return false;
-  if (hipMemsetAsync(c->d_flag, 0, 4, c->stream) != hipSuccess) return false;
-  hipLaunchKernelGGL(k_xpos_check, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rd, c->rdx.p, c->nreads, c->rw, d_tab,
-                     max_len, wide ? XPos<true>::MAX : XPos<false>::MAX, c->d_flag);
-  if (hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return false;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
-  c->xok = bad == 0;
-  c->xok_epoch = c->data_epoch;
-  c->xok_pmatch = P->pmatch;
-  c->xok_mmp1 = P->max_mismatch_p1;
-  return c->xok;
-}
-
-// Reads with X against a DATABASE with X fit the context path if every read lists all its X in its
-// xpos word and none of them falls into one of the run's windows (k_xpos_check_db).
-static bool reads_x_fit_db(musc_ctx* c, const musc_params* P, int wide) {
-  if (!c->rdm || !c->rd || !c->nreads) return false;
-  if (!reads_xpos(c, wide)) return false;
-  int32_t key[CTX_MAX_W + 3] = {P->n_windows, P->window_width, wide};
-  XWins wn;
-  memset(&wn, 0, sizeof wn);
-  wn.n = P->n_windows;
-  wn.ww = P->window_width;
-  for (int k = 0; k < P->n_windows && k < CTX_MAX_W; k++) key[3 + k] = wn.q1[k] = P->windows[k];
-  if (c->xokdb_epoch == c->data_epoch && memcmp(key, c->xokdb_key, sizeof key) == 0) return c->xokdb;
-  uint32_t bad = 1;
-  if (hipMemsetAsync(c->d_flag, 0, 4, c->stream) != hipSuccess) return false;
-  if (wide) hipLaunchKernelGGL(k_xpos_check_db<true>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rdx.p, c->nreads, wn, c->d_flag);
-  else hipLaunchKernelGGL(k_xpos_check_db<false>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rdx.p, c->nreads, wn, c->d_flag);
-  if (hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return false;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
-  c->xokdb = bad == 0;
-  c->xokdb_epoch = c->data_epoch;
-  memcpy(c->xokdb_key, key, sizeof key);
-  return c->xokdb;
-}
-
-// Which index a run with these parameters and reads of at most max_len bases uses: context
-// buckets when every read fits the context around each of at most CTX_MAX_W windows -- 120 bases
-// (three entries per bucket line) or, where k_match_t runs, 200 bases (two per line: *wide = 1) --
-// the database holds no X (the context has no mask plane; reads may hold some where
-// k_match_t runs, see reads_x_fit) and positions fit 32 bits.
-static bool ctx_eligible(musc_ctx* c, const musc_params* P, uint32_t max_len, int* CL, int* wide) {
-  if (c->env.index != EnvKnobs::IDX_AUTO) return false;  // the two-kernel path
-  // (the planes themselves may exist without an X: an all-zero one is made for the side that has
-  // none when the other side does, and the database's stays for the context's lifetime)
-  // a database with X: k_match_t only (an entry whose context holds an X is flagged in bit 31 of its
-  // position, the X's place or "several: see the mask plane" in the top byte of its target number)
-  if (c->db_has_x && (c->max_tlen >= 0x80000000ull || c->nseq > (1u << 24) || c->env.no_x_context)) return false;
-  if (c->nbases >= 0xFFFFFFF0ull || c->env.force_wide) return false;
-  if (P->n_windows > CTX_MAX_W) return false;
-  int q1min = P->windows[0], q1max = P->windows[0];
-  for (int k = 1; k < P->n_windows; k++) {
-    q1min = std::min(q1min, P->windows[k]);
-    q1max = std::max(q1max, P->windows[k]);
-  }
-  const int64_t span = (int64_t)q1max - q1min + (int64_t)max_len;
-  const int wenv = c->env.context;  // experiments: "narrow" (1) keeps runs beyond 120 bases on the two-kernel path, "wide" (2) puts every run on wide buckets
-  *CL = q1max;
-  *wide = 0;
-  if (span > CTX_BASES || q1max > CTX_BASES || wenv == 2) {
-    // wide buckets: k_match_t only; records of up to 16 words hold 200-base reads and their length word
-    if (wenv == 1) return false;
-    if (span > CTXW_BASES || q1max > CTXW_BASES) return false;
-    *wide = 1;
-  }
-  // reads with X: k_match_t handles them, and only while every read either lists all its X
-  // in its xpos word or has more X than mismatches allowed (reads_x_fit, cached per reads + budget)
-  if (c->reads_have_x && !(c->db_has_x ? reads_x_fit_db(c, P, *wide) : reads_x_fit(c, P, max_len, *wide))) return false;
-  return true;
-}
-
-// ---- partitions
-enum { PK_CTX = 1, PK_LINES = 2, PK_CLASSIC64 = 3 };
-static const uint32_t MAX_PARTITIONS = 4096;
-
-// The index kind the usual cascade (context -> line -> 64-byte buckets) builds over `bases` bases if it fits the
-// device memory (less each kind's reserve for the pass, and `extra`), 0 if none does.  fit = false: the kind
-// regardless of memory.
-static int index_kind_for(musc_ctx* c, int32_t ww, bool ctx_ok, int wide, uint64_t bases, bool fit, uint64_t extra) {
-  int bits, direct;
-  if (ctx_ok) {
-    ctx_table(c, ww, bases, &bits, &direct);
-    if (ctx_need(bits, wide, bases) <= index_room(c, CTX_RESERVE + extra)) return PK_CTX;
-  }
-  classic_table(c, ww, bases, &bits, &direct);
-  const uint64_t nb = 1ull << bits;
-  const bool lines = bits <= 30 && (c->env.index == EnvKnobs::IDX_LINES ||
-                                    (c->env.index != EnvKnobs::IDX_CLASSIC64 && direct && bases >= 4 * nb &&
-                                     lines_need(nb, bases) <= index_room(c, LINES_RESERVE + extra)));
-  if (lines) return !fit || lines_need(nb, bases) <= index_room(c, LINES_RESERVE + extra) ? PK_LINES : 0;
-  return !fit || classic64_need(nb, bases) <= index_room(c, CLASSIC_RESERVE + extra) ? PK_CLASSIC64 : 0;
-}
-
-// What a partitioned pass holds beside the index and the usual pass buffers (match_partitioned; all of it released
-// when the pass ends): 20 B per read (best, survivor count / cursor, run offset), the summed block counters, and the
-// accumulated tuple lists -- 20 B per tuple (the list and one scan word), estimated from the tuple buffer of the passes
-// so far and at least one tuple per read
-static uint64_t merge_reserve(const musc_ctx* c) {
-  const uint64_t tuples = std::max<uint64_t>(c->hits.cap, c->nreads);
-  return 20 * (c->nreads + 1) + (4ull << BLOCK_TABLE_BITS) + 20 * tuples;
-}
-
-// Cut the targets into ranges of at most `limit` bases (a target longer than that is a range of its own); returns
-// false beyond MAX_PARTITIONS ranges
-static bool cut_targets(const musc_ctx* c, uint64_t limit, std::vector<uint32_t>* first, uint64_t* largest) {
-  const std::vector<uint64_t>& off = c->h_seq_off;
-  limit = std::min(limit, c->nbases);
-  first->assign(1, 0u);
-  *largest = 0;
-  uint32_t g = 0;
-  while (g < c->nseq) {
-    // the last boundary within `limit` bases of target g's start
-    uint32_t g1 = (uint32_t)(std::upper_bound(off.begin() + g + 1, off.begin() + c->nseq + 1, off[g] + limit) - off.begin()) - 1;
-    if (g1 <= g) g1 = g + 1;
-    *largest = std::max<uint64_t>(*largest, off[g1] - off[g]);
-    first->push_back(g1);
-    if (first->size() > MAX_PARTITIONS + 1) return false;
-    g = g1;
-  }
-  return true;
-}
-
-// The partition plan of a pass with these parameters: one partition (the unpartitioned path) whenever the index fits,
-// or the limit of musc_db_set_partition_bases allows; otherwise the fewest ranges of about equal bases whose index
-// fits.  Every partition then builds the same index kind and table size, settled on the largest one.
-static int plan_partitions(musc_ctx* c, const musc_params* P, uint32_t max_len) {
-  const int32_t ww = P->window_width;
-  const std::vector<uint32_t> one = {0u, c->nseq};
-  // automatic, and an index of the whole database is resident: it fits (nothing to decide, nothing to query)
-  if (!c->part_bases && c->idx_ww == ww && c->idx_g0 == 0 && c->idx_g1 == c->nseq && c->nseq) {
-    c->part_first = one;
-    return 0;
-  }
-  int CL = 0, wide = 0;
-  const bool ctx_ok = ctx_eligible(c, P, max_len, &CL, &wide);
-  std::vector<uint32_t> first;
-  uint64_t largest = 0;
-  int kind = 0;
-  if (c->part_bases) {
-    if (!cut_targets(c, c->part_bases, &first, &largest))
-      return fail(c, 5, "DbPartitionBases %llu cuts the database into more than %u partitions",
-                  (unsigned long long)c->part_bases, MAX_PARTITIONS);
-    const uint64_t extra = first.size() > 2 ? merge_reserve(c) : 0;
-    kind = index_kind_for(c, ww, ctx_ok, wide, largest, true, extra);
-    if (!kind) kind = index_kind_for(c, ww, false, wide, largest, false, 0);  // (then the build reports what failed)
-  } else if (index_kind_for(c, ww, ctx_ok, wide, c->nbases, true, 0)) {
-    first = one;
-  } else {
-    // the fewest partitions whose largest index fits: a binary search over the number of equal shares
-    uint32_t lo = 2, hi = MAX_PARTITIONS;
-    bool found = false;
-    while (lo <= hi) {
-      const uint32_t n = lo + (hi - lo) / 2;
-      std::vector<uint32_t> f;
-      uint64_t lg = 0;
-      const bool ok = cut_targets(c, (c->nbases + n - 1) / n, &f, &lg);
-      const int k = ok ? index_kind_for(c, ww, ctx_ok, wide, lg, true, merge_reserve(c)) : 0;
-      if (k) {
-        first.swap(f);
-        largest = lg;
-        kind = k;
-        found = true;
-        hi = n - 1;
-      } else {
-        lo = n + 1;
-      }
-    }
-    if (!found)
-      return fail(c, 5, "the index of this database does not fit the device even in %u partitions", MAX_PARTITIONS);
-  }
-  c->part_first = first;
-  c->part_kind = first.size() > 2 ? kind : 0;
-  c->part_size = first.size() > 2 ? largest : c->nbases;
-  return 0;
-}
-
-static int ensure_index(musc_ctx* c, const musc_params* P, uint32_t max_len) {
-  int CL = 0, wide = 0;
-  if (c->part_first.size() > 2) {  // one partition of a partitioned pass: the kind settled by plan_partitions
-    const uint32_t p = c->cur_part;
-    const uint32_t g0 = c->part_first[p], g1 = c->part_first[p + 1];
-    const IdxRange R{g0, g1, c->h_seq_off[g0], c->h_seq_off[g1], c->part_size};
-    if (c->part_kind == PK_CTX) {
-      if (!ctx_eligible(c, P, max_len, &CL, &wide)) return fail(c, 12, "internal: a partition lost context-bucket eligibility");
-      const int rc = build_index_ctx(c, P->window_width, CL, wide, R);
-      if (rc == 100)
-        return fail(c, 5, "the context index of partition %u (%llu bases) does not fit the device", p,
-                    (unsigned long long)(R.b1 - R.b0));
-      return rc;
-    }
-    return build_index_classic(c, P->window_width, R, c->part_kind == PK_LINES ? 1 : 0);
-  }
-  if (ctx_eligible(c, P, max_len, &CL, &wide)) {
-    const int rc = build_index_ctx(c, P->window_width, CL, wide, whole_db(c));
-    if (rc != 100) return rc;
-    // (does not fit the free memory: the classic index is a quarter of the size)
-  }
-  return musc_db_build_index(c, P->window_width);
-}
-
-int musc_db_build_index_for(musc_ctx* c, const musc_params* P, int32_t max_read_len) {
-  if (!c) return 1;
-  int rc = check_params(c, P);
-  if (rc) return rc;
-  if (!c->db2) return fail(c, 4, "no database loaded");
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t ml = max_read_len > 0 ? (uint32_t)max_read_len
-                                       : (P->max_read_length > 0 ? (uint32_t)P->max_read_length : c->max_len);
-  if ((rc = plan_partitions(c, P, ml))) return rc;
-  c->cur_part = 0;  // (several partitions: the first one's index)
-  return ensure_index(c, P, ml);
-}
-
-int musc_db_set_partition_bases(musc_ctx* c, uint64_t max_bases) {
-  if (!c) return 1;
-  c->part_bases = max_bases;
-  return 0;
-}
-
-int musc_db_partitions(musc_ctx* c, uint32_t* first_target, uint32_t cap, uint32_t* n) {
-  if (!c) return 1;
-  if (!n) return fail(c, 2, "musc_db_partitions: n is NULL");
-  *n = c->part_first.empty() ? 0u : (uint32_t)c->part_first.size() - 1;
-  if (!first_target || !*n) return 0;
-  if (cap < *n + 1) return fail(c, 2, "musc_db_partitions: room for %u boundaries < %u", cap, *n + 1);
-  memcpy(first_target, c->part_first.data(), (*n + 1) * sizeof(uint32_t));
-  return 0;
-}
+extern "C" {
 
 // ---------------------------------------------------------------- reads
 

@@ -1,14 +1,31 @@
 // muscato_pass.hpp -- the host side of musc_match_device: the kernel-instance resolvers and launchers of both paths, and
-// the pass driver (set-up, batches, finish, retries).  Part of libmuscato_hip.so: included by muscato_hip.hip after the
-// index and upload code it calls (ensure_index, plan_partitions, upload_prepare, db_xblocks, match_kind).
+// the pass driver (set-up, batches, finish, retries).  Part of libmuscato_hip.so: included by muscato_hip.hip after
+// muscato_index.hpp (ensure_index, plan_partitions; the resident index is read through c->idx) and the upload and
+// database code it calls (upload_prepare, db_xblocks).
 #pragma once
 
 namespace {
 
+inline bool idx_is_ctx(const musc_ctx* c) { return musc_index::is_ctx(c->idx.kind); }
+inline bool idx_is_wide(const musc_ctx* c) { return c->idx.kind == musc_index::K_CTXW; }
+inline bool idx_is_lines(const musc_ctx* c) { return c->idx.kind == musc_index::K_LINES; }
+
+// Which of the two fused kernels on context buckets runs
+enum MatchKind { MK_LANE = 2, MK_DMA = 3 };
+// MK_LANE = k_match_t (kernels_match_lane.hpp): every run on context buckets.  MK_DMA = k_match_g
+// (kernels_match_dma.hpp): the same comparisons at three to four waves per SIMD, everything from memory by LDS-DMA --
+// built for two windows on 120-base buckets, records of 8 words, no X on either side (BASELINE configs 2-4).  It is
+// the second implementation (MUSC_MATCH=dma; the parity tests run both): on cfg3 its launch takes as long as
+// k_match_t's.
+int match_kind(const musc_ctx* c, int W) {
+  if (c->env.match_dma && W == 2 && c->rw == 8 && c->idx.kind == musc_index::K_CTX && !c->db_has_x && !c->reads_have_x) return MK_DMA;
+  return MK_LANE;
+}
+
 // line buckets without X anywhere, record strides k_screen_t is built for: the wave-autonomous screen
 // (kernels_screen_lane.hpp); MUSC_SCREEN=wg keeps k_screen (A/B runs)
 bool screen_lane(const musc_ctx* c, bool mask) {
-  return c->idx_lines && !mask && !c->rdm && (c->rw == 4 || c->rw == 8 || c->rw == 12 || c->rw == 16) && !c->env.screen_wg;
+  return idx_is_lines(c) && !mask && !c->rdm && (c->rw == 4 || c->rw == 8 || c->rw == 12 || c->rw == 16) && !c->env.screen_wg;
 }
 
 // f(std::integral_constant<int, RW>{}) for the record strides that have kernel instances of their own (RW = 0: any other)
@@ -151,13 +168,13 @@ void launch_screen(musc_ctx* c, const PassPlan& pl, uint64_t r0, uint32_t n) {
     const auto k = screen_t_instance(c->rw);
     c->last_inst[1] = k.id;
     hipLaunchKernelGGL(k.fn, sgrid, dim3(64), 0, c->stream, c->rd, r0, n, c->d_pp, c->nmiss_tab.p,
-                       reinterpret_cast<const LineBucket*>(c->idx_T), c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p,
+                       static_cast<const LineBucket*>(c->idx_T.p), static_cast<const uint4*>(c->idx_E.p), b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p,
                        b.tbase.p, b.tcount.p, c->counters + CNT_BATCH, c->counters + CNT_FLAGS);
   } else {
-    const auto k = screen_instance(c->rw, c->rdm != nullptr, pl.pp.W, c->idx_lines);
+    const auto k = screen_instance(c->rw, c->rdm != nullptr, pl.pp.W, idx_is_lines(c));
     c->last_inst[1] = k.id;
     hipLaunchKernelGGL(k.fn, sgrid, dim3(TILE), 0, c->stream, c->rd, c->rdm, r0, n, c->rw, c->d_pp,
-                       c->nmiss_tab.p, c->idx_T, c->idx_E, b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p, b.tbase.p, b.tcount.p,
+                       c->nmiss_tab.p, static_cast<const Bucket*>(c->idx_T.p), static_cast<const uint4*>(c->idx_E.p), b.cdesc.p, b.cdesc.cap, b.rvalid.p, b.wb.p, b.tbase.p, b.tcount.p,
                        c->counters + CNT_BATCH, c->counters + CNT_FLAGS);
   }
 }
@@ -243,8 +260,8 @@ static unsigned match_resident(musc_ctx* c, match_kernel_t kern, int W, int bloc
 static void launch_match(musc_ctx* c, const PassPlan& pl, uint64_t r0, uint32_t n, unsigned ngrid) {
   const size_t lds = match_dyn_lds(match_kind(c, pl.pp.W), pl.pp.W, pl.block_mode);
   const uint32_t* const rdx = c->reads_have_x ? (const uint32_t*)c->rdx.p : (const uint32_t*)nullptr;
-  hipLaunchKernelGGL(pl.kern, dim3(ngrid), dim3(TILE), lds, c->stream, c->rd, r0, n, c->d_mp, c->nmiss_tab.p, c->ctx_T,
-                     c->ctx_E, c->stage.p, c->stage.cap, c->spill.p, c->spill.cap, c->bs[0].tbase.p, c->tcount2.p,
+  hipLaunchKernelGGL(pl.kern, dim3(ngrid), dim3(TILE), lds, c->stream, c->rd, r0, n, c->d_mp, c->nmiss_tab.p, static_cast<const CtxBucket*>(c->ctx_T.p),
+                     static_cast<const CtxEntry*>(c->ctx_E.p), c->stage.p, c->stage.cap, c->spill.p, c->spill.cap, c->bs[0].tbase.p, c->tcount2.p,
                      pl.block_mode, pl.block_thr, c->block_table.p, c->counters, rdx);
 }
 
@@ -264,7 +281,7 @@ static bool spec_geom_equals(const MatchParams& mp) {
 }
 static int spec_geom_matches(const musc_ctx* c, const MatchParams& mp) {
   if (c->env.no_spec) return 0;
-  if (c->rw != 8 || c->idx_wide || c->db_has_x || c->reads_have_x) return 0;  // the instances that exist: <8, 2, 0, false, g>
+  if (c->rw != 8 || idx_is_wide(c) || c->db_has_x || c->reads_have_x) return 0;  // the instances that exist: <8, 2, 0, false, g>
   return spec_geom_equals<1>(mp) ? 1 : 0;
 }
 
@@ -272,12 +289,12 @@ static int spec_geom_matches(const musc_ctx* c, const MatchParams& mp) {
 // depends on c->spec_geom), the instance, its persistent grid
 static int match_setup(musc_ctx* c, PassPlan* pl) {
   const PathParams& pp = pl->pp;
-  if (c->rw != 4 && c->rw != 8 && c->rw != 12 && !(c->rw == 16 && c->idx_wide))
+  if (c->rw != 4 && c->rw != 8 && c->rw != 12 && !(c->rw == 16 && idx_is_wide(c)))
     return fail(c, 12, "internal: record stride %d on the context path", c->rw);
   static thread_local MatchParams mp;  // 16 KB with its mask tables: not on the stack
   memset(&mp, 0, sizeof mp);
   mp.W = pp.W; mp.ww = pp.ww; mp.min_dinuc = pp.min_dinuc; mp.bits = pp.bits; mp.direct = pp.direct;
-  mp.mmtol = pp.mmtol; mp.apply_mmtol = pp.apply_mmtol; mp.max_len = pp.max_len; mp.CL = c->idx_CL;
+  mp.mmtol = pp.mmtol; mp.apply_mmtol = pp.apply_mmtol; mp.max_len = pp.max_len; mp.CL = c->idx.CL;
   mp.q1zero_mask = pp.q1zero_mask;
   mp.seq_off = c->db_has_x ? c->seq_off : nullptr;
   mp.dbm2 = c->db_has_x ? c->dbm2 : nullptr;
@@ -296,7 +313,7 @@ static int match_setup(musc_ctx* c, PassPlan* pl) {
   // (a grid of 2 to 16 times the resident workgroups, dispatched dynamically, is slower: 1.03 to 1.11 ms against 0.98-0.99 on
   // cfg3, profiles/r04_ab_shape_spec_dma.txt -- the waves that finish early leave their share of the memory system to the slow ones)
   const int xm = c->db_has_x ? 2 : c->reads_have_x ? 1 : 0;
-  const MatchInst inst = match_instance(match_kind(c, pp.W), c->spec_geom, c->rw, c->idx_wide != 0, pp.W, xm);
+  const MatchInst inst = match_instance(match_kind(c, pp.W), c->spec_geom, c->rw, idx_is_wide(c), pp.W, xm);
   pl->kern = inst.fn;
   c->last_inst[0] = inst.id;
   if (!pl->kern) return fail(c, 12, "internal: no fused kernel instance for record stride %d, %d windows", c->rw, pp.W);
@@ -321,8 +338,8 @@ static int pass_setup(musc_ctx* c, const musc_params* P, PassPlan* pl, BatchCurs
   pp.W = P->n_windows;
   pp.ww = P->window_width;
   pp.min_dinuc = P->min_dinuc;
-  pp.bits = c->idx_bits;
-  pp.direct = c->idx_direct;
+  pp.bits = c->idx.bits;
+  pp.direct = c->idx.direct;
   pp.mmtol = P->mmtol > 0xFFFF ? 0xFFFF : P->mmtol;
   pp.apply_mmtol = P->apply_mmtol;
   pp.wide = c->wide;
@@ -375,13 +392,12 @@ static int pass_setup(musc_ctx* c, const musc_params* P, PassPlan* pl, BatchCurs
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->h_pp_valid = true;
   }
-  c->stats.index_kind = c->idx_kind == 1 ? (c->idx_wide ? 2u : 1u) : (c->idx_lines ? 3u : 0u);
+  c->stats.index_kind = c->idx.kind;
   c->last_inst[0] = c->last_inst[1] = c->last_inst[2] = 0;  // (the resolvers of this pass fill them in)
   c->last_inst[3] = (uint32_t)pl->block_mode | (c->force_exact_blocks ? 0x100u : 0u);
-  c->stats.index_bytes = c->idx_kind == 1
-                             ? ((1ull << c->idx_bits) + 1) * sizeof(CtxBucket) + ctx_entries_bytes(c->idx_novf + 16, c->idx_wide)
-                             : ((1ull << c->idx_bits) + 1) * (c->idx_lines ? sizeof(LineBucket) : sizeof(Bucket)) + (c->idx_novf + 16) * sizeof(uint4);
-  if (c->idx_kind == 1) {
+  c->stats.index_bytes = ((1ull << c->idx.bits) + 1) * musc_index::bucket_bytes(c->idx.kind) +
+                         (idx_is_ctx(c) ? ctx_entries_bytes(c->idx_novf + 16, idx_is_wide(c)) : (c->idx_novf + 16) * sizeof(uint4));
+  if (idx_is_ctx(c)) {
     if ((rc = match_setup(c, pl))) return rc;
     const uint32_t thr_resident = thr_for(pl->resident);
     if (pl->block_mode == 1 && thr_resident < 2) {  // (the pass clears the table with its batch block)
@@ -452,7 +468,7 @@ static int pass_close(musc_ctx* c, const PassPlan& pl, hipEvent_t ev1) {
 // them from the block itself, which it cleared once).
 static int pass_verdict(musc_ctx* c, const PassPlan& pl, const BatchCursor& cur, const uint64_t* tot, PassClock& clk,
                         PassOutcome* what) {
-  const bool fused = c->idx_kind == 1;
+  const bool fused = idx_is_ctx(c);
   c->last_pp = pl.pp;
   c->last_max_matches = (uint32_t)pl.max_matches;
   c->last_exact_blocks = pl.block_mode == 2;
@@ -485,7 +501,7 @@ static int pass_verdict(musc_ctx* c, const PassPlan& pl, const BatchCursor& cur,
   if (fused) {
     c->stats.n_pairs = tot[MB_CMP];
     c->stats.n_overflow_entries = tot[MB_OVF];
-    const uint64_t ent_b = c->idx_wide ? sizeof(CtxEntryW) : sizeof(CtxEntry);
+    const uint64_t ent_b = idx_is_wide(c) ? sizeof(CtxEntryW) : sizeof(CtxEntry);
     c->stats.match_bytes = c->nreads * rec_b + tot[MB_WINDOWS] * sizeof(CtxBucket) + tot[MB_OVF] * ent_b + 16 * c->stats.n_hits;
     c->stats.match_bytes_strict = c->nreads * rec_b + tot[MB_WINDOWS] * 8 + tot[MB_CAND] * ent_b + 16 * c->stats.n_hits;
   } else {
@@ -770,7 +786,7 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
     if ((rc = ensure_index(c, P, c->max_len))) break;
     if (nhits) *nhits = 0;
     if ((rc = pass_setup(c, P, &pl, &cur))) break;
-    rc = c->idx_kind == 1 ? pass_fused(c, pl, cur, &what) : pass_two_kernel(c, pl, cur, &what);
+    rc = idx_is_ctx(c) ? pass_fused(c, pl, cur, &what) : pass_two_kernel(c, pl, cur, &what);
     if (rc || what == PASS_DONE) break;
     if (what == PASS_RERUN_CAREFUL) {
       c->sized_epoch = 0;

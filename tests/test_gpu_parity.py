@@ -325,7 +325,7 @@ def test_specialised_instance_is_guarded(eng):
     geometry-specialised kernel instance (SpecGeom<1>: BASELINE configs 3 / 4) turns into a constant -- on a database
     small enough to get a HASHED table, which that instance was not built for (it takes the key for the bucket: the
     r03 fault, gpurun_out/var.err, was a development build of that kind reading past cfg2's 2^27-bucket table).  The
-    instance is in the library; the host's guard (spec_geom_matches: idx_direct / idx_bits are part of the comparison)
+    instance is in the library; the host's guard (spec_geom_matches: idx.direct / idx.bits are part of the comparison)
     must pick the GENERAL instance, and the tuples must equal the CPU port's.  (The other direction -- a direct
     2^30-bucket table with the same geometry runs the specialised instance -- is tested at small size by
     tests/test_gpu_spec.py, which forces the direct table with MUSC_DEBUG_CTX_DIRECT=1, and at full size by the

@@ -323,3 +323,27 @@ def test_automatic_plan_under_an_index_budget(engine_for):
         check_read_major(e, got)
         assert (srt(got) == ref[a]).all()
     assert e.stats()["index_kind"] == 0  # (1500 MiB: neither context table fits; 64-byte buckets of half the database do)
+
+
+def test_resident_window_index_survives_an_unfitting_context_table(engine_for):
+    """Context buckets are eligible but do not fit (WindowWidth 15 over 116 182 bases under 15 MiB: the hashed context
+    table needs 19 899 300 B, 64-byte buckets 12 344 752 B), so the pass runs on the window-start index -- and later
+    passes with the same parameters find it resident.  stats()["ms_index_build"] is kept across passes and rewritten
+    only by a build (a fresh event time), so it stays bit-equal exactly when nothing was rebuilt."""
+    c = ocfg(PMatch=0.95, MMTol=1)
+    full = oracle_full(READS, TARGETS_NOX, c)
+    e = engine_for({"MUSC_DEBUG_INDEX_BUDGET_MB": "15"})
+    e.load_targets(TARGETS_NOX)
+    e.load_reads(READS)
+    first = srt(raw_hits(e, c, False))
+    st = e.stats()
+    print("pass 1: index_kind", st["index_kind"], "ms_index_build", repr(st["ms_index_build"]))
+    assert e.partitions() == [0, len(TARGETS_NOX)]
+    assert st["index_kind"] == 0
+    assert first.shape == full.shape and (first == full).all()
+    for n in (2, 3):
+        again = srt(raw_hits(e, c, False))
+        st_n = e.stats()
+        print("pass", n, ": ms_index_build", repr(st_n["ms_index_build"]))
+        assert again.shape == first.shape and (again == first).all()
+        assert st_n["ms_index_build"] == st["ms_index_build"], (n, st_n["ms_index_build"], st["ms_index_build"])

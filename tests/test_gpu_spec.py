@@ -439,7 +439,7 @@ def test_selection_boundaries(se):
 def test_other_geometries_and_the_knob(se):
     """One step off the geometry -- Windows 0,21 (20 + 1 bases of context), WindowWidth 14 (a direct 2^28 table) --
     runs the general instance.  Then the knob itself: MUSC_DEBUG_CTX_DIRECT unset through reload_env gives this
-    database its ordinary hashed table (the resident table's kind is part of build_index_ctx's comparison, so the
+    database its ordinary hashed table (the resident table's kind is part of ensure_index's comparison, so the
     table is rebuilt) and the general instance; set again, the direct table and the specialised one."""
     rng = np.random.default_rng(12)
     reads = reads_of(12, rng.integers(40, 100, size=8000))
