@@ -448,6 +448,36 @@ int musc_stream_plan(uint64_t nreads, uint32_t fixed_len, uint32_t batch_reads, 
 int musc_overflow_probes(musc_ctx* ctx, uint32_t** read_idx, uint32_t** window, uint64_t* n);
 void musc_free_u32(uint32_t* p);
 
+/* ---- the MaxMatches truncation replayed on the device: what apply_maxmatches of muscato_host.hpp does
+ * on the host from the downloaded tuples and musc_overflow_probes, without either leaving the device.  Needs the list
+ * of a musc_match* on this context with apply_mmtol = 0 (and n_shards <= 1, and the MaxMatches check not skipped) over
+ * the reads and the database in hand, and uses that pass's parameters: otherwise code 2.  The list of the pass becomes
+ * the reference's selection -- in every (window, key) block with more than MaxMatches accepted pairs the pairs that
+ * cmd/muscato_confirm/main.go:183-244, 424-448 keep (candidates in the bytewise order of their smatch line, reads in
+ * that of their win_k_sorted line; "first": the first MaxMatches + 1; "best": the sift-up heap cut at MaxMatches), and
+ * the union over the windows rebuilt for the reads of those blocks -- and, with apply_mmtol != 0, of that per read the
+ * tuples with nmiss <= best + MMTol (matches.txt).  It stays resident and read-major as "the list of the last pass":
+ * musc_hits_copy*, musc_results_order(hits = NULL), musc_results_hits and the side stage read it; a read or database
+ * load or a musc_match* replaces it as usual, and a second call without a new pass returns 2.
+ * *n_suspect_probes = the probes musc_overflow_probes would name, *n_truncated_blocks = the blocks that really held
+ * more than MaxMatches pairs (the others are false alarms of the hashed counters and are left alone), *nhits = the
+ * tuples of the new list; each pointer may be NULL.  No suspect probe: apply_mmtol = 0 changes nothing, apply_mmtol
+ * != 0 applies the per-read selection only.
+ * Code 10: a device allocation failed; the list of the pass stays as it was.  Code 12 is a refusal that leaves the
+ * context untouched (as musc_side_prepare's): the longest loaded read has more than MUSC_MM_MAX_READ_LEN bases (the
+ * flanks the lines are ordered by are compared base by base), WindowWidth is above that bound, MaxMatches is negative,
+ * or there are 2^32 - 16 tuples or 2^30 - 2 suspect probes or more.  The caller keeps its host path then.
+ * MUSC_DEBUG_MM_HEAP_LDS=<entries> (tests only, read by musc_init) lowers the LDS capacity of the replay kernel's heap,
+ * so that the path with the heap in global memory runs at small MaxMatches.  MUSC_ABI_VERSION is unchanged: additions. */
+#define MUSC_MM_MAX_READ_LEN 1024
+int musc_maxmatches_apply(musc_ctx* ctx, int apply_mmtol, uint64_t* nhits, uint64_t* n_suspect_probes,
+                          uint64_t* n_truncated_blocks);
+/* HIP-event time of the last successful musc_maxmatches_apply (allocations included). */
+int musc_maxmatches_last_ms(musc_ctx* ctx, float* ms);
+/* Of the same call: the accepted pairs the truncated blocks held (what the replay kernel walked), and the HIP-event
+ * time of that kernel, k_mm_replay, alone.  Either pointer may be NULL. */
+int musc_maxmatches_last_detail(musc_ctx* ctx, uint64_t* n_pairs, float* ms_replay);
+
 /* ---- several GPUs in one process (a Go host driving one ctx per GPU from locked threads):
  * concatenate the device-resident hits of ctxs[0..n) in rank order into one host array,
  * adding read_base[i] to the read_idx of shard i.  (The one-process-per-GPU path gathers

@@ -74,6 +74,7 @@ SYMBOLS = [
     "musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits", "musc_results_text",
     "musc_results_last_ms", "musc_results_number_key",
     "musc_side_prepare", "musc_side_text", "musc_side_last_ms",
+    "musc_maxmatches_apply", "musc_maxmatches_last_ms", "musc_maxmatches_last_detail",
 ]
 
 # `which` of musc_side_text (include/muscato_hip.h)
@@ -160,6 +161,12 @@ def load() -> ctypes.CDLL:
     lib.musc_side_prepare.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.musc_side_text.argtypes = [vp, ctypes.c_int, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
     lib.musc_side_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    lib.musc_maxmatches_apply.argtypes = [vp, ctypes.c_int, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.musc_maxmatches_apply.restype = ctypes.c_int
+    lib.musc_maxmatches_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.musc_maxmatches_last_ms.restype = ctypes.c_int
+    lib.musc_maxmatches_last_detail.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]
+    lib.musc_maxmatches_last_detail.restype = ctypes.c_int
     for name in ("musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits",
                  "musc_results_text", "musc_results_last_ms", "musc_results_number_key",
                  "musc_side_prepare", "musc_side_text", "musc_side_last_ms"):

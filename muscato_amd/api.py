@@ -392,6 +392,37 @@ class Engine:
         self._lib.musc_free_u32(pw)
         return out
 
+    def apply_maxmatches(self, apply_mmtol: bool = True) -> dict:
+        """Replay the reference's MaxMatches truncation on the device (musc_maxmatches_apply): after a match with
+        apply_mmtol=False the resident list becomes what the reference keeps (with apply_mmtol=True: of that, per read,
+        nmiss <= best + MMTol).  hits_to*, results_order() and the side stage read the new list.
+        -> {"nhits", "suspect_probes", "truncated_blocks"}.  MuscatoError "(2)": no such pass; "(12)": a shape the
+        device stage does not take (the context is untouched)."""
+        n, ns, nt = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.musc_maxmatches_apply(self._h, 1 if apply_mmtol else 0, ctypes.byref(n), ctypes.byref(ns),
+                                                    ctypes.byref(nt)), "musc_maxmatches_apply")
+        return {"nhits": int(n.value), "suspect_probes": int(ns.value), "truncated_blocks": int(nt.value)}
+
+    def maxmatches_ms(self) -> float:
+        """HIP-event time of the last apply_maxmatches."""
+        ms = ctypes.c_float()
+        self._check(self._lib.musc_maxmatches_last_ms(self._h, ctypes.byref(ms)), "musc_maxmatches_last_ms")
+        return float(ms.value)
+
+    def maxmatches_detail(self) -> dict:
+        """Of the last apply_maxmatches: the pairs its truncated blocks held, and the time of k_mm_replay alone."""
+        n, ms = ctypes.c_uint64(), ctypes.c_float()
+        self._check(self._lib.musc_maxmatches_last_detail(self._h, ctypes.byref(n), ctypes.byref(ms)), "musc_maxmatches_last_detail")
+        return {"pairs": int(n.value), "replay_ms": float(ms.value)}
+
+    def hits(self) -> np.ndarray:
+        """The resident list (of the last match, or of apply_maxmatches) -> uint32 [n, 4]."""
+        n = int(self.stats()["n_hits"])
+        out = np.zeros((n, 4), dtype=np.uint32)
+        if n:
+            self.hits_to(out.ctypes.data, n, False)
+        return out
+
     def last_instance(self) -> dict:
         """The kernel instances the last match launched, from the resolver that returned their function pointers:
         {"path": "fused" | "two-kernel" | "none", "match": k_match_t / k_match_g descriptor or None, "screen": k_screen /

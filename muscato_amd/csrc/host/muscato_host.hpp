@@ -1011,7 +1011,16 @@ inline std::vector<musc_hit> best_filter(const std::vector<musc_hit>& all, size_
 // musc_ctx per device, as the ABI's threading rule asks), run the hot path, gather.
 // keep0 (one GPU only): the context stays alive and is handed to the caller, with every read and the database
 // loaded, for the results stage; *list_on_device = the returned tuples are the list the last pass left on the device
-// (false after the MaxMatches replay, whose selection exists on the host only).
+// (true after the MaxMatches replay on the device, which leaves its selection resident; false after the host replay,
+// whose selection exists on the host only).
+//
+// MUSC_MAXMATCHES_DEFAULT_DEVICE -- 1: the CLI replays the MaxMatches truncation on the device unless
+// MUSC_MAXMATCHES=host; 0: only with MUSC_MAXMATCHES=device.  Measured (profiles/maxmatches.py): on a
+// 2 M-read run with 150 truncated blocks the replay, results.txt and side-output laps add up to 0.39 s with the replay
+// on the device against 1.52 s with it on the host, the runs of either side within 0.08 s of each other.
+#ifndef MUSC_MAXMATCHES_DEFAULT_DEVICE
+#define MUSC_MAXMATCHES_DEFAULT_DEVICE 1
+#endif
 inline std::vector<musc_hit> run_hot_path(const Config& cfg, const std::vector<UniqueRead>& reads,
                                           const std::vector<std::string>& targets, Logger& log, musc_stats* stats0,
                                           musc_ctx** keep0 = nullptr, bool* list_on_device = nullptr) {
@@ -1106,6 +1115,7 @@ inline std::vector<musc_hit> run_hot_path(const Config& cfg, const std::vector<U
     overflow = overflow || (s.n_overflow_blocks != 0 && s.n_overflow_blocks != ~0ull);
   }
   for (int g = 1; g < G; g++) if (ctxs[g]) { musc_destroy(ctxs[g]); ctxs[g] = nullptr; }
+  bool replayed_on_device = false;
   if (err.empty() && overflow) {
     // Some (window,key) block may exceed MaxMatches: redo the pass on one GPU with every read,
     // take all accepted tuples and replay the reference's truncation on the host.
@@ -1115,28 +1125,70 @@ inline std::vector<musc_hit> run_hot_path(const Config& cfg, const std::vector<U
     P1.apply_mmtol = 0;
     P1.n_shards = 0;
     const Concat rd = concat(reads.begin(), reads.end(), [](const UniqueRead& u) -> const std::string& { return u.seq; });
-    musc_hit* h = nullptr;
-    uint64_t n = 0, np = 0;
-    uint32_t *pr = nullptr, *pw = nullptr;
-    if (musc_reads_load_ascii(c, rd.buf.data(), rd.off.data(), reads.size(), 0) || musc_match(c, &P1, &h, &n) ||
-        musc_overflow_probes(c, &pr, &pw, &np)) {
-      err = musc_last_error(c);
-    } else {
-      size_t ntrunc = 0;
-      std::vector<musc_hit> all(h, h + n);
-      all = apply_maxmatches(cfg, reads, targets, std::move(all), pr, pw, np, &ntrunc);
-      out = best_filter(all, reads.size(), cfg.MMTol);
-      log.printf("MaxMatches: %llu suspect probes, %zu blocks truncated as the reference does", (unsigned long long)np, ntrunc);
-      if (stats0) stats0->n_overflow_blocks = 0;  // handled exactly
+    // MUSC_MAXMATCHES=host|device: where the truncation is replayed.  The device stage
+    // (musc_maxmatches_apply) leaves the selection resident, so that results.txt and the side outputs still come from
+    // the device; a refusal (12), a failed allocation (10) and a post-chain over several GPUs keep the host replay.
+    const char* mm_env = getenv("MUSC_MAXMATCHES");
+    const bool mm_env_device = mm_env && !strcmp(mm_env, "device"), mm_env_host = mm_env && !strcmp(mm_env, "host");
+    bool mm_device = mm_env_device || (!mm_env_host && MUSC_MAXMATCHES_DEFAULT_DEVICE);
+    if (mm_device && G > 1) {
+      log.printf("MaxMatches replay on the host: the post-chain of %d GPUs runs on the host", G);
+      mm_device = false;
     }
-    musc_free_hits(h);
-    musc_free_u32(pr);
-    musc_free_u32(pw);
+    uint64_t n = 0;
+    const double t_load = StageClock::now();
+    if (musc_reads_load_ascii(c, rd.buf.data(), rd.off.data(), reads.size(), 0) || musc_match_device(c, &P1, &n)) {
+      err = musc_last_error(c);
+      mm_device = false;
+    }
+    const double t_replay = StageClock::now();
+    if (err.empty() && mm_device) {
+      uint64_t nh = 0, np = 0, ntrunc = 0;
+      const int rc = musc_maxmatches_apply(c, 1, &nh, &np, &ntrunc);
+      if (rc == 0) {
+        out.resize(nh);
+        if (musc_hits_copy(c, out.data(), nh, 0)) err = musc_last_error(c);
+        float ms = 0, ms_replay = 0;
+        uint64_t npairs = 0;
+        musc_maxmatches_last_ms(c, &ms);
+        musc_maxmatches_last_detail(c, &npairs, &ms_replay);
+        log.printf("MaxMatches: %llu suspect probes, %llu blocks truncated as the reference does", (unsigned long long)np,
+                   (unsigned long long)ntrunc);
+        log.printf("MaxMatches replay on the device: %.3f s (device %.3f ms, k_mm_replay %.3f ms, %llu pairs in the truncated blocks), "
+                   "%llu tuples; the pass before it %.3f s",
+                   StageClock::now() - t_replay, ms, ms_replay, (unsigned long long)npairs, (unsigned long long)nh, t_replay - t_load);
+        replayed_on_device = true;
+        if (stats0) stats0->n_overflow_blocks = 0;  // handled exactly
+      } else if (rc == 12 || rc == 10) {
+        log.printf("MaxMatches replay on the host: the device stage returned %d (%s)", rc, musc_last_error(c));
+        mm_device = false;
+      } else {
+        err = musc_last_error(c);
+      }
+    }
+    if (err.empty() && !mm_device) {
+      std::vector<musc_hit> all(n);
+      uint64_t np = 0;
+      uint32_t *pr = nullptr, *pw = nullptr;
+      if (musc_hits_copy(c, all.data(), n, 0) || musc_overflow_probes(c, &pr, &pw, &np)) {
+        err = musc_last_error(c);
+      } else {
+        size_t ntrunc = 0;
+        all = apply_maxmatches(cfg, reads, targets, std::move(all), pr, pw, np, &ntrunc);
+        out = best_filter(all, reads.size(), cfg.MMTol);
+        log.printf("MaxMatches: %llu suspect probes, %zu blocks truncated as the reference does", (unsigned long long)np, ntrunc);
+        log.printf("MaxMatches replay on the host: %.3f s, %zu tuples; the pass before it %.3f s", StageClock::now() - t_replay,
+                   out.size(), t_replay - t_load);
+        if (stats0) stats0->n_overflow_blocks = 0;  // handled exactly
+      }
+      musc_free_u32(pr);
+      musc_free_u32(pw);
+    }
   }
   if (keep0 && G == 1 && err.empty()) {
     *keep0 = ctxs[0];
     ctxs[0] = nullptr;
-    if (list_on_device) *list_on_device = !overflow;
+    if (list_on_device) *list_on_device = !overflow || replayed_on_device;
   }
   for (auto c : ctxs) if (c) musc_destroy(c);
   if (!err.empty()) throw Die(1, "muscato hot path failed:\n" + err);

@@ -49,6 +49,7 @@
 #include "kernels_results.hpp"
 #include "side_names.hpp"
 #include "kernels_side.hpp"
+#include "kernels_maxmatches.hpp"
 MUSC_LANE_INSTANCES_4(extern)
 MUSC_LANE_INSTANCES_8(extern)
 MUSC_LANE_INSTANCES_12(extern)
@@ -230,6 +231,7 @@ struct EnvKnobs : musc_index::Knobs {
   long batch_reads = 0;       // MUSC_BATCH_READS (0: not set)
   uint64_t stage_bytes = 64ull << 20;  // MUSC_DEBUG_STAGE_BYTES: device staging of a text call for a host destination (tests)
   uint64_t stage_lines = 1ull << 20;   // MUSC_DEBUG_STAGE_LINES: record offsets such a call fetches to the host at a time (tests)
+  long mm_heap_lds = 0;                // MUSC_DEBUG_MM_HEAP_LDS: LDS heap entries of k_mm_replay, lowered (tests; 0: not set)
   void read() {
     *this = EnvKnobs();
     auto is = [](const char* v, const char* w) { return v && !strcmp(v, w); };
@@ -253,6 +255,7 @@ struct EnvKnobs : musc_index::Knobs {
     if ((e = getenv("MUSC_DEBUG_INDEX_BUDGET_MB"))) index_budget_mb = atol(e);
     if ((e = getenv("MUSC_DEBUG_STAGE_BYTES")) && atoll(e) > 0) stage_bytes = (uint64_t)atoll(e);
     if ((e = getenv("MUSC_DEBUG_STAGE_LINES")) && atoll(e) > 0) stage_lines = (uint64_t)atoll(e);
+    if ((e = getenv("MUSC_DEBUG_MM_HEAP_LDS"))) mm_heap_lds = atol(e);
   }
 };
 
@@ -413,6 +416,12 @@ struct musc_ctx {
   uint64_t side_nel = 0;
   uint64_t side_nrec[3] = {0, 0, 0}, side_nbytes[3] = {0, 0, 0};
   float side_ms_prepare = 0, side_ms_text = 0;
+
+  // the MaxMatches replay on the device
+  musc_params mm_params;            // of the last musc_match* that succeeded
+  bool mm_list = false;             // `hits` is that pass's list as the pass left it (musc_maxmatches_apply replaces it)
+  float mm_ms = 0, mm_ms_replay = 0;  // event time of the last musc_maxmatches_apply; of its k_mm_replay
+  uint64_t mm_pairs = 0;            // pairs in the blocks which that call truncated
 
   uint32_t batch_reads = 16u << 20;
   // A pass over the same reads, database and parameters as the last completed one needs no
@@ -1312,6 +1321,8 @@ int musc_hits_copy(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_dev
 
 // results.txt and the side outputs as text from the resident tuples (musc_results_*, musc_side_*)
 #include "muscato_text.hpp"
+// the MaxMatches truncation replayed on the device (musc_maxmatches_*)
+#include "muscato_maxmatches.hpp"
 
 extern "C" {
 
@@ -1529,48 +1540,32 @@ int musc_overflow_probes(musc_ctx* c, uint32_t** read_idx, uint32_t** window, ui
   if (c->stats.n_overflow_blocks == 0 || c->stats.n_overflow_blocks == ~0ull) return 0;
   if (!c->last_exact_blocks || !c->block_table.p) return fail(c, 4, "no exact block counters from the last pass");
   HIPCHK(c, hipSetDevice(c->device));
-  uint64_t cap = 1u << 20;
-  for (;;) {
-    TmpBufs B;  // released at the end of every iteration and on every return
-    uint2* d_out = nullptr;
-    HIPCHK(c, B.alloc(&d_out, cap * sizeof(uint2)));
-    HIPCHK(c, hipMemsetAsync(c->counters + CNT_BATCH, 0, 8, c->stream));
-    const dim3 grid(std::min(nblk(c->nreads, 256), MAX_GRID)), block(256);
-    switch (c->rw) {
-      case 4: hipLaunchKernelGGL((k_hot_probes<4>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-      case 8: hipLaunchKernelGGL((k_hot_probes<8>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-      case 12: hipLaunchKernelGGL((k_hot_probes<12>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-      case 16: hipLaunchKernelGGL((k_hot_probes<16>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-      default: hipLaunchKernelGGL((k_hot_probes<0>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(c->h_pinned, c->counters + CNT_BATCH, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  DevOwner own;  // the probes on the device (muscato_maxmatches.hpp), released on every return
+  uint2* d_out = nullptr;
+  uint64_t found = 0;
+  const int rc = hot_probes_device(c, &d_out, &found);
+  if (rc) return rc;
+  own.p = d_out;
+  std::vector<uint2> h(found ? found : 1);
+  if (found) {
+    const hipError_t e = hipMemcpy(h.data(), d_out, found * sizeof(uint2), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, 10, "musc_overflow_probes: %s", hipGetErrorString(e));
-    const uint64_t found = c->h_pinned[0];
-    if (found > cap) {  // retry with room for all of them
-      cap = found + 16;
-      continue;
-    }
-    std::vector<uint2> h(found ? found : 1);
-    if (found) e = hipMemcpy(h.data(), d_out, found * sizeof(uint2), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(c, 10, "musc_overflow_probes: %s", hipGetErrorString(e));
-    uint32_t* r = (uint32_t*)malloc(sizeof(uint32_t) * (found ? found : 1));
-    uint32_t* w = (uint32_t*)malloc(sizeof(uint32_t) * (found ? found : 1));
-    if (!r || !w) {
-      free(r);
-      free(w);
-      return fail(c, 7, "musc_overflow_probes: out of host memory");
-    }
-    for (uint64_t j = 0; j < found; j++) {
-      r[j] = h[j].x;
-      w[j] = h[j].y;
-    }
-    *read_idx = r;
-    *window = w;
-    *n = found;
-    return 0;
   }
+  uint32_t* r = (uint32_t*)malloc(sizeof(uint32_t) * (found ? found : 1));
+  uint32_t* w = (uint32_t*)malloc(sizeof(uint32_t) * (found ? found : 1));
+  if (!r || !w) {
+    free(r);
+    free(w);
+    return fail(c, 7, "musc_overflow_probes: out of host memory");
+  }
+  for (uint64_t j = 0; j < found; j++) {
+    r[j] = h[j].x;
+    w[j] = h[j].y;
+  }
+  *read_idx = r;
+  *window = w;
+  *n = found;
+  return 0;
 }
 
 void musc_free_u32(uint32_t* p) { free(p); }

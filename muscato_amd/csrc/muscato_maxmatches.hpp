@@ -1,0 +1,265 @@
+// muscato_maxmatches.hpp -- the host side of the MaxMatches replay on the device (musc_maxmatches_*).
+// Part of libmuscato_hip.so: included by muscato_hip.hip after muscato_text.hpp (timed, grid).  The kernels are in
+// kernels_maxmatches.hpp, the decisions that need no device in maxmatches_plan.hpp.
+#pragma once
+
+// The suspect probes of the last pass, on the device: the (read, window) pairs whose (window, key) block counter is above
+// MaxMatches.  *out is hipMalloc'ed (the caller frees it) and holds *found pairs; k_hot_probes runs again with room for
+// all of them when the first buffer was too small.
+static int hot_probes_device(musc_ctx* c, uint2** out, uint64_t* found) {
+  *out = nullptr;
+  *found = 0;
+  uint64_t cap = 1u << 20;
+  for (;;) {
+    uint2* d_out = nullptr;
+    HIPCHK(c, hipMalloc((void**)&d_out, cap * sizeof(uint2)));
+    hipError_t e = hipMemsetAsync(c->counters + CNT_BATCH, 0, 8, c->stream);
+    const dim3 grid(std::max(1u, std::min(nblk(c->nreads, 256), MAX_GRID))), block(256);
+    if (e == hipSuccess) {
+      switch (c->rw) {
+        case 4: hipLaunchKernelGGL((k_hot_probes<4>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+        case 8: hipLaunchKernelGGL((k_hot_probes<8>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+        case 12: hipLaunchKernelGGL((k_hot_probes<12>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+        case 16: hipLaunchKernelGGL((k_hot_probes<16>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+        default: hipLaunchKernelGGL((k_hot_probes<0>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
+      }
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(c->h_pinned, c->counters + CNT_BATCH, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(d_out);
+      (void)hipGetLastError();
+      return fail(c, 10, "the suspect probes: %s", hipGetErrorString(e));
+    }
+    const uint64_t n = c->h_pinned[0];
+    if (n > cap) {  // again, with room for all of them
+      (void)hipFree(d_out);
+      cap = n + 16;
+      continue;
+    }
+    *out = d_out;
+    *found = n;
+    return 0;
+  }
+}
+
+namespace {
+
+struct DevOwner {  // one hipMalloc'ed pointer, freed on every exit
+  void* p = nullptr;
+  ~DevOwner() { if (p) (void)hipFree(p); }
+};
+
+MmData mm_data(const musc_ctx* c, const musc_params& P) {
+  MmData D;
+  D.rd = c->rd;
+  D.rdm = c->reads_have_x ? c->rdm : nullptr;
+  D.db2 = c->db2;
+  D.dbm2 = c->db_has_x ? c->dbm2 : nullptr;
+  D.seq_off = c->seq_off;
+  D.nreads = c->nreads;
+  D.nseq = c->nseq;
+  D.rw = c->rw;
+  D.W = P.n_windows;
+  D.ww = P.window_width;
+  D.min_dinuc = P.min_dinuc;
+  D.max_read_length = P.max_read_length;
+  for (int k = 0; k < MUSC_MAX_WINDOWS; k++) D.win[k] = k < P.n_windows ? P.windows[k] : 0;
+  return D;
+}
+
+// rocprim::merge_sort of n uint2 under `less`, in -> out; its temporary storage goes through T
+template <class Less>
+int mm_sort(musc_ctx* c, TmpBufs& T, uint2* in, uint2* out, uint64_t n, Less less) {
+  size_t bytes = 0;
+  void* tmp = nullptr;
+  HIPCHK(c, rocprim::merge_sort(nullptr, bytes, in, out, (size_t)n, less, c->stream));
+  HIPCHK(c, T.alloc(&tmp, bytes));
+  HIPCHK(c, rocprim::merge_sort(tmp, bytes, in, out, (size_t)n, less, c->stream));
+  return 0;
+}
+
+// The stage proper, queued on the context's stream.  The pass's list is read until the last step, which copies the
+// survivors over it: every failure before that leaves the list as it was.
+int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* n_suspect, uint64_t* n_trunc) {
+  const uint64_t N = c->nhits;
+  const int W = P.n_windows;
+  const dim3 B256(256);
+  const MmData D = mm_data(c, P);
+  const uint4* const hits = reinterpret_cast<const uint4*>(c->hits.p);
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned + 8);
+  int rc;
+
+  DevOwner probes_own;
+  uint64_t np = 0;
+  if (c->stats.n_overflow_blocks != 0) {
+    if (!c->last_exact_blocks || !c->block_table.p) return fail(c, 4, "musc_maxmatches_apply: no exact block counters from the last pass");
+    uint2* p = nullptr;
+    if ((rc = hot_probes_device(c, &p, &np))) return rc;
+    probes_own.p = p;
+  }
+  *n_suspect = np;
+  if (np >= musc_mm::MAX_BLOCKS) return fail(c, 12, "musc_maxmatches_apply: %llu suspect probes are more than the device stage takes", (unsigned long long)np);
+  if (N == 0 || (np == 0 && !apply_mmtol)) return 0;
+
+  TmpBufs A, B;  // A: the blocks and the pairs; B: the sorts' storage and the survivors
+  uint32_t* words = nullptr;
+  uint64_t* sizes = nullptr;
+  uint64_t ntrunc = 0;
+  if (np) {
+    // ---- 1. the suspect blocks: the probes in (window, key) order, one representative each
+    uint2 *sorted = nullptr, *blocks = nullptr;
+    uint32_t *heads = nullptr, *excl = nullptr, *stmp = nullptr;
+    HIPCHK(c, A.alloc(&sorted, np * 8));
+    {
+      TmpBufs S;
+      if ((rc = mm_sort(c, S, reinterpret_cast<uint2*>(probes_own.p), sorted, np, MmProbeLess{D}))) return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    HIPCHK(c, A.alloc(&heads, np * 4));
+    HIPCHK(c, A.alloc(&excl, np * 4));
+    HIPCHK(c, A.alloc(&stmp, scan_tmp_elems(np) * 4));
+    hipLaunchKernelGGL(k_mm_heads, grid(np), B256, 0, c->stream, D, sorted, np, heads);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = scan_u32(c, heads, excl, np, false, stmp))) return rc;
+    HIPCHK(c, hipMemcpyAsync(h32, excl + (np - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h32 + 1, heads + (np - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t nb = h32[0] + h32[1];
+    HIPCHK(c, A.alloc(&blocks, (uint64_t)nb * 8));
+    hipLaunchKernelGGL(k_mm_blocks, grid(np), B256, 0, c->stream, sorted, heads, excl, np, blocks);
+    HIPCHK(c, hipGetLastError());
+
+    // ---- 2. pairs: every (tuple, window) finds its block; the blocks count what their windows emit
+    uint32_t *cnt = nullptr, *fill = nullptr;
+    uint64_t *off = nullptr, *tmp64 = nullptr;
+    HIPCHK(c, A.alloc(&words, N * (uint64_t)W * 4));
+    HIPCHK(c, A.alloc(&cnt, (uint64_t)nb * 4));
+    HIPCHK(c, A.alloc(&fill, (uint64_t)nb * 4));
+    HIPCHK(c, A.alloc(&sizes, ((uint64_t)nb + 1) * 8));
+    HIPCHK(c, A.alloc(&off, ((uint64_t)nb + 1) * 8));
+    HIPCHK(c, A.alloc(&tmp64, scan_tmp_elems((uint64_t)nb + 1) * 8));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, (uint64_t)nb * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(fill, 0, (uint64_t)nb * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_mm_pairs, grid(N * (uint64_t)W), B256, 0, c->stream, D, hits, N, blocks, nb, words, cnt);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_mm_sizes, grid((uint64_t)nb + 1), B256, 0, c->stream, cnt, nb, (uint32_t)P.max_matches, sizes, c->counters + CNT_SCRATCH);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = scan_u64(c, sizes, off, (uint64_t)nb + 1, tmp64))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, off + nb, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ntrunc = c->h_pinned[0];
+    const uint64_t M = c->h_pinned[1];
+    *n_trunc = ntrunc;
+    c->mm_pairs = M;
+    if (ntrunc == 0) {  // false alarms only
+      if (!apply_mmtol) return 0;
+      words = nullptr;
+    } else {
+      // ---- 3. order: the pairs of the truncated blocks, block-major, in the order of their lines
+      uint2 *pairs = nullptr, *psorted = nullptr, *gheap = nullptr;
+      HIPCHK(c, B.alloc(&pairs, M * 8));
+      HIPCHK(c, A.alloc(&psorted, M * 8));
+      hipLaunchKernelGGL(k_mm_fill, grid(N * (uint64_t)W), B256, 0, c->stream, words, N, W, sizes, off, fill, pairs);
+      HIPCHK(c, hipGetLastError());
+      if ((rc = mm_sort(c, B, pairs, psorted, M, MmPairLess{D, hits, blocks}))) return rc;
+      // ---- 4. replay
+      const uint32_t lds_cap = musc_mm::heap_lds_entries(c->env.mm_heap_lds);
+      const bool in_lds = musc_mm::heap_in_lds(P.max_matches, lds_cap);
+      if (!in_lds && P.match_mode == 0) HIPCHK(c, B.alloc(&gheap, M * 8));
+      hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
+      if (e0) (void)hipEventRecord(e0, c->stream);
+      hipLaunchKernelGGL(k_mm_replay, dim3(std::min<uint32_t>(nb, 65536u)), dim3(64), 0, c->stream, hits, psorted, blocks, sizes, off, nb, W,
+                         (uint32_t)P.max_matches, P.match_mode == 1 ? 1 : 0, lds_cap, gheap, words);
+      HIPCHK(c, hipGetLastError());
+      if (e1) (void)hipEventRecord(e1, c->stream);
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      c->mm_ms_replay = 0;
+      if (e0 && e1) (void)hipEventElapsedTime(&c->mm_ms_replay, e0, e1);
+      B.release();
+    }
+  }
+
+  // ---- 5. survivors, the per-read selection, and the new list
+  uint32_t *flags = nullptr, *excl = nullptr, *stmp = nullptr, *best = nullptr;
+  HIPCHK(c, B.alloc(&flags, N * 4));
+  HIPCHK(c, B.alloc(&excl, N * 4));
+  HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(N) * 4));
+  if (apply_mmtol) {
+    HIPCHK(c, B.alloc(&best, c->nreads * 4));
+    HIPCHK(c, hipMemsetAsync(best, 0xFF, c->nreads * 4, c->stream));
+  }
+  hipLaunchKernelGGL(k_mm_survive, grid(N), B256, 0, c->stream, hits, N, words, W, sizes, apply_mmtol ? 1 : 0, flags, best);
+  HIPCHK(c, hipGetLastError());
+  if (apply_mmtol) {
+    hipLaunchKernelGGL(k_mm_best, grid(N), B256, 0, c->stream, hits, N, best, (uint32_t)P.mmtol, flags);
+    HIPCHK(c, hipGetLastError());
+  }
+  if ((rc = scan_u32(c, flags, excl, N, false, stmp))) return rc;
+  HIPCHK(c, hipMemcpyAsync(h32, excl + (N - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h32 + 1, flags + (N - 1), 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint64_t m = (uint64_t)h32[0] + h32[1];
+  uint4* out = nullptr;
+  HIPCHK(c, B.alloc(&out, m * 16));
+  hipLaunchKernelGGL(k_mm_compact, grid(N), B256, 0, c->stream, hits, N, flags, excl, out);
+  HIPCHK(c, hipGetLastError());
+  // from here on the list changes.  (The survivors go back into the pass's own buffer: a captured graph of the pass
+  // holds its address.)
+  if (m) HIPCHK(c, hipMemcpyAsync(c->hits.p, out, m * 16, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->nhits = m;
+  c->stats.n_hits = m;
+  c->mm_list = false;            // the list is no longer that of a pass: a second call needs a new pass
+  c->side_after_match = true;    // (an order taken before is not this list's)
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int musc_maxmatches_apply(musc_ctx* c, int apply_mmtol, uint64_t* nhits, uint64_t* n_suspect_probes, uint64_t* n_truncated_blocks) {
+  if (!c) return 1;
+  uint64_t ns = 0, nt = 0;
+  if (nhits) *nhits = 0;
+  if (n_suspect_probes) *n_suspect_probes = 0;
+  if (n_truncated_blocks) *n_truncated_blocks = 0;
+  if (!c->hits_current || !c->mm_list)
+    return fail(c, 2, "musc_maxmatches_apply: the resident tuple list is not that of a musc_match* over the reads and the database in hand");
+  const musc_params P = c->mm_params;
+  if (P.apply_mmtol != 0) return fail(c, 2, "musc_maxmatches_apply: the last pass ran with apply_mmtol = 1: its list lacks the tuples the replay needs");
+  if (P.n_shards > 1) return fail(c, 2, "musc_maxmatches_apply: the last pass saw one shard of the reads (n_shards = %d)", P.n_shards);
+  if (c->stats.n_overflow_blocks == ~0ull) return fail(c, 2, "musc_maxmatches_apply: the last pass skipped the MaxMatches check");
+  if (const char* why = musc_mm::refusal(musc_mm::Shape{c->max_len, P.window_width, P.max_matches, c->nhits}))
+    return fail(c, 12, "musc_maxmatches_apply: %s", why);
+  HIPCHK(c, hipSetDevice(c->device));
+  float ms = 0;
+  c->mm_ms_replay = 0;
+  c->mm_pairs = 0;
+  const int rc = timed(c, &ms, [&]() -> int { return mm_apply_impl(c, P, apply_mmtol, &ns, &nt); });
+  if (rc) return rc;
+  c->mm_ms = ms;
+  if (nhits) *nhits = c->nhits;
+  if (n_suspect_probes) *n_suspect_probes = ns;
+  if (n_truncated_blocks) *n_truncated_blocks = nt;
+  return 0;
+}
+
+int musc_maxmatches_last_ms(musc_ctx* c, float* ms) {
+  if (!c || !ms) return 1;
+  *ms = c->mm_ms;
+  return 0;
+}
+
+int musc_maxmatches_last_detail(musc_ctx* c, uint64_t* n_pairs, float* ms_replay) {
+  if (!c) return 1;
+  if (n_pairs) *n_pairs = c->mm_pairs;
+  if (ms_replay) *ms_replay = c->mm_ms_replay;
+  return 0;
+}
+
+}  // extern "C"

@@ -827,5 +827,7 @@ extern "C" int musc_match_device(musc_ctx* c, const musc_params* P, uint64_t* nh
   const int rc = match_device_impl(c, P, nhits);
   if (rc != 0 && c->up.active && c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);
   c->hits_current = rc == 0;
+  c->mm_list = rc == 0;  // musc_maxmatches_apply: the list and the parameters it replays
+  if (rc == 0) c->mm_params = *P;
   return rc;
 }
