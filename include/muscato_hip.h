@@ -176,7 +176,11 @@ void musc_destroy(musc_ctx* ctx);
 const char* musc_last_error(musc_ctx* ctx); /* ctx may be NULL: error of a failed musc_init */
 /* The MUSC_* environment knobs (tests, A/B runs: MUSC_INDEX, MUSC_MATCH, MUSC_GRAPH ...) are read once, by
  * musc_init; a pass never calls getenv.  This re-reads them for a live context (a test hook; the next pass sizes
- * its buffers again).  The reference has no counterpart: its knobs are the Config fields. */
+ * its buffers again).  The reference has no counterpart: its knobs are the Config fields.
+ * The rule: every MUSC_* knob is latched when the context is made.  Setting or clearing one in the environment of a
+ * live context changes nothing until musc_reload_env, which latches all of them again -- except MUSC_BATCH_READS,
+ * which keeps its value of musc_init (a streamed load in flight was planned with it), and MUSC_RCCL_LIB, which is
+ * read once per process.  musc_reload_env also lets a MUSC_GRAPH whose capture failed once be tried again. */
 int musc_reload_env(musc_ctx* ctx);
 
 /* ---- target database: replaces muscato_screen's scan of GeneFileName
@@ -234,7 +238,10 @@ int musc_db_partitions(musc_ctx* ctx, uint32_t* first_target, uint32_t cap, uint
 /* ---- reads: replaces reading reads_sorted.txt.sz (cmd/muscato_screen/main.go:120-191,
  * cmd/muscato_window_reads/main.go:94-141).  Reads must already be prepared as the
  * reference does (non-ACGT -> X, truncated to MaxReadLength, de-duplicated); read_idx in the
- * hits is the index into this array. --------------------------------------------------- */
+ * hits is the index into this array.
+ * One rule for every loader below (and the two read-prep calls): a load replaces the reads in hand, and after a load
+ * that failed, at whatever point, the context holds no reads: musc_match* answers 4, "no reads loaded", until a load
+ * succeeds. --------------------------------------------------------------------------- */
 int musc_reads_load_ascii(musc_ctx* ctx, const char* seqs, const uint64_t* offsets,
                           uint64_t nreads, int on_device);
 int musc_reads_load_packed(musc_ctx* ctx, const uint8_t* bases2bit, const uint8_t* nmask,

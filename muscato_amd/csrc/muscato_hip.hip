@@ -36,6 +36,8 @@
 
 #include "../../include/muscato_hip.h"
 
+#include "ctx_state.hpp"
+#include "dev_mem.hpp"
 #include "index_plan.hpp"
 
 #include "kernels_common.hpp"
@@ -67,10 +69,18 @@ namespace {
 
 thread_local std::string g_init_error;  // musc_init may run on one host thread per GPU
 
+// a work buffer of the passes: grown by half when it is too small (ensure), freed with its owner
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   uint64_t cap = 0;  // elements
+  DevBuf() = default;  // (move-only: the moves delete the copies)
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) release(), p = std::exchange(o.p, nullptr), cap = std::exchange(o.cap, 0);
+    return *this;
+  }
+  ~DevBuf() { release(); }
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
@@ -78,24 +88,6 @@ struct DevBuf {
   }
 };
 
-// A table of the index: grown to what a build asks for and never shrunk (hipMalloc / hipFree of tens of GiB take
-// seconds), at exact sizes (DevBuf's growth by half is wrong for a 64 GiB table)
-struct DevTable {
-  void* p = nullptr;
-  uint64_t bytes = 0;
-  hipError_t grow(uint64_t n) {
-    if (p && bytes >= n) return hipSuccess;
-    release();
-    const hipError_t e = hipMalloc(&p, n);
-    if (e == hipSuccess) bytes = n; else p = nullptr;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-};
 
 // roctx ranges around the kernel families (the reference's tracing hook is the
 // CPUProfile flag, cmd/muscato_screen/main.go:530-538): visible in `rocprofv3 --marker-trace`.
@@ -264,29 +256,25 @@ struct musc_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   EnvKnobs env;
+  // what is still valid (ctx_state.hpp); the caches of a pass below carry st.g.pass_inputs (in a PassKey, or as `gen`)
+  musc_state::State st;
 
   // database
-  uint32_t* db2 = nullptr;
-  uint32_t* dbm2 = nullptr;  // null when the database holds no X (or an all-zero plane made for reads that do)
+  DevPtr<uint32_t> db2;
+  DevPtr<uint32_t> dbm2;     // null when the database holds no X (or an all-zero plane made for reads that do)
   bool db_has_x = false;     // the database holds an X
   bool reads_have_x = false; // some loaded read holds an X
   // reads with X on context buckets (k_match_t<.., XM = 1 | 2>): where each read's X are (k_read_xpos), and
   // whether the reads in hand fit that form under a given mismatch budget (k_xpos_check), cached
   DevBuf<uint32_t> rdx;
-  uint64_t rdx_epoch = ~0ull;
-  int rdx_wide = -1;  // the format of rdx: XPos<false> or XPos<true>
-  uint64_t xok_epoch = ~0ull;
-  double xok_pmatch = -1.0;
-  int32_t xok_mmp1 = -1;
-  bool xok = false;
-  uint32_t* dbx = nullptr;   // with dbm2: one bit per 64-base block that holds an X
+  struct { uint64_t gen = 0; int wide = -1; } rdx_of;  // wide: the format of rdx, XPos<false> or XPos<true>
+  struct { uint64_t gen = 0; double pmatch = -1.0; int32_t mmp1 = -1; bool ok = false; } xok;
+  DevPtr<uint32_t> dbx;      // with dbm2: one bit per 64-base block that holds an X
   uint64_t max_tlen = 0;     // longest target (context buckets flag an entry in bit 31 of its position)
   // a database with X on context buckets (k_match_t<.., XM = 2>): whether the reads in hand keep their X
   // out of the run's windows and within their xpos words (k_xpos_check_db), cached per read set and windows
-  uint64_t xokdb_epoch = ~0ull;
-  int32_t xokdb_key[CTX_MAX_W + 3] = {0};
-  bool xokdb = false;
-  uint64_t* seq_off = nullptr;
+  struct { uint64_t gen = 0; int32_t key[CTX_MAX_W + 3] = {0}; bool ok = false; } xokdb;
+  DevPtr<uint64_t> seq_off;
   uint32_t nseq = 0;
   uint64_t nbases = 0;
   uint64_t db_words = 0;
@@ -311,34 +299,34 @@ struct musc_ctx {
   int wide = 0;  // database >= 2^32 bases: 40-bit positions, gene numbers < 2^24
   // only one kind is resident at a time: the window-start index (2^bits + 1 Bucket or LineBucket, uint4 overflow
   // entries) or context buckets (CtxBucket, CtxEntry / CtxEntryW: kernels_match.hpp)
-  DevTable idx_T, idx_E, ctx_T, ctx_E;
+  DevMem idx_T, idx_E, ctx_T, ctx_E;  // (DevMem::grow: exact sizes -- DevBuf's growth by half is wrong for a 64 GiB table)
   unsigned scrt_resident = 0;  // k_screen_t: waves resident at once (queried once per record stride)
   int scrt_rw = 0;
   uint64_t idx_novf = 0;    // overflow entries of the index in hand
-  PathParams* d_pp = nullptr;   // k_screen / k_confirm / k_hot_probes: the run's parameters
+  DevPtr<PathParams> d_pp;      // k_screen / k_confirm / k_hot_probes: the run's parameters
   PathParams h_pp;              // what d_pp holds
   bool h_pp_valid = false;
-  MatchParams* d_mp = nullptr;  // k_match's parameter block
+  DevPtr<MatchParams> d_mp;     // k_match's parameter block
   MatchParams h_mp;             // what d_mp holds
   bool h_mp_valid = false;
   int spec_geom = 0;            // the geometry-specialised k_match_t instance this pass launches (SpecGeom<n>), 0 = the general one
   DevBuf<uint4> spill;          // k_match: reported candidates beyond a tile's LDS list
 
-  // reads
-  uint32_t* rd = nullptr;
+  // reads: nreads, rw and max_len are committed together, with the records allocated (reads_records)
+  DevPtr<uint32_t> rd;
   uint64_t rd_cap = 0;      // bytes of rd when a fixed-length load made it (kept from load to load), 0: sized for the reads in hand
-  uint32_t* rdm = nullptr;  // null when no read holds an X
+  DevPtr<uint32_t> rdm;     // null when no read holds an X
   uint64_t nreads = 0;
   int rw = 0;
   uint32_t max_len = 0;
+  bool reads_failed = false;  // the last load failed: no pass until one succeeds
 
   // musc_reads_load_packed32(async): reads of one length on their way from the host -- the 2-bit
   // stream goes to `stage` in pieces on the copy stream s_up, an event per piece; a pass packs the
   // records of a batch (k_pack_reads_fixed) when the batch's pieces have arrived.  stream_plan decides
   // the pieces and the batches of the pass that consumes them.
   struct Upload {
-    uint32_t* stage = nullptr;
-    uint64_t stage_words = 0;
+    DevPtr<uint32_t> stage;            // (grown when a load needs more, never shrunk)
     hipStream_t s_up = nullptr;
     std::vector<hipEvent_t> ev;
     StreamPlan plan;                   // piece ends and batch ends of this upload, in reads
@@ -367,46 +355,40 @@ struct musc_ctx {
   bool force_exact_blocks = false;
   // the MaxMatches screening of these reads, database and parameters was inconclusive once: later passes over the same
   // combination start with the exact per-block counters instead of screening, failing and repeating
-  uint64_t exact_epoch = 0;
-  musc_params exact_params;
+  struct { musc_state::PassKey key; } exact;
   PathParams last_pp;          // of the last musc_match_device
   uint32_t last_max_matches = 0;
   uint32_t last_inst[MUSC_INSTANCE_WORDS] = {0, 0, 0, 0};  // musc_last_instance: what the resolvers of the last pass returned
   bool last_exact_blocks = false;  // block_table holds exact counters of that pass
-  unsigned long long* counters = nullptr;  // CNT_WORDS u64: the pass block and the batch block (kernels_common.hpp)
-  uint64_t* h_pinned = nullptr;            // their pinned mirror (and 16 x u64 of staging for whoever reads a scalar back)
+  DevPtr<unsigned long long> counters;     // CNT_WORDS u64: the pass block and the batch block (kernels_common.hpp)
+  PinnedPtr<uint64_t> h_pinned;            // their pinned mirror (and 16 x u64 of staging for whoever reads a scalar back)
 
   DevBuf<musc_hit> hits;
   uint64_t nhits = 0;
   DevBuf<uint64_t> packed;      // staging of musc_hits_copy_packed / musc_hits_unpack for host pointers
   std::vector<hipEvent_t> dl_ev;  // download_chunks: one event per chunk
   DevBuf<musc_hit> gathered;    // musc_gather_rccl: every context's tuples on this device
-  uint32_t* d_flag = nullptr;   // one device word for kernels that report "does not fit"
+  DevPtr<uint32_t> d_flag;      // one device word for kernels that report "does not fit"
 
   // results.txt on the device: the texts the lines quote, and the ordered list of the last
-  // musc_results_order with its line offsets
-  char* res_gtext = nullptr;        // every gene's name\tlen (musc_results_set_gene_text); released with the database
-  uint64_t* res_goff = nullptr;     // nseq + 1 byte offsets into it
-  uint32_t* res_rank = nullptr;     // per gene: rank of its text among all genes' texts, RES_ABSENT without an id line
-  char* res_ttext = nullptr;        // every read's count\tnames (musc_results_set_read_text); released with the reads
-  uint64_t* res_toff = nullptr;     // nreads + 1 byte offsets into it
+  // musc_results_order with its line offsets (valid: st.ordered_current())
+  DevPtr<char> res_gtext;           // every gene's name\tlen (musc_results_set_gene_text); released with the database
+  DevPtr<uint64_t> res_goff;        // nseq + 1 byte offsets into it
+  DevPtr<uint32_t> res_rank;        // per gene: rank of its text among all genes' texts, RES_ABSENT without an id line
+  DevPtr<char> res_ttext;           // every read's count\tnames (musc_results_set_read_text); released with the reads
+  DevPtr<uint64_t> res_toff;        // nreads + 1 byte offsets into it
   DevBuf<musc_hit> res_hits;        // the ordered tuples
   DevBuf<uint64_t> res_off;         // res_n + 1 line offsets
   DevBuf<unsigned char> res_stage;  // musc_results_text: the bytes on their way to a host buffer
   uint64_t res_n = 0, res_bytes = 0;
-  bool res_valid = false;           // res_hits / res_off describe the reads, database and texts in hand
-  bool hits_current = false;        // `hits` is the list of a pass over the reads and the database in hand
   float res_ms_order = 0, res_ms_text = 0;
 
-  // the side outputs on the device: what musc_side_prepare leaves for musc_side_text
-  uint32_t* side_nrank = nullptr;   // per gene: rank of its name among all names, RES_ABSENT without an id line
-  uint2* side_names = nullptr;      // per name rank: a gene with that name, the name's bytes
+  // the side outputs on the device: what musc_side_prepare leaves for musc_side_text (valid: st.may_side_text())
+  DevPtr<uint32_t> side_nrank;      // per gene: rank of its name among all names, RES_ABSENT without an id line
+  DevPtr<uint2> side_names;         // per name rank: a gene with that name, the name's bytes
   uint32_t side_nnames = 0;
   bool side_form_ok = false;        // every present gene's text is name\tlen in the simple form
   uint32_t side_bad_gene = 0;       // the first gene whose text is not
-  bool side_after_match = false;    // a pass ran since the last musc_results_order: its list is not that order's
-  bool side_tok_valid = false;      // side_tok describes the read text in hand
-  bool side_valid = false;          // the tables below describe the last musc_results_order
   DevBuf<uint4> side_tok;           // per read: count span and token span of its tail
   DevBuf<uint32_t> side_cnt;        // per name rank: kept tuples
   DevBuf<uint32_t> side_idx[2];     // nonmatch: the reads of the records; genestats: the name ranks of the lines
@@ -418,36 +400,31 @@ struct musc_ctx {
   float side_ms_prepare = 0, side_ms_text = 0;
 
   // the MaxMatches replay on the device
-  musc_params mm_params;            // of the last musc_match* that succeeded
-  bool mm_list = false;             // `hits` is that pass's list as the pass left it (musc_maxmatches_apply replaces it)
+  musc_params mm_params;            // of the last musc_match* that succeeded (its list may be replayed: st.may_replay())
   float mm_ms = 0, mm_ms_replay = 0;  // event time of the last musc_maxmatches_apply; of its k_mm_replay
   uint64_t mm_pairs = 0;            // pairs in the blocks which that call truncated
 
   uint32_t batch_reads = 16u << 20;
   // A pass over the same reads, database and parameters as the last completed one needs no
   // sizing: its buffers are known to suffice, so it runs without host round trips.
-  uint64_t data_epoch = 1;       // bumped whenever reads or database change
-  uint64_t sized_epoch = 0;      // data_epoch of the last completed pass
-  musc_params sized_params;      // its parameters
-  bool sized_exact_blocks = false;
-  uint32_t sized_bsz = 0;        // reads per batch it ended up with
+  struct { musc_state::PassKey key; uint32_t bsz = 0; } sized;  // of the last completed pass (block_mode: 2 or 0); its reads per batch
   musc_stats stats;
   // MUSC_GRAPH=1: the sized pass on context buckets as a hipGraph (one launch instead of seven per
   // batch; no per-kernel timing in that mode)
-  hipGraphExec_t graph_exec = nullptr;
-  bool graph_failed = false;  // capture or instantiation failed once: sized passes run launch by launch
-  uint64_t graph_epoch = 0;
-  musc_params graph_params;
-  int graph_block_mode = -1;
-  uint32_t graph_batches = 0;
+  struct {
+    hipGraphExec_t exec = nullptr;
+    musc_state::PassKey key;
+    uint32_t batches = 0;
+    bool failed = false;  // capture or instantiation failed once: sized passes run launch by launch
+    void drop() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; }
+  } graph;
   // timing events are created once and reused by every pass (creating and destroying a pair per
   // kernel family per batch cost more than the kernels of a small pass)
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
   // the mismatch-budget table on the device is valid for these inputs
-  double nm_pmatch = -1.0;
-  int32_t nm_mmp1 = -1;
-  uint32_t nm_maxlen = 0xFFFFFFFFu;
+  struct { double pmatch = -1.0; int32_t mmp1 = -1; uint32_t maxlen = 0xFFFFFFFFu; } nm;
+  musc_state::PassKey pass_key(const musc_params& P, int block_mode) const { return musc_state::PassKey{st.g.pass_inputs, P, block_mode}; }
 };
 
 namespace {
@@ -552,51 +529,27 @@ void free_index(musc_ctx* c);  // muscato_index.hpp
 
 // the gene text of the results stage belongs to a database, the read text to a read set
 void drop_gene_text(musc_ctx* c) {
-  if (c->res_gtext) (void)hipFree(c->res_gtext);
-  if (c->res_goff) (void)hipFree(c->res_goff);
-  if (c->res_rank) (void)hipFree(c->res_rank);
-  if (c->side_nrank) (void)hipFree(c->side_nrank);
-  if (c->side_names) (void)hipFree(c->side_names);
-  c->side_nrank = nullptr;
-  c->side_names = nullptr;
+  for (DevMem* m : std::initializer_list<DevMem*>{&c->res_gtext, &c->res_goff, &c->res_rank, &c->side_nrank, &c->side_names}) m->release();
   c->side_nnames = 0;
   c->side_form_ok = false;
-  c->side_valid = false;
-  c->res_gtext = nullptr;
-  c->res_goff = nullptr;
-  c->res_rank = nullptr;
-  c->res_valid = false;
-  c->hits_current = false;  // (called when the database goes)
+  c->st.gene_text_dropped();
 }
 void drop_read_text(musc_ctx* c) {
-  if (c->res_ttext) (void)hipFree(c->res_ttext);
-  if (c->res_toff) (void)hipFree(c->res_toff);
-  c->res_ttext = nullptr;
-  c->res_toff = nullptr;
-  c->res_valid = false;
-  c->side_tok_valid = false;
-  c->side_valid = false;
-}
-void forget_read_text(musc_ctx* c) {  // the reads go: so do their text and the standing of the resident tuple list
-  drop_read_text(c);
-  c->hits_current = false;
+  c->res_ttext.release();
+  c->res_toff.release();
+  c->st.read_text_dropped();
 }
 
 void free_db(musc_ctx* c) {
   free_index(c);
   drop_gene_text(c);
-  if (c->db2) (void)hipFree(c->db2);
-  if (c->dbm2) (void)hipFree(c->dbm2);
-  if (c->dbx) (void)hipFree(c->dbx);
-  if (c->seq_off) (void)hipFree(c->seq_off);
-  c->db2 = c->dbm2 = c->dbx = nullptr;
+  for (DevMem* m : std::initializer_list<DevMem*>{&c->db2, &c->dbm2, &c->dbx, &c->seq_off}) m->release();
   c->db_has_x = false;
-  c->seq_off = nullptr;
   c->nseq = 0;
   c->nbases = 0;
   c->h_seq_off.clear();
   c->part_first.clear();
-  c->data_epoch++;
+  c->st.db_freed();
 }
 
 // Forget the reads in hand.  keep_rd: the record buffer stays allocated for the fixed-length load that follows
@@ -607,20 +560,30 @@ void drop_reads(musc_ctx* c, bool keep_rd) {
     (void)hipStreamSynchronize(c->up.s_up);
     c->up.active = false;
   }
-  if (c->rd && !(keep_rd && c->rd_cap)) {
-    (void)hipFree(c->rd);
-    c->rd = nullptr;
+  if (!(keep_rd && c->rd_cap)) {
+    c->rd.release();
     c->rd_cap = 0;
   }
-  if (c->rdm) (void)hipFree(c->rdm);
-  c->rdm = nullptr;
-  forget_read_text(c);
+  c->rdm.release();
+  drop_read_text(c);
   c->reads_have_x = false;
+  c->reads_failed = false;
   c->nreads = 0;
   c->rw = 0;
-  c->data_epoch++;
+  c->st.reads_dropped();
 }
 void free_reads(musc_ctx* c) { drop_reads(c, false); }
+
+// The one rule for a load that failed, wherever it failed: nothing of it stays, and musc_match* answers 4, "no reads
+// loaded", until a load succeeds.  (The message of the failure stays the context's last error.)
+int reads_load_done(musc_ctx* c, int rc) {
+  if (rc) {
+    if (c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);  // (pieces of a fixed-length load may still be on their way)
+    free_reads(c);
+    c->reads_failed = true;
+  }
+  return rc;
+}
 
 struct EvPair {
   hipEvent_t a, b;
@@ -715,11 +678,11 @@ int musc_init(int device_ordinal, musc_ctx** out) {
       (e = hipEventCreateWithFlags(&c->ev_free[0], hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&c->ev_free[1], hipEventDisableTiming)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess ||
-      (e = hipMalloc((void**)&c->counters, CNT_WORDS * sizeof(unsigned long long))) != hipSuccess ||
-      (e = hipMalloc((void**)&c->d_flag, 4)) != hipSuccess ||
-      (e = hipMalloc((void**)&c->d_mp, sizeof(MatchParams))) != hipSuccess ||
-      (e = hipMalloc((void**)&c->d_pp, sizeof(PathParams))) != hipSuccess ||
-      (e = hipHostMalloc((void**)&c->h_pinned, CNT_WORDS * sizeof(uint64_t))) != hipSuccess) {
+      (e = c->counters.alloc(CNT_WORDS * sizeof(unsigned long long))) != hipSuccess ||
+      (e = c->d_flag.alloc(4)) != hipSuccess ||
+      (e = c->d_mp.alloc(sizeof(MatchParams))) != hipSuccess ||
+      (e = c->d_pp.alloc(sizeof(PathParams))) != hipSuccess ||
+      (e = c->h_pinned.alloc(CNT_WORDS * sizeof(uint64_t))) != hipSuccess) {
     fail(nullptr, 3, "musc_init: %s", hipGetErrorString(e));
     musc_destroy(c);
     return 3;
@@ -731,57 +694,30 @@ int musc_init(int device_ordinal, musc_ctx** out) {
 }
 
 // Re-read the MUSC_* knobs (musc_init reads them once; MUSC_BATCH_READS stays as it was read then).  A test hook:
-// a knob that changes which index or kernel a pass takes makes the next pass size itself again.
+// a knob that changes which index or kernel a pass takes makes the next pass size itself again, and a MUSC_GRAPH
+// whose capture failed once is tried again.
 int musc_reload_env(musc_ctx* c) {
   if (!c) return 1;
   c->env.read();
-  c->sized_epoch = 0;
+  c->sized.key = musc_state::PassKey();
+  c->graph.failed = false;
   return 0;
 }
 
 void musc_destroy(musc_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-  free_db(c);
-  free_reads(c);
-  for (DevTable* t : {&c->idx_T, &c->idx_E, &c->ctx_T, &c->ctx_E}) t->release();
-  if (c->d_mp) (void)hipFree(c->d_mp);
-  if (c->d_pp) (void)hipFree(c->d_pp);
-  c->spill.release();
-  for (int i = 0; i < 2; i++) {
-    c->bs[i].wb.release(); c->bs[i].tbase.release(); c->bs[i].rvalid.release(); c->bs[i].tcount.release();
-    c->bs[i].cdesc.release();
-  }
-  c->scan_tmp.release(); c->tcount2.release(); c->tpre.release(); c->stage.release(); c->rdx.release();
-  c->p_nx.release();
-  c->nmiss_tab.release();
-  c->block_table.release();
-  c->pacc.release(); c->pbest.release(); c->pcnt.release(); c->padj.release(); c->pflags.release(); c->pflags_tmp.release();
-  c->block_acc.release();
-  c->hits.release();
-  c->packed.release();
-  c->gathered.release();
-  c->res_hits.release(); c->res_off.release(); c->res_stage.release();
-  c->side_tok.release(); c->side_cnt.release(); c->side_el.release(); c->side_eloff.release();
-  c->side_first.release(); c->side_runread.release();
-  for (auto& b : c->side_idx) b.release();
-  for (auto& b : c->side_off) b.release();
-  if (c->d_flag) (void)hipFree(c->d_flag);
-  if (c->counters) (void)hipFree(c->counters);
-  if (c->h_pinned) (void)hipHostFree(c->h_pinned);
+  for (hipStream_t s : {c->stream, c->stream2})
+    if (s) (void)hipStreamSynchronize(s);
+  if (c->up.active && c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);  // (an upload nobody matched)
+  c->graph.drop();
   for (hipEvent_t ev : {c->ev_ready[0], c->ev_ready[1], c->ev_free[0], c->ev_free[1], c->ev_join})
     if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
-  if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
-  for (hipEvent_t ev : c->up.ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : c->dl_ev) (void)hipEventDestroy(ev);
-  if (c->up.stage) (void)hipFree(c->up.stage);
-  if (c->up.s_up) (void)hipStreamDestroy(c->up.s_up);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  for (const std::vector<hipEvent_t>* v : {&c->ev_pool, &c->up.ev, &c->dl_ev})
+    for (hipEvent_t ev : *v) (void)hipEventDestroy(ev);
+  for (hipStream_t s : {c->up.s_up, c->stream2, c->stream})
+    if (s) (void)hipStreamDestroy(s);
+  delete c;  // (every buffer goes with its owner)
 }
 
 // ---------------------------------------------------------------- database
@@ -790,9 +726,7 @@ void musc_destroy(musc_ctx* c) {
 static int db_xblocks(musc_ctx* c) {
   const uint64_t nblk64 = (c->db_words + 64 + 3) / 4;
   const uint64_t nw = nblk64 / 32 + 4;
-  if (c->dbx) (void)hipFree(c->dbx);
-  c->dbx = nullptr;
-  HIPCHK(c, hipMalloc((void**)&c->dbx, nw * 4));
+  HIPCHK(c, c->dbx.alloc(nw * 4));
   HIPCHK(c, hipMemsetAsync(c->dbx, 0, nw * 4, c->stream));
   hipLaunchKernelGGL(k_db_xblocks, dim3(nblk(nblk64, 256)), dim3(256), 0, c->stream, c->dbm2, c->db_words, c->dbx);
   HIPCHK(c, hipGetLastError());
@@ -813,8 +747,7 @@ static int db_finish(musc_ctx* c) {
   c->max_tlen = tl;
   c->db_has_x = hasx != 0;
   if (!hasx) {
-    (void)hipFree(c->dbm2);
-    c->dbm2 = nullptr;
+    c->dbm2.release();
     return 0;
   }
   return db_xblocks(c);
@@ -856,11 +789,11 @@ static int db_alloc(musc_ctx* c, const uint64_t* offsets, uint32_t nseq, int on_
   // record's last base word -- the record's own length word, then the next record or the 256 spare bytes behind rd
   // and rdm).  The results and side kernels take c->rw only to find a record and its length word.
   const uint64_t alloc_words = c->db_words + 64;
-  HIPCHK(c, hipMalloc((void**)&c->db2, alloc_words * 4));
-  HIPCHK(c, hipMalloc((void**)&c->dbm2, alloc_words * 4));
+  HIPCHK(c, c->db2.alloc(alloc_words * 4));
+  HIPCHK(c, c->dbm2.alloc(alloc_words * 4));
   HIPCHK(c, hipMemsetAsync(c->db2, 0, alloc_words * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(c->dbm2, 0, alloc_words * 4, c->stream));
-  HIPCHK(c, hipMalloc((void**)&c->seq_off, ((uint64_t)nseq + 1) * 8));
+  HIPCHK(c, c->seq_off.alloc(((uint64_t)nseq + 1) * 8));
   HIPCHK(c, hipMemcpyAsync(c->seq_off, offsets, ((uint64_t)nseq + 1) * 8,
                            on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));  // raised by the packing kernel when it meets an X
@@ -943,12 +876,53 @@ static int upload_prepare(musc_ctx* c, uint64_t r0, uint64_t n, hipStream_t st) 
   return 0;
 }
 
+// The read records, built in one way by every loader (reads_load, reads_load_fixed, reads_sort_unique_dev): a record is
+// rw words -- the 2-bit bases of the longest read, then the length word, rounded up to four words -- and both planes
+// end in 256 zeroed bytes (what reads past a plane's end: db_alloc).  reads_shape: rw and the words of all records, or
+// one of the three refusals (fixed: the wording of the fixed-length loader, which knows no single read to blame).
+struct RecShape { int rw = 4; uint64_t words = 0; };
+static int reads_shape(musc_ctx* c, uint64_t nreads, uint64_t maxlen, bool fixed, RecShape* s) {
+  if (nreads >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read_idx");
+  if (maxlen > 65535)
+    return fixed ? fail(c, 2, "read length exceeds the 65535-base record limit")
+                 : fail(c, 2, "read of %llu bases exceeds the 65535-base record limit", (unsigned long long)maxlen);
+  s->rw = std::max(((int)((2 * maxlen + 31) / 32) + 1 + 3) & ~3, 4);
+  s->words = nreads * (uint64_t)s->rw;
+  if (s->words >= (1ull << 32)) return fail(c, 2, "too many read words for one dispatch (reads x record words >= 2^32)");
+  return 0;
+}
+// The planes of that shape: rd -- keep: the buffer of the last fixed-length load where it is large enough, and the new
+// one is kept in turn -- and, with mask, rdm.  nreads, rw and max_len are committed here, together, once the planes exist.
+static int reads_records(musc_ctx* c, const RecShape& s, uint64_t nreads, uint64_t maxlen, bool mask, bool keep) {
+  const uint64_t bytes = s.words * 4 + 256;
+  if (!keep || c->rd_cap < bytes) {
+    c->rd_cap = 0;
+    HIPCHK(c, c->rd.alloc(bytes));
+    if (keep) c->rd_cap = bytes;
+  }
+  HIPCHK(c, hipMemsetAsync(c->rd + s.words, 0, 256, c->stream));
+  if (mask) {
+    HIPCHK(c, c->rdm.alloc(bytes));
+    HIPCHK(c, hipMemsetAsync(c->rdm + s.words, 0, 256, c->stream));
+  }
+  c->nreads = nreads;
+  c->rw = s.rw;
+  c->max_len = (uint32_t)maxlen;
+  return 0;
+}
+// what the pack kernel left in d_flag says whether a read holds an X; a mask plane nobody needs goes
+static void reads_settle_x(musc_ctx* c, uint32_t hasx) {
+  c->reads_have_x = hasx != 0;
+  if (!hasx) c->rdm.release();
+}
+
 static int reads_load(musc_ctx* c, const unsigned char* ascii, const uint8_t* bases2bit, const uint8_t* nmask,
                       const uint64_t* offsets, uint64_t nreads, int on_device, bool packed) {
   HIPCHK(c, hipSetDevice(c->device));
   free_reads(c);
-  if (nreads >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read_idx");
-  c->nreads = nreads;
+  RecShape shape;
+  int rc = reads_shape(c, nreads, 0, false, &shape);  // (the read count alone, before anything is uploaded)
+  if (rc) return rc;
   if (nreads == 0) {
     c->rw = 4;
     return 0;
@@ -971,22 +945,10 @@ static int reads_load(musc_ctx* c, const unsigned char* ascii, const uint8_t* ba
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const uint64_t maxlen = c->h_pinned[0];
   if (first != 0) return fail(c, 2, "read offsets[0] must be 0");
-  if (maxlen > 65535) return fail(c, 2, "read of %llu bases exceeds the 65535-base record limit", (unsigned long long)maxlen);
-  c->max_len = (uint32_t)maxlen;
-  int rw = (int)((2 * maxlen + 31) / 32) + 1;
-  rw = (rw + 3) & ~3;
-  if (rw < 4) rw = 4;
-  c->rw = rw;
-  const uint64_t words = nreads * (uint64_t)rw;
-  if (words >= (1ull << 32)) return fail(c, 2, "too many read words for one dispatch (reads x record words >= 2^32)");
-  HIPCHK(c, hipMalloc((void**)&c->rd, words * 4 + 256));
-  HIPCHK(c, hipMemsetAsync(c->rd + words, 0, 256, c->stream));
   // the mask plane only where an X can turn up: ASCII input, or packed input that comes with a mask
-  const bool may_have_x = !packed || nmask != nullptr;
-  if (may_have_x) {
-    HIPCHK(c, hipMalloc((void**)&c->rdm, words * 4 + 256));
-    HIPCHK(c, hipMemsetAsync(c->rdm + words, 0, 256, c->stream));
-  }
+  if ((rc = reads_shape(c, nreads, maxlen, false, &shape)) || (rc = reads_records(c, shape, nreads, maxlen, !packed || nmask != nullptr, false)))
+    return rc;
+  const auto [rw, words] = shape;
   uint32_t* d_hasx = c->d_flag;
   HIPCHK(c, hipMemsetAsync(d_hasx, 0, 4, c->stream));
   unsigned char *t1 = nullptr, *t2 = nullptr;
@@ -1017,11 +979,7 @@ static int reads_load(musc_ctx* c, const unsigned char* ascii, const uint8_t* ba
   uint32_t hasx = 0;
   HIPCHK(c, hipMemcpyAsync(&hasx, d_hasx, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->reads_have_x = hasx != 0;
-  if (!hasx && c->rdm) {
-    (void)hipFree(c->rdm);
-    c->rdm = nullptr;
-  }
+  reads_settle_x(c, hasx);
   return 0;
 }
 
@@ -1034,36 +992,17 @@ static int reads_load_fixed(musc_ctx* c, const uint8_t* bases2bit, uint32_t L, u
   // before anything else that takes time, and in the steady state (a read set that fits the buffers of the last one)
   // this call neither frees nor allocates.
   drop_reads(c, true);
-  int rw = (int)((2ull * L + 31) / 32) + 1;
-  rw = (rw + 3) & ~3;
-  if (rw < 4) rw = 4;
-  const uint64_t words = nreads * (uint64_t)rw;
-  const char* refuse = nreads >= 0xFFFFFFF0ull ? "too many reads for 32-bit read_idx"
-                       : L > 65535             ? "read length exceeds the 65535-base record limit"
-                       : words >= (1ull << 32) ? "too many read words for one dispatch (reads x record words >= 2^32)"
-                                               : nullptr;
-  if (refuse) {
-    free_reads(c);
-    return fail(c, 2, "%s", refuse);
-  }
-  c->nreads = nreads;
+  RecShape shape;
+  const int rc_shape = reads_shape(c, nreads, L, true, &shape);
+  if (rc_shape) return rc_shape;
   if (nreads == 0) {
     c->rw = 4;
     return 0;
   }
-  c->max_len = L;
-  c->rw = rw;
-  c->reads_have_x = false;
   musc_ctx::Upload& u = c->up;
   const uint64_t total_bytes = (nreads * (uint64_t)L + 3) / 4;
   const uint64_t need_words = (total_bytes + 3) / 4 + 4;  // (k_pack_reads_fixed reads up to two words past a read's last)
-  if (u.stage_words < need_words) {
-    if (u.stage) (void)hipFree(u.stage);
-    u.stage = nullptr;
-    u.stage_words = 0;
-    HIPCHK(c, hipMalloc((void**)&u.stage, need_words * 4));
-    u.stage_words = need_words;
-  }
+  HIPCHK(c, u.stage.grow(need_words * 4));
   if (!u.s_up) HIPCHK(c, hipStreamCreateWithFlags(&u.s_up, hipStreamNonBlocking));
   // the pieces: whole bytes of the stream and whole wave-tiles (64 | every end but the last), each batch of the pass
   // that consumes them a whole number of pieces -- a batch needs all of its pieces, and the next batch's pieces arrive
@@ -1082,35 +1021,26 @@ static int reads_load_fixed(musc_ctx* c, const uint8_t* bases2bit, uint32_t L, u
   for (size_t i = 0; i < ends.size(); i++) {
     const uint64_t b0 = (i ? ends[i - 1] : 0) * (uint64_t)L / 4;  // (64 | end: a whole number of bytes)
     const uint64_t b1 = std::min<uint64_t>((ends[i] * (uint64_t)L + 3) / 4, total_bytes);
-    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<uint8_t*>(u.stage) + b0, bases2bit + b0, b1 - b0, hipMemcpyHostToDevice, u.s_up));
+    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<uint8_t*>(u.stage.get()) + b0, bases2bit + b0, b1 - b0, hipMemcpyHostToDevice, u.s_up));
     HIPCHK(c, hipEventRecord(u.ev[i], u.s_up));
   }
   u.active = true;
   // the records (nothing reads them before the first piece has landed): the buffer of the last fixed-length load where
   // it is large enough, its zeroed 256-byte tail at its new place
-  if (c->rd_cap < words * 4 + 256) {
-    if (c->rd) (void)hipFree(c->rd);
-    c->rd = nullptr;
-    c->rd_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->rd, words * 4 + 256));
-    c->rd_cap = words * 4 + 256;
-  }
-  HIPCHK(c, hipMemsetAsync(c->rd + words, 0, 256, c->stream));
+  int rc = reads_records(c, shape, nreads, L, false, true);
+  if (rc) return rc;
+  reads_settle_x(c, 0);
   if (!async) {
-    int rc = upload_prepare(c, 0, nreads, c->stream);
-    if (rc) return rc;
+    if ((rc = upload_prepare(c, 0, nreads, c->stream))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return 0;
 }
 
-int musc_reads_load_packed32(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint32_t* lengths,
-                             uint32_t fixed_len, uint64_t nreads, int async) {
-  if (!c) return 1;
-  if (!bases2bit && nreads) return fail(c, 2, "musc_reads_load_packed32: NULL input");
-  if (!lengths && !nmask) return reads_load_fixed(c, bases2bit, fixed_len, nreads, async);
-  // lengths and / or a mask: offsets are made on the device (a scan of the lengths, or multiples of
-  // fixed_len) and the general loader takes over
+// lengths and / or a mask: offsets are made on the device (a scan of the lengths, or multiples of
+// fixed_len) and the general loader takes over
+static int reads_load_lengths(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint32_t* lengths,
+                              uint32_t fixed_len, uint64_t nreads) {
   HIPCHK(c, hipSetDevice(c->device));
   TmpBufs B;
   uint64_t *d_off = nullptr, *stmp = nullptr;
@@ -1131,17 +1061,25 @@ int musc_reads_load_packed32(musc_ctx* c, const uint8_t* bases2bit, const uint8_
   return reads_load(c, nullptr, bases2bit, nmask, d_off, nreads, 1, true);
 }
 
+int musc_reads_load_packed32(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint32_t* lengths,
+                             uint32_t fixed_len, uint64_t nreads, int async) {
+  if (!c) return 1;
+  if (!bases2bit && nreads) return fail(c, 2, "musc_reads_load_packed32: NULL input");
+  return reads_load_done(c, !lengths && !nmask ? reads_load_fixed(c, bases2bit, fixed_len, nreads, async)
+                                               : reads_load_lengths(c, bases2bit, nmask, lengths, fixed_len, nreads));
+}
+
 int musc_reads_load_ascii(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads, int on_device) {
   if (!c) return 1;
   if ((!seqs || !offsets) && nreads) return fail(c, 2, "musc_reads_load_ascii: NULL input");
-  return reads_load(c, (const unsigned char*)seqs, nullptr, nullptr, offsets, nreads, on_device, false);
+  return reads_load_done(c, reads_load(c, (const unsigned char*)seqs, nullptr, nullptr, offsets, nreads, on_device, false));
 }
 
 int musc_reads_load_packed(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint64_t* read_offsets,
                            uint64_t nreads) {
   if (!c) return 1;
   if ((!bases2bit || !read_offsets) && nreads) return fail(c, 2, "musc_reads_load_packed: NULL input");
-  return reads_load(c, nullptr, bases2bit, nmask, read_offsets, nreads, 0, true);
+  return reads_load_done(c, reads_load(c, nullptr, bases2bit, nmask, read_offsets, nreads, 0, true));
 }
 
 // ---------------------------------------------------------------- hot path
@@ -1294,12 +1232,7 @@ static int match_partitioned(musc_ctx* c, const musc_params* P, uint64_t* nhits)
   const int rc = match_partitions_run(c, P, nhits);
   c->force_exact_blocks = keep_force;
   (void)hipStreamSynchronize(c->stream);  // (an error path may leave merge kernels queued)
-  c->pacc.release();
-  c->pbest.release();
-  c->pcnt.release();
-  c->padj.release();
-  c->pflags.release();
-  c->pflags_tmp.release();
+  c->pacc.release(); c->pbest.release(); c->pcnt.release(); c->padj.release(); c->pflags.release(); c->pflags_tmp.release();
   c->block_acc.release();
   return rc;
 }
@@ -1411,7 +1344,7 @@ int musc_hits_copy_packed(musc_ctx* c, uint64_t* dst, uint64_t capacity, int dst
     hipLaunchKernelGGL(k_pack_hits, dim3(std::min(nblk(t1 - t0, 256), MAX_GRID)), dim3(256), 0, c->stream, hits + t0, t1 - t0,
                        read_base, b, out + t0, c->d_flag);
   };
-  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned);
+  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   if (dst_on_device) {
     pack(0, c->nhits);
     HIPCHK(c, hipGetLastError());
@@ -1456,7 +1389,7 @@ int musc_hits_copy_compact(musc_ctx* c, uint32_t* words, uint64_t words_cap, uin
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
   if (c->nreads) HIPCHK(c, hipMemsetAsync(dc, 0, c->nreads, c->stream));
   const uint4* const hits = reinterpret_cast<const uint4*>(c->hits.p);
-  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned);
+  uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   if (dst_on_device) {
     if (c->nhits) {
       hipLaunchKernelGGL(k_pack_compact, dim3(std::min(nblk(c->nhits, 256), MAX_GRID)), dim3(256), 0, c->stream, hits, c->nhits,
@@ -1540,12 +1473,10 @@ int musc_overflow_probes(musc_ctx* c, uint32_t** read_idx, uint32_t** window, ui
   if (c->stats.n_overflow_blocks == 0 || c->stats.n_overflow_blocks == ~0ull) return 0;
   if (!c->last_exact_blocks || !c->block_table.p) return fail(c, 4, "no exact block counters from the last pass");
   HIPCHK(c, hipSetDevice(c->device));
-  DevOwner own;  // the probes on the device (muscato_maxmatches.hpp), released on every return
-  uint2* d_out = nullptr;
+  DevPtr<uint2> d_out;  // the probes on the device, released on every return
   uint64_t found = 0;
   const int rc = hot_probes_device(c, &d_out, &found);
   if (rc) return rc;
-  own.p = d_out;
   std::vector<uint2> h(found ? found : 1);
   if (found) {
     const hipError_t e = hipMemcpy(h.data(), d_out, found * sizeof(uint2), hipMemcpyDeviceToHost);

@@ -17,13 +17,7 @@ namespace {
 void free_index(musc_ctx* c) {
   // (the allocations stay for the next build; musc_destroy releases them)
   c->idx = mi::Resident();
-  c->data_epoch++;
-}
-
-// release the context-bucket tables (the window-start index is being built)
-void drop_ctx_index(musc_ctx* c) {
-  c->ctx_T.release();
-  c->ctx_E.release();
+  c->st.index_freed();
 }
 
 // The targets (and their bases) an index build covers, and the base count its size-dependent choices are made on:
@@ -53,7 +47,7 @@ uint64_t index_avail(const musc_ctx* c) {
 // them (an error code if they cannot be numbered).  cursors: one more zeroed u32 per bucket for count and fill.
 // soft: an allocation that fails means "does not fit" (100: the caller falls back) instead of error 10.
 template <class Count, class Sizes, class Set, class Cap, class Fill>
-int build_index_table(musc_ctx* c, int bits, uint64_t bucket_b, bool cursors, bool soft, DevTable& T, DevTable& E,
+int build_index_table(musc_ctx* c, int bits, uint64_t bucket_b, bool cursors, bool soft, DevMem& T, DevMem& E,
                       Count count, Sizes sizes, Set set, Cap cap, Fill fill) {
   const uint64_t nb = 1ull << bits;
   auto no_mem = [&](hipError_t e, const char* what) {
@@ -173,7 +167,8 @@ int build_index(musc_ctx* c, const mi::Resident& want, const IdxRange& R) {
     c->idx_E.release();
     rc = build_ctx_index(c, want, R);
   } else {
-    drop_ctx_index(c);
+    c->ctx_T.release();
+    c->ctx_E.release();
     rc = want.kind == mi::K_LINES ? build_window_index<LineBucket>(c, want, R) : build_window_index<Bucket>(c, want, R);
   }
   if (!rc) c->idx = want;
@@ -182,18 +177,31 @@ int build_index(musc_ctx* c, const mi::Resident& want, const IdxRange& R) {
 
 // The xpos words of the reads in hand, in the format of the bucket width
 bool reads_xpos(musc_ctx* c, int wide) {
-  if (c->rdx_epoch == c->data_epoch && c->rdx_wide == wide) return true;
+  if (c->rdx_of.gen == c->st.g.pass_inputs && c->rdx_of.wide == wide) return true;
   if (ensure(c, c->rdx, c->nreads)) return false;
   if (wide)
     hipLaunchKernelGGL(k_read_xpos<true>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->rdx.p);
   else
     hipLaunchKernelGGL(k_read_xpos<false>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->rdx.p);
   if (hipGetLastError() != hipSuccess) return false;
-  c->rdx_epoch = c->data_epoch;
-  c->rdx_wide = wide;
-  c->xok_epoch = ~0ull;
-  c->xokdb_epoch = ~0ull;
+  c->rdx_of.gen = c->st.g.pass_inputs;
+  c->rdx_of.wide = wide;
+  c->xok.gen = c->xokdb.gen = 0;
   return true;
+}
+
+// nmiss budget per read length 0 .. max_len + 1: int((1-PMatch)*float64(len)), IEEE double, truncation
+// (cmd/muscato_confirm/main.go:198) -- evaluated on the host exactly as Go does; --MaxMismatch replaces it.
+std::vector<uint16_t> nmiss_budget(const musc_params* P, uint32_t max_len) {
+  std::vector<uint16_t> tab((size_t)max_len + 2);
+  for (uint32_t L = 0; L < tab.size(); L++) {
+    volatile double a = 1.0 - P->pmatch;
+    volatile double b = a * (double)L;
+    long long v = (long long)b;
+    if (P->max_mismatch_p1 > 0) v = P->max_mismatch_p1 - 1;
+    tab[L] = (uint16_t)std::min<long long>(std::max<long long>(v, 0), 0xFFFE);
+  }
+  return tab;
 }
 
 // Reads with X fit the context path if every read that holds more of them than its xpos word lists
@@ -206,17 +214,8 @@ bool reads_x_fit(musc_ctx* c, const musc_params* P, uint32_t max_len, int wide) 
   if (!reads_xpos(c, wide)) return false;
   // (the budget table covers the reads in hand whatever length the caller planned the index for)
   max_len = std::max(max_len, c->max_len);
-  if (c->xok_epoch == c->data_epoch && c->xok_pmatch == P->pmatch && c->xok_mmp1 == P->max_mismatch_p1) return c->xok;
-  std::vector<uint16_t> tab((size_t)max_len + 2);
-  for (uint32_t L = 0; L < tab.size(); L++) {  // the budget exactly as musc_match_device builds it
-    volatile double a = 1.0 - P->pmatch;
-    volatile double b = a * (double)L;
-    long long v = (long long)b;
-    if (P->max_mismatch_p1 > 0) v = P->max_mismatch_p1 - 1;
-    if (v < 0) v = 0;
-    if (v > 0xFFFE) v = 0xFFFE;
-    tab[L] = (uint16_t)v;
-  }
+  if (c->xok.gen == c->st.g.pass_inputs && c->xok.pmatch == P->pmatch && c->xok.mmp1 == P->max_mismatch_p1) return c->xok.ok;
+  const std::vector<uint16_t> tab = nmiss_budget(P, max_len);  // the budget musc_match_device applies
   TmpBufs B;
   uint16_t* d_tab = nullptr;
   uint32_t bad = 1;
@@ -227,11 +226,11 @@ bool reads_x_fit(musc_ctx* c, const musc_params* P, uint32_t max_len, int wide) 
                      max_len, wide ? XPos<true>::MAX : XPos<false>::MAX, c->d_flag);
   if (hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return false;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
-  c->xok = bad == 0;
-  c->xok_epoch = c->data_epoch;
-  c->xok_pmatch = P->pmatch;
-  c->xok_mmp1 = P->max_mismatch_p1;
-  return c->xok;
+  c->xok.ok = bad == 0;
+  c->xok.gen = c->st.g.pass_inputs;
+  c->xok.pmatch = P->pmatch;
+  c->xok.mmp1 = P->max_mismatch_p1;
+  return c->xok.ok;
 }
 
 // Reads with X against a DATABASE with X fit the context path if every read lists all its X in its
@@ -245,17 +244,17 @@ bool reads_x_fit_db(musc_ctx* c, const musc_params* P, int wide) {
   wn.n = P->n_windows;
   wn.ww = P->window_width;
   for (int k = 0; k < P->n_windows && k < CTX_MAX_W; k++) key[3 + k] = wn.q1[k] = P->windows[k];
-  if (c->xokdb_epoch == c->data_epoch && memcmp(key, c->xokdb_key, sizeof key) == 0) return c->xokdb;
+  if (c->xokdb.gen == c->st.g.pass_inputs && std::equal(key, key + CTX_MAX_W + 3, c->xokdb.key)) return c->xokdb.ok;
   uint32_t bad = 1;
   if (hipMemsetAsync(c->d_flag, 0, 4, c->stream) != hipSuccess) return false;
   if (wide) hipLaunchKernelGGL(k_xpos_check_db<true>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rdx.p, c->nreads, wn, c->d_flag);
   else hipLaunchKernelGGL(k_xpos_check_db<false>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rdx.p, c->nreads, wn, c->d_flag);
   if (hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return false;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
-  c->xokdb = bad == 0;
-  c->xokdb_epoch = c->data_epoch;
-  memcpy(c->xokdb_key, key, sizeof key);
-  return c->xokdb;
+  c->xokdb.ok = bad == 0;
+  c->xokdb.gen = c->st.g.pass_inputs;
+  std::copy(key, key + CTX_MAX_W + 3, c->xokdb.key);
+  return c->xokdb.ok;
 }
 
 // Which index a run with these parameters and reads of at most max_len bases uses: context

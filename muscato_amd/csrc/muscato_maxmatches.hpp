@@ -4,52 +4,40 @@
 #pragma once
 
 // The suspect probes of the last pass, on the device: the (read, window) pairs whose (window, key) block counter is above
-// MaxMatches.  *out is hipMalloc'ed (the caller frees it) and holds *found pairs; k_hot_probes runs again with room for
-// all of them when the first buffer was too small.
-static int hot_probes_device(musc_ctx* c, uint2** out, uint64_t* found) {
-  *out = nullptr;
+// MaxMatches.  *out holds *found pairs; k_hot_probes runs again with room for all of them when the first buffer was
+// too small.
+static int hot_probes_device(musc_ctx* c, DevPtr<uint2>* out, uint64_t* found) {
   *found = 0;
   uint64_t cap = 1u << 20;
   for (;;) {
-    uint2* d_out = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_out, cap * sizeof(uint2)));
+    HIPCHK(c, out->alloc(cap * sizeof(uint2)));
+    uint2* const d_out = out->get();
     hipError_t e = hipMemsetAsync(c->counters + CNT_BATCH, 0, 8, c->stream);
     const dim3 grid(std::max(1u, std::min(nblk(c->nreads, 256), MAX_GRID))), block(256);
     if (e == hipSuccess) {
-      switch (c->rw) {
-        case 4: hipLaunchKernelGGL((k_hot_probes<4>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-        case 8: hipLaunchKernelGGL((k_hot_probes<8>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-        case 12: hipLaunchKernelGGL((k_hot_probes<12>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-        case 16: hipLaunchKernelGGL((k_hot_probes<16>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-        default: hipLaunchKernelGGL((k_hot_probes<0>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp, c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH); break;
-      }
+      by_rw(c->rw, [&](auto r) {
+        hipLaunchKernelGGL((k_hot_probes<decltype(r)::value>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp,
+                           c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH);
+      });
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(c->h_pinned, c->counters + CNT_BATCH, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      (void)hipFree(d_out);
+    if (e != hipSuccess) {  // (the block goes with the caller's owner)
       (void)hipGetLastError();
       return fail(c, 10, "the suspect probes: %s", hipGetErrorString(e));
     }
     const uint64_t n = c->h_pinned[0];
     if (n > cap) {  // again, with room for all of them
-      (void)hipFree(d_out);
       cap = n + 16;
       continue;
     }
-    *out = d_out;
     *found = n;
     return 0;
   }
 }
 
 namespace {
-
-struct DevOwner {  // one hipMalloc'ed pointer, freed on every exit
-  void* p = nullptr;
-  ~DevOwner() { if (p) (void)hipFree(p); }
-};
 
 MmData mm_data(const musc_ctx* c, const musc_params& P) {
   MmData D;
@@ -91,13 +79,11 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
   uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned + 8);
   int rc;
 
-  DevOwner probes_own;
+  DevPtr<uint2> probes;
   uint64_t np = 0;
   if (c->stats.n_overflow_blocks != 0) {
     if (!c->last_exact_blocks || !c->block_table.p) return fail(c, 4, "musc_maxmatches_apply: no exact block counters from the last pass");
-    uint2* p = nullptr;
-    if ((rc = hot_probes_device(c, &p, &np))) return rc;
-    probes_own.p = p;
+    if ((rc = hot_probes_device(c, &probes, &np))) return rc;
   }
   *n_suspect = np;
   if (np >= musc_mm::MAX_BLOCKS) return fail(c, 12, "musc_maxmatches_apply: %llu suspect probes are more than the device stage takes", (unsigned long long)np);
@@ -114,7 +100,7 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
     HIPCHK(c, A.alloc(&sorted, np * 8));
     {
       TmpBufs S;
-      if ((rc = mm_sort(c, S, reinterpret_cast<uint2*>(probes_own.p), sorted, np, MmProbeLess{D}))) return rc;
+      if ((rc = mm_sort(c, S, probes.get(), sorted, np, MmProbeLess{D}))) return rc;
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     HIPCHK(c, A.alloc(&heads, np * 4));
@@ -209,12 +195,12 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
   HIPCHK(c, hipGetLastError());
   // from here on the list changes.  (The survivors go back into the pass's own buffer: a captured graph of the pass
   // holds its address.)
+  c->st.list_changes();  // (nobody's list until the copy has landed; an order taken before is not this list's)
   if (m) HIPCHK(c, hipMemcpyAsync(c->hits.p, out, m * 16, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->nhits = m;
   c->stats.n_hits = m;
-  c->mm_list = false;            // the list is no longer that of a pass: a second call needs a new pass
-  c->side_after_match = true;    // (an order taken before is not this list's)
+  c->st.list_made(musc_state::LIST_REPLAYED);  // no longer that of a pass: a second call needs a new pass
   return 0;
 }
 
@@ -228,7 +214,7 @@ int musc_maxmatches_apply(musc_ctx* c, int apply_mmtol, uint64_t* nhits, uint64_
   if (nhits) *nhits = 0;
   if (n_suspect_probes) *n_suspect_probes = 0;
   if (n_truncated_blocks) *n_truncated_blocks = 0;
-  if (!c->hits_current || !c->mm_list)
+  if (!c->st.may_replay())
     return fail(c, 2, "musc_maxmatches_apply: the resident tuple list is not that of a musc_match* over the reads and the database in hand");
   const musc_params P = c->mm_params;
   if (P.apply_mmtol != 0) return fail(c, 2, "musc_maxmatches_apply: the last pass ran with apply_mmtol = 1: its list lacks the tuples the replay needs");

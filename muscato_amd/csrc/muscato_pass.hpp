@@ -349,23 +349,14 @@ static int pass_setup(musc_ctx* c, const musc_params* P, PassPlan* pl, BatchCurs
     if (P->windows[k] == 0) pp.q1zero_mask |= 1u << k;
   }
 
-  // nmiss budget per read length: int((1-PMatch)*float64(len)), IEEE double, truncation
-  // (cmd/muscato_confirm/main.go:198) -- evaluated on the host exactly as Go does.
-  if (c->nm_pmatch != P->pmatch || c->nm_mmp1 != P->max_mismatch_p1 || c->nm_maxlen != c->max_len || !c->nmiss_tab.p) {
-    std::vector<uint16_t> tab((size_t)c->max_len + 2);
-    for (uint32_t L = 0; L < tab.size(); L++) {
-      volatile double a = 1.0 - P->pmatch;
-      volatile double b = a * (double)L;
-      long long v = (long long)b;
-      if (P->max_mismatch_p1 > 0) v = P->max_mismatch_p1 - 1;  // --MaxMismatch addition
-      tab[L] = (uint16_t)std::min<long long>(std::max<long long>(v, 0), 0xFFFE);
-    }
+  if (c->nm.pmatch != P->pmatch || c->nm.mmp1 != P->max_mismatch_p1 || c->nm.maxlen != c->max_len || !c->nmiss_tab.p) {
+    const std::vector<uint16_t> tab = nmiss_budget(P, c->max_len);
     if ((rc = ensure(c, c->nmiss_tab, tab.size()))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->nmiss_tab.p, tab.data(), tab.size() * 2, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // tab goes out of scope
-    c->nm_pmatch = P->pmatch;
-    c->nm_mmp1 = P->max_mismatch_p1;
-    c->nm_maxlen = c->max_len;
+    c->nm.pmatch = P->pmatch;
+    c->nm.mmp1 = P->max_mismatch_p1;
+    c->nm.maxlen = c->max_len;
   }
 
   HIPCHK(c, hipMemsetAsync(c->counters, 0, CNT_PASS_WORDS * sizeof(unsigned long long), c->stream));
@@ -380,7 +371,7 @@ static int pass_setup(musc_ctx* c, const musc_params* P, PassPlan* pl, BatchCurs
   // once (match_setup, further down: it needs the block mode decided here for the kernel's LDS).
   auto thr_for = [&](uint64_t grid) { return (uint32_t)std::min<uint64_t>(pl->max_matches / (pl->planned_batches * grid), 0x7FFFFFFFull); };
   const uint32_t thr_host = thr_for(MAX_GRID);
-  const bool known_exact = c->exact_epoch == c->data_epoch && memcmp(&c->exact_params, P, sizeof *P) == 0;
+  const bool known_exact = c->exact.key == c->pass_key(*P, 2);
   pl->block_mode = P->skip_block_check ? 0 : (c->force_exact_blocks || known_exact || thr_host < 2 ? 2 : 1);
   if (pl->block_mode == 2) {
     if ((rc = ensure(c, c->block_table, 1ull << BLOCK_TABLE_BITS))) return rc;
@@ -411,9 +402,8 @@ static int pass_setup(musc_ctx* c, const musc_params* P, PassPlan* pl, BatchCurs
   }
   pl->mask = c->reads_have_x || c->db_has_x;  // (a stale all-zero plane of an earlier batch does not count)
 
-  pl->sized = c->sized_epoch == c->data_epoch && c->sized_exact_blocks == (pl->block_mode == 2) &&
-              memcmp(&c->sized_params, P, sizeof *P) == 0 && !c->env.debug_sync;
-  cur->bsz = pl->sized ? c->sized_bsz : c->batch_reads;
+  pl->sized = c->sized.key == c->pass_key(*P, pl->block_mode == 2 ? 2 : 0) && !c->env.debug_sync;
+  cur->bsz = pl->sized ? c->sized.bsz : c->batch_reads;
   cur->plan = c->up.active && !pl->sized ? &c->up.plan : nullptr;
   return 0;
 }
@@ -518,10 +508,9 @@ static int pass_verdict(musc_ctx* c, const PassPlan& pl, const BatchCursor& cur,
         return rc;
     }
   }
-  c->sized_epoch = cur.plan ? 0 : c->data_epoch;  // (a streamed pass leaves the context unsized: BatchCursor)
-  c->sized_params = *pl.P;
-  c->sized_exact_blocks = pl.block_mode == 2;
-  c->sized_bsz = cur.bsz;
+  // (a streamed pass leaves the context unsized: BatchCursor)
+  c->sized.key = cur.plan ? musc_state::PassKey() : c->pass_key(*pl.P, pl.block_mode == 2 ? 2 : 0);
+  c->sized.bsz = cur.bsz;
   return 0;
 }
 
@@ -537,11 +526,8 @@ static int pass_fused(musc_ctx* c, const PassPlan& pl, BatchCursor cur, PassOutc
   // and the final readback are captured once per (reads, database, parameters) and then cost one
   // launch per pass.  Every buffer of a sized pass is fixed, so the captured arguments stay valid;
   // any pass that sizes drops the graph.
-  const bool use_graph = sized && c->env.graph > 0 && !c->graph_failed;
-  if (!sized && c->graph_exec) {
-    (void)hipGraphExecDestroy(c->graph_exec);
-    c->graph_exec = nullptr;
-  }
+  const bool use_graph = sized && c->env.graph > 0 && !c->graph.failed;
+  if (!sized) c->graph.drop();
   // A batch's staged tuples go to their place in `hits` by a k_compact_w of their own.  (r02 / r03 moved them from inside
   // the NEXT batch's match launch instead; r04's A/B on cfg3 / the cfg4 shard, profiles/r04_ab_shape_spec_dma.txt: the pass
   // takes the same time either way, but the match launch grows by work its algorithmic bytes do not bill.)
@@ -549,13 +535,9 @@ static int pass_fused(musc_ctx* c, const PassPlan& pl, BatchCursor cur, PassOutc
     if (attempt > 40) return fail(c, 12, "internal: the context pass did not converge on buffer sizes");
     PassClock clk(c);
     if (!clk.ev0 || !clk.ev1) return fail(c, 10, "hipEventCreate failed");
-    const bool replay = use_graph && c->graph_exec && c->graph_epoch == c->data_epoch && c->graph_block_mode == pl.block_mode &&
-                        memcmp(&c->graph_params, pl.P, sizeof *pl.P) == 0;
+    const bool replay = use_graph && c->graph.exec && c->graph.key == c->pass_key(*pl.P, pl.block_mode);
     const bool capture = use_graph && !replay;
-    if (capture && c->graph_exec) {
-      (void)hipGraphExecDestroy(c->graph_exec);
-      c->graph_exec = nullptr;
-    }
+    if (capture) c->graph.drop();
     clk.tm.off = capture || replay;
     CaptureGuard cap;  // (ends the capture if this attempt leaves early)
     if (capture) {
@@ -629,23 +611,21 @@ static int pass_fused(musc_ctx* c, const PassPlan& pl, BatchCursor cur, PassOutc
     if (capture) {
       hipGraph_t g = nullptr;
       hipError_t ge = cap.end(&g);
-      if (ge == hipSuccess) ge = hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0);
+      if (ge == hipSuccess) ge = hipGraphInstantiate(&c->graph.exec, g, nullptr, nullptr, 0);
       if (g) (void)hipGraphDestroy(g);
       if (ge != hipSuccess) {  // the graph is an optimisation: without it the pass runs launch by launch
         (void)hipGetLastError();
-        c->graph_exec = nullptr;
+        c->graph.exec = nullptr;
         *what = PASS_RERUN_NO_GRAPH;
         return 0;
       }
-      c->graph_epoch = c->data_epoch;
-      c->graph_params = *pl.P;
-      c->graph_block_mode = pl.block_mode;
-      c->graph_batches = c->stats.n_batches;
+      c->graph.key = c->pass_key(*pl.P, pl.block_mode);
+      c->graph.batches = c->stats.n_batches;
     }
     if (capture || replay) {
-      c->stats.n_batches = c->stats.match_launches = c->graph_batches;
+      c->stats.n_batches = c->stats.match_launches = c->graph.batches;
       HIPCHK(c, hipEventRecord(clk.ev0, c->stream));
-      HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
+      HIPCHK(c, hipGraphLaunch(c->graph.exec, c->stream));
       HIPCHK(c, hipEventRecord(clk.ev1, c->stream));
     }
     return pass_verdict(c, pl, cur, tot, clk, what);
@@ -664,11 +644,11 @@ static int pass_two_kernel(musc_ctx* c, const PassPlan& pl, BatchCursor cur, Pas
   // a mask plane on only one side: allocate the missing all-zero plane once
   if (pl.mask && !c->rdm && c->nreads) {
     const uint64_t words = c->nreads * (uint64_t)c->rw;
-    HIPCHK(c, hipMalloc((void**)&c->rdm, words * 4 + 256));
+    HIPCHK(c, c->rdm.alloc(words * 4 + 256));
     HIPCHK(c, hipMemsetAsync(c->rdm, 0, words * 4 + 256, c->stream));
   }
   if (pl.mask && !c->dbm2) {
-    HIPCHK(c, hipMalloc((void**)&c->dbm2, (c->db_words + 64) * 4));
+    HIPCHK(c, c->dbm2.alloc((c->db_words + 64) * 4));
     // (the index stays valid: bucket_of treats a null and an all-zero mask plane alike)
     HIPCHK(c, hipMemsetAsync(c->dbm2, 0, (c->db_words + 64) * 4, c->stream));
     if ((rc = db_xblocks(c))) return rc;
@@ -789,13 +769,12 @@ static int match_index_pass(musc_ctx* c, const musc_params* P, uint64_t* nhits) 
     rc = idx_is_ctx(c) ? pass_fused(c, pl, cur, &what) : pass_two_kernel(c, pl, cur, &what);
     if (rc || what == PASS_DONE) break;
     if (what == PASS_RERUN_CAREFUL) {
-      c->sized_epoch = 0;
+      c->sized.key = musc_state::PassKey();
     } else if (what == PASS_RERUN_NO_GRAPH) {
-      c->graph_failed = true;
+      c->graph.failed = true;
     } else {  // PASS_RERUN_EXACT: this attempt chain runs exact, and later passes over the same inputs start exact
       c->force_exact_blocks = forced_exact = true;
-      c->exact_epoch = c->data_epoch;
-      c->exact_params = *P;
+      c->exact.key = c->pass_key(*P, 2);
     }
   }
   if (forced_exact) c->force_exact_blocks = false;
@@ -808,7 +787,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
   int rc = check_params(c, P);
   if (rc) return rc;
   if (!c->db2) return fail(c, 4, "no database loaded");
-  if (!c->rd && c->nreads) return fail(c, 4, "no reads loaded");
+  if (c->reads_failed) return fail(c, 4, "no reads loaded");
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = plan_partitions(c, P, c->max_len))) return rc;
   c->cur_part = 0;
@@ -822,12 +801,12 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
 // device, so a later pass packs and matches them.
 extern "C" int musc_match_device(musc_ctx* c, const musc_params* P, uint64_t* nhits) {
   if (!c) return 1;
-  c->hits_current = false;
-  c->side_after_match = true;  // (musc_side_prepare: the ordered list is no longer that of the last pass)
+  c->st.list_changes();  // (an order taken before is not this pass's; a pass that fails leaves no list)
   const int rc = match_device_impl(c, P, nhits);
   if (rc != 0 && c->up.active && c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);
-  c->hits_current = rc == 0;
-  c->mm_list = rc == 0;  // musc_maxmatches_apply: the list and the parameters it replays
-  if (rc == 0) c->mm_params = *P;
+  if (rc == 0) {
+    c->st.list_made(musc_state::LIST_PASS);
+    c->mm_params = *P;  // musc_maxmatches_apply: the list and the parameters it replays
+  }
   return rc;
 }

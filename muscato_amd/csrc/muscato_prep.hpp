@@ -191,18 +191,9 @@ static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const ui
   const uint64_t nu = nu32;
 
   // ---- the distinct sequences become the context's reads
-  c->nreads = nu;
-  c->max_len = (uint32_t)maxlen;
-  int rw = (int)((2 * maxlen + 31) / 32) + 1;
-  rw = (rw + 3) & ~3;
-  if (rw < 4) rw = 4;
-  c->rw = rw;
-  const uint64_t words = nu * (uint64_t)rw;
-  if (words >= (1ull << 32)) return fail(c, 2, "too many read words for one dispatch (reads x record words >= 2^32)");
-  HIPCHK(c, hipMalloc((void**)&c->rd, words * 4 + 256));
-  HIPCHK(c, hipMalloc((void**)&c->rdm, words * 4 + 256));
-  HIPCHK(c, hipMemsetAsync(c->rd + words, 0, 256, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->rdm + words, 0, 256, c->stream));
+  RecShape shape;
+  if ((rc = reads_shape(c, nu, maxlen, false, &shape)) || (rc = reads_records(c, shape, nu, maxlen, true, false))) return rc;
+  const auto [rw, words] = shape;
   uint32_t* d_hasx = c->d_flag;
   HIPCHK(c, hipMemsetAsync(d_hasx, 0, 4, c->stream));
   hipLaunchKernelGGL(k_prep_pack, dim3(nblk(words, 256)), dim3(256), 0, c->stream, d_s, d_off, d_uhead, nu, rw, c->rd,
@@ -228,11 +219,7 @@ static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const ui
     free(h_ustart);
     return fail(c, 10, "musc_reads_sort_unique: %s", hipGetErrorString(e));
   }
-  c->reads_have_x = hasx != 0;
-  if (!hasx) {
-    (void)hipFree(c->rdm);
-    c->rdm = nullptr;
-  }
+  reads_settle_x(c, hasx);
   float ms = 0;
   (void)hipEventElapsedTime(&ms, e0, e1);
   c->stats.ms_read_prep = ms;  // device time of the last sort + collapse
@@ -242,13 +229,8 @@ static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const ui
   return 0;
 }
 
-extern "C" int musc_reads_sort_unique(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads,
-                                      int on_device, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
-  if (!c) return 1;
-  if (!order || !ustart || !nunique) return fail(c, 2, "musc_reads_sort_unique: NULL output pointer");
-  *order = *ustart = nullptr;
-  *nunique = 0;
-  if ((!seqs || !offsets) && nreads) return fail(c, 2, "musc_reads_sort_unique: NULL input");
+static int reads_sort_unique_run(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads, int on_device,
+                                 uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
   HIPCHK(c, hipSetDevice(c->device));
   free_reads(c);
   if (nreads >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read numbers");
@@ -279,6 +261,16 @@ extern "C" int musc_reads_sort_unique(musc_ctx* c, const char* seqs, const uint6
   }
   HIPCHK(c, hipEventRecord(e0, c->stream));
   return reads_sort_unique_dev(c, d_s, d_off, n, e0, e1, order, ustart, nunique);
+}
+
+extern "C" int musc_reads_sort_unique(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads,
+                                      int on_device, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
+  if (!c) return 1;
+  if (!order || !ustart || !nunique) return fail(c, 2, "musc_reads_sort_unique: NULL output pointer");
+  *order = *ustart = nullptr;
+  *nunique = 0;
+  if ((!seqs || !offsets) && nreads) return fail(c, 2, "musc_reads_sort_unique: NULL input");
+  return reads_load_done(c, reads_sort_unique_run(c, seqs, offsets, nreads, on_device, order, ustart, nunique));
 }
 
 // ---------------------------------------------------------------- FASTQ text -> prepared reads (kernels_fastq.hpp)
@@ -426,11 +418,8 @@ extern "C" int musc_reads_prep_fastq(musc_ctx* c, const char* text, uint64_t nby
   if (!text && nbytes) return fail(c, 2, "musc_reads_prep_fastq: NULL input");
   HIPCHK(c, hipSetDevice(c->device));
   free_reads(c);
-  if (max_read_len < 0) return fail(c, 2, "musc_reads_prep_fastq: max_read_len %d is negative", max_read_len);
+  if (max_read_len < 0) return reads_load_done(c, fail(c, 2, "musc_reads_prep_fastq: max_read_len %d is negative", max_read_len));
   const int rc = fastq_prep_run(c, text, nbytes, on_device, min_read_len, (uint32_t)max_read_len, out);
-  if (rc) {  // nothing stale: no reads, no arrays
-    musc_fastq_prep_free(out);
-    free_reads(c);
-  }
-  return rc;
+  if (rc) musc_fastq_prep_free(out);  // nothing stale: no arrays, and (reads_load_done) no reads
+  return reads_load_done(c, rc);
 }

@@ -125,14 +125,14 @@ static ResData res_data(const musc_ctx* c) {
 }
 
 // text + offsets of n items to the device (the offsets must not decrease; item i = bytes [offsets[i], offsets[i + 1]))
-static int upload_text(musc_ctx* c, const char* what, const char* text, const uint64_t* offsets, uint64_t n, char** d_text, uint64_t** d_off) {
+static int upload_text(musc_ctx* c, const char* what, const char* text, const uint64_t* offsets, uint64_t n, DevPtr<char>* d_text, DevPtr<uint64_t>* d_off) {
   for (uint64_t i = 0; i < n; i++)
     if (offsets[i + 1] < offsets[i]) return fail(c, 2, "%s: offsets decrease at item %llu", what, (unsigned long long)i);
   const uint64_t bytes = offsets[n];
-  HIPCHK(c, hipMalloc((void**)d_text, bytes + 16));
-  HIPCHK(c, hipMalloc((void**)d_off, (n + 1) * 8));
-  if (bytes) HIPCHK(c, hipMemcpyAsync(*d_text, text, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(*d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, d_text->alloc(bytes + 16));
+  HIPCHK(c, d_off->alloc((n + 1) * 8));
+  if (bytes) HIPCHK(c, hipMemcpyAsync(d_text->get(), text, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_off->get(), offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -143,14 +143,11 @@ int musc_results_set_gene_text(musc_ctx* c, const char* text, const uint64_t* of
   if (!c->db2 || nseq != c->nseq)
     return fail(c, 2, "musc_results_set_gene_text: text of %u genes for a database of %u targets", nseq, c->nseq);
   HIPCHK(c, hipSetDevice(c->device));
-  const bool list_ok = c->hits_current;  // (a new text leaves the tuple list as good as it was)
-  drop_gene_text(c);
-  c->hits_current = list_ok;
+  drop_gene_text(c);  // (a new text leaves the tuple list as good as it was)
+  // ... and one that cannot be put in place leaves no text and no list, as it always has
+  auto failed = [c](int rc) { return drop_gene_text(c), c->st.list_forgotten(), rc; };
   int rc = upload_text(c, "musc_results_set_gene_text", text, offsets, nseq, &c->res_gtext, &c->res_goff);
-  if (rc) {
-    drop_gene_text(c);
-    return rc;
-  }
+  if (rc) return failed(rc);
   // rank of each gene's text among all of them, bytewise; equal texts share a rank
   std::vector<uint32_t> order;
   order.reserve(nseq);
@@ -168,12 +165,9 @@ int musc_results_set_gene_text(musc_ctx* c, const char* text, const uint64_t* of
     if (i && cmp(order[i - 1], order[i]) != 0) rk++;
     rank[order[i]] = rk;
   }
-  hipError_t e = hipMalloc((void**)&c->res_rank, (uint64_t)nseq * 4 + 16);
+  hipError_t e = c->res_rank.alloc((uint64_t)nseq * 4 + 16);
   if (e == hipSuccess) e = hipMemcpy(c->res_rank, rank.data(), (uint64_t)nseq * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    drop_gene_text(c);
-    return fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return failed(fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e)));
   // for the side outputs: the form of the texts, and the rank of each gene's name alone
   c->side_bad_gene = musc_side::first_bad_form(text, offsets, absent, nseq);
   c->side_form_ok = c->side_bad_gene == nseq;
@@ -181,14 +175,11 @@ int musc_results_set_gene_text(musc_ctx* c, const char* text, const uint64_t* of
     const musc_side::NameRanks R = musc_side::name_ranks(text, offsets, absent, nseq);
     std::vector<uint2> names(R.rep.size());
     for (size_t k = 0; k < names.size(); k++) names[k] = make_uint2(R.rep[k], R.len[k]);
-    e = hipMalloc((void**)&c->side_nrank, (uint64_t)nseq * 4 + 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->side_names, names.size() * 8 + 16);
+    e = c->side_nrank.alloc((uint64_t)nseq * 4 + 16);
+    if (e == hipSuccess) e = c->side_names.alloc(names.size() * 8 + 16);
     if (e == hipSuccess) e = hipMemcpy(c->side_nrank, R.rank.data(), (uint64_t)nseq * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && !names.empty()) e = hipMemcpy(c->side_names, names.data(), names.size() * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      drop_gene_text(c);
-      return fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return failed(fail(c, 10, "musc_results_set_gene_text: %s", hipGetErrorString(e)));
     c->side_nnames = (uint32_t)names.size();
   }
   return 0;
@@ -217,7 +208,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   const uint4* d_in = reinterpret_cast<const uint4*>(hits);
   TmpBufs B;
   if (!hits) {
-    if (!c->hits_current)
+    if (!c->st.may_order_resident())
       return fail(c, 2, "musc_results_order: the resident tuple list is not that of a pass over the reads and the database in hand");
     d_in = reinterpret_cast<const uint4*>(c->hits.p);
     n = c->nhits;
@@ -256,7 +247,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   hipLaunchKernelGGL(k_results_flag, grid(n), B256, 0, c->stream, d_in, n, c->nreads, c->nseq, c->seq_off, c->res_rank, keep, c->d_flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, keep, excl, n, false, stmp))) return rc;
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   HIPCHK(c, hipMemcpyAsync(h32, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(h32 + 1, excl + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(h32 + 2, keep + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
@@ -369,8 +360,7 @@ int musc_results_order(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_dev
   if (!c) return 1;
   if (nlines) *nlines = 0;
   if (nbytes) *nbytes = 0;
-  c->res_valid = false;
-  c->side_valid = false;
+  c->st.order_begins();  // (whatever comes of this call, the last order and what was prepared from it are gone)
   c->res_n = c->res_bytes = 0;
   if (!c->db2 || !c->res_gtext || !c->res_rank) return fail(c, 2, "musc_results_order: no gene text (musc_results_set_gene_text)");
   if (c->up.active) return fail(c, 2, "musc_results_order: a streamed read load has not been matched yet");
@@ -378,8 +368,7 @@ int musc_results_order(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_dev
   const int rc = timed(c, &c->res_ms_order, [&] { return results_order_impl(c, hits, n, on_device); });
   if (rc) return rc;
   c->res_ms_text = 0;
-  c->res_valid = true;
-  c->side_after_match = false;
+  c->st.order_made();
   if (nlines) *nlines = c->res_n;
   if (nbytes) *nbytes = c->res_bytes;
   return 0;
@@ -387,7 +376,7 @@ int musc_results_order(musc_ctx* c, const musc_hit* hits, uint64_t n, int on_dev
 
 int musc_results_hits(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_device) {
   if (!c) return 1;
-  if (!c->res_valid) return fail(c, 2, "musc_results_hits: no ordered list (musc_results_order)");
+  if (!c->st.ordered_current()) return fail(c, 2, "musc_results_hits: no ordered list (musc_results_order)");
   if (capacity < c->res_n) return fail(c, 2, "musc_results_hits: capacity %llu < %llu tuples", (unsigned long long)capacity, (unsigned long long)c->res_n);
   if (c->res_n == 0) return 0;
   if (!dst) return fail(c, 2, "musc_results_hits: dst is NULL");
@@ -408,7 +397,7 @@ int musc_results_text(musc_ctx* c, uint64_t line0, uint64_t nlines, char* dst, u
   if (!c) return 1;
   if (!nbytes) return fail(c, 2, "musc_results_text: nbytes is NULL");
   *nbytes = 0;
-  if (!c->res_valid) return fail(c, 2, "musc_results_text: no ordered list (musc_results_order)");
+  if (!c->st.ordered_current()) return fail(c, 2, "musc_results_text: no ordered list (musc_results_order)");
   const TextDesc t = {c->res_off.p, c->res_n, "musc_results_text",
                       "a line of the ordered list no longer fits the reads, the database or the texts in hand", &c->res_ms_text};
   return text_range(c, t, line0, nlines, dst, capacity, dst_on_device, nbytes,
@@ -454,7 +443,7 @@ static int side_records(musc_ctx* c, int which, const uint32_t* flag, uint32_t* 
   int rc;
   if ((rc = scan_u32(c, flag, excl, n + 1, false, stmp))) return rc;
   if ((rc = scan_u64(c, len, len, n + 1, stmp64))) return rc;
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   HIPCHK(c, hipMemcpyAsync(h32, excl + n, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, len + n, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -472,13 +461,13 @@ static int side_prepare_impl(musc_ctx* c) {
   const dim3 B256(256);
   const uint64_t nreads = c->nreads, m = c->res_n, nnames = c->side_nnames;
   const uint4* const hits = reinterpret_cast<const uint4*>(c->res_hits.p);
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned);
+  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   int rc;
   TmpBufs B;
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
 
   // ---- tokens: once per read text
-  if (!c->side_tok_valid) {
+  if (!c->st.tokens_current()) {
     if ((rc = ensure(c, c->side_tok, std::max<uint64_t>(nreads, 1)))) return rc;
     hipLaunchKernelGGL(k_side_tokens, grid(nreads), B256, 0, c->stream, c->res_ttext, c->res_toff, nreads, c->side_tok.p, c->d_flag);
     HIPCHK(c, hipGetLastError());
@@ -505,7 +494,7 @@ static int side_prepare_impl(musc_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(h32 + 4, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (h32[4]) return fail(c, 11, "musc_side_prepare: a read's text is longer than 4 GiB, or the ordered list no longer fits the reads and the gene text in hand");
-  c->side_tok_valid = true;
+  c->st.tokens_made();
   const SideData D = side_data(c);
 
   // ---- nonmatch: the unmatched reads that have a token
@@ -592,18 +581,20 @@ int musc_side_prepare(musc_ctx* c, uint64_t* nrecords, uint64_t* nbytes) {
     if (nrecords) nrecords[w] = 0;
     if (nbytes) nbytes[w] = 0;
   }
-  c->side_valid = false;
-  if (!c->res_valid) return fail(c, 2, "musc_side_prepare: no ordered list (musc_results_order) of the reads, the database and the texts in hand");
-  if (c->side_after_match) return fail(c, 2, "musc_side_prepare: a pass ran after the last musc_results_order: order its list first");
-  if (!c->res_ttext) return fail(c, 2, "musc_side_prepare: no read text (musc_results_set_read_text)");
-  if (!c->side_form_ok)
-    return fail(c, MUSC_SIDE_ERR_FORM, "musc_side_prepare: gene text not in the simple form (gene %u is not name\\tlen without blanks)", c->side_bad_gene);
-  if (c->nreads >= 0xFFFFFFF0ull) return fail(c, 2, "musc_side_prepare: too many reads for 32-bit record numbers");
+  c->st.side_begins();
+  switch (c->st.side_prepare_refusal(c->res_ttext != nullptr, c->side_form_ok, c->nreads)) {
+    case musc_state::SIDE_OK: break;
+    case musc_state::SIDE_NO_ORDER: return fail(c, 2, "musc_side_prepare: no ordered list (musc_results_order) of the reads, the database and the texts in hand");
+    case musc_state::SIDE_PASS_AFTER: return fail(c, 2, "musc_side_prepare: a pass ran after the last musc_results_order: order its list first");
+    case musc_state::SIDE_NO_READ_TEXT: return fail(c, 2, "musc_side_prepare: no read text (musc_results_set_read_text)");
+    case musc_state::SIDE_FORM: return fail(c, MUSC_SIDE_ERR_FORM, "musc_side_prepare: gene text not in the simple form (gene %u is not name\\tlen without blanks)", c->side_bad_gene);
+    case musc_state::SIDE_TOO_MANY_READS: return fail(c, 2, "musc_side_prepare: too many reads for 32-bit record numbers");
+  }
   HIPCHK(c, hipSetDevice(c->device));
   const int rc = timed(c, &c->side_ms_prepare, [&] { return side_prepare_impl(c); });
   if (rc) return rc;
   c->side_ms_text = 0;
-  c->side_valid = true;
+  c->st.side_made();
   for (int w = 0; w < 3; w++) {
     if (nrecords) nrecords[w] = c->side_nrec[w];
     if (nbytes) nbytes[w] = c->side_nbytes[w];
@@ -629,7 +620,7 @@ int musc_side_text(musc_ctx* c, int which, uint64_t rec0, uint64_t nrec, char* d
   if (!nbytes) return fail(c, 2, "musc_side_text: nbytes is NULL");
   *nbytes = 0;
   if (which < 0 || which > 2) return fail(c, 2, "musc_side_text: no such text (%d)", which);
-  if (!c->side_valid || !c->res_valid || c->side_after_match) return fail(c, 2, "musc_side_text: nothing prepared (musc_side_prepare)");
+  if (!c->st.may_side_text()) return fail(c, 2, "musc_side_text: nothing prepared (musc_side_prepare)");
   const TextDesc t = {c->side_off[which].p, c->side_nrec[which], "musc_side_text", "a record no longer fits the reads or the texts in hand",
                       &c->side_ms_text};
   return text_range(c, t, rec0, nrec, dst, capacity, dst_on_device, nbytes,
