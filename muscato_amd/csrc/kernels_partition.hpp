@@ -18,19 +18,25 @@ MUSC_KERNEL __launch_bounds__(256) void k_add_u32(uint32_t* __restrict__ acc, co
     acc[i] += src[i];
 }
 
-// Segmented reduction over the lanes of a wave that hold the same read (they are contiguous: the list is read-major).
-// Afterwards a lane holds op(v) over itself and the later lanes of its read within the wave; the first lane of each
-// run (within the wave) returns true.
+// Segmented reduction over the RUNS of a wave: consecutive lanes that hold the same read.  Afterwards a lane holds
+// op(v) over itself and the later lanes of its run within the wave; the first lane of each run (within the wave)
+// returns true.  A run is named by its number within the wave, not by its read: the accumulation buffer is read-major
+// per segment only, so where segments are shorter than a wave one read turns up in several runs of the same wave, with
+// other reads in between, and lanes d apart that hold the same read need not belong together (counted as one run they
+// added a later run's sum to an earlier one: one slot too many for the read, left unwritten in the merged list).
 template <class Op>
 DEV bool wave_run_reduce(uint32_t r, uint32_t& v, Op op) {
   const int lane = threadIdx.x & 63;
+  const uint32_t prev = __shfl_up(r, 1);
+  const bool head = lane == 0 || prev != r;
+  const unsigned long long heads = __ballot(head);
+  const uint32_t run = (uint32_t)__popcll(heads & ((2ull << lane) - 1ull));  // (lane 63: 2 << 63 wraps to 0, the mask to all ones)
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t ov = __shfl_down(v, d), orr = __shfl_down(r, d);
-    if (lane + d < 64 && orr == r) v = op(v, ov);
+    const uint32_t ov = __shfl_down(v, d), orun = __shfl_down(run, d);
+    if (lane + d < 64 && orun == run) v = op(v, ov);
   }
-  const uint32_t prev = __shfl_up(r, 1);
-  return r != PART_NO_READ && (lane == 0 || prev != r);
+  return r != PART_NO_READ && head;
 }
 
 DEV bool part_keep(uint32_t nmiss, uint32_t best, uint32_t mmtol, int apply_mmtol) {

@@ -787,7 +787,7 @@ static int match_device_impl(musc_ctx* c, const musc_params* P, uint64_t* nhits)
   int rc = check_params(c, P);
   if (rc) return rc;
   if (!c->db2) return fail(c, 4, "no database loaded");
-  if (c->reads_failed) return fail(c, 4, "no reads loaded");
+  if (c->reads_failed || !c->rw) return fail(c, 4, "no reads loaded");  // (rw == 0: no load yet; a load of zero reads sets it)
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = plan_partitions(c, P, c->max_len))) return rc;
   c->cur_part = 0;

@@ -3,7 +3,8 @@ runs make_case(seed) for seed in [LO, HI) through one Engine -- all accepted tup
 three times (the later passes are sync-free; with MUSC_GRAPH=1 the last is a graph replay), and the same reads through the GPU read prep -- against
 the Python oracle.  Round 1: seeds 0..100000 with the final kernels, no mismatch (270 s on one MI355X); round 2 (context
 buckets wherever a case fits them): seeds 0..90000 with k_match and again with k_match_d (up to two
-windows; k_match otherwise), no mismatch (308 s each); 30000 of them with MUSC_GRAPH=1; round 3 (k_match_t): seeds 0..60000, no mismatch (153 s)."""
+windows; k_match otherwise), no mismatch (308 s each); 30000 of them with MUSC_GRAPH=1; round 3 (k_match_t): seeds 0..60000, no mismatch (153 s).
+`python tests/fuzz_gpu.py walk LO HI [STEPS]` runs the random walks of tests/walk_cases.py instead (one context per seed)."""
 import os
 import sys
 import time
@@ -13,6 +14,21 @@ import numpy as np
 from cases import make_case
 from oracle import muscato_oracle as orc
 from muscato_amd import Engine, Config, sorted_hits
+if sys.argv[1] == "walk":
+    # `python tests/fuzz_gpu.py walk LO HI [STEPS]`: the walks of tests/walk_cases.py for seeds [LO, HI) on one context each,
+    # every step held to the oracle (tests/test_gpu_walk.py runs the committed seeds); ends at the first walk that fails
+    import walk_cases as wc
+    from test_gpu_walk import run_walk
+    lo, hi = int(sys.argv[2]), int(sys.argv[3])
+    nsteps = int(sys.argv[4]) if len(sys.argv) > 4 else wc.STEPS
+    tally, t0 = {}, time.time()
+    for seed in range(lo, hi):
+        run_walk(wc.generate(seed, nsteps), "seed %d" % seed, wc.batch64_of(seed), tally)
+        if seed % 20 == 0: print("seed", seed, "elapsed %.0fs" % (time.time() - t0), flush=True)
+    print("fuzz walk", lo, hi, "no mismatch in %.0fs" % (time.time() - t0))
+    print("passes per path class:", ", ".join("%s x %d" % (c, tally.get(c, 0)) for c in wc.CLASSES))
+    print("passes that repeated exact:", tally.get("exact rerun", 0), "-- with several batches:", tally.get("batches > 1", 0))
+    sys.exit(0)
 lo, hi = int(sys.argv[1]), int(sys.argv[2])
 e = Engine(0)
 bad = 0
