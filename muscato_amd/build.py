@@ -37,7 +37,7 @@ def needs_build() -> bool:
 
 HOST = os.path.join(CSRC, "host")
 BIN = os.path.join(HERE, "bin")
-HOST_HEADERS = [os.path.join(HOST, "muscato_host.hpp"), os.path.join(HOST, "sz.hpp")]
+HOST_HEADERS = [os.path.join(HOST, f) for f in sorted(os.listdir(HOST)) if f.endswith(".hpp")]
 TOOLS = {"muscato": "muscato_cli.cpp", "muscato_prep_targets": "muscato_prep_targets.cpp",
          "muscato_screen": "muscato_screen.cpp", "muscato_confirm": "muscato_confirm.cpp"}
 GPU_TOOLS = ("muscato", "muscato_screen", "muscato_confirm")

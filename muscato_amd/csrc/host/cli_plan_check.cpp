@@ -1,0 +1,308 @@
+// cli_plan_check.cpp -- the placement plan of the `muscato` driver (cli_plan.hpp) against the boolean expressions it
+// replaced, and the one name path of read preparation (cli_names.hpp) against the two loops it replaced, as a program of
+// its own so that it runs under the sanitizers:
+//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o cli_plan_check cli_plan_check.cpp
+//     ./cli_plan_check
+// Old is the driver before the plan, transcribed expression by expression from run_muscato and run_hot_path as they
+// were (prep_device, res_device, side_device, mm_device, want_rccl, list_on_device, and the conditions of the log
+// lines); New makes the calls the driver makes now, in its order.  Both see the whole product of: each of the five
+// variables over {unset, "", host, device, rccl, junk}, GPUs over {1, 2, 3}, odd target bytes or none, an overflow or
+// none, each run-time demotion fired or not, and both values of each *_DEFAULT_DEVICE macro.
+// The name rules run on fixed cases and on seeded random groups whose names sit in heap blocks of their exact size.
+// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "cli_names.hpp"
+#include "cli_plan.hpp"
+
+namespace {
+
+using namespace musc;
+
+int failures = 0;
+#define EXPECT(cond)                                              \
+  do {                                                            \
+    if (!(cond)) {                                                \
+      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
+      failures++;                                                 \
+    }                                                             \
+  } while (0)
+
+// ---- the plan -------------------------------------------------------------------------------------------------
+
+// what a stage finds when it runs
+struct Events {
+  bool overflow, prep_no_memory, rccl_failed, replay_pass_failed, replay_refused, side_refused;
+};
+
+// everything of a run that depends on the placement
+struct Outcome {
+  bool prep_on_device = false;     // the read file was parsed on the device
+  bool rccl = false;               // the tuples were gathered over RCCL
+  bool note_odd = false;           // "results on the host: the targets hold bytes ..." was logged
+  bool note_gpus = false;          // "MaxMatches replay on the host: the post-chain of %d GPUs ..." was logged
+  bool died = false;               // the hot path threw
+  bool replayed_on_device = false, replayed_on_host = false;
+  bool results_on_device = false;  // context 0 outlives the hot path and orders results.txt
+  bool list_on_device = false;     // ... from the resident list
+  bool ctx_to_side = false;        // context 0 outlives results.txt
+  bool side_from_device = false;   // the three side outputs are the device's
+  bool operator==(const Outcome& o) const {
+    return prep_on_device == o.prep_on_device && rccl == o.rccl && note_odd == o.note_odd && note_gpus == o.note_gpus &&
+           died == o.died && replayed_on_device == o.replayed_on_device && replayed_on_host == o.replayed_on_host &&
+           results_on_device == o.results_on_device && list_on_device == o.list_on_device && ctx_to_side == o.ctx_to_side &&
+           side_from_device == o.side_from_device;
+  }
+};
+
+Outcome old_run(const PlanEnv& env, int GPUs, size_t nodd, const Events& ev, const PlanDefaults& D) {
+  const int MUSC_PREP_DEFAULT = D.prep, MUSC_RESULTS_DEFAULT = D.results, MUSC_SIDE_DEFAULT = D.side, MUSC_MAXMATCHES_DEFAULT = D.maxmatches;
+  Outcome o;
+  // run_muscato, read prep
+  const char* prep_env = env.prep;
+  const bool prep_device = prep_env ? !strcmp(prep_env, "device") : MUSC_PREP_DEFAULT != 0;
+  o.prep_on_device = prep_device && !ev.prep_no_memory;  // (prep_reads_device ran prep_reads in its place)
+  // run_muscato, in front of the hot path
+  const char* res_env = env.results;
+  const bool env_device = res_env && !strcmp(res_env, "device"), env_host = res_env && !strcmp(res_env, "host");
+  const bool res_device = GPUs == 1 && nodd == 0 && (env_device || (!env_host && MUSC_RESULTS_DEFAULT));
+  if (nodd && GPUs == 1 && !env_host) o.note_odd = true;
+  // run_hot_path(keep0 = res_device ? &ctx0 : nullptr)
+  const int G = GPUs;
+  bool err = false;
+  const char* genv = env.gather;
+  const bool want_rccl = G > 1 && genv && !strcmp(genv, "rccl");
+  o.rccl = want_rccl && !ev.rccl_failed;
+  const bool overflow = ev.overflow;
+  bool replayed_on_device = false;
+  if (overflow) {
+    const char* mm_env = env.maxmatches;
+    const bool mm_env_device = mm_env && !strcmp(mm_env, "device"), mm_env_host = mm_env && !strcmp(mm_env, "host");
+    bool mm_device = mm_env_device || (!mm_env_host && MUSC_MAXMATCHES_DEFAULT);
+    if (mm_device && G > 1) {
+      o.note_gpus = true;
+      mm_device = false;
+    }
+    if (ev.replay_pass_failed) {
+      err = true;
+      mm_device = false;
+    }
+    if (!err && mm_device) {
+      if (!ev.replay_refused) replayed_on_device = true;
+      else mm_device = false;
+    }
+    if (!err && !mm_device) o.replayed_on_host = true;
+  }
+  o.replayed_on_device = replayed_on_device;
+  bool ctx0 = false, list_on_device = false;
+  if (res_device && G == 1 && !err) {
+    ctx0 = true;
+    list_on_device = !overflow || replayed_on_device;
+  }
+  if (err) {
+    o.died = true;
+    return o;
+  }
+  // run_muscato, results.txt and the side outputs
+  const char* side_env = env.side;
+  const bool side_env_device = side_env && !strcmp(side_env, "device"), side_env_host = side_env && !strcmp(side_env, "host");
+  const bool side_device = ctx0 && (side_env_device || (!side_env_host && MUSC_SIDE_DEFAULT));
+  o.results_on_device = ctx0;
+  o.list_on_device = list_on_device;
+  if (ctx0 && !side_device) ctx0 = false;
+  o.ctx_to_side = ctx0;
+  bool from_device = false;
+  if (ctx0) from_device = !ev.side_refused;
+  o.side_from_device = from_device;
+  return o;
+}
+
+Outcome new_run(const PlanEnv& env, int GPUs, size_t nodd, const Events& ev, const PlanDefaults& D) {
+  Outcome o;
+  Placement plan = make_placement(env, GPUs, D);
+  // stage_read_prep
+  if (plan.prep == Where::Device && ev.prep_no_memory) plan.demote(Demotion::PrepNoMemory);
+  o.prep_on_device = plan.prep == Where::Device;
+  // stage_target_files, stage_hot_path
+  if (nodd) plan.demote(Demotion::OddTargetBytes);
+  o.note_odd = plan.note_odd_targets;
+  // run_hot_path
+  if (plan.gather_rccl && ev.rccl_failed) plan.demote(Demotion::GatherFailed);
+  o.rccl = plan.gather_rccl;
+  if (ev.overflow) {
+    o.note_gpus = plan.note_replay_gpus;
+    if (ev.replay_pass_failed) {
+      plan.demote(Demotion::ReplayPassFailed);
+      o.died = true;
+      return o;
+    }
+    if (plan.maxmatches == Where::Device && ev.replay_refused) plan.demote(Demotion::ReplayRefused);
+    o.replayed_on_device = plan.maxmatches == Where::Device;
+    o.replayed_on_host = plan.maxmatches == Where::Host;
+  }
+  o.list_on_device = plan.list_on_device(ev.overflow);
+  // stage_results
+  o.results_on_device = plan.results == Where::Device;
+  o.ctx_to_side = plan.side == Where::Device;
+  EXPECT(!o.ctx_to_side || o.results_on_device);  // the side outputs need the list results.txt was ordered from
+  // stage_side_outputs
+  if (plan.side == Where::Device && ev.side_refused) plan.demote(Demotion::SideRefused);
+  o.side_from_device = plan.side == Where::Device;
+  return o;
+}
+
+void check_plan() {
+  static const char* const V[6] = {nullptr, "", "host", "device", "rccl", "junk"};
+  unsigned long long n = 0;
+  for (int d = 0; d < 16; d++) {
+    PlanDefaults D;
+    D.prep = d & 1, D.maxmatches = d & 2, D.results = d & 4, D.side = d & 8;
+    for (int e = 0; e < 6 * 6 * 6 * 6 * 6; e++) {
+      PlanEnv env;
+      env.prep = V[e % 6], env.maxmatches = V[e / 6 % 6], env.results = V[e / 36 % 6], env.side = V[e / 216 % 6], env.gather = V[e / 1296];
+      for (int gpus = 1; gpus <= 3; gpus++)
+        for (size_t nodd = 0; nodd <= 1; nodd++)
+          for (int x = 0; x < 64; x++) {
+            const Events ev = {(x & 1) != 0, (x & 2) != 0, (x & 4) != 0, (x & 8) != 0, (x & 16) != 0, (x & 32) != 0};
+            const Outcome a = old_run(env, gpus, nodd, ev, D), b = new_run(env, gpus, nodd, ev, D);
+            n++;
+            if (!(a == b) && failures < 20) {
+              fprintf(stderr, "plan differs: defaults %d env %s|%s|%s|%s|%s GPUs %d nodd %zu events %d\n", d, env.prep ? env.prep : "(unset)",
+                      env.maxmatches ? env.maxmatches : "(unset)", env.results ? env.results : "(unset)", env.side ? env.side : "(unset)",
+                      env.gather ? env.gather : "(unset)", gpus, nodd, x);
+              failures++;
+            }
+          }
+    }
+  }
+  printf("plan: %llu combinations\n", n);
+  // the compiled defaults are what the measurements behind them decided
+  const PlanDefaults compiled;
+  EXPECT(!compiled.prep && compiled.maxmatches && compiled.results && compiled.side);
+  // and the two parse rules differ where the comment of cli_plan.hpp says they do
+  EXPECT(place_prep_by_env("junk", true) == Where::Host && place_by_env("junk", true) == Where::Device);
+  EXPECT(place_prep_by_env("", true) == Where::Host && place_by_env("", true) == Where::Device);
+  EXPECT(place_prep_by_env(nullptr, true) == Where::Device && place_by_env(nullptr, true) == Where::Device);
+}
+
+// ---- the names ------------------------------------------------------------------------------------------------
+
+// a name in a heap block of its exact size (no terminator, no slack): a read past it is the sanitizer's to see
+struct Block {
+  std::unique_ptr<char[]> p;
+  size_t n;
+  explicit Block(const std::string& s) : p(new char[s.size()]), n(s.size()) { s.copy(p.get(), n); }
+  std::string str() const { return std::string(p.get(), n); }
+};
+
+// prep_reads as it was: names clipped when parsed, a group sorted as pointers to the whole names
+std::string old_host_names(const std::vector<Block>& raw) {
+  std::vector<std::string> names;
+  for (auto& b : raw) {
+    std::string rn = b.str();
+    if (rn.size() > 1000) rn = rn.substr(0, 995) + "...";
+    names.push_back(std::move(rn));
+  }
+  std::vector<const std::string*> grp;
+  for (auto& s : names) grp.push_back(&s);
+  std::sort(grp.begin(), grp.end(), [](const std::string* a, const std::string* b) { return *a < *b; });
+  std::string na;
+  for (size_t i = 0; i < grp.size(); i++) {
+    if (i) na += ';';
+    na += grp[i]->substr(0, grp[i]->find('\t'));
+  }
+  if (na.size() > 1000) na = na.substr(0, 996) + "...";
+  return na;
+}
+
+// prep_reads_device as it was: the clipped names of a group sorted as strings
+std::string old_device_names(const std::vector<Block>& raw) {
+  std::vector<std::string> grp;
+  for (auto& b : raw) {
+    std::string rn = b.str();
+    if (rn.size() > 1000) rn = rn.substr(0, 995) + "...";
+    grp.push_back(std::move(rn));
+  }
+  std::sort(grp.begin(), grp.end());
+  std::string na;
+  for (size_t i = 0; i < grp.size(); i++) {
+    if (i) na += ';';
+    na += grp[i].substr(0, grp[i].find('\t'));
+  }
+  if (na.size() > 1000) na = na.substr(0, 996) + "...";
+  return na;
+}
+
+std::string new_names(const std::vector<Block>& raw) {
+  std::vector<std::string> grp;
+  for (auto& b : raw) grp.push_back(clip_name(b.str()));
+  return join_group_names(grp.data(), grp.data() + grp.size());
+}
+
+// all three agree (so the two old loops agree with each other: one comparison serves both callers); returns the join
+std::string check_group(const std::vector<std::string>& group) {
+  std::vector<Block> raw;
+  for (auto& s : group) raw.emplace_back(s);
+  const std::string a = old_host_names(raw), b = old_device_names(raw), c = new_names(raw);
+  EXPECT(a == b);
+  EXPECT(a == c);
+  return c;
+}
+
+void check_names() {
+  const std::string x999(999, 'x'), x1000(1000, 'y'), x1001(1001, 'z');
+  EXPECT(clip_name(x999) == x999 && clip_name(x1000) == x1000);
+  EXPECT(clip_name(x1001) == std::string(995, 'z') + "...");
+  EXPECT(check_group({x999}) == x999);
+  EXPECT(check_group({x1000}) == x1000);
+  EXPECT(check_group({x1001}).size() == 998);
+  EXPECT(check_group({x1001, x999, x1000}) == x999.substr(0, 996) + "...");
+  // a join of exactly 1000 bytes stays, one of 1001 is clipped
+  EXPECT(check_group({std::string(500, 'b'), std::string(499, 'a')}) == std::string(499, 'a') + ";" + std::string(500, 'b'));
+  EXPECT(check_group({std::string(500, 'b'), std::string(500, 'a')}) == std::string(500, 'a') + ";" + std::string(495, 'b') + "...");
+  // a clipped name cut at a tab beyond byte 995 keeps its "..."; one cut before it does not
+  EXPECT(check_group({std::string(10, 'q') + "\t" + std::string(1200, 'r')}) == std::string(10, 'q'));
+  EXPECT(check_group({"\tabc"}) == "");                    // a tab at byte 0
+  EXPECT(check_group({"\tabc", "d"}) == ";d");
+  EXPECT(check_group({"a\tb\tc"}) == "a");                 // two tabs
+  EXPECT(check_group({"n\tz", "n\ta", "m"}) == "m;n;n");   // equal up to the tab, different after it
+  EXPECT(check_group({"n\tz", "n", "n\t"}) == "n;n;n");
+  EXPECT(check_group({"only"}) == "only");                 // a single name
+  EXPECT(check_group({""}) == "");                         // an empty name
+  EXPECT(check_group({"", "a", ""}) == ";;a");
+  EXPECT(check_group({"b;a", "a"}) == "a;b;a");
+  EXPECT(check_group({"B", "a", "\x80", "A"}) == std::string("A;B;a;\x80"));  // bytewise: unsigned
+
+  std::mt19937 rng(20);
+  static const char alphabet[] = {'a', 'b', '\t', ';', ' ', '\xff'};
+  unsigned long long n = 0;
+  for (int it = 0; it < 4000; it++) {
+    std::vector<std::string> group(1 + rng() % 8);
+    for (auto& s : group) {
+      const unsigned kind = rng() % 16;
+      const size_t len = kind == 0 ? 990 + rng() % 20 : kind == 1 ? 120 + rng() % 140 : rng() % 12;
+      for (size_t i = 0; i < len; i++) s += alphabet[rng() % (kind ? 6 : 3)];
+    }
+    check_group(group);
+    n++;
+  }
+  printf("names: %llu random groups\n", n);
+}
+
+}  // namespace
+
+int main() {
+  check_plan();
+  check_names();
+  if (failures) {
+    fprintf(stderr, "%d failures\n", failures);
+    return 1;
+  }
+  puts("ok");
+  return 0;
+}

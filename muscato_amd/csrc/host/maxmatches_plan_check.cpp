@@ -34,7 +34,7 @@ static uint32_t qinsert_hole(std::vector<std::pair<uint32_t, uint32_t>>& heap, u
   return size + 1 > max_matches ? max_matches : size + 1;
 }
 
-// cmd/muscato_confirm/main.go:424-448 as apply_maxmatches of muscato_host.hpp writes it: append, swap up, cut
+// cmd/muscato_confirm/main.go:424-448 as apply_maxmatches of cli_maxmatches_host.hpp writes it: append, swap up, cut
 static void qinsert_literal(std::vector<std::pair<uint32_t, uint32_t>>& q, uint32_t max_matches, uint32_t mm, uint32_t idx) {
   q.push_back({mm, idx});
   size_t ii = q.size() - 1;

@@ -42,8 +42,9 @@ int main(int argc, char** argv) {
     one.GPUs = 1;
     std::string out;
     if (!reads.empty()) {
-      musc_ctx* c = nullptr;
-      if (musc_init(cfg.Device, &c)) throw Die(1, std::string("muscato_confirm: ") + musc_last_error(nullptr));
+      Ctx ctx = Ctx::init(cfg.Device);
+      if (!ctx) throw Die(1, std::string("muscato_confirm: ") + musc_last_error(nullptr));
+      musc_ctx* const c = ctx.get();
       const Concat db = concat(targets.begin(), targets.end(), [](const std::string& s) -> const std::string& { return s; });
       const Concat rd = concat(reads.begin(), reads.end(), [](const UniqueRead& u) -> const std::string& { return u.seq; });
       musc_params P = to_params(one);
@@ -53,21 +54,22 @@ int main(int argc, char** argv) {
       if (musc_db_load_ascii(c, db.buf.data(), db.off.data(), (uint32_t)targets.size(), 0) ||
           musc_reads_load_ascii(c, rd.buf.data(), rd.off.data(), reads.size(), 0) || musc_match(c, &P, &h, &n))
         throw Die(1, std::string("muscato_confirm: ") + musc_last_error(c));
+      LibHits own(h);
       std::vector<musc_hit> hits(h, h + n);
-      musc_free_hits(h);
+      own.reset();
       musc_stats st;
       musc_get_stats(c, &st);
       if (st.n_overflow_blocks != 0 && st.n_overflow_blocks != ~0ull) {
         uint32_t *pr = nullptr, *pw = nullptr;
         uint64_t np = 0;
-        if (musc_overflow_probes(c, &pr, &pw, &np)) throw Die(1, std::string("muscato_confirm: ") + musc_last_error(c));
+        const int rc = musc_overflow_probes(c, &pr, &pw, &np);
+        const LibU32 own_r(pr), own_w(pw);
+        if (rc) throw Die(1, std::string("muscato_confirm: ") + musc_last_error(c));
         size_t ntrunc = 0;
         hits = apply_maxmatches(one, reads, targets, std::move(hits), pr, pw, np, &ntrunc);
-        musc_free_u32(pr);
-        musc_free_u32(pw);
         log.printf("%zu blocks truncated at MaxMatches", ntrunc);
       }
-      musc_destroy(c);
+      ctx.reset();
       for (auto& x : hits) {
         const std::string& r = reads[x.read_idx].seq;
         out += r;

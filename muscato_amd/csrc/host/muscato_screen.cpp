@@ -29,8 +29,9 @@ int main(int argc, char** argv) {
     for (auto& l : split_lines(read_maybe_sz(cfg.GeneFileName))) targets.push_back(l.substr(0, l.find('\t')));
     log.printf("%zu reads, %zu targets", reads.size(), targets.size());
 
-    musc_ctx* c = nullptr;
-    if (musc_init(cfg.Device, &c)) throw Die(1, std::string("muscato_screen: ") + musc_last_error(nullptr));
+    const Ctx ctx = Ctx::init(cfg.Device);
+    if (!ctx) throw Die(1, std::string("muscato_screen: ") + musc_last_error(nullptr));
+    musc_ctx* const c = ctx.get();
     const Concat db = concat(targets.begin(), targets.end(), [](const std::string& s) -> const std::string& { return s; });
     const Concat rd = concat(reads.begin(), reads.end(), [](const std::string& s) -> const std::string& { return s; });
     if (musc_db_load_ascii(c, db.buf.data(), db.off.data(), (uint32_t)targets.size(), 0) ||
@@ -48,10 +49,11 @@ int main(int argc, char** argv) {
       musc_hit* h = nullptr;
       uint64_t n = 0;
       if (musc_match(c, &P, &h, &n)) throw Die(1, std::string("muscato_screen: ") + musc_last_error(c));
+      LibHits own(h);
       const int q1 = cfg.Windows[k], q2 = q1 + ww;
       std::vector<std::pair<uint32_t, uint32_t>> cand(n);
       for (uint64_t i = 0; i < n; i++) cand[i] = std::make_pair(h[i].gene_idx, h[i].pos + (uint32_t)q1);
-      musc_free_hits(h);
+      own.reset();
       std::sort(cand.begin(), cand.end());
       cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
       std::string out;
@@ -78,7 +80,6 @@ int main(int argc, char** argv) {
       spit(join_path(tmpdir, "bmatch_" + std::to_string(k) + ".txt.sz"), sz_encode(out));
       log.printf("window %zu: %zu candidates", k, cand.size());
     }
-    musc_destroy(c);
     log.printf("Done checking target sequences for matches");
     return 0;
   } catch (const Die& d) {
