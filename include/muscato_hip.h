@@ -506,6 +506,39 @@ int musc_gather_rccl(musc_ctx* const* ctxs, int n, const uint64_t* read_base, mu
  * is looked up once per process: MUSC_RCCL_LIB names it, else the ROCm tree's, else the loader's. */
 int musc_rccl_probe(char* msg, uint64_t cap);
 
+/* ---- the gene file from its raw bytes (additions; MUSC_ABI_VERSION is unchanged) -----------------------------------
+ * The reference writes GeneFileName through snappy's framed writer (cmd/muscato_prep_targets/main.go:246-258) and reads
+ * it back under bufio.ScanLines (cmd/muscato_screen/main.go:408-452).  These two calls do on the device what the host
+ * chain slurp -> sz_decode -> split_lines -> cut at the first tab -> concat -> musc_db_load_ascii does.
+ *
+ * musc_sz_decode: `bytes` is a framed snappy stream in host memory.  *nout = the decoded length; dst == NULL only
+ * sizes (the chunk headers are walked, no block is decoded).  Otherwise the decoded bytes go to dst (host, or device at
+ * any alignment when dst_on_device != 0), capacity >= *nout bytes.  A failed call leaves dst as it was.
+ *
+ * musc_db_load_text: `bytes` is the raw gene file.  framed = 1: a framed stream; 0: plain text; -1: a framed stream
+ * exactly when it begins with the ten-byte stream identifier.  A framed stream must be a host pointer (on_device != 0
+ * with one: 2).  Plain text may be a device pointer at any alignment; bytes outside [bytes, bytes + nbytes) are never
+ * read.  Lines are bufio's: a line ends at '\n', one trailing '\r' is dropped, an unterminated last line is kept,
+ * there is no empty line after a final '\n'.  The target is the line up to its first tab (a '\r' in front of that
+ * tab is data).  Afterwards the context holds exactly the database musc_db_load_ascii holds for those targets.  A
+ * failed call leaves no database.
+ *
+ * Codes: 2 bad arguments, and no line at all ("database has no sequences"); 10 a HIP failure ("out of memory" in the
+ * text when an allocation failed); 12 a refusal: a chunk declares more than 65 536 uncompressed bytes, which the
+ * framing format forbids (the caller falls back to its host decoder); 13 a bad stream: a framing, block or checksum
+ * error -- the text names the chunk's index (counting every chunk of the stream from 0) and the error. */
+typedef struct musc_db_text_info {
+  uint64_t n_targets, n_bases;      /* lines, and bases over all of them                          */
+  uint64_t n_odd;                   /* target bytes that are none of A C G T X                    */
+  uint32_t first_odd_target, reserved;
+  uint64_t n_text_bytes, n_chunks;  /* decoded text; data chunks of the stream (0 for plain text) */
+  float ms_decode, ms_parse;        /* device time: frames -> text; text -> planes + seq_off      */
+} musc_db_text_info;
+int musc_sz_decode(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint8_t* dst, uint64_t capacity,
+                   int dst_on_device, uint64_t* nout);
+int musc_db_load_text(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int on_device, int framed,
+                      musc_db_text_info* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,15 @@ class MuscFastqPrep(ctypes.Structure):
     ]
 
 
+class MuscDbTextInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_targets", ctypes.c_uint64), ("n_bases", ctypes.c_uint64), ("n_odd", ctypes.c_uint64),
+        ("first_odd_target", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("n_text_bytes", ctypes.c_uint64), ("n_chunks", ctypes.c_uint64),
+        ("ms_decode", ctypes.c_float), ("ms_parse", ctypes.c_float),
+    ]
+
+
 # every symbol include/muscato_hip.h declares
 SYMBOLS = [
     "musc_abi_version", "musc_init", "musc_destroy", "musc_last_error", "musc_reload_env",
@@ -75,6 +84,7 @@ SYMBOLS = [
     "musc_results_last_ms", "musc_results_number_key",
     "musc_side_prepare", "musc_side_text", "musc_side_last_ms",
     "musc_maxmatches_apply", "musc_maxmatches_last_ms", "musc_maxmatches_last_detail",
+    "musc_sz_decode", "musc_db_load_text",
 ]
 
 # `which` of musc_side_text (include/muscato_hip.h)
@@ -167,6 +177,10 @@ def load() -> ctypes.CDLL:
     lib.musc_maxmatches_last_ms.restype = ctypes.c_int
     lib.musc_maxmatches_last_detail.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]
     lib.musc_maxmatches_last_detail.restype = ctypes.c_int
+    lib.musc_sz_decode.argtypes = [vp, vp, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
+    lib.musc_sz_decode.restype = ctypes.c_int
+    lib.musc_db_load_text.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MuscDbTextInfo)]
+    lib.musc_db_load_text.restype = ctypes.c_int
     for name in ("musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits",
                  "musc_results_text", "musc_results_last_ms", "musc_results_number_key",
                  "musc_side_prepare", "musc_side_text", "musc_side_last_ms"):

@@ -24,6 +24,19 @@ class MuscatoError(RuntimeError):
 
 
 @dataclass
+class DbTextInfo:
+    """musc_db_text_info: what Engine.load_db_text found in the gene file."""
+    n_targets: int
+    n_bases: int
+    n_odd: int               # target bytes that are none of A C G T X
+    first_odd_target: int
+    n_text_bytes: int
+    n_chunks: int            # data chunks of the stream (0 for plain text)
+    ms_decode: float
+    ms_parse: float
+
+
+@dataclass
 class Config:
     """utils/config.go:10-101 -- same names; defaults of cmd/muscato/main.go:833-904."""
     ReadFileName: str = ""
@@ -209,6 +222,34 @@ class Engine:
         self._check(self._lib.musc_db_load_packed(self._h, packed.ctypes.data, mp, off.ctypes.data, len(off) - 1),
                     "musc_db_load_packed")
         self.n_targets = len(off) - 1
+
+    def sz_decode(self, data: bytes) -> bytes:
+        """A framed snappy stream decoded on the GPU (musc_sz_decode)."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        sp = src.ctypes.data if len(src) else None
+        n = ctypes.c_uint64()
+        self._check(self._lib.musc_sz_decode(self._h, sp, len(src), None, 0, 0, ctypes.byref(n)), "musc_sz_decode")
+        out = np.empty(max(int(n.value), 1), dtype=np.uint8)
+        self._check(self._lib.musc_sz_decode(self._h, sp, len(src), out.ctypes.data, int(n.value), 0, ctypes.byref(n)),
+                    "musc_sz_decode")
+        return out[:int(n.value)].tobytes()
+
+    def load_db_text(self, data, framed: int = -1, on_device: bool = False) -> "DbTextInfo":
+        """The raw bytes of a gene file -- a framed snappy stream or plain text, one target per line up to its first
+        tab -- decoded, split and packed on the GPU (musc_db_load_text).  data: bytes, or (on_device) a pair
+        (device pointer, nbytes) of plain text at any alignment.  framed: 1, 0, or -1 to go by the stream identifier."""
+        if on_device:
+            ptr, nbytes = data
+        else:
+            buf = np.frombuffer(data, dtype=np.uint8)
+            ptr, nbytes = (buf.ctypes.data if len(buf) else None), len(buf)
+        info = _lib.MuscDbTextInfo()
+        self.n_targets = 0
+        self._check(self._lib.musc_db_load_text(self._h, ptr, int(nbytes), 1 if on_device else 0, int(framed), ctypes.byref(info)),
+                    "musc_db_load_text")
+        self.n_targets = int(info.n_targets)
+        return DbTextInfo(int(info.n_targets), int(info.n_bases), int(info.n_odd), int(info.first_odd_target),
+                          int(info.n_text_bytes), int(info.n_chunks), float(info.ms_decode), float(info.ms_parse))
 
     def build_index(self, window_width: int) -> None:
         self._check(self._lib.musc_db_build_index(self._h, int(window_width)), "musc_db_build_index")

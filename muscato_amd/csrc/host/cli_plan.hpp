@@ -1,5 +1,5 @@
 // cli_plan.hpp -- where each stage of a `muscato` run takes place, decided once.  Plain C++17: no
-// library call and no getenv here; the driver reads the five environment values in one place and passes them in.
+// library call and no getenv here; the driver reads the six environment values in one place and passes them in.
 // Included by muscato_host.hpp and by cli_plan_check.cpp, the stand-alone program that holds it to the boolean
 // expressions it replaced, under the sanitizers.
 #pragma once
@@ -36,11 +36,20 @@ namespace musc {
 #define MUSC_PREP_DEFAULT_DEVICE 0
 #endif
 
+// 1: the CLI decodes, splits and packs the gene file on the device unless MUSC_TARGETS=host; 0: only with
+// MUSC_TARGETS=device.  Measured (profiles/targets_load.py): the laps `windows check, target files` and
+// `hot path (init, load, match)` of a 2 M-read run over a 100 MB gene file add up to 0.229 s with the gene file on the
+// device against 0.503 s on the host, the runs of either side within 0.021 s of each other.
+#ifndef MUSC_TARGETS_DEFAULT_DEVICE
+#define MUSC_TARGETS_DEFAULT_DEVICE 1
+#endif
+
 enum class Where { Host, Device };
 
-// the five environment values as the process has them, each possibly null
+// the six environment values as the process has them, each possibly null
 struct PlanEnv {
   const char *prep = nullptr, *maxmatches = nullptr, *results = nullptr, *side = nullptr, *gather = nullptr;
+  const char* targets = nullptr;
 };
 
 // what a stage does when its variable does not say: the *_DEFAULT_DEVICE macros (arguments, so that the check program
@@ -48,10 +57,12 @@ struct PlanEnv {
 struct PlanDefaults {
   bool prep = MUSC_PREP_DEFAULT_DEVICE != 0, maxmatches = MUSC_MAXMATCHES_DEFAULT_DEVICE != 0,
        results = MUSC_RESULTS_DEFAULT_DEVICE != 0, side = MUSC_SIDE_DEFAULT_DEVICE != 0;
+  bool targets = MUSC_TARGETS_DEFAULT_DEVICE != 0;
 };
 
 // The parse rules, which are not the same for every variable (and stay so here):
-//   MUSC_RESULTS, MUSC_SIDE, MUSC_MAXMATCHES   "device" and "host" say so; unset, empty and every other value mean the
+//   MUSC_RESULTS, MUSC_SIDE, MUSC_MAXMATCHES,
+//   MUSC_TARGETS                               "device" and "host" say so; unset, empty and every other value mean the
 //                                              compiled default
 //   MUSC_PREP                                  unset means the compiled default; once set, only "device" means the
 //                                              device: empty and every other value mean the host
@@ -76,6 +87,9 @@ enum class Demotion {
   ReplayPassFailed,  // the reload or the pass in front of the replay failed (the run ends with that error)
   ReplayRefused,     // musc_maxmatches_apply returned 12 (refusal) or 10 (no memory)
   SideRefused,       // musc_side_prepare returned 12: a gene text that is not name\tlen without blanks
+  TargetsNoMemory,   // musc_db_load_text found no device memory (10, "out of memory")
+  TargetsRefused,    // ... returned 12: a chunk that declares more than 65 536 bytes, which sz_decode takes
+  TargetsBadStream,  // ... returned 13: the host decoder then ends the run with its own message
 };
 
 struct Placement {
@@ -86,6 +100,7 @@ struct Placement {
   bool note_odd_targets = false;  // "results on the host: the targets hold bytes that are none of ACGTX ..."
   int gpus = 1;
   bool results_env_host = false;
+  Where targets = Where::Host;  // the gene file: snappy frames, lines, 2-bit pack
 
   // The one place a stage is moved to the host.  The side outputs are made from the ordered list behind results.txt,
   // which exists on the device only when results.txt was ordered there: whatever takes the results to the host takes
@@ -105,6 +120,9 @@ struct Placement {
       case Demotion::ReplayPassFailed:
       case Demotion::ReplayRefused: maxmatches = Where::Host; break;
       case Demotion::SideRefused: side = Where::Host; break;
+      case Demotion::TargetsNoMemory:
+      case Demotion::TargetsRefused:
+      case Demotion::TargetsBadStream: targets = Where::Host; break;
     }
   }
 
@@ -126,6 +144,7 @@ inline Placement make_placement(const PlanEnv& env, int gpus, const PlanDefaults
   p.results = place_by_env(env.results, def.results);
   p.side = p.results == Where::Device ? place_by_env(env.side, def.side) : Where::Host;
   p.gather_rccl = gpus > 1 && env.gather && !strcmp(env.gather, "rccl");
+  p.targets = place_by_env(env.targets, def.targets);
   if (gpus > 1) p.demote(Demotion::SeveralGpus);
   return p;
 }

@@ -164,23 +164,23 @@ inline std::string device_text(const char* what, uint64_t nrec, uint64_t nbytes,
 // The same bytes from the device (musc_results_*): `c` holds the database and every read; device_list =
 // the tuples are the list the last pass left on the device, else `hits`.  Throws Die on a library error.
 inline std::string results_text_device(musc_ctx* c, bool device_list, const std::vector<musc_hit>& hits, const std::vector<UniqueRead>& reads,
-                                       const std::vector<std::string>& targets, const std::map<uint64_t, std::string>& id_rest,
+                                       size_t n_targets, const std::map<uint64_t, std::string>& id_rest,
                                        float* ms_order, float* ms_text) {
   auto check = [&](int rc) { if (rc) throw Die(1, std::string("results on the device failed: ") + musc_last_error(c)); };
   {
     std::string text;
-    std::vector<uint64_t> off(targets.size() + 1, 0);
-    std::vector<uint8_t> absent(targets.size(), 1);
+    std::vector<uint64_t> off(n_targets + 1, 0);
+    std::vector<uint8_t> absent(n_targets, 1);
     for (auto& kv : id_rest) {
-      if (kv.first >= targets.size()) continue;  // (no tuple names such a gene)
+      if (kv.first >= n_targets) continue;  // (no tuple names such a gene)
       absent[kv.first] = 0;
       off[kv.first + 1] = kv.second.size();
     }
-    for (size_t g = 0; g < targets.size(); g++) off[g + 1] += off[g];
+    for (size_t g = 0; g < n_targets; g++) off[g + 1] += off[g];
     text.resize(off.back());
     for (auto& kv : id_rest)
-      if (kv.first < targets.size()) memcpy(&text[off[kv.first]], kv.second.data(), kv.second.size());
-    check(musc_results_set_gene_text(c, text.data(), off.data(), absent.data(), (uint32_t)targets.size()));
+      if (kv.first < n_targets) memcpy(&text[off[kv.first]], kv.second.data(), kv.second.size());
+    check(musc_results_set_gene_text(c, text.data(), off.data(), absent.data(), (uint32_t)n_targets));
   }
   {
     std::string text;
@@ -432,13 +432,43 @@ struct Shards {
   std::vector<uint64_t> base;  // the first read of each
 };
 
-inline Shards match_shards(const Config& cfg, const musc_params& P, const std::vector<UniqueRead>& reads,
-                           const std::vector<std::string>& targets) {
+// The gene file and the id file.  The targets as strings are host data that only host stages need (results_text and
+// the MaxMatches replay on the host): targets() makes them on first use, with the host chain (decode_maybe_sz,
+// split_lines, the cut at the first tab).  When the gene file went through the device (MUSC_TARGETS), ctx0
+// is GPU 0's context with the database loaded and gene_raw the file's bytes, which the other GPUs load themselves.
+struct TargetFiles {
+  size_t n_targets = 0;                     // gene number = line index
+  std::map<uint64_t, std::string> id_rest;  // gene number -> "name\tlen"
+  std::string gene_path;
+  mutable std::string gene_raw;  // (given up to the host chain unless the GPUs still load it)
+  bool on_device = false;        // the database comes from musc_db_load_text of gene_raw
+  Ctx ctx0;
+  const std::vector<std::string>& targets() const {
+    if (!have_strings) {
+      const std::string text = on_device ? decode_maybe_sz(gene_raw, gene_path) : decode_maybe_sz(std::move(gene_raw), gene_path);
+      for (auto& l : split_lines(text)) strings.push_back(l.substr(0, l.find('\t')));
+      have_strings = true;
+    }
+    return strings;
+  }
+  int gene_framed() const { return ends_with(to_lower(gene_path), ".sz") ? 1 : -1; }  // as decode_maybe_sz decides
+
+ private:
+  mutable std::vector<std::string> strings;
+  mutable bool have_strings = false;
+};
+
+inline Shards match_shards(const Config& cfg, const musc_params& P, const std::vector<UniqueRead>& reads, TargetFiles& tf) {
   const int G = cfg.GPUs;
-  const Concat db = concat(targets.begin(), targets.end(), [](const std::string& s) -> const std::string& { return s; });
-  if (targets.size() >= 0xFFFFFFFFull) throw Die(1, "too many targets");
+  Concat db;
+  if (!tf.on_device) {
+    const std::vector<std::string>& targets = tf.targets();
+    db = concat(targets.begin(), targets.end(), [](const std::string& s) -> const std::string& { return s; });
+    if (targets.size() >= 0xFFFFFFFFull) throw Die(1, "too many targets");
+  }
   Shards sh;
   sh.ctx.resize(G);
+  if (tf.on_device) sh.ctx[0] = std::move(tf.ctx0);
   sh.base.assign(G, 0);
   std::vector<std::string> errs(G);
   std::vector<std::thread> th;
@@ -446,14 +476,17 @@ inline Shards match_shards(const Config& cfg, const musc_params& P, const std::v
     const size_t lo = reads.size() * (size_t)g / G, hi = reads.size() * (size_t)(g + 1) / G;
     sh.base[g] = lo;
     th.emplace_back([&, g, lo, hi] {
-      sh.ctx[g] = Ctx::init(cfg.Device + g);
+      const bool loaded = sh.ctx[g] != nullptr;  // GPU 0's context came with the database (stage_target_files)
+      if (!loaded) sh.ctx[g] = Ctx::init(cfg.Device + g);
       musc_ctx* c = sh.ctx[g].get();
       if (!c) { errs[g] = musc_last_error(nullptr); return; }
-      musc_db_set_partition_bases(c, (uint64_t)cfg.DbPartitionBases);  // (the MaxMatches replay reuses the first context)
+      if (!loaded) musc_db_set_partition_bases(c, (uint64_t)cfg.DbPartitionBases);  // (the MaxMatches replay reuses the first context)
       const Concat rd = concat(reads.begin() + lo, reads.begin() + hi, [](const UniqueRead& u) -> const std::string& { return u.seq; });
       uint64_t n = 0;
-      if (musc_db_load_ascii(c, db.buf.data(), db.off.data(), (uint32_t)targets.size(), 0) ||
-          musc_reads_load_ascii(c, rd.buf.data(), rd.off.data(), hi - lo, 0) || musc_match_device(c, &P, &n))
+      const int db_rc = loaded ? 0
+                        : tf.on_device ? musc_db_load_text(c, (const uint8_t*)tf.gene_raw.data(), tf.gene_raw.size(), 0, tf.gene_framed(), nullptr)
+                                       : musc_db_load_ascii(c, db.buf.data(), db.off.data(), (uint32_t)tf.n_targets, 0);
+      if (db_rc || musc_reads_load_ascii(c, rd.buf.data(), rd.off.data(), hi - lo, 0) || musc_match_device(c, &P, &n))
         errs[g] = musc_last_error(c);
     });
   }
@@ -612,10 +645,9 @@ inline void replay_on_host(musc_ctx* c, const ReplayPass& rp, const Config& cfg,
              out->size(), rp.t_replay - rp.t_load);
 }
 
-inline HotResult run_hot_path(const Config& cfg, const std::vector<UniqueRead>& reads, const std::vector<std::string>& targets,
-                              Placement& plan, Logger& log) {
+inline HotResult run_hot_path(const Config& cfg, const std::vector<UniqueRead>& reads, TargetFiles& tf, Placement& plan, Logger& log) {
   const musc_params P = to_params(cfg);
-  Shards sh = match_shards(cfg, P, reads, targets);
+  Shards sh = match_shards(cfg, P, reads, tf);
   HotResult r;
   const std::string gather_err = gather_hits(cfg, sh, plan, log, &r.hits);
   musc_get_stats(sh.ctx[0].get(), &r.st);
@@ -631,7 +663,7 @@ inline HotResult run_hot_path(const Config& cfg, const std::vector<UniqueRead>& 
     musc_ctx* c = sh.ctx[0].get();
     const ReplayPass rp = replay_pass(c, P, reads, plan);
     if (plan.maxmatches == Where::Device) replay_on_device(c, rp, plan, log, &r.hits);
-    if (plan.maxmatches == Where::Host) replay_on_host(c, rp, cfg, reads, targets, log, &r.hits);
+    if (plan.maxmatches == Where::Host) replay_on_host(c, rp, cfg, reads, tf.targets(), log, &r.hits);
     r.st.n_overflow_blocks = 0;  // handled exactly
   }
   r.list_on_device = plan.list_on_device(overflow);
@@ -643,9 +675,10 @@ inline HotResult run_hot_path(const Config& cfg, const std::vector<UniqueRead>& 
 // the pipeline (cmd/muscato/main.go:1005-1058) as its stages, in the order run_muscato calls them
 // ------------------------------------------------------------------------------------
 
-// the five values the plan is made from: the only place the host tools read the environment
+// the six values the plan is made from: the only place the host tools read the environment
 inline PlanEnv plan_env_of_process() {
-  return PlanEnv{getenv("MUSC_PREP"), getenv("MUSC_MAXMATCHES"), getenv("MUSC_RESULTS"), getenv("MUSC_SIDE"), getenv("MUSC_GATHER")};
+  return PlanEnv{getenv("MUSC_PREP"), getenv("MUSC_MAXMATCHES"), getenv("MUSC_RESULTS"), getenv("MUSC_SIDE"), getenv("MUSC_GATHER"),
+                 getenv("MUSC_TARGETS")};
 }
 
 // setupEnvs/makeTemp/setupLog/saveConfig (cmd/muscato/main.go:906-967, 680-706)
@@ -701,25 +734,56 @@ inline void stage_window_check(const Config& cfg, const std::vector<UniqueRead>&
   }
 }
 
-struct TargetFiles {
-  std::vector<std::string> targets;         // gene number = line index
-  std::map<uint64_t, std::string> id_rest;  // gene number -> "name\tlen"
-};
+// The gene file on the device (MUSC_TARGETS): GPU 0's context is made here and musc_db_load_text takes the
+// file's bytes to the resident database; the census of odd bytes comes back with it.  False when the stage left the
+// device -- no memory (10), a chunk beyond the format's 65 536 bytes (12), a bad stream (13) -- and the host chain is
+// to run in its place: a corrupt file then ends the run with the host decoder's own message.
+inline bool load_targets_device(const Config& cfg, TargetFiles& tf, Placement& plan, Logger& log, size_t* nodd, size_t* first_t) {
+  Ctx ctx = Ctx::init(cfg.Device);
+  if (!ctx) throw hot_path_failed("GPU " + std::to_string(cfg.Device) + ": " + musc_last_error(nullptr) + "\n");
+  musc_db_set_partition_bases(ctx.get(), (uint64_t)cfg.DbPartitionBases);
+  musc_db_text_info info;
+  const int rc = musc_db_load_text(ctx.get(), (const uint8_t*)tf.gene_raw.data(), tf.gene_raw.size(), 0, tf.gene_framed(), &info);
+  if (rc) {
+    const std::string e = musc_last_error(ctx.get());
+    if (rc == 12) plan.demote(Demotion::TargetsRefused);
+    else if (rc == 13) plan.demote(Demotion::TargetsBadStream);
+    else if (rc == 10 && e.find("out of memory") != std::string::npos) plan.demote(Demotion::TargetsNoMemory);
+    else throw hot_path_failed("GPU " + std::to_string(cfg.Device) + ": " + e + "\n");
+    log.printf("targets on the host: the device stage returned %d (%s)", rc, e.c_str());
+    return false;
+  }
+  log.printf("targets on the device: %llu targets, %llu bases, %llu bytes of text in %llu chunks, decode %.3f ms, parse %.3f ms",
+             (unsigned long long)info.n_targets, (unsigned long long)info.n_bases, (unsigned long long)info.n_text_bytes,
+             (unsigned long long)info.n_chunks, info.ms_decode, info.ms_parse);
+  tf.n_targets = info.n_targets;
+  tf.on_device = true;
+  tf.ctx0 = std::move(ctx);
+  *nodd = info.n_odd;
+  *first_t = info.first_odd_target;
+  return true;
+}
 
 // gene file: sequence = text before the first tab, gene number = line index
 // (cmd/muscato_screen/main.go:439-452); id file: "%011d\tname\tlen" (join field 1)
 inline TargetFiles stage_target_files(const Config& cfg, Placement& plan, Logger& log) {
   TargetFiles tf;
-  for (auto& l : split_lines(read_maybe_sz(cfg.GeneFileName))) tf.targets.push_back(l.substr(0, l.find('\t')));
+  tf.gene_path = cfg.GeneFileName;
+  tf.gene_raw = slurp(cfg.GeneFileName);
+  size_t nodd = 0, first_t = 0;  // target bytes that are none of ACGTX
+  if (plan.targets == Where::Device) load_targets_device(cfg, tf, plan, log, &nodd, &first_t);
+  if (plan.targets == Where::Host) {
+    const std::vector<std::string>& targets = tf.targets();
+    tf.n_targets = targets.size();
+    for (size_t t = 0; t < targets.size(); t++)
+      for (unsigned char ch : targets[t])
+        if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T' && ch != 'X' && nodd++ == 0) first_t = t;
+  }
   // Targets are compared as 2-bit bases + an "X" plane: every byte that is not A, C, G or T is an
   // X here.  muscato_prep_targets writes nothing else (it leaves the LAST FASTA record un-substituted,
   // cmd/muscato_prep_targets/main.go:204-212), but a hand-made gene file may: the reference then
   // compares the raw byte, so an 'N' in a target would mismatch an 'X' in a read where this tool
   // counts a match.  Say so instead of differing silently.
-  size_t nodd = 0, first_t = 0;  // target bytes that are none of ACGTX
-  for (size_t t = 0; t < tf.targets.size(); t++)
-    for (unsigned char ch : tf.targets[t])
-      if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T' && ch != 'X' && nodd++ == 0) first_t = t;
   if (nodd) {
     fprintf(stderr, "Warning: %zu target bytes are none of ACGTX (first in target %zu); they are treated as X\n", nodd, first_t);
     log.printf("%zu target bytes are none of ACGTX (first in target %zu): treated as X; the reference compares them "
@@ -737,12 +801,12 @@ inline TargetFiles stage_target_files(const Config& cfg, Placement& plan, Logger
   return tf;
 }
 
-inline HotResult stage_hot_path(const Config& cfg, const std::vector<UniqueRead>& reads, const TargetFiles& tf, Placement& plan,
+inline HotResult stage_hot_path(const Config& cfg, const std::vector<UniqueRead>& reads, TargetFiles& tf, Placement& plan,
                                 Logger& log) {
   fputs("Screening...\nConfirming...\n", stderr);
   if (plan.note_odd_targets)
     log.printf("results on the host: the targets hold bytes that are none of ACGTX, which the device would render as X");
-  HotResult hot = run_hot_path(cfg, reads, tf.targets, plan, log);
+  HotResult hot = run_hot_path(cfg, reads, tf, plan, log);
   if (hot.st.n_overflow_blocks)
     fprintf(stderr, "Warning: %llu window-key blocks may exceed MaxMatches; results keep all their matches\n",
             (unsigned long long)hot.st.n_overflow_blocks);
@@ -757,11 +821,11 @@ inline std::string stage_results(const Config& cfg, const Placement& plan, HotRe
   std::string res;
   if (plan.results == Where::Device) {
     float ms_order = 0, ms_text = 0;
-    res = results_text_device(hot.ctx.get(), hot.list_on_device, hot.hits, reads, tf.targets, tf.id_rest, &ms_order, &ms_text);
+    res = results_text_device(hot.ctx.get(), hot.list_on_device, hot.hits, reads, tf.n_targets, tf.id_rest, &ms_order, &ms_text);
     log.printf("results on the device: %zu bytes, order %.3f ms, text %.3f ms", res.size(), ms_order, ms_text);
     if (plan.side == Where::Host) hot.ctx.reset();
   } else {
-    res = results_text(hot.hits.data(), hot.hits.size(), reads, tf.targets, tf.id_rest);
+    res = results_text(hot.hits.data(), hot.hits.size(), reads, tf.targets(), tf.id_rest);
     log.printf("results on the host: %zu bytes", res.size());
   }
   spit(cfg.ResultsFileName, res);
@@ -815,7 +879,7 @@ inline int run_muscato(Config cfg) {
   const std::vector<UniqueRead> reads = stage_read_prep(cfg, plan, log);
   clk.lap("read prep");
   stage_window_check(cfg, reads, log);
-  const TargetFiles tf = stage_target_files(cfg, plan, log);
+  TargetFiles tf = stage_target_files(cfg, plan, log);
   clk.lap("windows check, target files");
   HotResult hot = stage_hot_path(cfg, reads, tf, plan, log);
   clk.lap("hot path (init, load, match)");

@@ -190,8 +190,7 @@ inline std::string gz_decode_file(const std::string& path) {
 
 // Read a file, transparently un-snappy-ing ".sz" (as tests/test.go:71-89 does for comparisons
 // and as every reference tool does for its inputs).
-inline std::string read_maybe_sz(const std::string& path) {
-  std::string raw = slurp(path);
+inline std::string decode_maybe_sz(std::string raw, const std::string& path) {
   // A framed snappy stream says so itself: stream identifier chunk ff 06 00 00 "sNaPpY".  The
   // reference reads its inputs through snappy.NewReader whatever they are called
   // (cmd/muscato_screen/main.go:417), so the name must not decide; a file named .sz that is not
@@ -201,6 +200,7 @@ inline std::string read_maybe_sz(const std::string& path) {
   if (is_stream || ends_with(to_lower(path), ".sz")) return sz_decode(raw);
   return raw;
 }
+inline std::string read_maybe_sz(const std::string& path) { return decode_maybe_sz(slurp(path), path); }
 
 // Split into lines the way bufio.Scanner(ScanLines) does: '\n' terminated, a trailing "\r" is
 // dropped, a final unterminated line is kept, no empty line after a trailing '\n'.

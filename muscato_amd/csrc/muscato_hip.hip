@@ -1739,3 +1739,6 @@ int musc_gather_rccl(musc_ctx* const* ctxs, int n, const uint64_t* read_base, mu
 // ---------------------------------------------------------------- read prep (FASTQ parse, sort + collapse)
 #include "kernels_fastq.hpp"
 #include "muscato_prep.hpp"
+
+// ---------------------------------------------------------------- the gene file: snappy frames, lines, 2-bit pack
+#include "muscato_db_text.hpp"
