@@ -186,6 +186,9 @@ int musc_reload_env(musc_ctx* ctx);
 /* ---- target database: replaces muscato_screen's scan of GeneFileName
  * (cmd/muscato_screen/main.go:408-452; gene number = sequence index). --------------------
  *
+ * A failed call of any loader (musc_db_load_ascii, musc_db_load_packed, musc_db_load_text) leaves no database: the
+ * next pass answers "no database loaded".  (The first two refuse a NULL argument before they touch the database in hand.)
+ *
  * ASCII form: `seqs` holds nseq sequences back to back, sequence i = bytes
  * [offsets[i], offsets[i+1]).  'A','C','G','T' are bases, every other byte is the
  * reference's 'X' (cmd/muscato_prep_targets/main.go:68-80).  on_device != 0 means both
@@ -520,8 +523,7 @@ int musc_rccl_probe(char* msg, uint64_t cap);
  * with one: 2).  Plain text may be a device pointer at any alignment; bytes outside [bytes, bytes + nbytes) are never
  * read.  Lines are bufio's: a line ends at '\n', one trailing '\r' is dropped, an unterminated last line is kept,
  * there is no empty line after a final '\n'.  The target is the line up to its first tab (a '\r' in front of that
- * tab is data).  Afterwards the context holds exactly the database musc_db_load_ascii holds for those targets.  A
- * failed call leaves no database.
+ * tab is data).  Afterwards the context holds exactly the database musc_db_load_ascii holds for those targets.
  *
  * Codes: 2 bad arguments, and no line at all ("database has no sequences"); 10 a HIP failure ("out of memory" in the
  * text when an allocation failed); 12 a refusal: a chunk declares more than 65 536 uncompressed bytes, which the

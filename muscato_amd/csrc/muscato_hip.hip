@@ -39,6 +39,7 @@
 #include "ctx_state.hpp"
 #include "dev_mem.hpp"
 #include "index_plan.hpp"
+#include "load_plan.hpp"
 
 #include "kernels_common.hpp"
 #include "kernels_index.hpp"
@@ -52,6 +53,7 @@
 #include "side_names.hpp"
 #include "kernels_side.hpp"
 #include "kernels_maxmatches.hpp"
+#include "kernels_fastq.hpp"
 MUSC_LANE_INSTANCES_4(extern)
 MUSC_LANE_INSTANCES_8(extern)
 MUSC_LANE_INSTANCES_12(extern)
@@ -171,39 +173,12 @@ struct TmpBufs {
 
 }  // namespace
 
-// The read ranges of a streamed load (musc_reads_load_packed32 with async = 1) and of the pass that consumes it: the
-// pieces the upload is queued in, and the batches the pass launches, every batch a whole number of pieces.  The upload
-// is several times slower per read than the match, so the GPU idles through most of a streamed pass and what shows in
-// its wall time is the work left after the last byte has landed: the pack and the match of the LAST batch.  Hence full
-// batches (batch_reads, rounded up to whole wave-tiles) while at least two of them remain, then batches that take half
-// of what is left each, down to a last batch of at most batch_reads / 16.  No batch holds more than twice the reads of
-// the batch after it (give or take the rounding to 64), so the match of one batch ends well before the upload of the
-// next one does, whatever the two rates are as long as the match is the faster one per read.  Every end but the last is
-// a multiple of 64 reads: whole wave-tiles, and whole bytes of the 2-bit stream for any read length.
-struct StreamPlan {
-  std::vector<uint64_t> piece_end, batch_end;  // ascending; the last of each is the read count
-};
-static void stream_plan(uint64_t nreads, uint64_t batch_reads, StreamPlan* sp) {
-  auto up64 = [](uint64_t x) { return (x + 63) & ~63ull; };
-  sp->piece_end.clear();
-  sp->batch_end.clear();
-  const uint64_t full = std::max<uint64_t>(up64(batch_reads), 64);
-  const uint64_t last_max = std::max<uint64_t>(up64(batch_reads / 16), 64);
-  const uint64_t piece = up64(std::max<uint64_t>(batch_reads / 4, 64));  // a quarter of a full batch
-  for (uint64_t r0 = 0; r0 < nreads;) {
-    const uint64_t left = nreads - r0;
-    const uint64_t n = left >= 2 * full ? full : left <= last_max ? left : up64((left + 1) / 2);
-    for (uint64_t p = r0 + piece; p < r0 + n; p += piece) sp->piece_end.push_back(p);
-    r0 += n;
-    sp->piece_end.push_back(r0);
-    sp->batch_end.push_back(r0);
-  }
-}
-// reads of the batch that starts at r0 on that schedule
-static uint64_t stream_plan_batch(const StreamPlan& sp, uint64_t r0) {
-  const auto it = std::upper_bound(sp.batch_end.begin(), sp.batch_end.end(), r0);
-  return it == sp.batch_end.end() ? 0 : *it - r0;
-}
+// the size rules of the loaders (load_plan.hpp): the record shape, and the schedule of a streamed load, which the pass
+// that consumes it follows
+using musc_load::RecShape;
+using musc_load::StreamPlan;
+using musc_load::stream_plan;
+using musc_load::stream_plan_batch;
 
 // The MUSC_* environment knobs (tests, A/B runs, experiments), read ONCE per context at musc_init -- a pass
 // never calls getenv -- and again only on musc_reload_env (tests that flip a knob on a live context).
@@ -599,6 +574,41 @@ hipEvent_t pool_event(musc_ctx* c) {
   return c->ev_pool[c->ev_used++];
 }
 
+// Up to three points in time on the context's stream, for a call that reports the time between them: it starts from an
+// empty pool, marks each point where it passes it, and reads a span once the stream has been waited for.
+struct Marks {
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  int start(musc_ctx* c) {
+    c->ev_used = 0;
+    for (hipEvent_t& x : e)
+      if (!(x = pool_event(c))) return fail(c, 10, "hipEventCreate failed");
+    return 0;
+  }
+  hipError_t mark(musc_ctx* c, int i) const { return hipEventRecord(e[i], c->stream); }
+  float ms(int a, int b) const {
+    float t = 0;
+    (void)hipEventElapsedTime(&t, e[a], e[b]);
+    return t;
+  }
+};
+
+// `body()` between two such marks: *ms = the time between them.  The stream is waited for on every path, so nothing of
+// a failed body is still queued when its temporaries go; *ms is written on success only.
+template <class Body>
+int timed(musc_ctx* c, float* ms, Body body) {
+  Marks m;
+  if (const int e = m.start(c)) return e;
+  HIPCHK(c, m.mark(c, 0));
+  const int rc = body();
+  const hipError_t er = m.mark(c, 1);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIPCHK(c, er);
+  HIPCHK(c, es);
+  *ms = m.ms(0, 1);
+  return 0;
+}
+
 // HIP-event timing of the kernel families of one pass; the events belong to the context's pool
 struct Timer {
   musc_ctx* c;
@@ -720,367 +730,17 @@ void musc_destroy(musc_ctx* c) {
   delete c;  // (every buffer goes with its owner)
 }
 
-// ---------------------------------------------------------------- database
-
-// the X-block bitmap of the mask plane (all zero for a plane that exists only because reads hold X)
-static int db_xblocks(musc_ctx* c) {
-  const uint64_t nblk64 = (c->db_words + 64 + 3) / 4;
-  const uint64_t nw = nblk64 / 32 + 4;
-  HIPCHK(c, c->dbx.alloc(nw * 4));
-  HIPCHK(c, hipMemsetAsync(c->dbx, 0, nw * 4, c->stream));
-  hipLaunchKernelGGL(k_db_xblocks, dim3(nblk(nblk64, 256)), dim3(256), 0, c->stream, c->dbm2, c->db_words, c->dbx);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-static int db_finish(musc_ctx* c) {
-  uint32_t hasx = 0;
-  HIPCHK(c, hipMemcpyAsync(&hasx, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  // the longest target
-  unsigned long long tl = 0;
-  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(c->nseq, 256), MAX_GRID)), dim3(256), 0, c->stream, c->seq_off, (uint64_t)c->nseq, c->counters + CNT_SCRATCH);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(&tl, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->max_tlen = tl;
-  c->db_has_x = hasx != 0;
-  if (!hasx) {
-    c->dbm2.release();
-    return 0;
-  }
-  return db_xblocks(c);
-}
-
-static int db_alloc(musc_ctx* c, const uint64_t* offsets, uint32_t nseq, int on_device) {
-  HIPCHK(c, hipSetDevice(c->device));
-  free_db(c);
-  if (nseq == 0) return fail(c, 2, "database has no sequences");
-  uint64_t first = 0, last = 0;
-  if (on_device) {
-    HIPCHK(c, hipMemcpy(&first, offsets, 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&last, offsets + nseq, 8, hipMemcpyDeviceToHost));
-  } else {
-    first = offsets[0];
-    last = offsets[nseq];
-  }
-  if (first != 0) return fail(c, 2, "offsets[0] must be 0");
-  if (last >= (1ull << 36)) return fail(c, 2, "database larger than 2^36 bases");
-  c->nseq = nseq;
-  c->nbases = last;
-  c->db_words = (last + 15) / 16;
-  c->h_seq_off.resize((size_t)nseq + 1);
-  if (on_device) HIPCHK(c, hipMemcpy(c->h_seq_off.data(), offsets, ((uint64_t)nseq + 1) * 8, hipMemcpyDeviceToHost));
-  else memcpy(c->h_seq_off.data(), offsets, ((uint64_t)nseq + 1) * 8);
-  // 64 words of zeroed slack behind both planes (pass_two_kernel allocates a missing mask plane the same way, and
-  // db_xblocks sizes dbx for db_words + 64).  What reads into it, and what bounds each access:
-  //   - k_confirm<RW != 0> (pair_issue): RW <= 16 words from the word of the placement's first base, whatever the
-  //     read's length -- at most 15 words past the last one.  db_span_has_x looks at the same RW * 16 bases.
-  //   - k_confirm<0> (confirm_pair, runtime stride): ceil(len / 16) steps, each reading one word ahead -- at most ONE
-  //     word past the word of the read's last base, and a read ends inside its target.  The bound is the read's own
-  //     length: bounded by the stride of the longest read loaded it walked up to 4 099 words past the last base.
-  //   - ext64 on a plane (bucket_of in the index build, res_span_word): two words past the word of its first bit,
-  //     and that bit belongs to a base of the database.  ctx_words (the context index build) takes the words of a
-  //     context of at most 200 bases around a window that starts inside the database.
-  //   - k_results_render / the side kernels read single words of bases inside [0, nbases).
-  // k_screen<0>, k_screen_t and k_hot_probes<0> never touch the planes: they read the index and the read records
-  // (Rec<0>::ext = ext64 on the record: a window that takes part ends inside len, so at most two words past the
-  // record's last base word -- the record's own length word, then the next record or the 256 spare bytes behind rd
-  // and rdm).  The results and side kernels take c->rw only to find a record and its length word.
-  const uint64_t alloc_words = c->db_words + 64;
-  HIPCHK(c, c->db2.alloc(alloc_words * 4));
-  HIPCHK(c, c->dbm2.alloc(alloc_words * 4));
-  HIPCHK(c, hipMemsetAsync(c->db2, 0, alloc_words * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->dbm2, 0, alloc_words * 4, c->stream));
-  HIPCHK(c, c->seq_off.alloc(((uint64_t)nseq + 1) * 8));
-  HIPCHK(c, hipMemcpyAsync(c->seq_off, offsets, ((uint64_t)nseq + 1) * 8,
-                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));  // raised by the packing kernel when it meets an X
-  return 0;
-}
-
-int musc_db_load_ascii(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint32_t nseq, int on_device) {
-  if (!c) return 1;
-  if (!seqs || !offsets) return fail(c, 2, "musc_db_load_ascii: NULL input");
-  int rc = db_alloc(c, offsets, nseq, on_device);
-  if (rc) return rc;
-  const unsigned char* src = (const unsigned char*)seqs;
-  TmpBufs B;
-  unsigned char* tmp = nullptr;
-  if (!on_device && c->nbases) {
-    HIPCHK(c, B.alloc(&tmp, c->nbases));
-    HIPCHK(c, hipMemcpyAsync(tmp, seqs, c->nbases, hipMemcpyHostToDevice, c->stream));
-    src = tmp;
-  }
-  if (c->db_words) {
-    hipLaunchKernelGGL(k_pack_db_ascii, dim3(nblk(c->db_words, 256)), dim3(256), 0, c->stream, src, c->nbases,
-                       c->db2, c->dbm2, c->db_words, c->d_flag);
-    HIPCHK(c, hipGetLastError());
-  }
-  return db_finish(c);
-}
-
-int musc_db_load_packed(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint64_t* seq_offsets,
-                        uint32_t nseq) {
-  if (!c) return 1;
-  if (!bases2bit || !seq_offsets) return fail(c, 2, "musc_db_load_packed: NULL input");
-  int rc = db_alloc(c, seq_offsets, nseq, 0);
-  if (rc) return rc;
-  TmpBufs B;
-  uint32_t* t2 = nullptr;
-  uint16_t* tm = nullptr;
-  const uint64_t w = c->db_words;
-  if (w) {
-    HIPCHK(c, B.alloc(&t2, w * 4));
-    HIPCHK(c, hipMemsetAsync(t2, 0, w * 4, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t2, bases2bit, (c->nbases + 3) / 4, hipMemcpyHostToDevice, c->stream));
-    if (nmask) {
-      HIPCHK(c, B.alloc(&tm, w * 2));
-      HIPCHK(c, hipMemsetAsync(tm, 0, w * 2, c->stream));
-      HIPCHK(c, hipMemcpyAsync(tm, nmask, (c->nbases + 7) / 8, hipMemcpyHostToDevice, c->stream));
-    }
-    hipLaunchKernelGGL(k_pack_db_packed, dim3(nblk(w, 256)), dim3(256), 0, c->stream, t2, tm, c->db2, c->dbm2, w,
-                       c->d_flag);
-    HIPCHK(c, hipGetLastError());
-  }
-  return db_finish(c);
-}
-
 }  // extern "C"
+
+// the loaders: databases and reads from packed or ASCII input, then from text (FASTQ; the gene file)
+#include "muscato_load.hpp"
+#include "muscato_prep.hpp"
+#include "muscato_db_text.hpp"
 
 // the index layer: the build driver, eligibility, the partition planner, ensure_index, musc_db_build_index*
 #include "muscato_index.hpp"
 
 extern "C" {
-
-// ---------------------------------------------------------------- reads
-
-// The records of reads [r0, r0 + n) must exist before stream `st` goes on: for the pieces of an
-// asynchronous upload (reads_load_fixed) that are still missing, `st` waits for their arrival and
-// packs them.  A no-op once every record exists.
-static int upload_prepare(musc_ctx* c, uint64_t r0, uint64_t n, hipStream_t st) {
-  musc_ctx::Upload& u = c->up;
-  if (!u.active) return 0;
-  const uint64_t want = std::min<uint64_t>(r0 + n, c->nreads);
-  while (u.packed_upto < want && u.next_piece < u.plan.piece_end.size()) {
-    const uint64_t i = u.next_piece;
-    const uint64_t first = u.packed_upto, cnt = u.plan.piece_end[i] - first;
-    HIPCHK(c, hipStreamWaitEvent(st, u.ev[i], 0));
-    hipLaunchKernelGGL(k_pack_reads_fixed, dim3(nblk(cnt * (uint64_t)c->rw, 256)), dim3(256), 0, st, u.stage, first, cnt, u.L, c->rw, c->rd);
-    HIPCHK(c, hipGetLastError());
-    u.packed_upto = first + cnt;
-    u.next_piece = i + 1;
-  }
-  if (u.packed_upto >= c->nreads) u.active = false;
-  return 0;
-}
-
-// The read records, built in one way by every loader (reads_load, reads_load_fixed, reads_sort_unique_dev): a record is
-// rw words -- the 2-bit bases of the longest read, then the length word, rounded up to four words -- and both planes
-// end in 256 zeroed bytes (what reads past a plane's end: db_alloc).  reads_shape: rw and the words of all records, or
-// one of the three refusals (fixed: the wording of the fixed-length loader, which knows no single read to blame).
-struct RecShape { int rw = 4; uint64_t words = 0; };
-static int reads_shape(musc_ctx* c, uint64_t nreads, uint64_t maxlen, bool fixed, RecShape* s) {
-  if (nreads >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read_idx");
-  if (maxlen > 65535)
-    return fixed ? fail(c, 2, "read length exceeds the 65535-base record limit")
-                 : fail(c, 2, "read of %llu bases exceeds the 65535-base record limit", (unsigned long long)maxlen);
-  s->rw = std::max(((int)((2 * maxlen + 31) / 32) + 1 + 3) & ~3, 4);
-  s->words = nreads * (uint64_t)s->rw;
-  if (s->words >= (1ull << 32)) return fail(c, 2, "too many read words for one dispatch (reads x record words >= 2^32)");
-  return 0;
-}
-// The planes of that shape: rd -- keep: the buffer of the last fixed-length load where it is large enough, and the new
-// one is kept in turn -- and, with mask, rdm.  nreads, rw and max_len are committed here, together, once the planes exist.
-static int reads_records(musc_ctx* c, const RecShape& s, uint64_t nreads, uint64_t maxlen, bool mask, bool keep) {
-  const uint64_t bytes = s.words * 4 + 256;
-  if (!keep || c->rd_cap < bytes) {
-    c->rd_cap = 0;
-    HIPCHK(c, c->rd.alloc(bytes));
-    if (keep) c->rd_cap = bytes;
-  }
-  HIPCHK(c, hipMemsetAsync(c->rd + s.words, 0, 256, c->stream));
-  if (mask) {
-    HIPCHK(c, c->rdm.alloc(bytes));
-    HIPCHK(c, hipMemsetAsync(c->rdm + s.words, 0, 256, c->stream));
-  }
-  c->nreads = nreads;
-  c->rw = s.rw;
-  c->max_len = (uint32_t)maxlen;
-  return 0;
-}
-// what the pack kernel left in d_flag says whether a read holds an X; a mask plane nobody needs goes
-static void reads_settle_x(musc_ctx* c, uint32_t hasx) {
-  c->reads_have_x = hasx != 0;
-  if (!hasx) c->rdm.release();
-}
-
-static int reads_load(musc_ctx* c, const unsigned char* ascii, const uint8_t* bases2bit, const uint8_t* nmask,
-                      const uint64_t* offsets, uint64_t nreads, int on_device, bool packed) {
-  HIPCHK(c, hipSetDevice(c->device));
-  free_reads(c);
-  RecShape shape;
-  int rc = reads_shape(c, nreads, 0, false, &shape);  // (the read count alone, before anything is uploaded)
-  if (rc) return rc;
-  if (nreads == 0) {
-    c->rw = 4;
-    return 0;
-  }
-  TmpBufs B;
-  uint64_t* d_off = nullptr;
-  const uint64_t* offp = offsets;
-  if (!on_device) {
-    HIPCHK(c, B.alloc(&d_off, (nreads + 1) * 8));
-    HIPCHK(c, hipMemcpyAsync(d_off, offsets, (nreads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    offp = d_off;
-  }
-  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(nreads, 256), MAX_GRID)), dim3(256), 0, c->stream, offp, nreads, c->counters + CNT_SCRATCH);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
-  uint64_t first = 0, total = 0;
-  HIPCHK(c, hipMemcpyAsync(&first, offp, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&total, offp + nreads, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t maxlen = c->h_pinned[0];
-  if (first != 0) return fail(c, 2, "read offsets[0] must be 0");
-  // the mask plane only where an X can turn up: ASCII input, or packed input that comes with a mask
-  if ((rc = reads_shape(c, nreads, maxlen, false, &shape)) || (rc = reads_records(c, shape, nreads, maxlen, !packed || nmask != nullptr, false)))
-    return rc;
-  const auto [rw, words] = shape;
-  uint32_t* d_hasx = c->d_flag;
-  HIPCHK(c, hipMemsetAsync(d_hasx, 0, 4, c->stream));
-  unsigned char *t1 = nullptr, *t2 = nullptr;
-  if (!packed) {
-    const unsigned char* src = ascii;
-    if (!on_device && total) {
-      HIPCHK(c, B.alloc(&t1, total));
-      HIPCHK(c, hipMemcpyAsync(t1, ascii, total, hipMemcpyHostToDevice, c->stream));
-      src = t1;
-    }
-    hipLaunchKernelGGL(k_pack_reads<false>, dim3(nblk(words, 256)), dim3(256), 0, c->stream, src,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, offp, nreads, rw, c->rd, c->rdm, d_hasx);
-  } else {
-    const uint64_t b2 = ((total + 3) / 4 + 7) & ~3ull, bm = ((total + 7) / 8 + 7) & ~3ull;
-    HIPCHK(c, B.alloc(&t1, b2 + 16));
-    HIPCHK(c, hipMemsetAsync(t1, 0, b2 + 16, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t1, bases2bit, (total + 3) / 4, hipMemcpyHostToDevice, c->stream));
-    if (nmask) {
-      HIPCHK(c, B.alloc(&t2, bm + 16));
-      HIPCHK(c, hipMemsetAsync(t2, 0, bm + 16, c->stream));
-      HIPCHK(c, hipMemcpyAsync(t2, nmask, (total + 7) / 8, hipMemcpyHostToDevice, c->stream));
-    }
-    hipLaunchKernelGGL(k_pack_reads<true>, dim3(nblk(words, 256)), dim3(256), 0, c->stream,
-                       (const unsigned char*)nullptr, (const uint32_t*)t1, (const uint32_t*)t2, offp, nreads, rw,
-                       c->rd, c->rdm, d_hasx);
-  }
-  HIPCHK(c, hipGetLastError());
-  uint32_t hasx = 0;
-  HIPCHK(c, hipMemcpyAsync(&hasx, d_hasx, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  reads_settle_x(c, hasx);
-  return 0;
-}
-
-// Reads of one length without X: the 2-bit stream is all that crosses PCIe.  async: the upload is
-// queued in pieces on a copy stream and the records are made batch by batch by the pass that needs
-// them (upload_prepare), so that upload and matching overlap.
-static int reads_load_fixed(musc_ctx* c, const uint8_t* bases2bit, uint32_t L, uint64_t nreads, int async) {
-  HIPCHK(c, hipSetDevice(c->device));
-  // The reads in hand go, the record buffer stays: a streamed step is bound by the link, so the first bytes are queued
-  // before anything else that takes time, and in the steady state (a read set that fits the buffers of the last one)
-  // this call neither frees nor allocates.
-  drop_reads(c, true);
-  RecShape shape;
-  const int rc_shape = reads_shape(c, nreads, L, true, &shape);
-  if (rc_shape) return rc_shape;
-  if (nreads == 0) {
-    c->rw = 4;
-    return 0;
-  }
-  musc_ctx::Upload& u = c->up;
-  const uint64_t total_bytes = (nreads * (uint64_t)L + 3) / 4;
-  const uint64_t need_words = (total_bytes + 3) / 4 + 4;  // (k_pack_reads_fixed reads up to two words past a read's last)
-  HIPCHK(c, u.stage.grow(need_words * 4));
-  if (!u.s_up) HIPCHK(c, hipStreamCreateWithFlags(&u.s_up, hipStreamNonBlocking));
-  // the pieces: whole bytes of the stream and whole wave-tiles (64 | every end but the last), each batch of the pass
-  // that consumes them a whole number of pieces -- a batch needs all of its pieces, and the next batch's pieces arrive
-  // while it is matched
-  stream_plan(nreads, c->batch_reads, &u.plan);
-  const std::vector<uint64_t>& ends = u.plan.piece_end;
-  u.L = L;
-  u.packed_upto = 0;
-  u.next_piece = 0;
-  while (u.ev.size() < ends.size()) {
-    hipEvent_t e = nullptr;
-    HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    u.ev.push_back(e);
-  }
-  HIPCHK(c, hipMemsetAsync(u.stage + (need_words - 4), 0, 16, u.s_up));
-  for (size_t i = 0; i < ends.size(); i++) {
-    const uint64_t b0 = (i ? ends[i - 1] : 0) * (uint64_t)L / 4;  // (64 | end: a whole number of bytes)
-    const uint64_t b1 = std::min<uint64_t>((ends[i] * (uint64_t)L + 3) / 4, total_bytes);
-    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<uint8_t*>(u.stage.get()) + b0, bases2bit + b0, b1 - b0, hipMemcpyHostToDevice, u.s_up));
-    HIPCHK(c, hipEventRecord(u.ev[i], u.s_up));
-  }
-  u.active = true;
-  // the records (nothing reads them before the first piece has landed): the buffer of the last fixed-length load where
-  // it is large enough, its zeroed 256-byte tail at its new place
-  int rc = reads_records(c, shape, nreads, L, false, true);
-  if (rc) return rc;
-  reads_settle_x(c, 0);
-  if (!async) {
-    if ((rc = upload_prepare(c, 0, nreads, c->stream))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return 0;
-}
-
-// lengths and / or a mask: offsets are made on the device (a scan of the lengths, or multiples of
-// fixed_len) and the general loader takes over
-static int reads_load_lengths(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint32_t* lengths,
-                              uint32_t fixed_len, uint64_t nreads) {
-  HIPCHK(c, hipSetDevice(c->device));
-  TmpBufs B;
-  uint64_t *d_off = nullptr, *stmp = nullptr;
-  uint32_t* d_len = nullptr;
-  HIPCHK(c, B.alloc(&d_off, (nreads + 2) * 8));
-  if (lengths) {
-    HIPCHK(c, B.alloc(&d_len, (nreads + 1) * 4));
-    HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(nreads + 1) * 8));
-    HIPCHK(c, hipMemcpyAsync(d_len, lengths, nreads * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_widen_u32, dim3(nblk(nreads + 1, 256)), dim3(256), 0, c->stream, d_len, nreads, d_off);
-    HIPCHK(c, hipGetLastError());
-    int rc = scan_u64(c, d_off, d_off, nreads + 1, stmp);
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(k_iota_mul, dim3(nblk(nreads + 1, 256)), dim3(256), 0, c->stream, d_off, nreads, (uint64_t)fixed_len);
-    HIPCHK(c, hipGetLastError());
-  }
-  return reads_load(c, nullptr, bases2bit, nmask, d_off, nreads, 1, true);
-}
-
-int musc_reads_load_packed32(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint32_t* lengths,
-                             uint32_t fixed_len, uint64_t nreads, int async) {
-  if (!c) return 1;
-  if (!bases2bit && nreads) return fail(c, 2, "musc_reads_load_packed32: NULL input");
-  return reads_load_done(c, !lengths && !nmask ? reads_load_fixed(c, bases2bit, fixed_len, nreads, async)
-                                               : reads_load_lengths(c, bases2bit, nmask, lengths, fixed_len, nreads));
-}
-
-int musc_reads_load_ascii(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads, int on_device) {
-  if (!c) return 1;
-  if ((!seqs || !offsets) && nreads) return fail(c, 2, "musc_reads_load_ascii: NULL input");
-  return reads_load_done(c, reads_load(c, (const unsigned char*)seqs, nullptr, nullptr, offsets, nreads, on_device, false));
-}
-
-int musc_reads_load_packed(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint64_t* read_offsets,
-                           uint64_t nreads) {
-  if (!c) return 1;
-  if ((!bases2bit || !read_offsets) && nreads) return fail(c, 2, "musc_reads_load_packed: NULL input");
-  return reads_load_done(c, reads_load(c, nullptr, bases2bit, nmask, read_offsets, nreads, 0, true));
-}
 
 // ---------------------------------------------------------------- hot path
 
@@ -1735,10 +1395,3 @@ int musc_gather_rccl(musc_ctx* const* ctxs, int n, const uint64_t* read_base, mu
 }
 
 }  // extern "C"
-
-// ---------------------------------------------------------------- read prep (FASTQ parse, sort + collapse)
-#include "kernels_fastq.hpp"
-#include "muscato_prep.hpp"
-
-// ---------------------------------------------------------------- the gene file: snappy frames, lines, 2-bit pack
-#include "muscato_db_text.hpp"

@@ -2,7 +2,8 @@
 // eligibility, the partition planner and ensure_index, and the musc_db_build_index* / musc_db_*partition* entry points.
 // It owns the resident index (musc_ctx::idx and the four tables) and acts on what index_plan.hpp decides: the planner
 // and the builds ask the same cascade.  Part of libmuscato_hip.so: included by muscato_hip.hip after the context, the
-// scans and the event pool it calls (fail, HIPCHK, ensure, TmpBufs, scan_u64, pool_event, check_params).
+// scans and the event pool it calls (fail, HIPCHK, ensure, TmpBufs, scan_u64, pool_event, check_params), behind the
+// loaders (muscato_load.hpp: the database it indexes).
 #pragma once
 
 namespace mi = musc_index;

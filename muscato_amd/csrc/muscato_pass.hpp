@@ -1,7 +1,7 @@
 // muscato_pass.hpp -- the host side of musc_match_device: the kernel-instance resolvers and launchers of both paths, and
 // the pass driver (set-up, batches, finish, retries).  Part of libmuscato_hip.so: included by muscato_hip.hip after
-// muscato_index.hpp (ensure_index, plan_partitions; the resident index is read through c->idx) and the upload and
-// database code it calls (upload_prepare, db_xblocks).
+// muscato_index.hpp (ensure_index, plan_partitions; the resident index is read through c->idx) and muscato_load.hpp,
+// whose upload and database code it calls (upload_prepare, db_xblocks).
 #pragma once
 
 namespace {

@@ -1,6 +1,7 @@
 // muscato_prep.hpp -- read prep on the GPU: bytewise sort of the prepared reads and collapse of
-// identical sequences.  Included at the end of muscato_hip.hip (one
-// translation unit: it uses musc_ctx and the helpers defined there).
+// identical sequences, and the FASTQ parse in front of it (kernels_fastq.hpp).
+// Included by muscato_hip.hip right behind muscato_load.hpp (one translation unit: it uses musc_ctx,
+// the record functions and the loaders' helpers -- staged, tmp_alloc, offsets_census, text_lines).
 //
 // Reference: cmd/muscato/main.go sortReads (GNU `sort` of the `seq\tname` lines under LC_ALL=C)
 // followed by cmd/muscato_uniqify/main.go:83-135 (adjacent lines with the same sequence become
@@ -131,37 +132,30 @@ MUSC_KERNEL void k_prep_pack(const unsigned char* __restrict__ s, const uint64_t
   if (mv) atomicOr(has_x, 1u);
 }
 
-typedef TmpBufs PrepBufs;  // temporaries of musc_reads_sort_unique, released on every exit path
-
 // The device stage of musc_reads_sort_unique on n > 0 prepared reads that are already in device memory (d_s, d_off as
-// musc_reads_load_ascii takes them).  e0 has been recorded by the caller, in front of whatever device work of its own
-// the time is to cover; e1 is recorded here.
-static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const uint64_t* d_off, const uint64_t n,
-                                 hipEvent_t e0, hipEvent_t e1, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
-  PrepBufs B;
-  HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(n, 256), MAX_GRID)), dim3(256), 0, c->stream, d_off, n, c->counters + CNT_SCRATCH);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
-  uint64_t first = 0;
-  HIPCHK(c, hipMemcpyAsync(&first, d_off, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t maxlen = c->h_pinned[0];
+// musc_reads_load_ascii takes them), for the public call `who`.  Mark 0 has been set by the caller, in front of whatever
+// device work of its own the time is to cover; mark 1 is set here.
+static int reads_sort_unique_dev(musc_ctx* c, const char* who, const unsigned char* d_s, const uint64_t* d_off, const uint64_t n,
+                                 const Marks& m, uint32_t** order, uint32_t** ustart, uint64_t* nunique) {
+  TmpBufs B;
+  RecShape shape;
+  uint64_t first = 0, last = 0, maxlen = 0;
+  int rc = offsets_census(c, d_off, n, &first, &last, &maxlen);
+  if (rc) return rc;
   if (first != 0) return fail(c, 2, "read offsets[0] must be 0");
-  if (maxlen > 65535) return fail(c, 2, "read of %llu bases exceeds the 65535-base record limit", (unsigned long long)maxlen);
+  if ((rc = reads_shape(c, 0, maxlen, false, &shape))) return rc;  // (the longest read alone, before anything is sorted)
 
   // ---- LSD sort over the key words
   const uint32_t nw = (uint32_t)std::max<uint64_t>((maxlen + PREP_BASES_PER_WORD - 1) / PREP_BASES_PER_WORD, 1);
   uint64_t *k0 = nullptr, *k1 = nullptr;
   uint32_t *p0 = nullptr, *p1 = nullptr;
-  HIPCHK(c, B.alloc(&k0, n * 8));
-  HIPCHK(c, B.alloc(&k1, n * 8));
-  HIPCHK(c, B.alloc(&p0, n * 4));
-  HIPCHK(c, B.alloc(&p1, n * 4));
+  if ((rc = tmp_alloc(c, who, B, &k0, n * 8)) || (rc = tmp_alloc(c, who, B, &k1, n * 8)) || (rc = tmp_alloc(c, who, B, &p0, n * 4)) ||
+      (rc = tmp_alloc(c, who, B, &p1, n * 4)))
+    return rc;
   size_t tmp_bytes = 0;
   HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, k0, k1, p0, p1, (size_t)n, 0u, 63u, c->stream));
   void* tmp = nullptr;
-  HIPCHK(c, B.alloc(&tmp, tmp_bytes));
+  if ((rc = tmp_alloc(c, who, B, &tmp, tmp_bytes))) return rc;
   const dim3 grid(std::min(nblk(n, 256), MAX_GRID));
   hipLaunchKernelGGL(k_prep_iota, grid, dim3(256), 0, c->stream, p0, n);
   HIPCHK(c, hipGetLastError());
@@ -174,15 +168,13 @@ static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const ui
 
   // ---- groups of identical sequences
   uint32_t *head = nullptr, *incl = nullptr, *stmp = nullptr, *d_ustart = nullptr, *d_uhead = nullptr;
-  HIPCHK(c, B.alloc(&head, n * 4));
-  HIPCHK(c, B.alloc(&incl, n * 4));
-  HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(n) * 4));
-  HIPCHK(c, B.alloc(&d_ustart, (n + 1) * 4));
-  HIPCHK(c, B.alloc(&d_uhead, n * 4));
+  if ((rc = tmp_alloc(c, who, B, &head, n * 4)) || (rc = tmp_alloc(c, who, B, &incl, n * 4)) ||
+      (rc = tmp_alloc(c, who, B, &stmp, scan_tmp_elems(n) * 4)) || (rc = tmp_alloc(c, who, B, &d_ustart, (n + 1) * 4)) ||
+      (rc = tmp_alloc(c, who, B, &d_uhead, n * 4)))
+    return rc;
   hipLaunchKernelGGL(k_prep_heads, grid, dim3(256), 0, c->stream, d_s, d_off, p0, n, head);
   HIPCHK(c, hipGetLastError());
-  int rc = scan_u32(c, head, incl, n, true, stmp);
-  if (rc) return rc;
+  if ((rc = scan_u32(c, head, incl, n, true, stmp))) return rc;
   hipLaunchKernelGGL(k_prep_starts, grid, dim3(256), 0, c->stream, head, incl, n, d_ustart, d_uhead, p0);
   HIPCHK(c, hipGetLastError());
   uint32_t nu32 = 0;
@@ -191,7 +183,6 @@ static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const ui
   const uint64_t nu = nu32;
 
   // ---- the distinct sequences become the context's reads
-  RecShape shape;
   if ((rc = reads_shape(c, nu, maxlen, false, &shape)) || (rc = reads_records(c, shape, nu, maxlen, true, false))) return rc;
   const auto [rw, words] = shape;
   uint32_t* d_hasx = c->d_flag;
@@ -199,7 +190,7 @@ static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const ui
   hipLaunchKernelGGL(k_prep_pack, dim3(nblk(words, 256)), dim3(256), 0, c->stream, d_s, d_off, d_uhead, nu, rw, c->rd,
                      c->rdm, d_hasx);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(e1, c->stream));
+  HIPCHK(c, m.mark(c, 1));
 
   // ---- order and group boundaries for the host (names, counts)
   uint32_t* h_order = (uint32_t*)malloc(n * 4);
@@ -220,9 +211,7 @@ static int reads_sort_unique_dev(musc_ctx* c, const unsigned char* d_s, const ui
     return fail(c, 10, "musc_reads_sort_unique: %s", hipGetErrorString(e));
   }
   reads_settle_x(c, hasx);
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  c->stats.ms_read_prep = ms;  // device time of the last sort + collapse
+  c->stats.ms_read_prep = m.ms(0, 1);  // device time of the last sort + collapse
   *order = h_order;
   *ustart = h_ustart;
   *nunique = nu;
@@ -241,26 +230,20 @@ static int reads_sort_unique_run(musc_ctx* c, const char* seqs, const uint64_t* 
     if (!*order || !*ustart) return fail(c, 7, "out of host memory");
     return 0;
   }
-  c->ev_used = 0;
-  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
-  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
-  PrepBufs B;  // the upload: released when the device stage has returned
-  const uint64_t n = nreads;
-  const unsigned char* d_s = (const unsigned char*)seqs;
-  const uint64_t* d_off = offsets;
-  if (!on_device) {
-    const uint64_t total = offsets[n];
-    unsigned char* ds = nullptr;
-    uint64_t* doff = nullptr;
-    HIPCHK(c, B.alloc(&ds, total + 64));
-    HIPCHK(c, B.alloc(&doff, (n + 1) * 8));
-    HIPCHK(c, hipMemcpyAsync(ds, seqs, total, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(doff, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    d_s = ds;
-    d_off = doff;
-  }
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  return reads_sort_unique_dev(c, d_s, d_off, n, e0, e1, order, ustart, nunique);
+  static const char* const who = "musc_reads_sort_unique";
+  Marks m;
+  int rc = m.start(c);
+  if (rc) return rc;
+  TmpBufs B;  // the upload: released when the device stage has returned
+  const unsigned char* d_s = nullptr;
+  const uint64_t* d_off = nullptr;
+  // (64 spare bytes behind the sequences, as behind the prepared reads of the FASTQ stage: k_prep_keys, k_prep_heads and
+  // k_prep_pack read the bytes of each read only; no slack behind the offsets: nothing reads past offsets[nreads])
+  if ((rc = staged(c, who, B, (const unsigned char*)seqs, on_device ? 0 : offsets[nreads], on_device, 64, &d_s)) ||
+      (rc = staged(c, who, B, offsets, (nreads + 1) * 8, on_device, 0, &d_off)))
+    return rc;
+  HIPCHK(c, m.mark(c, 0));
+  return reads_sort_unique_dev(c, who, d_s, d_off, nreads, m, order, ustart, nunique);
 }
 
 extern "C" int musc_reads_sort_unique(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint64_t nreads,
@@ -286,58 +269,23 @@ extern "C" void musc_fastq_prep_free(musc_fastq_prep* p) {
   memset(p, 0, sizeof *p);
 }
 
-// a failed device allocation of the stage: the library's code for a failed HIP call, the text says which and why
-#define FQ_ALLOC(c, B, ptr, bytes)                                                                                   \
-  do {                                                                                                               \
-    const hipError_t e_ = (B).alloc((ptr), (bytes));                                                                 \
-    if (e_ != hipSuccess) {                                                                                          \
-      (void)hipGetLastError();                                                                                       \
-      return fail((c), 10, "musc_reads_prep_fastq: device allocation of %llu bytes failed: %s",                      \
-                  (unsigned long long)(bytes), hipGetErrorString(e_));                                               \
-    }                                                                                                                \
-  } while (0)
-
 static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on_device, int32_t min_len, uint32_t max_len,
                           musc_fastq_prep* out) {
-  c->ev_used = 0;
-  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
-  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
-  PrepBufs P;  // the text and the record tables: released before the sort takes its own temporaries
-  PrepBufs S;  // the prepared reads
-  const unsigned char* d_text = (const unsigned char*)text;
-  if (!on_device && nbytes) {
-    unsigned char* dt = nullptr;
-    FQ_ALLOC(c, P, &dt, nbytes + 16);
-    HIPCHK(c, hipMemcpyAsync(dt, text, nbytes, hipMemcpyHostToDevice, c->stream));
-    d_text = dt;
-  }
-  HIPCHK(c, hipEventRecord(e0, c->stream));
+  static const char* const who = "musc_reads_prep_fastq";
+  Marks m;
+  int rc = m.start(c);
+  if (rc) return rc;
+  TmpBufs P;  // the text and the record tables: released before the sort takes its own temporaries
+  TmpBufs S;  // the prepared reads
+  const unsigned char* d_text = nullptr;
+  // (16 spare bytes: the text's last 16-byte lane lies inside the block; fq_load16 reads no byte past the text itself)
+  if ((rc = staged(c, who, P, (const unsigned char*)text, nbytes, on_device, 16, &d_text))) return rc;
+  HIPCHK(c, m.mark(c, 0));
 
   // ---- lines: newlines per tile, tile bases
-  const uint64_t lo = (uint64_t)((uintptr_t)d_text & (FQ_LANE_BYTES - 1)), hi = lo + nbytes;
-  const unsigned char* base16 = d_text - lo;
-  const uint64_t ntiles = (hi + FQ_TILE_BYTES - 1) / FQ_TILE_BYTES;
-  const dim3 tgrid((unsigned)std::min<uint64_t>(std::max<uint64_t>(ntiles, 1), 4 * MAX_GRID));
-  uint64_t* cnt = nullptr;
-  uint64_t nrec = 0, newlines = 0;
-  uint32_t virt = 0;
-  if (nbytes) {
-    uint64_t* stmp = nullptr;
-    FQ_ALLOC(c, P, &cnt, (ntiles + 1) * 8);
-    FQ_ALLOC(c, P, &stmp, scan_tmp_elems(ntiles + 1) * 8);
-    HIPCHK(c, hipMemsetAsync(cnt + ntiles, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_fq_count, tgrid, dim3(FQ_BLOCK), 0, c->stream, base16, lo, hi, ntiles, cnt);
-    HIPCHK(c, hipGetLastError());
-    int rc = scan_u64(c, cnt, cnt, ntiles + 1, stmp);
-    if (rc) return rc;
-    c->h_pinned[1] = 0;
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, cnt + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, d_text + (nbytes - 1), 1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    newlines = c->h_pinned[0];
-    virt = *reinterpret_cast<const unsigned char*>(c->h_pinned + 1) != '\n';  // a last line without a newline is a line
-    nrec = (newlines + virt) / 4;                                              // an incomplete last record is dropped
-  }
+  TextLines L;
+  if (nbytes && (rc = text_lines(c, who, P, d_text, nbytes, &L))) return rc;
+  const uint64_t nrec = (L.newlines + L.virt) / 4;  // an incomplete last record is dropped
   if (nrec >= 0xFFFFFFF0ull) return fail(c, 2, "too many reads for 32-bit read numbers");
 
   // ---- records: spans, the \r rule, the length rules; kept reads' numbers and offsets
@@ -347,24 +295,21 @@ static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on
   if (nrec) {
     uint64_t* stmp64 = nullptr;
     uint32_t* stmp32 = nullptr;
-    FQ_ALLOC(c, P, &lines, (3 * (nrec + 1) + 2) * 8);  // three tables and the two counters of k_fq_records
-    FQ_ALLOC(c, P, &len, (nrec + 1) * 8);
-    FQ_ALLOC(c, P, &kidx, (nrec + 1) * 4);
-    FQ_ALLOC(c, P, &name_len, (nrec + 1) * 4);
-    FQ_ALLOC(c, P, &stmp64, scan_tmp_elems(nrec + 1) * 8);
-    FQ_ALLOC(c, P, &stmp32, scan_tmp_elems(nrec + 1) * 4);
+    if ((rc = tmp_alloc(c, who, P, &lines, (3 * (nrec + 1) + 2) * 8)) ||  // three tables and the two counters of k_fq_records
+        (rc = tmp_alloc(c, who, P, &len, (nrec + 1) * 8)) || (rc = tmp_alloc(c, who, P, &kidx, (nrec + 1) * 4)) ||
+        (rc = tmp_alloc(c, who, P, &name_len, (nrec + 1) * 4)) || (rc = tmp_alloc(c, who, P, &stmp64, scan_tmp_elems(nrec + 1) * 8)) ||
+        (rc = tmp_alloc(c, who, P, &stmp32, scan_tmp_elems(nrec + 1) * 4)))
+      return rc;
     uint64_t *name_begin = lines, *name_end = lines + (nrec + 1), *seq_end = lines + 2 * (nrec + 1);
     unsigned long long* st = reinterpret_cast<unsigned long long*>(lines + 3 * (nrec + 1));
-    hipLaunchKernelGGL(k_fq_lines, tgrid, dim3(FQ_BLOCK), 0, c->stream, base16, lo, hi, ntiles, cnt, nrec, virt, newlines,
+    hipLaunchKernelGGL(k_fq_lines, L.tgrid, dim3(FQ_BLOCK), 0, c->stream, L.base16, L.lo, L.hi, L.ntiles, L.cnt, nrec, L.virt, L.newlines,
                        name_begin, name_end, seq_end);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemsetAsync(st, 0, 16, c->stream));
     hipLaunchKernelGGL(k_fq_records, dim3(std::min(nblk(nrec + 1, 256), MAX_GRID)), dim3(256), 0, c->stream, d_text, nrec,
                        name_begin, name_end, seq_end, min_len, max_len, kidx, len, name_len, st);
     HIPCHK(c, hipGetLastError());
-    int rc = scan_u32(c, kidx, kidx, nrec + 1, false, stmp32);
-    if (rc) return rc;
-    if ((rc = scan_u64(c, len, len, nrec + 1, stmp64))) return rc;
+    if ((rc = scan_u32(c, kidx, kidx, nrec + 1, false, stmp32)) || (rc = scan_u64(c, len, len, nrec + 1, stmp64))) return rc;
     uint32_t nk32 = 0;
     HIPCHK(c, hipMemcpyAsync(&nk32, kidx + nrec, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_pinned, len + nrec, 8, hipMemcpyDeviceToHost, c->stream));
@@ -394,10 +339,9 @@ static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on
   unsigned char* prep = nullptr;
   uint64_t *prep_off = nullptr, *o64 = nullptr;
   uint32_t* o32 = nullptr;
-  FQ_ALLOC(c, S, &prep, total + 64);
-  FQ_ALLOC(c, S, &prep_off, (nkept + 1) * 8);
-  FQ_ALLOC(c, P, &o64, 2 * nkept * 8);
-  FQ_ALLOC(c, P, &o32, 2 * nkept * 4);
+  if ((rc = tmp_alloc(c, who, S, &prep, total + 64)) || (rc = tmp_alloc(c, who, S, &prep_off, (nkept + 1) * 8)) ||
+      (rc = tmp_alloc(c, who, P, &o64, 2 * nkept * 8)) || (rc = tmp_alloc(c, who, P, &o32, 2 * nkept * 4)))
+    return rc;
   hipLaunchKernelGGL(k_fq_gather, dim3(std::min(nblk(nrec, 256 / FQ_GROUP), 4 * MAX_GRID)), dim3(256), 0, c->stream, d_text, nbytes,
                      nrec, lines, lines + (nrec + 1), kidx, len, name_len, prep, prep_off, o64, o64 + nkept, o32, o32 + nkept);
   HIPCHK(c, hipGetLastError());
@@ -407,7 +351,7 @@ static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on
   HIPCHK(c, hipMemcpyAsync(out->seq_len, o32 + nkept, nkept * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   P.release();
-  return reads_sort_unique_dev(c, prep, prep_off, nkept, e0, e1, &out->order, &out->ustart, &out->n_unique);
+  return reads_sort_unique_dev(c, who, prep, prep_off, nkept, m, &out->order, &out->ustart, &out->n_unique);
 }
 
 extern "C" int musc_reads_prep_fastq(musc_ctx* c, const char* text, uint64_t nbytes, int on_device, int32_t min_read_len,

@@ -1,6 +1,6 @@
 // muscato_text.hpp -- the host side of the texts rendered on the device: results.txt (musc_results_*) and
 // the nonmatch FASTQ, genestats and readstats (musc_side_*).  Part of libmuscato_hip.so: included by
-// muscato_hip.hip after the context, the scans and the loaders (drop_gene_text, drop_read_text).  Both families build
+// muscato_hip.hip after the context, the scans, the event marks (timed) and the loaders (drop_gene_text, drop_read_text).  Both families build
 // record lists with 64-bit byte offsets and render ranges of them through one driver, text_range.
 #pragma once
 
@@ -8,25 +8,6 @@
 
 // the grid of a grid-stride kernel over k items
 static dim3 grid(uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); }
-
-// `body()` between two events of the context's pool on its stream: *ms = the time between them.  The stream is waited
-// for on every path, so nothing of a failed body is still queued when its temporaries go; *ms is written on success only.
-template <class Body>
-static int timed(musc_ctx* c, float* ms, Body body) {
-  c->ev_used = 0;
-  hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
-  if (!e0 || !e1) return fail(c, 10, "hipEventCreate failed");
-  HIPCHK(c, hipEventRecord(e0, c->stream));
-  const int rc = body();
-  const hipError_t er = hipEventRecord(e1, c->stream);
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  if (rc) return rc;
-  HIPCHK(c, er);
-  HIPCHK(c, es);
-  *ms = 0;
-  (void)hipEventElapsedTime(ms, e0, e1);
-  return 0;
-}
 
 // A text as musc_results_text and musc_side_text see it: n records, record i = bytes [off[i], off[i + 1]) of the text.
 struct TextDesc {

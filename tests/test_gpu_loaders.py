@@ -300,7 +300,7 @@ def refused(call):
 
 def test_refused_loads_leave_nothing_stale(eng):
     """A load that the library refuses from the offsets or the lengths alone (offsets[0] != 0, a read of more than 65 535
-    bases) leaves no reads -- or no database -- behind: the next match raises or returns nothing, never the tuples of
+    bases, a database of no targets or of 2^36 bases) leaves no reads -- or no database -- behind: the next match raises or returns nothing, never the tuples of
     what was loaded before."""
     ocfg, reads, targets = small_case()
     cfg = Config(Windows=list(ocfg.Windows), WindowWidth=ocfg.WindowWidth, PMatch=ocfg.PMatch, MinDinuc=ocfg.MinDinuc,
@@ -346,6 +346,24 @@ def test_refused_loads_leave_nothing_stale(eng):
     toff1[0] = 1
     refused(lambda: eng.load_targets_arrays(tbuf, toff1))
     nothing()
+    # every early exit of the database's shape, through both loaders that reach it: no target at all, offsets that do not
+    # start at 0, and more than 2^36 bases (refused from the offsets alone: the 16 bytes are never read)
+    pk = Packed(targets)
+    no_off = np.zeros(1, dtype=np.uint64)
+    huge_off = np.array([0, 1 << 36], dtype=np.uint64)
+    dummy = np.zeros(16, dtype=np.uint8)
+
+    def load_packed(off, nseq):
+        eng._check(eng._lib.musc_db_load_packed(eng._h, pk.b2.ctypes.data, None, off.ctypes.data, nseq), "musc_db_load_packed")
+
+    for call in (lambda: eng.load_targets_arrays(tbuf, no_off),
+                 lambda: load_packed(no_off, 0),
+                 lambda: eng.load_targets_arrays(dummy, huge_off),
+                 lambda: load_packed(toff1, len(targets))):
+        eng.load_targets(targets)
+        good()
+        refused(call)
+        nothing()
     eng.load_targets(targets)
     good()
 
