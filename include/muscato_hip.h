@@ -541,6 +541,60 @@ int musc_sz_decode(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint8_t
 int musc_db_load_text(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int on_device, int framed,
                       musc_db_text_info* out);
 
+/* ---- target preparation from the raw file (additions; MUSC_ABI_VERSION is unchanged) --------------------------------
+ * cmd/muscato_prep_targets/main.go turns a FASTA file (processFasta, :143-213) or id<TAB>sequence text (processText,
+ * :82-141) into two texts -- the sequences, one per line, and the id lines "%011d\tname\tlen" -- and writes both through
+ * snappy's framed writer (:246-258).  These calls do on the device what the host chain slurp -> split_lines -> concat
+ * -> subx -> revcomp -> snprintf -> sz_encode does; the host functions stay the specification and the fallback.
+ *
+ * musc_targets_prep (replaces :82-213 with :48-80): `bytes` is the plain text, in host memory or (on_device != 0) in
+ * device memory at any alignment; bytes outside [bytes, bytes + nbytes) are never read.  Lines are bufio's, as for
+ * musc_db_load_text.  fasta = 0: the records are the lines in front of the first stop line -- a line that is empty or
+ * does not hold exactly one tab; the name is what stands before the tab, the sequence what follows it, every byte that
+ * is none of A C G T made X.  fasta = 1: an empty line fails the call (14); a line that begins with '>' is a header,
+ * its record the lines up to the next header, its name the whole header line; lines in front of the first header form
+ * a record with the empty name; a record without bases is dropped and takes no number; every record is substituted
+ * EXCEPT the one that reaches the end of the input with bases (:204-212).  rev = 1: every record is followed by its
+ * reverse complement (A<->T, C<->G, X->X, any other byte -> 0x00), named name_r; numbers count both strands.  The two
+ * texts stay resident in the context until the next musc_targets_prep, musc_targets_prep_free or musc_destroy; no
+ * other call touches them and they touch no other state.  A failed call leaves no prepared texts, those of an earlier
+ * call included.  nbytes == 0 succeeds with two empty texts.
+ *
+ * musc_targets_prep_text: bytes [off, off + nbytes) of one text (which: 0 sequences, 1 ids) to dst -- host memory, or
+ * device memory at any alignment; nothing outside [dst, dst + nbytes) is written.  A range beyond the text: 2.
+ *
+ * musc_targets_prep_load (replaces the write of :246-258 and the read back of cmd/muscato_screen/main.go:408-452): the
+ * resident sequence text becomes the context's database, exactly as musc_db_load_text(on_device = 1, framed = 0) on
+ * that buffer.  Without a prepared text: 2.  The prepared texts survive the load.
+ *
+ * musc_sz_frame (replaces snappy.NewBufferedWriter of :246-258): byte for byte the stream the host writer makes -- the
+ * ten identifier bytes, then uncompressed chunks of 65 536 bytes, the last one shorter, each with the masked CRC-32C of
+ * its data.  `bytes` in host or device memory at any alignment, dst likewise.  dst == NULL only sizes:
+ * *nout = 10 + 8 * chunks + nbytes.  A failed call leaves dst as it was.
+ *
+ * Codes: 2 bad arguments (fasta or rev outside 0 / 1, a NULL pointer with bytes, a range or capacity that does not
+ * fit); 10 a HIP failure ("out of memory" in the text when an allocation failed); 12 a refusal: 0xFFFFFFF0 targets or
+ * more, both strands counted (the caller keeps its host chain); 14 a bad text:
+ * "musc_targets_prep: empty line in FASTA input (line N)", N the 0-based number of the first empty line. */
+typedef struct musc_targets_prep_info {
+  uint64_t n_lines;       /* input lines                                                     */
+  uint64_t n_records;     /* kept records (one strand)                                       */
+  uint64_t n_targets;     /* lines of the sequence text = n_records * (rev ? 2 : 1)          */
+  uint64_t n_dropped;     /* FASTA records without bases                                     */
+  uint64_t stop_line;     /* text format: the first stop line, ~0 when the input ran out     */
+  uint64_t n_subx;        /* bytes that subx changed                                         */
+  uint64_t n_seq_bytes, n_id_bytes;
+  float ms;               /* device time of the stage                                        */
+  uint32_t reserved;
+} musc_targets_prep_info;
+int musc_targets_prep(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int on_device, int fasta, int rev,
+                      musc_targets_prep_info* out);
+int musc_targets_prep_text(musc_ctx* ctx, int which, uint64_t off, uint64_t nbytes, uint8_t* dst, int dst_on_device);
+int musc_targets_prep_load(musc_ctx* ctx, musc_db_text_info* out);
+int musc_targets_prep_free(musc_ctx* ctx);
+int musc_sz_frame(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int on_device, uint8_t* dst, uint64_t capacity,
+                  int dst_on_device, uint64_t* nout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,15 @@ class MuscDbTextInfo(ctypes.Structure):
     ]
 
 
+class MuscTargetsPrepInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_lines", ctypes.c_uint64), ("n_records", ctypes.c_uint64), ("n_targets", ctypes.c_uint64),
+        ("n_dropped", ctypes.c_uint64), ("stop_line", ctypes.c_uint64), ("n_subx", ctypes.c_uint64),
+        ("n_seq_bytes", ctypes.c_uint64), ("n_id_bytes", ctypes.c_uint64),
+        ("ms", ctypes.c_float), ("reserved", ctypes.c_uint32),
+    ]
+
+
 # every symbol include/muscato_hip.h declares
 SYMBOLS = [
     "musc_abi_version", "musc_init", "musc_destroy", "musc_last_error", "musc_reload_env",
@@ -85,6 +94,7 @@ SYMBOLS = [
     "musc_side_prepare", "musc_side_text", "musc_side_last_ms",
     "musc_maxmatches_apply", "musc_maxmatches_last_ms", "musc_maxmatches_last_detail",
     "musc_sz_decode", "musc_db_load_text",
+    "musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame",
 ]
 
 # `which` of musc_side_text (include/muscato_hip.h)
@@ -181,6 +191,13 @@ def load() -> ctypes.CDLL:
     lib.musc_sz_decode.restype = ctypes.c_int
     lib.musc_db_load_text.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MuscDbTextInfo)]
     lib.musc_db_load_text.restype = ctypes.c_int
+    lib.musc_targets_prep.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MuscTargetsPrepInfo)]
+    lib.musc_targets_prep_text.argtypes = [vp, ctypes.c_int, u64, u64, vp, ctypes.c_int]
+    lib.musc_targets_prep_load.argtypes = [vp, ctypes.POINTER(MuscDbTextInfo)]
+    lib.musc_targets_prep_free.argtypes = [vp]
+    lib.musc_sz_frame.argtypes = [vp, vp, u64, ctypes.c_int, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
+    for name in ("musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame"):
+        getattr(lib, name).restype = ctypes.c_int
     for name in ("musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits",
                  "musc_results_text", "musc_results_last_ms", "musc_results_number_key",
                  "musc_side_prepare", "musc_side_text", "musc_side_last_ms"):

@@ -37,6 +37,20 @@ class DbTextInfo:
 
 
 @dataclass
+class TargetsPrepInfo:
+    """musc_targets_prep_info: what Engine.prep_targets made of the raw target file."""
+    n_lines: int
+    n_records: int           # kept records (one strand)
+    n_targets: int           # lines of the sequence text: both strands with rev
+    n_dropped: int           # FASTA records without bases
+    stop_line: int           # text format: the first stop line, 2**64 - 1 when the input ran out
+    n_subx: int              # bytes that subx changed
+    n_seq_bytes: int
+    n_id_bytes: int
+    ms: float
+
+
+@dataclass
 class Config:
     """utils/config.go:10-101 -- same names; defaults of cmd/muscato/main.go:833-904."""
     ReadFileName: str = ""
@@ -250,6 +264,58 @@ class Engine:
         self.n_targets = int(info.n_targets)
         return DbTextInfo(int(info.n_targets), int(info.n_bases), int(info.n_odd), int(info.first_odd_target),
                           int(info.n_text_bytes), int(info.n_chunks), float(info.ms_decode), float(info.ms_parse))
+
+    # ---- target preparation on the device (musc_targets_prep*, musc_sz_frame)
+    def prep_targets(self, data, fasta: bool, rev: bool, on_device: bool = False) -> "TargetsPrepInfo":
+        """The raw bytes of a target file -- FASTA, or id<TAB>sequence text -- prepared on the GPU: the sequence text and
+        the id text stay resident (prepared_text, load_db_prepared) until the next call, free_prepared or close.  data:
+        bytes, or (on_device) a pair (device pointer, nbytes) at any alignment."""
+        if on_device:
+            ptr, nbytes = data
+        else:
+            buf = np.frombuffer(data, dtype=np.uint8)
+            ptr, nbytes = (buf.ctypes.data if len(buf) else None), len(buf)
+        info = _lib.MuscTargetsPrepInfo()
+        self._prep_bytes = None
+        self._check(self._lib.musc_targets_prep(self._h, ptr, int(nbytes), 1 if on_device else 0, int(fasta), int(rev), ctypes.byref(info)),
+                    "musc_targets_prep")
+        self._prep_bytes = (int(info.n_seq_bytes), int(info.n_id_bytes))
+        return TargetsPrepInfo(int(info.n_lines), int(info.n_records), int(info.n_targets), int(info.n_dropped), int(info.stop_line),
+                               int(info.n_subx), int(info.n_seq_bytes), int(info.n_id_bytes), float(info.ms))
+
+    def prepared_text(self, which: int, off: int = 0, nbytes: Optional[int] = None) -> bytes:
+        """Bytes [off, off + nbytes) of a prepared text (which: 0 sequences, 1 ids); nbytes None: to the text's end."""
+        if nbytes is None:
+            have = getattr(self, "_prep_bytes", None)
+            if have is None or which not in (0, 1):
+                raise MuscatoError("prepared_text: no prepared text (prep_targets first)" if have is None else "prepared_text: which must be 0 or 1")
+            nbytes = max(have[which] - int(off), 0)
+        out = np.empty(max(int(nbytes), 1), dtype=np.uint8)
+        self._check(self._lib.musc_targets_prep_text(self._h, int(which), int(off), int(nbytes), out.ctypes.data, 0), "musc_targets_prep_text")
+        return out[:int(nbytes)].tobytes()
+
+    def load_db_prepared(self) -> "DbTextInfo":
+        """The resident sequence text becomes the database (musc_targets_prep_load); the prepared texts stay."""
+        info = _lib.MuscDbTextInfo()
+        self.n_targets = 0
+        self._check(self._lib.musc_targets_prep_load(self._h, ctypes.byref(info)), "musc_targets_prep_load")
+        self.n_targets = int(info.n_targets)
+        return DbTextInfo(int(info.n_targets), int(info.n_bases), int(info.n_odd), int(info.first_odd_target),
+                          int(info.n_text_bytes), int(info.n_chunks), float(info.ms_decode), float(info.ms_parse))
+
+    def free_prepared(self) -> None:
+        self._prep_bytes = None
+        self._check(self._lib.musc_targets_prep_free(self._h), "musc_targets_prep_free")
+
+    def sz_frame(self, data: bytes) -> bytes:
+        """`data` as a framed snappy stream of uncompressed chunks, made on the GPU (musc_sz_frame)."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        sp = src.ctypes.data if len(src) else None
+        n = ctypes.c_uint64()
+        self._check(self._lib.musc_sz_frame(self._h, sp, len(src), 0, None, 0, 0, ctypes.byref(n)), "musc_sz_frame")
+        out = np.empty(int(n.value), dtype=np.uint8)
+        self._check(self._lib.musc_sz_frame(self._h, sp, len(src), 0, out.ctypes.data, int(n.value), 0, ctypes.byref(n)), "musc_sz_frame")
+        return out[:int(n.value)].tobytes()
 
     def build_index(self, window_width: int) -> None:
         self._check(self._lib.musc_db_build_index(self._h, int(window_width)), "musc_db_build_index")

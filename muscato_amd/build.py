@@ -40,7 +40,7 @@ BIN = os.path.join(HERE, "bin")
 HOST_HEADERS = [os.path.join(HOST, f) for f in sorted(os.listdir(HOST)) if f.endswith(".hpp")]
 TOOLS = {"muscato": "muscato_cli.cpp", "muscato_prep_targets": "muscato_prep_targets.cpp",
          "muscato_screen": "muscato_screen.cpp", "muscato_confirm": "muscato_confirm.cpp"}
-GPU_TOOLS = ("muscato", "muscato_screen", "muscato_confirm")
+GPU_TOOLS = ("muscato", "muscato_prep_targets", "muscato_screen", "muscato_confirm")
 
 
 def build_tools(force: bool = False, verbose: bool = False) -> None:

@@ -124,20 +124,92 @@ inline PreparedTargets prep_targets_fasta(const std::string& raw, bool rev) {  /
 
 // targets() + main (:215-333): .gz/.sz inputs, "fasta" decided on the original file name,
 // outputs musc_<file>.sz and musc_ids_<file>.sz next to the input
-inline void prep_targets_file(const std::string& path, bool rev, std::string* seq_out, std::string* id_out) {
+// 1: muscato_prep_targets prepares on the device unless MUSC_PREP_TARGETS=host; 0: only with MUSC_PREP_TARGETS=device
+// (read as MUSC_RESULTS is: place_by_env).  The tool has always run without a GPU, and the host chain stays its default
+// (DESIGN.md 22).
+#ifndef MUSC_PREP_TARGETS_DEFAULT_DEVICE
+#define MUSC_PREP_TARGETS_DEFAULT_DEVICE 0
+#endif
+
+// what both sides of prep_targets_file share: the input's kind, decided on the original file name, and the outputs' names
+struct PrepTargetsNames {
+  bool gz = false, sz = false, fasta = false;
+  std::string seq_out, id_out;
+};
+inline PrepTargetsNames prep_targets_names(const std::string& path) {
+  PrepTargetsNames n;
   const std::string low = to_lower(path);
-  std::string raw;
-  if (ends_with(low, ".gz")) raw = gz_decode_file(path);
-  else if (ends_with(low, ".sz")) raw = sz_decode(slurp(path));
-  else raw = slurp(path);
-  PreparedTargets pt = ends_with(low, "fasta") ? prep_targets_fasta(raw, rev) : prep_targets_text(raw, rev);
+  n.gz = ends_with(low, ".gz");
+  n.sz = !n.gz && ends_with(low, ".sz");
+  n.fasta = ends_with(low, "fasta");
   size_t slash = path.rfind('/');
   std::string dir = slash == std::string::npos ? "" : path.substr(0, slash + 1);
   std::string file = slash == std::string::npos ? path : path.substr(slash + 1);
   std::string lowf = to_lower(file);
   if (ends_with(lowf, ".gz") || ends_with(lowf, ".sz")) file = file.substr(0, file.size() - 3);
-  *seq_out = dir + "musc_" + file + ".sz";
-  *id_out = dir + "musc_ids_" + file + ".sz";
+  n.seq_out = dir + "musc_" + file + ".sz";
+  n.id_out = dir + "musc_ids_" + file + ".sz";
+  return n;
+}
+
+// The device side (musc_targets_prep, musc_sz_frame).  false, after one line on stderr: the host chain
+// runs instead -- no device, no device memory (10, "out of memory"), a refusal (12), or a bad .sz stream (13), which
+// the host decoder then ends with its own message.  An empty FASTA line (14) ends the run as the host's Die does.
+inline bool prep_targets_device(const std::string& path, const PrepTargetsNames& n, bool rev) {
+  Ctx ctx = Ctx::init(0);
+  if (!ctx) {
+    fprintf(stderr, "targets prep on the host: no device (%s)\n", musc_last_error(nullptr));
+    return false;
+  }
+  musc_ctx* c = ctx.get();
+  auto demoted = [&](int rc, const std::string& e) {
+    if (!(rc == 12 || rc == 13 || (rc == 10 && e.find("out of memory") != std::string::npos))) throw Die(1, "targets prep: " + e + "\n");
+    fprintf(stderr, "targets prep on the host: the device stage returned %d (%s)\n", rc, e.c_str());
+    return false;
+  };
+  auto u8 = [](const std::string& s) { return reinterpret_cast<const uint8_t*>(s.data()); };
+  auto m8 = [](std::string& s) { return reinterpret_cast<uint8_t*>(&s[0]); };
+  std::string raw = n.gz ? gz_decode_file(path) : slurp(path);
+  if (n.sz) {
+    uint64_t nout = 0;
+    int rc = musc_sz_decode(c, u8(raw), raw.size(), nullptr, 0, 0, &nout);
+    if (rc) return demoted(rc, musc_last_error(c));
+    std::string text(nout, '\0');
+    if ((rc = musc_sz_decode(c, u8(raw), raw.size(), m8(text), nout, 0, &nout))) return demoted(rc, musc_last_error(c));
+    raw.swap(text);
+  }
+  musc_targets_prep_info info;
+  int rc = musc_targets_prep(c, u8(raw), raw.size(), 0, n.fasta ? 1 : 0, rev ? 1 : 0, &info);
+  if (rc == 14) throw Die(1, "muscato_prep_targets: empty line in FASTA input (the reference panics here)");
+  if (rc) return demoted(rc, musc_last_error(c));
+  std::string framed[2];
+  const uint64_t nb[2] = {info.n_seq_bytes, info.n_id_bytes};
+  for (int w = 0; w < 2; w++) {
+    std::string text(nb[w], '\0');
+    if ((rc = musc_targets_prep_text(c, w, 0, nb[w], m8(text), 0))) return demoted(rc, musc_last_error(c));
+    uint64_t nout = 0;
+    if ((rc = musc_sz_frame(c, u8(text), text.size(), 0, nullptr, 0, 0, &nout))) return demoted(rc, musc_last_error(c));
+    framed[w].resize(nout);
+    if ((rc = musc_sz_frame(c, u8(text), text.size(), 0, m8(framed[w]), nout, 0, &nout))) return demoted(rc, musc_last_error(c));
+  }
+  spit(n.seq_out, framed[0]);
+  spit(n.id_out, framed[1]);
+  fprintf(stderr, "targets prep on the device: %llu lines, %llu targets, %llu + %llu bytes of text, %.3f ms\n", (unsigned long long)info.n_lines,
+          (unsigned long long)info.n_targets, (unsigned long long)nb[0], (unsigned long long)nb[1], info.ms);
+  return true;
+}
+
+inline void prep_targets_file(const std::string& path, bool rev, std::string* seq_out, std::string* id_out,
+                              Where where = Where::Host) {
+  const PrepTargetsNames n = prep_targets_names(path);
+  *seq_out = n.seq_out;
+  *id_out = n.id_out;
+  if (where == Where::Device && prep_targets_device(path, n, rev)) return;
+  std::string raw;
+  if (n.gz) raw = gz_decode_file(path);
+  else if (n.sz) raw = sz_decode(slurp(path));
+  else raw = slurp(path);
+  PreparedTargets pt = n.fasta ? prep_targets_fasta(raw, rev) : prep_targets_text(raw, rev);
   std::string a, b;
   for (auto& s : pt.seqs) { a += s; a += '\n'; }
   for (auto& s : pt.ids) { b += s; b += '\n'; }

@@ -12,7 +12,9 @@ int main(int argc, char** argv) {
       return 1;
     }
     std::string seqout, idout;
-    musc::prep_targets_file(rest[0], fl.count("rev") && fl["rev"] == "true", &seqout, &idout);
+    // MUSC_PREP_TARGETS = device | host: where the texts are prepared; anything else: the compiled default
+    const musc::Where where = musc::place_by_env(getenv("MUSC_PREP_TARGETS"), MUSC_PREP_TARGETS_DEFAULT_DEVICE != 0);
+    musc::prep_targets_file(rest[0], fl.count("rev") && fl["rev"] == "true", &seqout, &idout, where);
     fprintf(stderr, "Gene sequence file: %s\nGene ids file: %s\n", seqout.c_str(), idout.c_str());
     return 0;
   } catch (const musc::Die& d) {

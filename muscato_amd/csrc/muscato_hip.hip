@@ -379,6 +379,12 @@ struct musc_ctx {
   float mm_ms = 0, mm_ms_replay = 0;  // event time of the last musc_maxmatches_apply; of its k_mm_replay
   uint64_t mm_pairs = 0;            // pairs in the blocks which that call truncated
 
+  // target preparation on the device: the two texts of the last musc_targets_prep (0 sequences, 1 ids),
+  // until the next one, musc_targets_prep_free or musc_destroy; no other call touches them
+  DevPtr<unsigned char> tp_text[2];
+  uint64_t tp_bytes[2] = {0, 0};
+  bool tp_have = false;
+
   uint32_t batch_reads = 16u << 20;
   // A pass over the same reads, database and parameters as the last completed one needs no
   // sizing: its buffers are known to suffice, so it runs without host round trips.
@@ -732,10 +738,12 @@ void musc_destroy(musc_ctx* c) {
 
 }  // extern "C"
 
-// the loaders: databases and reads from packed or ASCII input, then from text (FASTQ; the gene file)
+// the loaders: databases and reads from packed or ASCII input, then from text (FASTQ; the gene file); target
+// preparation from the raw FASTA or id<TAB>sequence file, whose sequence text the gene-file loader takes
 #include "muscato_load.hpp"
 #include "muscato_prep.hpp"
 #include "muscato_db_text.hpp"
+#include "muscato_targets_prep.hpp"
 
 // the index layer: the build driver, eligibility, the partition planner, ensure_index, musc_db_build_index*
 #include "muscato_index.hpp"
