@@ -60,6 +60,30 @@ def build_tools(force: bool = False, verbose: bool = False) -> None:
         subprocess.check_call(cmd)
 
 
+# Stand-alone check programs of the plain-C++ plan headers (their own main, no GPU, no library): built next to the tools,
+# plain; tests/test_read_names_abi.py builds and runs the same source under the host sanitizers.
+CHECKS = {"read_names_plan_check": ("read_names_plan_check.cpp", ("read_names_plan.hpp",))}
+# (the runtimes linked statically: the program runs the same whatever else the loader is told to bring in)
+SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+
+
+def build_checks(force: bool = False, verbose: bool = False, sanitize: bool = False, out_dir: str = BIN) -> dict:
+    """-> {name: path of the program}.  sanitize: compiled with AddressSanitizer and UBSan (host code only)."""
+    os.makedirs(out_dir, exist_ok=True)
+    built = {}
+    for name, (src, hdrs) in CHECKS.items():
+        out = os.path.join(out_dir, name + ("_san" if sanitize else ""))
+        srcp = os.path.join(HOST, src)
+        deps = [srcp] + [os.path.join(CSRC, h) for h in hdrs]
+        if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+            cmd = ["g++", "-std=c++17", "-Wall"] + (SANITIZE if sanitize else ["-O2"]) + ["-o", out, srcp]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd)
+        built[name] = out
+    return built
+
+
 def _compile(src: str, force: bool, verbose: bool, defines=(), tag: str = "") -> str:
     obj = os.path.join(OBJ, os.path.basename(src) + tag + ".o")
     base = os.path.basename(src)
@@ -83,6 +107,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     build_tools(force=force, verbose=verbose)
+    build_checks(force=force, verbose=verbose)
     return LIB
 
 
