@@ -60,28 +60,54 @@ def build_tools(force: bool = False, verbose: bool = False) -> None:
         subprocess.check_call(cmd)
 
 
-# Stand-alone check programs of the plain-C++ plan headers (their own main, no GPU, no library): built next to the tools,
-# plain; tests/test_read_names_abi.py builds and runs the same source under the host sanitizers.
-CHECKS = {"read_names_plan_check": ("read_names_plan_check.cpp", ("read_names_plan.hpp",))}
+# Stand-alone check programs of the plain-C++ plan headers (their own main over host/check.hpp, no GPU, no library): built
+# next to the tools, plain; tests/test_check_programs.py runs them, and builds and runs the same sources under the host
+# sanitizers.  name: (source, the headers it includes -- relative to csrc/, those reached through muscato_host.hpp, sz.hpp
+# and cli_plan.hpp too --, the fewest checks it may report: what it printed when the entry was last touched, so that a
+# program cannot be hollowed out and still pass, and the libraries it links).
+_API = "../../include/muscato_hip.h"
+_HOST_CHAIN = ("host/muscato_host.hpp", "host/cli_config.hpp", "host/cli_maxmatches_host.hpp", "host/cli_names.hpp", "host/cli_plan.hpp",
+               "host/cli_text.hpp", "host/sz.hpp", _API)
+CHECKS = {
+    "cli_plan_check": ("cli_plan_check.cpp", ("host/check.hpp", "host/cli_names.hpp", "host/cli_plan.hpp"), 83_615_609, ()),
+    "ctx_state_check": ("ctx_state_check.cpp", ("host/check.hpp", "ctx_state.hpp", _API), 58_376_821, ()),
+    "dev_mem_check": ("dev_mem_check.cpp", ("host/check.hpp", "dev_mem.hpp"), 492, ()),
+    "index_plan_check": ("index_plan_check.cpp", ("host/check.hpp", "index_plan.hpp"), 567_030, ()),
+    "load_plan_check": ("load_plan_check.cpp", ("host/check.hpp", "load_plan.hpp"), 35_240_767, ()),
+    "maxmatches_plan_check": ("maxmatches_plan_check.cpp", ("host/check.hpp", "maxmatches_plan.hpp"), 548_365, ()),
+    "read_names_plan_check": ("read_names_plan_check.cpp", ("host/check.hpp", "read_names_plan.hpp"), 21_577_989, ()),
+    "side_names_check": ("side_names_check.cpp", ("host/check.hpp", "side_names.hpp"), 100_517, ()),
+    "sz_plan_check": ("sz_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "host/sz.hpp"), 3_599_466, ("-lz",)),
+    "targets_prep_plan_check": ("targets_prep_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "targets_prep_plan.hpp") + _HOST_CHAIN, 12_757_977, ("-lz",)),
+    "text_stage_check": ("text_stage_check.cpp", ("host/check.hpp", "text_stage.hpp"), 1_711_086, ()),
+}
 # (the runtimes linked statically: the program runs the same whatever else the loader is told to bring in)
 SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+
+
+def check_headers(name: str) -> list:
+    """The headers a check program is rebuilt for, as build.HEADERS and build.HOST_HEADERS spell them."""
+    return [os.path.normpath(os.path.join(CSRC, h)) for h in CHECKS[name][1]]
 
 
 def build_checks(force: bool = False, verbose: bool = False, sanitize: bool = False, out_dir: str = BIN) -> dict:
     """-> {name: path of the program}.  sanitize: compiled with AddressSanitizer and UBSan (host code only)."""
     os.makedirs(out_dir, exist_ok=True)
-    built = {}
-    for name, (src, hdrs) in CHECKS.items():
+
+    def one(name: str) -> str:
+        src, _, _, libs = CHECKS[name]
         out = os.path.join(out_dir, name + ("_san" if sanitize else ""))
         srcp = os.path.join(HOST, src)
-        deps = [srcp] + [os.path.join(CSRC, h) for h in hdrs]
+        deps = [srcp] + check_headers(name)
         if force or not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            cmd = ["g++", "-std=c++17", "-Wall"] + (SANITIZE if sanitize else ["-O2"]) + ["-o", out, srcp]
+            cmd = ["g++", "-std=c++17", "-Wall"] + (SANITIZE if sanitize else ["-O2"]) + ["-o", out, srcp] + list(libs)
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)
-        built[name] = out
-    return built
+        return out
+
+    with ThreadPoolExecutor(max_workers=len(CHECKS)) as ex:  # (one compiler each: eleven small programs)
+        return dict(zip(CHECKS, ex.map(one, CHECKS)))
 
 
 def _compile(src: str, force: bool, verbose: bool, defines=(), tag: str = "") -> str:

@@ -1,15 +1,13 @@
 // cli_plan_check.cpp -- the placement plan of the `muscato` driver (cli_plan.hpp) against the boolean expressions it
 // replaced, and the one name path of read preparation (cli_names.hpp) against the two loops it replaced, as a program of
-// its own so that it runs under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o cli_plan_check cli_plan_check.cpp
-//     ./cli_plan_check
+// its own so that it runs under the sanitizers: muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 // Old is the driver before the plan, transcribed expression by expression from run_muscato and run_hot_path as they
 // were (prep_device, res_device, side_device, mm_device, want_rccl, list_on_device, and the conditions of the log
 // lines); New makes the calls the driver makes now, in its order.  Both see the whole product of: each of the five
 // variables over {unset, "", host, device, rccl, junk}, GPUs over {1, 2, 3}, odd target bytes or none, an overflow or
 // none, each run-time demotion fired or not, and both values of each *_DEFAULT_DEVICE macro.
 // The name rules run on fixed cases and on seeded random groups whose names sit in heap blocks of their exact size.
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// It needs no GPU and is not part of the library.
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -17,21 +15,13 @@
 #include <string>
 #include <vector>
 
+#include "check.hpp"
 #include "cli_names.hpp"
 #include "cli_plan.hpp"
 
 namespace {
 
 using namespace musc;
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 // ---- the plan -------------------------------------------------------------------------------------------------
 
@@ -156,7 +146,7 @@ Outcome new_run(const PlanEnv& env, int GPUs, size_t nodd, const Events& ev, con
   return o;
 }
 
-void check_plan() {
+unsigned long long check_plan() {  // -> the combinations seen
   static const char* const V[6] = {nullptr, "", "host", "device", "rccl", "junk"};
   unsigned long long n = 0;
   for (int d = 0; d < 16; d++) {
@@ -171,16 +161,12 @@ void check_plan() {
             const Events ev = {(x & 1) != 0, (x & 2) != 0, (x & 4) != 0, (x & 8) != 0, (x & 16) != 0, (x & 32) != 0};
             const Outcome a = old_run(env, gpus, nodd, ev, D), b = new_run(env, gpus, nodd, ev, D);
             n++;
-            if (!(a == b) && failures < 20) {
-              fprintf(stderr, "plan differs: defaults %d env %s|%s|%s|%s|%s GPUs %d nodd %zu events %d\n", d, env.prep ? env.prep : "(unset)",
-                      env.maxmatches ? env.maxmatches : "(unset)", env.results ? env.results : "(unset)", env.side ? env.side : "(unset)",
-                      env.gather ? env.gather : "(unset)", gpus, nodd, x);
-              failures++;
-            }
+            EXPECT_MSG(a == b, "plan differs: defaults %d env %s|%s|%s|%s|%s GPUs %d nodd %zu events %d", d, env.prep ? env.prep : "(unset)",
+                       env.maxmatches ? env.maxmatches : "(unset)", env.results ? env.results : "(unset)", env.side ? env.side : "(unset)",
+                       env.gather ? env.gather : "(unset)", gpus, nodd, x);
           }
     }
   }
-  printf("plan: %llu combinations\n", n);
   // the compiled defaults are what the measurements behind them decided
   const PlanDefaults compiled;
   EXPECT(!compiled.prep && compiled.maxmatches && compiled.results && compiled.side);
@@ -188,6 +174,7 @@ void check_plan() {
   EXPECT(place_prep_by_env("junk", true) == Where::Host && place_by_env("junk", true) == Where::Device);
   EXPECT(place_prep_by_env("", true) == Where::Host && place_by_env("", true) == Where::Device);
   EXPECT(place_prep_by_env(nullptr, true) == Where::Device && place_by_env(nullptr, true) == Where::Device);
+  return n;
 }
 
 // ---- the names ------------------------------------------------------------------------------------------------
@@ -254,7 +241,7 @@ std::string check_group(const std::vector<std::string>& group) {
   return c;
 }
 
-void check_names() {
+unsigned long long check_names() {  // -> the random groups seen
   const std::string x999(999, 'x'), x1000(1000, 'y'), x1001(1001, 'z');
   EXPECT(clip_name(x999) == x999 && clip_name(x1000) == x1000);
   EXPECT(clip_name(x1001) == std::string(995, 'z') + "...");
@@ -291,18 +278,14 @@ void check_names() {
     check_group(group);
     n++;
   }
-  printf("names: %llu random groups\n", n);
+  return n;
 }
 
 }  // namespace
 
 int main() {
-  check_plan();
-  check_names();
-  if (failures) {
-    fprintf(stderr, "%d failures\n", failures);
-    return 1;
-  }
-  puts("ok");
-  return 0;
+  char census[96];
+  const unsigned long long n_plans = check_plan(), n_groups = check_names();
+  snprintf(census, sizeof census, "%llu plan combinations, %llu random name groups", n_plans, n_groups);
+  return check_done("cli_plan_check", census);
 }

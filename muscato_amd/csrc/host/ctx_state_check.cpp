@@ -1,32 +1,22 @@
 // ctx_state_check.cpp -- the stamps of csrc/ctx_state.hpp against the six booleans they replaced (hits_current, mm_list,
-// res_valid, side_after_match, side_tok_valid, side_valid), as a program of its own so that it runs under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o ctx_state_check ctx_state_check.cpp
-//     ./ctx_state_check
+// res_valid, side_after_match, side_tok_valid, side_valid), as a program of its own so that it runs under the sanitizers.
 // Old is the library before the header, transcribed event by event: each method sets and clears what the entry point of
 // that name set and cleared, in its order.  New makes the calls the library makes now.  Both are driven with the event
 // sequence of tests/test_gpu_side.py::test_refusals and with random sequences, and after every event every question of
 // ctx_state.hpp has the same answer in both -- with one exception, which is the point of the change: a
 // musc_maxmatches_apply that fails after its first write into the list.  Old went on calling the half-written list
 // that of a pass; New must say LIST_NONE, and from there on Old is told so.
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 
 #include "../ctx_state.hpp"
+#include "check.hpp"
 
 namespace {
 
 using namespace musc_state;
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 // how a call ends, as the driver decides it
 enum How {
@@ -365,10 +355,5 @@ int main() {
   EXPECT(!(k == PassKey{7, Q, 1}));
   Q = P, Q.pmatch = 0.9;
   EXPECT(!(k == PassKey{7, Q, 1}));
-  if (failures) {
-    fprintf(stderr, "%d checks failed\n", failures);
-    return 1;
-  }
-  puts("ok");
-  return 0;
+  return check_done("ctx_state_check");
 }

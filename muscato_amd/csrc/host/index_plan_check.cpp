@@ -1,28 +1,18 @@
 // index_plan_check.cpp -- the decisions of the index layer (csrc/index_plan.hpp: table shapes, memory estimates, the
 // cascade context -> line -> 64-byte buckets, the partition cuts) against their properties and a recorded decision
-// table, as a program of its own so that it runs under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o index_plan_check index_plan_check.cpp
-//     ./index_plan_check
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// table, as a program of its own so that it runs under the sanitizers.
+// It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <vector>
 
 #include "../index_plan.hpp"
+#include "check.hpp"
 
 namespace {
 
 namespace mi = musc_index;
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 // ---- the partition cuts
 
@@ -298,10 +288,5 @@ int main() {
   EXPECT(mi::index_need(mi::K_CTX, 17, 116182) == 19899300ull);
   EXPECT(mi::index_need(mi::K_CLASSIC64, 17, 116182) == 12344752ull);
   EXPECT(BY_HAND.kind == mi::K_CLASSIC64 && BY_HAND.bits == 17 && BY_HAND.direct == 0 && BY_HAND.fits == 1);
-  if (failures) {
-    fprintf(stderr, "%d checks failed\n", failures);
-    return 1;
-  }
-  puts("ok");
-  return 0;
+  return check_done("index_plan_check");
 }

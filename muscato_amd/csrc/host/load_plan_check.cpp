@@ -1,27 +1,17 @@
 // load_plan_check.cpp -- the size rules of the loaders (csrc/load_plan.hpp: the record shape and its refusals, the
 // database's words, the schedule of a streamed load and the byte ranges of its pieces) against their properties, as a
-// program of its own so that it runs under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o load_plan_check load_plan_check.cpp
-//     ./load_plan_check
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// program of its own so that it runs under the sanitizers.
+// It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "../load_plan.hpp"
+#include "check.hpp"
 
 namespace {
 
 namespace ml = musc_load;
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 // ---- the record shape
 
@@ -135,10 +125,5 @@ int main() {
   check_shape(0);
   for (uint64_t nb = 0; nb <= 5000; nb++) check_db(nb);
   for (uint64_t nb : {(1ull << 32) - 1, 1ull << 32, (1ull << 36) - 1}) check_db(nb);
-  if (failures) {
-    fprintf(stderr, "load_plan_check: %d failures\n", failures);
-    return 1;
-  }
-  puts("load_plan_check: ok");
-  return 0;
+  return check_done("load_plan_check");
 }

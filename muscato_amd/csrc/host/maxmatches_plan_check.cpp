@@ -1,8 +1,6 @@
 // maxmatches_plan_check.cpp -- the decisions of the MaxMatches replay stage that need no device
 // (csrc/maxmatches_plan.hpp: the refusal bound, the heap's place) and the literal qinsert the kernel runs, stand-alone
-// and under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o maxmatches_plan_check maxmatches_plan_check.cpp
-//     ./maxmatches_plan_check
+// and under the sanitizers: muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -10,15 +8,7 @@
 #include <vector>
 
 #include "../maxmatches_plan.hpp"
-
-static int failures = 0;
-#define CHECK(x)                                                 \
-  do {                                                           \
-    if (!(x)) {                                                  \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #x);    \
-      failures++;                                                \
-    }                                                            \
-  } while (0)
+#include "check.hpp"
 
 // k_mm_replay's insertion (the new entry travels up in a register, parents move down) on a host array of exactly
 // MaxMatches + 1 entries: the sanitizer sees every index
@@ -48,22 +38,22 @@ static void qinsert_literal(std::vector<std::pair<uint32_t, uint32_t>>& q, uint3
 int main() {
   using namespace musc_mm;
   // the refusal bound: reads of 255 bases and up to the bound are taken, one base more is not
-  CHECK(refusal(Shape{255, 20, 1000, 10}) == nullptr);
-  CHECK(refusal(Shape{MAX_READ_LEN, 20, 0, 0}) == nullptr);
-  CHECK(refusal(Shape{MAX_READ_LEN + 1, 20, 1000, 10}) != nullptr);
-  CHECK(refusal(Shape{100, 0, 1000, 10}) != nullptr);
-  CHECK(refusal(Shape{100, (int32_t)MAX_READ_LEN, 1000, 10}) == nullptr);
-  CHECK(refusal(Shape{100, (int32_t)MAX_READ_LEN + 1, 1000, 10}) != nullptr);
-  CHECK(refusal(Shape{100, 20, -1, 10}) != nullptr);
-  CHECK(refusal(Shape{100, 20, 0x7FFFFFFF, MAX_TUPLES - 1}) == nullptr);
-  CHECK(refusal(Shape{100, 20, 1000, MAX_TUPLES}) != nullptr);
+  EXPECT(refusal(Shape{255, 20, 1000, 10}) == nullptr);
+  EXPECT(refusal(Shape{MAX_READ_LEN, 20, 0, 0}) == nullptr);
+  EXPECT(refusal(Shape{MAX_READ_LEN + 1, 20, 1000, 10}) != nullptr);
+  EXPECT(refusal(Shape{100, 0, 1000, 10}) != nullptr);
+  EXPECT(refusal(Shape{100, (int32_t)MAX_READ_LEN, 1000, 10}) == nullptr);
+  EXPECT(refusal(Shape{100, (int32_t)MAX_READ_LEN + 1, 1000, 10}) != nullptr);
+  EXPECT(refusal(Shape{100, 20, -1, 10}) != nullptr);
+  EXPECT(refusal(Shape{100, 20, 0x7FFFFFFF, MAX_TUPLES - 1}) == nullptr);
+  EXPECT(refusal(Shape{100, 20, 1000, MAX_TUPLES}) != nullptr);
   static_assert(MAX_READ_LEN >= 255, "the bound may not lie below reads of 255 bases");
   // the LDS knob only lowers the capacity
-  CHECK(heap_lds_entries(0) == HEAP_LDS_ENTRIES && heap_lds_entries(-5) == HEAP_LDS_ENTRIES);
-  CHECK(heap_lds_entries(1) == 1 && heap_lds_entries(4095) == 4095 && heap_lds_entries(1L << 40) == HEAP_LDS_ENTRIES);
+  EXPECT(heap_lds_entries(0) == HEAP_LDS_ENTRIES && heap_lds_entries(-5) == HEAP_LDS_ENTRIES);
+  EXPECT(heap_lds_entries(1) == 1 && heap_lds_entries(4095) == 4095 && heap_lds_entries(1L << 40) == HEAP_LDS_ENTRIES);
   // MaxMatches + 1 entries must fit
-  CHECK(heap_in_lds(0, 1) && !heap_in_lds(1, 1) && heap_in_lds(4095, 4096) && !heap_in_lds(4096, 4096));
-  CHECK(!heap_in_lds(0x7FFFFFFF, HEAP_LDS_ENTRIES));
+  EXPECT(heap_in_lds(0, 1) && !heap_in_lds(1, 1) && heap_in_lds(4095, 4096) && !heap_in_lds(4096, 4096));
+  EXPECT(!heap_in_lds(0x7FFFFFFF, HEAP_LDS_ENTRIES));
   // the two insertions keep the same array, entry for entry
   std::mt19937 rng(7);
   for (uint32_t mm : {0u, 1u, 2u, 3u, 6u, 63u, 64u, 65u}) {
@@ -75,12 +65,10 @@ int main() {
         const uint32_t v = rng() % 5;
         size = qinsert_hole(hole, size, mm, v, i);
         qinsert_literal(lit, mm, v, i);
-        CHECK(size == lit.size());
-        for (uint32_t j = 0; j < size; j++) CHECK(hole[j] == lit[j]);
+        EXPECT(size == lit.size());
+        for (uint32_t j = 0; j < size; j++) EXPECT(hole[j] == lit[j]);
       }
     }
   }
-  if (failures) return 1;
-  puts("maxmatches_plan_check: ok");
-  return 0;
+  return check_done("maxmatches_plan_check");
 }

@@ -1,8 +1,6 @@
 // side_names_check.cpp -- the host work of the side outputs (csrc/side_names.hpp: the form check of the gene text and
-// the name ranks) against a plain model, as a program of its own so that it runs under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o side_names_check side_names_check.cpp
-//     ./side_names_check
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// the name ranks) against a plain model, as a program of its own so that it runs under the sanitizers.
+// It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -10,17 +8,9 @@
 #include <string>
 
 #include "../side_names.hpp"
+#include "check.hpp"
 
 namespace {
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 struct Text {
   std::string text;
@@ -128,10 +118,5 @@ int main() {
     }
     check(T);
   }
-  if (failures) {
-    fprintf(stderr, "%d checks failed\n", failures);
-    return 1;
-  }
-  puts("ok");
-  return 0;
+  return check_done("side_names_check");
 }

@@ -1,9 +1,7 @@
 // sz_plan_check.cpp -- the chunk table, the element walk and CRC-32C by parts (csrc/sz_plan.hpp: what the device decoder
 // of framed snappy streams is planned and checked with) against sz.hpp's sz_decode, snappy_block_decode and crc32c, as
-// a program of its own so that it runs under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o sz_plan_check sz_plan_check.cpp -lz
-//     ./sz_plan_check
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// a program of its own so that it runs under the sanitizers: muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
+// It needs no GPU and is not part of the library.
 //
 // Over seeded small streams, every single-byte change (each byte to each other value) and every truncation:
 //   sz_decode throws  <=>  the plan rejects, or snappy_block_decode on a planned chunk throws, or a CRC differs
@@ -21,20 +19,12 @@
 #include <vector>
 
 #include "../sz_plan.hpp"
+#include "check.hpp"
 #include "sz.hpp"
 
 namespace {
 
 namespace ms = musc_sz;
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 const ms::X2n x2n;
 
@@ -264,10 +254,7 @@ int main() {
   }
   EXPECT(n_refused > 0);
   EXPECT(n_thrown > n_streams / 2 && n_thrown < n_streams);
-  if (failures) {
-    fprintf(stderr, "%d failures over %llu streams\n", failures, n_streams);
-    return 1;
-  }
-  printf("ok (%llu streams, %llu rejected, %llu refused)\n", n_streams, n_thrown, n_refused);
-  return 0;
+  char census[96];
+  snprintf(census, sizeof census, "%llu streams, %llu rejected, %llu refused", n_streams, n_thrown, n_refused);
+  return check_done("sz_plan_check", census);
 }

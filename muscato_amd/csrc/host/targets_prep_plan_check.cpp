@@ -1,9 +1,7 @@
 // targets_prep_plan_check.cpp -- the arithmetic of target preparation on the device (csrc/targets_prep_plan.hpp) and the
 // passes of kernels_targets_prep.hpp restated in plain C++, against prep_targets_text / prep_targets_fasta / sz_encode
-// of the host chain (muscato_host.hpp, sz.hpp), as a program of its own so that it runs under the sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o targets_prep_plan_check targets_prep_plan_check.cpp -lz
-//     ./targets_prep_plan_check
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// of the host chain (muscato_host.hpp, sz.hpp), as a program of its own so that it runs under the sanitizers.
+// It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 //
 // Over seeded texts (short ones over the bytes that matter, longer ones with records, CRLF, headers and stop lines),
 // each copied to a heap block of exactly its size so that a read past either end is an error under the address
@@ -27,20 +25,12 @@
 
 #include "../sz_plan.hpp"
 #include "../targets_prep_plan.hpp"
+#include "check.hpp"
 #include "muscato_host.hpp"
 
 namespace {
 
 namespace tp = musc_tp;
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 const musc_sz::X2n x2n;
 const uint64_t NONE = ~0ull;
@@ -358,10 +348,7 @@ int main() {
   }
   for (const char* t : {"", "\r", "\n", ">", ">\n", "A", "\t", "a\t", "\tA", ">a\nA\n>b\n", "A\n>b\nC"}) check_text(t, true);
   EXPECT(n_refused > 1000 && n_stopped > 1000 && n_exempt > 100);
-  if (failures) {
-    fprintf(stderr, "%d failures over %llu texts\n", failures, n_texts);
-    return 1;
-  }
-  printf("ok (%llu texts, %llu refused, %llu stopped, %llu with an unsubstituted last record)\n", n_texts, n_refused, n_stopped, n_exempt);
-  return 0;
+  char census[128];
+  snprintf(census, sizeof census, "%llu texts, %llu refused, %llu stopped, %llu with an unsubstituted last record", n_texts, n_refused, n_stopped, n_exempt);
+  return check_done("targets_prep_plan_check", census);
 }

@@ -1,26 +1,16 @@
 // text_stage_check.cpp -- the staging plan of the text calls (csrc/text_stage.hpp: how a window of records is cut into
 // pieces that fit the staging buffer) against a brute-force model, as a program of its own so that it runs under the
-// sanitizers:
-//     g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -o text_stage_check text_stage_check.cpp
-//     ./text_stage_check
-// It needs no GPU and is not part of the library build.  Exit status 0 and "ok" on success.
+// sanitizers.
+// It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <vector>
 
 #include "../text_stage.hpp"
+#include "check.hpp"
 
 namespace {
-
-int failures = 0;
-#define EXPECT(cond)                                              \
-  do {                                                            \
-    if (!(cond)) {                                                \
-      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-      failures++;                                                 \
-    }                                                             \
-  } while (0)
 
 // the model: the first record whatever its size, then records one by one while the sum still fits (after an oversize
 // record nothing does, not even an empty one)
@@ -76,10 +66,5 @@ int main() {
     }
     check(len, rng() % 3 ? rng() % (1ull << 40) : 0, stage);
   }
-  if (failures) {
-    fprintf(stderr, "%d checks failed\n", failures);
-    return 1;
-  }
-  puts("ok");
-  return 0;
+  return check_done("text_stage_check");
 }

@@ -71,26 +71,6 @@ namespace {
 
 thread_local std::string g_init_error;  // musc_init may run on one host thread per GPU
 
-// a work buffer of the passes: grown by half when it is too small (ensure), freed with its owner
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  uint64_t cap = 0;  // elements
-  DevBuf() = default;  // (move-only: the moves delete the copies)
-  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) release(), p = std::exchange(o.p, nullptr), cap = std::exchange(o.cap, 0);
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-
 // roctx ranges around the kernel families (the reference's tracing hook is the
 // CPUProfile flag, cmd/muscato_screen/main.go:530-538): visible in `rocprofv3 --marker-trace`.
 // The marker library is resolved at run time; without it the ranges are no-ops.
@@ -148,27 +128,6 @@ struct CaptureGuard {
     if (g) (void)hipGraphDestroy(g);
     (void)hipGetLastError();
   }
-};
-
-// temporary device allocations of one call, released on every exit path
-struct TmpBufs {
-  void* p[16] = {};
-  int n = 0;
-  template <class T>
-  hipError_t alloc(T** out, size_t bytes) {
-    void* q = nullptr;
-    *out = nullptr;
-    if (n >= 16) return hipErrorOutOfMemory;  // (more allocations than this helper was sized for)
-    const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-    if (e == hipSuccess) p[n++] = q;
-    *out = (T*)q;
-    return e;
-  }
-  void release() {
-    for (int i = 0; i < n; i++) (void)hipFree(p[i]);
-    n = 0;
-  }
-  ~TmpBufs() { release(); }
 };
 
 }  // namespace
@@ -434,10 +393,9 @@ int fail(musc_ctx* c, int code, const char* fmt, ...) {
 template <class T>
 int ensure(musc_ctx* c, DevBuf<T>& b, uint64_t n, bool keep = false) {
   if (n <= b.cap && b.p) return 0;
-  uint64_t ncap = std::max<uint64_t>(n, b.cap + b.cap / 2);
-  ncap = std::max<uint64_t>(ncap, 1024);
+  const uint64_t ncap = grown_cap(n, b.cap);
   T* np = nullptr;
-  HIPCHK(c, hipMalloc((void**)&np, ncap * sizeof(T) + 64));
+  HIPCHK(c, hipMalloc((void**)&np, grown_bytes(ncap, sizeof(T))));
   if (keep && b.p && b.cap) {
     hipError_t e = hipMemcpyAsync(np, b.p, b.cap * sizeof(T), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
