@@ -75,7 +75,7 @@ CHECKS = {
     "index_plan_check": ("index_plan_check.cpp", ("host/check.hpp", "index_plan.hpp"), 567_030, ()),
     "load_plan_check": ("load_plan_check.cpp", ("host/check.hpp", "load_plan.hpp"), 35_240_767, ()),
     "maxmatches_plan_check": ("maxmatches_plan_check.cpp", ("host/check.hpp", "maxmatches_plan.hpp"), 548_365, ()),
-    "read_names_plan_check": ("read_names_plan_check.cpp", ("host/check.hpp", "read_names_plan.hpp"), 21_577_989, ()),
+    "read_names_plan_check": ("read_names_plan_check.cpp", ("host/check.hpp", "read_names_lanes.hpp", "read_names_plan.hpp"), 21_627_000, ()),
     "side_names_check": ("side_names_check.cpp", ("host/check.hpp", "side_names.hpp"), 100_517, ()),
     "sz_plan_check": ("sz_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "host/sz.hpp"), 3_599_466, ("-lz",)),
     "targets_prep_plan_check": ("targets_prep_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "targets_prep_plan.hpp") + _HOST_CHAIN, 12_757_977, ("-lz",)),
