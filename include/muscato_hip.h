@@ -308,6 +308,45 @@ int  musc_reads_prep_fastq(musc_ctx* ctx, const char* text, uint64_t nbytes, int
                            int32_t min_read_len, int32_t max_read_len, musc_fastq_prep* out);
 void musc_fastq_prep_free(musc_fastq_prep* p);
 
+/* ---- the names of the reads on the device (additions; MUSC_ABI_VERSION is unchanged) -------------------------------
+ * What musc_reads_prep_fastq leaves to the caller, done in place on the raw text: a name of more than 1000 bytes becomes
+ * its first 995 and "..." (cmd/muscato_prep_reads/main.go:76-79); the members of a group of identical prepared reads
+ * are ordered by that clipped name bytewise (unsigned bytes, a proper prefix first, equal names in file order: the
+ * `sort` of the seq\tname lines under LC_ALL=C); a name ends at its first tab, the names of a group are joined with ';'
+ * and a join of more than 1000 bytes becomes its first 996 and "..." (cmd/muscato_uniqify/main.go:83-135).
+ * Groups of up to 64 members are ranked by counting; the members of larger groups by W + 2 stable radix-sort passes
+ * over 64-bit keys (clipped length and read number; the W 8-byte words of the longest clipped name, last to first; the
+ * group number).  No sort under a comparator runs.
+ *
+ * musc_reads_names_order: the ranking alone, on hand-fed groups.  text, name_off, name_len, order, ustart are what
+ * musc_reads_prep_fastq takes and returns (on_device != 0: text is a device pointer; the arrays are host arrays);
+ * n = the kept reads, nu = the groups, ranked_out[n] = the kept reads group by group in name order.  The arrays are
+ * checked before anything is indexed by them (a name outside the text, a member >= n, groups that are empty or do not
+ * span the n places: 2).  Needs no loaded reads and leaves the context's reads and texts alone. */
+int musc_reads_names_order(musc_ctx* ctx, const char* text, uint64_t nbytes, int on_device, const uint64_t* name_off,
+                           const uint32_t* name_len, uint64_t n, const uint32_t* order, const uint32_t* ustart, uint64_t nu,
+                           uint32_t* ranked_out);
+/* musc_reads_prep_fastq_names: musc_reads_prep_fastq with the text kept resident until the records count\tJ of all groups
+ * are rendered; they are left as the context's read text exactly as musc_results_set_read_text of the same bytes would
+ * leave them.  `out` as musc_reads_prep_fastq fills it (musc_fastq_prep_free); `info` as below, ranked[n_reads] =
+ * the kept reads group by group in name order, malloc'ed by the library: musc_free_u32.  After a failed call the context
+ * holds no reads and no read text, and both structs are all zero. */
+typedef struct musc_read_names {
+  uint64_t text_bytes, line_bytes;         /* of all records count\tJ / of all lines seq\tcount\tJ\n   */
+  uint64_t n_single, n_counted, n_sorted;  /* groups of 1 / of 2 to 64 / of more members              */
+  uint64_t n_pairs;                        /* members of the groups that went through the key passes  */
+  uint32_t key_passes;                     /* W + 2, or 0 when no group has more than 64 members      */
+  float ms_names;                          /* device time of the stage behind the sort + collapse     */
+  uint32_t* ranked;
+} musc_read_names;
+int musc_reads_prep_fastq_names(musc_ctx* ctx, const char* text, uint64_t nbytes, int on_device, int32_t min_read_len,
+                                int32_t max_read_len, musc_fastq_prep* out, musc_read_names* info);
+/* Records [rec0, rec0 + nrec) (clipped at the end) of the texts the call above left: which = 0, the records count\tJ;
+ * which = 1, the lines seq\tcount\tJ\n, which are reads_sorted.txt byte for byte.  dst, capacity, dst_on_device and
+ * *nbytes as musc_results_text.  Refused (2) once the reads or the read text have been replaced. */
+int musc_reads_names_text(musc_ctx* ctx, int which, uint64_t rec0, uint64_t nrec, char* dst, uint64_t capacity, int dst_on_device,
+                          uint64_t* nbytes);
+
 /* ---- the hot path: screen + confirm (+ per-read best filter) -------------------------
  * musc_match_device leaves the hits in device memory (count in *nhits);
  * musc_hits_copy copies them to `dst` (host, or device if dst_on_device) -- capacity in

@@ -62,6 +62,16 @@ class MuscFastqPrep(ctypes.Structure):
     ]
 
 
+class MuscReadNames(ctypes.Structure):
+    _fields_ = [
+        ("text_bytes", ctypes.c_uint64), ("line_bytes", ctypes.c_uint64),
+        ("n_single", ctypes.c_uint64), ("n_counted", ctypes.c_uint64), ("n_sorted", ctypes.c_uint64),
+        ("n_pairs", ctypes.c_uint64),
+        ("key_passes", ctypes.c_uint32), ("ms_names", ctypes.c_float),
+        ("ranked", ctypes.POINTER(ctypes.c_uint32)),
+    ]
+
+
 class MuscDbTextInfo(ctypes.Structure):
     _fields_ = [
         ("n_targets", ctypes.c_uint64), ("n_bases", ctypes.c_uint64), ("n_odd", ctypes.c_uint64),
@@ -87,6 +97,7 @@ SYMBOLS = [
     "musc_db_set_partition_bases", "musc_db_partitions",
     "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique",
     "musc_reads_prep_fastq", "musc_fastq_prep_free",
+    "musc_reads_names_order", "musc_reads_prep_fastq_names", "musc_reads_names_text",
     "musc_match_device", "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_free_hits",
     "musc_get_stats", "musc_last_instance", "musc_instances", "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
     "musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits", "musc_results_text",
@@ -151,6 +162,11 @@ def load() -> ctypes.CDLL:
     lib.musc_reads_prep_fastq.restype = ctypes.c_int
     lib.musc_fastq_prep_free.argtypes = [ctypes.POINTER(MuscFastqPrep)]
     lib.musc_fastq_prep_free.restype = None
+    lib.musc_reads_names_order.argtypes = [vp, vp, u64, ctypes.c_int, vp, vp, u64, vp, vp, u64, vp]
+    lib.musc_reads_prep_fastq_names.argtypes = [vp, vp, u64, ctypes.c_int, i32, i32, ctypes.POINTER(MuscFastqPrep), ctypes.POINTER(MuscReadNames)]
+    lib.musc_reads_names_text.argtypes = [vp, ctypes.c_int, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
+    for name in ("musc_reads_names_order", "musc_reads_prep_fastq_names", "musc_reads_names_text"):
+        getattr(lib, name).restype = ctypes.c_int
     lib.musc_match_device.argtypes = [vp, ctypes.POINTER(MuscParams), ctypes.POINTER(u64)]
     lib.musc_hits_copy.argtypes = [vp, vp, u64, ctypes.c_int]
     lib.musc_hits_copy_packed.argtypes = [vp, vp, u64, ctypes.c_int, u64, ctypes.POINTER(i32)]

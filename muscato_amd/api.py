@@ -417,6 +417,65 @@ class Engine:
         self.n_reads = nu
         return out
 
+    # ---- the names of the reads on the device
+    def names_order(self, raw: bytes, name_off, name_len, order, ustart) -> np.ndarray:
+        """The members of hand-fed groups in the order of their clipped names (musc_reads_names_order): the arrays are
+        those prep_fastq returns for `raw`.  -> the kept reads, group by group, ranked.  Touches no loaded reads."""
+        buf = np.frombuffer(raw, dtype=np.uint8)
+        no = np.ascontiguousarray(name_off, dtype=np.uint64)
+        nl = np.ascontiguousarray(name_len, dtype=np.uint32)
+        od = np.ascontiguousarray(order, dtype=np.uint32)
+        us = np.ascontiguousarray(ustart, dtype=np.uint32)
+        n = len(od)
+        if len(no) != n or len(nl) != n or len(us) < 1:
+            raise MuscatoError("names_order: name_off, name_len and order must have one entry per kept read, ustart one more than the groups")
+        ranked = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(self._lib.musc_reads_names_order(self._h, buf.ctypes.data if len(buf) else None, len(buf), 0, no.ctypes.data, nl.ctypes.data,
+                                                     n, od.ctypes.data, us.ctypes.data, len(us) - 1, ranked.ctypes.data),
+                    "musc_reads_names_order")
+        return ranked[:n]
+
+    def prep_fastq_names(self, raw: bytes, min_len: int, max_len: int) -> dict:
+        """prep_fastq with the names ordered, cut and joined on the device (musc_reads_prep_fastq_names): the record
+        ``count\\tnames`` of every distinct read is left as the context's read text, as set_read_text would leave it.
+        -> the dict of prep_fastq, and "ranked" (the kept reads group by group in name order) and "names" (text_bytes,
+        line_bytes, n_single, n_counted, n_sorted, n_pairs, key_passes, ms_names)."""
+        buf = np.frombuffer(raw, dtype=np.uint8)
+        return self.prep_fastq_names_device(buf.ctypes.data if len(buf) else None, len(buf), min_len, max_len, on_device=False)
+
+    def prep_fastq_names_device(self, ptr: Optional[int], nbytes: int, min_len: int, max_len: int, on_device: bool = True) -> dict:
+        fp, info = _lib.MuscFastqPrep(), _lib.MuscReadNames()
+        self.n_reads = 0
+        self._check(self._lib.musc_reads_prep_fastq_names(self._h, ptr, int(nbytes), 1 if on_device else 0, int(min_len), int(max_len),
+                                                          ctypes.byref(fp), ctypes.byref(info)), "musc_reads_prep_fastq_names")
+        try:
+            n, nu = int(fp.n_reads), int(fp.n_unique)
+
+            def arr(p, count):
+                return np.ctypeslib.as_array(p, shape=(max(count, 1),))[:count].copy() if count else np.zeros(0, dtype=p._type_)
+            out = {"n_records": int(fp.n_records), "n_short": int(fp.n_short), "n_reads": n, "n_unique": nu,
+                   "max_len": int(fp.max_len), "name_off": arr(fp.name_off, n), "seq_off": arr(fp.seq_off, n),
+                   "name_len": arr(fp.name_len, n), "seq_len": arr(fp.seq_len, n), "order": arr(fp.order, n),
+                   "ustart": arr(fp.ustart, nu + 1), "ranked": arr(info.ranked, n),
+                   "names": {k: getattr(info, k) for k, _ in _lib.MuscReadNames._fields_ if k != "ranked"}}
+        finally:
+            self._lib.musc_fastq_prep_free(ctypes.byref(fp))
+            self._lib.musc_free_u32(ctypes.cast(info.ranked, ctypes.c_void_p))
+        self.n_reads = nu
+        return out
+
+    def names_text(self, which: int = 0, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
+        """Records [rec0, rec0 + nrec) of what prep_fastq_names rendered: which 0, the records ``count\\tnames``; which
+        1, the lines ``seq\\tcount\\tnames\\n`` of reads_sorted.txt."""
+        return self._text_range("musc_reads_names_text", self._lib.musc_reads_names_text, (self._h, int(which)), rec0, nrec)
+
+    def names_text_into(self, which: int, rec0: int, nrec: int, dst_ptr: int, capacity: int, on_device: bool) -> int:
+        """The same into a buffer of the caller's, on the host or on the device -> the bytes written."""
+        nb = ctypes.c_uint64()
+        self._check(self._lib.musc_reads_names_text(self._h, int(which), int(rec0), int(nrec), dst_ptr, int(capacity), 1 if on_device else 0,
+                                                    ctypes.byref(nb)), "musc_reads_names_text")
+        return int(nb.value)
+
     def load_reads_packed(self, seqs: Sequence[bytes]) -> None:
         buf, off = concat(seqs)
         packed, mask = pack_2bit(buf, int(off[-1]))

@@ -69,13 +69,13 @@ _API = "../../include/muscato_hip.h"
 _HOST_CHAIN = ("host/muscato_host.hpp", "host/cli_config.hpp", "host/cli_maxmatches_host.hpp", "host/cli_names.hpp", "host/cli_plan.hpp",
                "host/cli_text.hpp", "host/sz.hpp", _API)
 CHECKS = {
-    "cli_plan_check": ("cli_plan_check.cpp", ("host/check.hpp", "host/cli_names.hpp", "host/cli_plan.hpp"), 83_615_609, ()),
+    "cli_plan_check": ("cli_plan_check.cpp", ("host/check.hpp", "host/cli_names.hpp", "host/cli_plan.hpp"), 184_205_945, ()),
     "ctx_state_check": ("ctx_state_check.cpp", ("host/check.hpp", "ctx_state.hpp", _API), 58_376_821, ()),
     "dev_mem_check": ("dev_mem_check.cpp", ("host/check.hpp", "dev_mem.hpp"), 492, ()),
     "index_plan_check": ("index_plan_check.cpp", ("host/check.hpp", "index_plan.hpp"), 567_030, ()),
     "load_plan_check": ("load_plan_check.cpp", ("host/check.hpp", "load_plan.hpp"), 35_240_767, ()),
     "maxmatches_plan_check": ("maxmatches_plan_check.cpp", ("host/check.hpp", "maxmatches_plan.hpp"), 548_365, ()),
-    "read_names_plan_check": ("read_names_plan_check.cpp", ("host/check.hpp", "read_names_lanes.hpp", "read_names_plan.hpp"), 21_627_000, ()),
+    "read_names_plan_check": ("read_names_plan_check.cpp", ("host/check.hpp", "read_names_keys.hpp", "read_names_lanes.hpp", "read_names_plan.hpp"), 21_928_502, ()),
     "side_names_check": ("side_names_check.cpp", ("host/check.hpp", "side_names.hpp"), 100_517, ()),
     "sz_plan_check": ("sz_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "host/sz.hpp"), 3_599_466, ("-lz",)),
     "targets_prep_plan_check": ("targets_prep_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "targets_prep_plan.hpp") + _HOST_CHAIN, 12_757_977, ("-lz",)),

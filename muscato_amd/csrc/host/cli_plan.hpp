@@ -1,5 +1,5 @@
 // cli_plan.hpp -- where each stage of a `muscato` run takes place, decided once.  Plain C++17: no
-// library call and no getenv here; the driver reads the six environment values in one place and passes them in.
+// library call and no getenv here; the driver reads the seven environment values in one place and passes them in.
 // Included by muscato_host.hpp and by cli_plan_check.cpp, the stand-alone program that holds it to the boolean
 // expressions it replaced, under the sanitizers.
 #pragma once
@@ -36,6 +36,13 @@ namespace musc {
 #define MUSC_PREP_DEFAULT_DEVICE 0
 #endif
 
+// 1: when the read file is parsed on the device the CLI also takes the names of the reads from it (their order within a
+// group, the cut at the first tab, the join: DESIGN.md 23) unless MUSC_PREP_NAMES=host; 0: only with
+// MUSC_PREP_NAMES=device.  0 until profiles/read_names.py has been run on more than one box.
+#ifndef MUSC_PREP_NAMES_DEFAULT_DEVICE
+#define MUSC_PREP_NAMES_DEFAULT_DEVICE 0
+#endif
+
 // 1: the CLI decodes, splits and packs the gene file on the device unless MUSC_TARGETS=host; 0: only with
 // MUSC_TARGETS=device.  Measured (profiles/targets_load.py): the laps `windows check, target files` and
 // `hot path (init, load, match)` of a 2 M-read run over a 100 MB gene file add up to 0.229 s with the gene file on the
@@ -46,10 +53,11 @@ namespace musc {
 
 enum class Where { Host, Device };
 
-// the six environment values as the process has them, each possibly null
+// the seven environment values as the process has them, each possibly null
 struct PlanEnv {
   const char *prep = nullptr, *maxmatches = nullptr, *results = nullptr, *side = nullptr, *gather = nullptr;
   const char* targets = nullptr;
+  const char* prep_names = nullptr;
 };
 
 // what a stage does when its variable does not say: the *_DEFAULT_DEVICE macros (arguments, so that the check program
@@ -58,11 +66,12 @@ struct PlanDefaults {
   bool prep = MUSC_PREP_DEFAULT_DEVICE != 0, maxmatches = MUSC_MAXMATCHES_DEFAULT_DEVICE != 0,
        results = MUSC_RESULTS_DEFAULT_DEVICE != 0, side = MUSC_SIDE_DEFAULT_DEVICE != 0;
   bool targets = MUSC_TARGETS_DEFAULT_DEVICE != 0;
+  bool prep_names = MUSC_PREP_NAMES_DEFAULT_DEVICE != 0;
 };
 
 // The parse rules, which are not the same for every variable (and stay so here):
 //   MUSC_RESULTS, MUSC_SIDE, MUSC_MAXMATCHES,
-//   MUSC_TARGETS                               "device" and "host" say so; unset, empty and every other value mean the
+//   MUSC_TARGETS, MUSC_PREP_NAMES              "device" and "host" say so; unset, empty and every other value mean the
 //                                              compiled default
 //   MUSC_PREP                                  unset means the compiled default; once set, only "device" means the
 //                                              device: empty and every other value mean the host
@@ -82,7 +91,8 @@ inline Where place_prep_by_env(const char* v, bool default_device) {
 enum class Demotion {
   SeveralGpus,       // the post-chain of several GPUs runs on the host: results, side outputs and the replay
   OddTargetBytes,    // targets with bytes that are none of ACGTX, which the device would render as X: results, hence side
-  PrepNoMemory,      // musc_reads_prep_fastq found no device memory
+  PrepNoMemory,      // musc_reads_prep_fastq found no device memory: the parse, and the names with it
+  PrepNamesNoMemory, // musc_reads_prep_fastq_names found no device memory: the parse runs again without the names
   GatherFailed,      // musc_gather_rccl failed: the host gather takes over
   ReplayPassFailed,  // the reload or the pass in front of the replay failed (the run ends with that error)
   ReplayRefused,     // musc_maxmatches_apply returned 12 (refusal) or 10 (no memory)
@@ -101,6 +111,9 @@ struct Placement {
   int gpus = 1;
   bool results_env_host = false;
   Where targets = Where::Host;  // the gene file: snappy frames, lines, 2-bit pack
+  // the names of the reads: on the device only when the parse is, since the stage reads them in the text
+  // the parse keeps resident
+  Where prep_names = Where::Host;
 
   // The one place a stage is moved to the host.  The side outputs are made from the ordered list behind results.txt,
   // which exists on the device only when results.txt was ordered there: whatever takes the results to the host takes
@@ -115,7 +128,8 @@ struct Placement {
         note_odd_targets = gpus == 1 && !results_env_host;
         results = side = Where::Host;
         break;
-      case Demotion::PrepNoMemory: prep = Where::Host; break;
+      case Demotion::PrepNoMemory: prep = prep_names = Where::Host; break;
+      case Demotion::PrepNamesNoMemory: prep_names = Where::Host; break;
       case Demotion::GatherFailed: gather_rccl = false; break;
       case Demotion::ReplayPassFailed:
       case Demotion::ReplayRefused: maxmatches = Where::Host; break;
@@ -140,6 +154,7 @@ inline Placement make_placement(const PlanEnv& env, int gpus, const PlanDefaults
   p.gpus = gpus;
   p.results_env_host = env.results && !strcmp(env.results, "host");
   p.prep = place_prep_by_env(env.prep, def.prep);
+  p.prep_names = p.prep == Where::Device ? place_by_env(env.prep_names, def.prep_names) : Where::Host;
   p.maxmatches = place_by_env(env.maxmatches, def.maxmatches);
   p.results = place_by_env(env.results, def.results);
   p.side = p.results == Where::Device ? place_by_env(env.side, def.side) : Where::Host;

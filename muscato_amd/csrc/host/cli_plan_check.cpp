@@ -5,7 +5,10 @@
 // were (prep_device, res_device, side_device, mm_device, want_rccl, list_on_device, and the conditions of the log
 // lines); New makes the calls the driver makes now, in its order.  Both see the whole product of: each of the five
 // variables over {unset, "", host, device, rccl, junk}, GPUs over {1, 2, 3}, odd target bytes or none, an overflow or
-// none, each run-time demotion fired or not, and both values of each *_DEFAULT_DEVICE macro.
+// none, each run-time demotion fired or not, and both values of each *_DEFAULT_DEVICE macro.  MUSC_PREP_NAMES, which came
+// after the plan, is held to its boolean expression in that product too -- its value, its default and its demotion
+// change with the combination, so that every pair of it with another input occurs -- and over the whole product of
+// what the expression reads (check_names_plan).
 // The name rules run on fixed cases and on seeded random groups whose names sit in heap blocks of their exact size.
 // It needs no GPU and is not part of the library.
 #include <cstdio>
@@ -28,6 +31,7 @@ using namespace musc;
 // what a stage finds when it runs
 struct Events {
   bool overflow, prep_no_memory, rccl_failed, replay_pass_failed, replay_refused, side_refused;
+  bool names_no_memory = false;
 };
 
 // everything of a run that depends on the placement
@@ -42,11 +46,13 @@ struct Outcome {
   bool list_on_device = false;     // ... from the resident list
   bool ctx_to_side = false;        // context 0 outlives results.txt
   bool side_from_device = false;   // the three side outputs are the device's
+  bool names_on_device = false;    // the names of the reads were ordered, cut and joined on the device
+  bool prep_ran_twice = false;     // ... or the device parse ran again without them
   bool operator==(const Outcome& o) const {
     return prep_on_device == o.prep_on_device && rccl == o.rccl && note_odd == o.note_odd && note_gpus == o.note_gpus &&
            died == o.died && replayed_on_device == o.replayed_on_device && replayed_on_host == o.replayed_on_host &&
            results_on_device == o.results_on_device && list_on_device == o.list_on_device && ctx_to_side == o.ctx_to_side &&
-           side_from_device == o.side_from_device;
+           side_from_device == o.side_from_device && names_on_device == o.names_on_device && prep_ran_twice == o.prep_ran_twice;
   }
 };
 
@@ -57,6 +63,12 @@ Outcome old_run(const PlanEnv& env, int GPUs, size_t nodd, const Events& ev, con
   const char* prep_env = env.prep;
   const bool prep_device = prep_env ? !strcmp(prep_env, "device") : MUSC_PREP_DEFAULT != 0;
   o.prep_on_device = prep_device && !ev.prep_no_memory;  // (prep_reads_device ran prep_reads in its place)
+  // (the names: the expression the plan's field stands for)
+  const char* names_env = env.prep_names;
+  const bool names_env_device = names_env && !strcmp(names_env, "device"), names_env_host = names_env && !strcmp(names_env, "host");
+  const bool names_device = prep_device && (names_env_device || (!names_env_host && D.prep_names));
+  o.prep_ran_twice = names_device && ev.names_no_memory && !ev.prep_no_memory;
+  o.names_on_device = names_device && !ev.names_no_memory && !ev.prep_no_memory;
   // run_muscato, in front of the hot path
   const char* res_env = env.results;
   const bool env_device = res_env && !strcmp(res_env, "device"), env_host = res_env && !strcmp(res_env, "host");
@@ -115,9 +127,17 @@ Outcome old_run(const PlanEnv& env, int GPUs, size_t nodd, const Events& ev, con
 Outcome new_run(const PlanEnv& env, int GPUs, size_t nodd, const Events& ev, const PlanDefaults& D) {
   Outcome o;
   Placement plan = make_placement(env, GPUs, D);
-  // stage_read_prep
+  // stage_read_prep: prep_reads_device with the names, without them when they found no memory, prep_reads when the
+  // parse found none (a device without memory for the parse has none for the parse and the names)
+  EXPECT(plan.prep_names == Where::Host || plan.prep == Where::Device);
   if (plan.prep == Where::Device && ev.prep_no_memory) plan.demote(Demotion::PrepNoMemory);
+  if (plan.prep_names == Where::Device && ev.names_no_memory) {
+    plan.demote(Demotion::PrepNamesNoMemory);
+    o.prep_ran_twice = true;
+  }
   o.prep_on_device = plan.prep == Where::Device;
+  o.names_on_device = plan.prep_names == Where::Device;
+  EXPECT(!o.names_on_device || o.prep_on_device);
   // stage_target_files, stage_hot_path
   if (nodd) plan.demote(Demotion::OddTargetBytes);
   o.note_odd = plan.note_odd_targets;
@@ -155,25 +175,61 @@ unsigned long long check_plan() {  // -> the combinations seen
     for (int e = 0; e < 6 * 6 * 6 * 6 * 6; e++) {
       PlanEnv env;
       env.prep = V[e % 6], env.maxmatches = V[e / 6 % 6], env.results = V[e / 36 % 6], env.side = V[e / 216 % 6], env.gather = V[e / 1296];
+      env.prep_names = V[(e / 6 + e / 7776 + d) % 6];  // (every value beside every value of each other variable)
+      D.prep_names = ((e / 36) + d) & 1;
       for (int gpus = 1; gpus <= 3; gpus++)
         for (size_t nodd = 0; nodd <= 1; nodd++)
           for (int x = 0; x < 64; x++) {
-            const Events ev = {(x & 1) != 0, (x & 2) != 0, (x & 4) != 0, (x & 8) != 0, (x & 16) != 0, (x & 32) != 0};
+            const Events ev = {(x & 1) != 0, (x & 2) != 0, (x & 4) != 0, (x & 8) != 0, (x & 16) != 0, (x & 32) != 0, ((x >> 1) + gpus + e) % 2 != 0};
             const Outcome a = old_run(env, gpus, nodd, ev, D), b = new_run(env, gpus, nodd, ev, D);
             n++;
-            EXPECT_MSG(a == b, "plan differs: defaults %d env %s|%s|%s|%s|%s GPUs %d nodd %zu events %d", d, env.prep ? env.prep : "(unset)",
+            EXPECT_MSG(a == b, "plan differs: defaults %d env %s|%s|%s|%s|%s|%s GPUs %d nodd %zu events %d", d, env.prep ? env.prep : "(unset)",
                        env.maxmatches ? env.maxmatches : "(unset)", env.results ? env.results : "(unset)", env.side ? env.side : "(unset)",
-                       env.gather ? env.gather : "(unset)", gpus, nodd, x);
+                       env.gather ? env.gather : "(unset)", env.prep_names ? env.prep_names : "(unset)", gpus, nodd, x);
           }
     }
   }
   // the compiled defaults are what the measurements behind them decided
   const PlanDefaults compiled;
-  EXPECT(!compiled.prep && compiled.maxmatches && compiled.results && compiled.side);
+  EXPECT(!compiled.prep && compiled.maxmatches && compiled.results && compiled.side && !compiled.prep_names);
   // and the two parse rules differ where the comment of cli_plan.hpp says they do
   EXPECT(place_prep_by_env("junk", true) == Where::Host && place_by_env("junk", true) == Where::Device);
   EXPECT(place_prep_by_env("", true) == Where::Host && place_by_env("", true) == Where::Device);
   EXPECT(place_prep_by_env(nullptr, true) == Where::Device && place_by_env(nullptr, true) == Where::Device);
+  return n;
+}
+
+// MUSC_PREP_NAMES over the whole product of what its expression reads -- itself and MUSC_PREP over the six values, both
+// defaults, both no-memory events -- with every other variable over {unset, host, device}, GPUs over {1, 2, 3}, odd
+// target bytes or none and an overflow or none: the rest of the outcome is what it is for MUSC_PREP_NAMES unset.
+unsigned long long check_names_plan() {
+  static const char* const V[6] = {nullptr, "", "host", "device", "rccl", "junk"};
+  static const char* const O[3] = {nullptr, "host", "device"};
+  unsigned long long n = 0;
+  for (int d = 0; d < 4; d++)
+    for (int e = 0; e < 36; e++)
+      for (int o = 0; o < 81; o++)
+        for (int gpus = 1; gpus <= 3; gpus++)
+          for (int x = 0; x < 16; x++) {
+            PlanDefaults D;
+            D.prep = d & 1, D.prep_names = d & 2;
+            PlanEnv env;
+            env.prep = V[e % 6], env.prep_names = V[e / 6];
+            env.maxmatches = O[o % 3], env.results = O[o / 3 % 3], env.side = O[o / 9 % 3], env.targets = O[o / 27];
+            Events ev = {(x & 1) != 0, (x & 2) != 0, false, false, false, false, (x & 4) != 0};
+            const size_t nodd = (x & 8) != 0;
+            const Outcome a = old_run(env, gpus, nodd, ev, D), b = new_run(env, gpus, nodd, ev, D);
+            EXPECT_MSG(a == b, "names plan differs: defaults %d env %d others %d GPUs %d events %d", d, e, o, gpus, x);
+            PlanEnv unset = env;
+            unset.prep_names = nullptr;
+            D.prep_names = false;
+            ev.names_no_memory = false;
+            Outcome c = new_run(unset, gpus, nodd, ev, D);
+            EXPECT(!c.names_on_device && !c.prep_ran_twice);
+            c.names_on_device = b.names_on_device, c.prep_ran_twice = b.prep_ran_twice;
+            EXPECT_MSG(b == c, "MUSC_PREP_NAMES moved another stage: defaults %d env %d others %d GPUs %d events %d", d, e, o, gpus, x);
+            n++;
+          }
   return n;
 }
 
@@ -285,7 +341,7 @@ unsigned long long check_names() {  // -> the random groups seen
 
 int main() {
   char census[96];
-  const unsigned long long n_plans = check_plan(), n_groups = check_names();
+  const unsigned long long n_plans = check_plan() + check_names_plan(), n_groups = check_names();
   snprintf(census, sizeof census, "%llu plan combinations, %llu random name groups", n_plans, n_groups);
   return check_done("cli_plan_check", census);
 }

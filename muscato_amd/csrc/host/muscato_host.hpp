@@ -444,30 +444,91 @@ inline std::vector<UniqueRead> prep_reads(const std::string& fastq, const Config
   return out;
 }
 
+// The names of the reads from the device too (MUSC_PREP_NAMES): musc_reads_prep_fastq_names has ordered,
+// cut and joined them and rendered the lines seq\tcount\tnames\n, which are reads_sorted.txt byte for byte.  They come
+// down in chunks of records and each line is cut into the three fields of a UniqueRead: no string is made per read of
+// the file.  *line_text keeps the bytes for reads_sorted.txt.sz.
+inline void reads_from_lines(musc_ctx* c, const musc_fastq_prep& fp, const musc_read_names& info, std::vector<UniqueRead>* out,
+                             std::string* line_text) {
+  const uint64_t chunk_records = 1ull << 20;
+  line_text->resize(info.line_bytes);
+  uint64_t pos = 0;
+  for (uint64_t r0 = 0; r0 < fp.n_unique; r0 += chunk_records) {
+    uint64_t nb = 0;
+    if (musc_reads_names_text(c, 1, r0, chunk_records, &(*line_text)[0] + pos, info.line_bytes - pos, 0, &nb))
+      throw Die(1, std::string("read prep: ") + musc_last_error(c));
+    pos += nb;
+  }
+  if (pos != info.line_bytes) throw Die(1, "read prep: the line text of the device has " + std::to_string(pos) + " bytes, " + std::to_string(info.line_bytes) + " were announced");
+  out->clear();
+  out->reserve(fp.n_unique);
+  const char* p = line_text->data();
+  const char* const end = p + line_text->size();
+  for (uint64_t g = 0; g < fp.n_unique; g++) {  // seq \t count \t names \n: the join holds no tab and no line end
+    const char* t1 = (const char*)memchr(p, '\t', (size_t)(end - p));
+    const char* t2 = t1 ? (const char*)memchr(t1 + 1, '\t', (size_t)(end - t1 - 1)) : nullptr;
+    const char* nl = t2 ? (const char*)memchr(t2 + 1, '\n', (size_t)(end - t2 - 1)) : nullptr;
+    if (!nl) throw Die(1, "read prep: line " + std::to_string(g) + " of the device's line text is incomplete");
+    size_t count = 0;
+    for (const char* q = t1 + 1; q < t2; q++) count = count * 10 + (size_t)(*q - '0');
+    out->push_back(UniqueRead{std::string(p, t1), count, std::string(t2 + 1, nl)});
+    p = nl + 1;
+  }
+  if (p != end) throw Die(1, "read prep: the device's line text holds more than its " + std::to_string(fp.n_unique) + " lines");
+}
+
 // The same with the parse on the device (musc_reads_prep_fastq: records, the \r rule, MinReadLength, subx,
 // MaxReadLength, sort and collapse); the host makes strings of the group heads' sequences and of the names only, and
-// keeps the name rules (cli_names.hpp).
+// keeps the name rules (cli_names.hpp) -- unless the plan puts the names on the device as well (reads_from_lines).
 // false: the device had no memory for the stage, the log says so and the host path is to run.
-inline bool prep_reads_device(const std::string& fastq, const Config& c, size_t* n_total, Logger& log, std::vector<UniqueRead>* out) {
+inline bool prep_reads_device(const std::string& fastq, const Config& c, Placement& plan, size_t* n_total, Logger& log,
+                              std::vector<UniqueRead>* out, std::string* line_text) {
   FastqPrep prep;
   musc_fastq_prep& fp = prep.fp;
   musc_stats st;
+  bool names_done = false;
   {  // (the context goes before the host makes its strings, and before the host path runs in its place)
     Ctx ctx = Ctx::init(c.Device);
     if (!ctx) throw Die(1, std::string("read prep: ") + musc_last_error(nullptr));
-    const int rc = musc_reads_prep_fastq(ctx.get(), fastq.data(), fastq.size(), 0, c.MinReadLength, c.MaxReadLength, &fp);
-    if (rc) {
-      const std::string e = musc_last_error(ctx.get());
+    auto no_memory = [&](int rc, const std::string& e) {  // any other failure ends the run
       if (rc != 10 || e.find("out of memory") == std::string::npos) throw Die(1, "read prep: " + e);
-      ctx.reset();
-      log.printf("read prep on the host: the device stage found no memory (%s)", e.c_str());
-      return false;
+    };
+    if (plan.prep_names == Where::Device) {
+      musc_read_names info{};
+      const int rc = musc_reads_prep_fastq_names(ctx.get(), fastq.data(), fastq.size(), 0, c.MinReadLength, c.MaxReadLength, &fp, &info);
+      if (rc) {
+        const std::string e = musc_last_error(ctx.get());
+        no_memory(rc, e);
+        log.printf("read names on the host: the device stage found no memory (%s)", e.c_str());
+        plan.demote(Demotion::PrepNamesNoMemory);
+      } else {
+        const LibU32 ranked(info.ranked);
+        musc_get_stats(ctx.get(), &st);
+        log.printf("read prep on the device: %llu records, %llu kept, %llu distinct, %.3f ms", (unsigned long long)fp.n_records,
+                   (unsigned long long)fp.n_reads, (unsigned long long)fp.n_unique, st.ms_read_prep);
+        log.printf("read names on the device: %llu groups of one, %llu counted, %llu sorted (%llu pairs, %u key passes), %llu bytes of lines, %.3f ms",
+                   (unsigned long long)info.n_single, (unsigned long long)info.n_counted, (unsigned long long)info.n_sorted,
+                   (unsigned long long)info.n_pairs, info.key_passes, (unsigned long long)info.line_bytes, info.ms_names);
+        reads_from_lines(ctx.get(), fp, info, out, line_text);
+        names_done = true;
+      }
     }
-    musc_get_stats(ctx.get(), &st);
+    if (!names_done) {
+      const int rc = musc_reads_prep_fastq(ctx.get(), fastq.data(), fastq.size(), 0, c.MinReadLength, c.MaxReadLength, &fp);
+      if (rc) {
+        const std::string e = musc_last_error(ctx.get());
+        no_memory(rc, e);
+        ctx.reset();
+        log.printf("read prep on the host: the device stage found no memory (%s)", e.c_str());
+        return false;
+      }
+      musc_get_stats(ctx.get(), &st);
+    }
   }
+  if (n_total) *n_total = fp.n_reads;
+  if (names_done) return true;
   log.printf("read prep on the device: %llu records, %llu kept, %llu distinct, %.3f ms", (unsigned long long)fp.n_records,
              (unsigned long long)fp.n_reads, (unsigned long long)fp.n_unique, st.ms_read_prep);
-  if (n_total) *n_total = fp.n_reads;
   out->clear();
   out->reserve(fp.n_unique);
   std::vector<std::string> grp;
@@ -747,10 +808,10 @@ inline HotResult run_hot_path(const Config& cfg, const std::vector<UniqueRead>& 
 // the pipeline (cmd/muscato/main.go:1005-1058) as its stages, in the order run_muscato calls them
 // ------------------------------------------------------------------------------------
 
-// the six values the plan is made from: the only place the host tools read the environment
+// the seven values the plan is made from: the only place the host tools read the environment
 inline PlanEnv plan_env_of_process() {
   return PlanEnv{getenv("MUSC_PREP"), getenv("MUSC_MAXMATCHES"), getenv("MUSC_RESULTS"), getenv("MUSC_SIDE"), getenv("MUSC_GATHER"),
-                 getenv("MUSC_TARGETS")};
+                 getenv("MUSC_TARGETS"), getenv("MUSC_PREP_NAMES")};
 }
 
 // setupEnvs/makeTemp/setupLog/saveConfig (cmd/muscato/main.go:906-967, 680-706)
@@ -779,9 +840,10 @@ inline std::vector<UniqueRead> stage_read_prep(const Config& cfg, Placement& pla
   fputs("Preparing reads...\n", stderr);
   size_t n_total = 0;
   std::vector<UniqueRead> reads;
+  std::string line_text;  // reads_sorted.txt as the device rendered it, when the names were made there
   {
     const std::string fastq = slurp(cfg.ReadFileName);
-    if (plan.prep == Where::Device && !prep_reads_device(fastq, cfg, &n_total, log, &reads)) plan.demote(Demotion::PrepNoMemory);
+    if (plan.prep == Where::Device && !prep_reads_device(fastq, cfg, plan, &n_total, log, &reads, &line_text)) plan.demote(Demotion::PrepNoMemory);
     if (plan.prep == Where::Host) reads = prep_reads(fastq, cfg, &n_total);
   }
   if (reads.empty()) throw Die(1, "muscato_uniqify: no input from -");
@@ -790,7 +852,9 @@ inline std::vector<UniqueRead> stage_read_prep(const Config& cfg, Placement& pla
        "{\"NumUnique\":" + std::to_string(reads.size()) + ",\"NumTotal\":" + std::to_string(n_total) + "}\n");
   if (cfg.NoCleanTemp) {  // keep the one intermediate other tools consume
     std::string t;
-    for (auto& u : reads) t += u.seq + "\t" + std::to_string(u.count) + "\t" + u.names + "\n";
+    if (plan.prep_names == Where::Device) t.swap(line_text);  // (the same bytes, framed as they came)
+    else
+      for (auto& u : reads) t += u.seq + "\t" + std::to_string(u.count) + "\t" + u.names + "\n";
     spit(join_path(cfg.TempDir, "reads_sorted.txt.sz"), sz_encode(t));
   }
   return reads;

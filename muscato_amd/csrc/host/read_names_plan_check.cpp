@@ -2,8 +2,9 @@
 // (cmd/muscato_prep_reads/main.go:76-79, cmd/muscato_uniqify/main.go:83-135), byte loop by byte loop: every name length
 // 0..1100 with a tab at every place that matters and without one, joins of every length around the bounds, the decimal
 // widths, the lengths of a record and a line, and the path of a group; and read_names_lanes.hpp, what a lane of the
-// stage computes, in lock step against the same string code (below).  Stand-alone, no GPU: muscato_amd/build.py
-// (CHECKS) builds it, plain and under the sanitizers.
+// stage computes, in lock step against the same string code (below); and read_names_keys.hpp, the order of the larger
+// groups as integer keys, whose W + 2 stable passes are held to std::sort under PairLess pair for pair, whatever the order
+// in which the pairs enter.  Stand-alone, no GPU: muscato_amd/build.py (CHECKS) builds it, plain and under the sanitizers.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../read_names_keys.hpp"
 #include "../read_names_lanes.hpp"
 #include "../read_names_plan.hpp"
 #include "check.hpp"
@@ -100,6 +102,41 @@ static std::string rand_name(Rng& r, uint32_t n, const std::string& head = "@L")
   return s;
 }
 
+// ---- the larger groups by keys (read_names_keys.hpp): what rocprim::radix_sort_pairs does on the device, here a stable
+// counting sort of the (key, pair number) list by the eight bytes of the key, the least significant first
+static void stable_by_key(std::vector<uint64_t>& key, std::vector<uint32_t>& perm) {
+  const size_t n = perm.size();
+  std::vector<uint64_t> k2(n);
+  std::vector<uint32_t> p2(n);
+  for (int b = 0; b < 8; b++) {
+    size_t count[257] = {};
+    for (size_t i = 0; i < n; i++) count[((key[i] >> (8 * b)) & 255u) + 1]++;
+    for (int v = 0; v < 256; v++) count[v + 1] += count[v];
+    for (size_t i = 0; i < n; i++) {
+      const size_t at = count[(key[i] >> (8 * b)) & 255u]++;
+      k2[at] = key[i], p2[at] = perm[i];
+    }
+    key.swap(k2), perm.swap(p2);
+  }
+}
+// the key passes over the pairs, which enter in the order `perm`; returns W
+template <class R, class P>
+static uint32_t radix_rank(const R& rd, const Names& N, const std::vector<P>& pairs, std::vector<uint32_t>& perm) {
+  uint32_t maxclip = 0;  // (k_rn_pairs: one atomicMax)
+  for (const P& p : pairs) maxclip = std::max(maxclip, clipped_len(N.name_len[p.y]));
+  const uint32_t W = key_words(maxclip);
+  std::vector<uint64_t> key(pairs.size());
+  for (uint32_t pass = 0; pass < key_passes(maxclip); pass++) {
+    for (uint64_t k = 0; k < pairs.size(); k++) key[k] = sortkey(rd, N, pairs.data(), perm.data(), k, pass, W);
+    if (pass == 0)
+      for (uint64_t v : key) EXPECT(v >> TAIL_BITS == 0);
+    if (pass == W + 1)
+      for (uint64_t v : key) EXPECT(v >> GROUP_BITS == 0);
+    stable_by_key(key, perm);
+  }
+  return W;
+}
+
 // a FASTQ text of groups of reads with one sequence each, and what the parse and the sort in front of the stage leave
 struct Fastq {
   std::string raw;
@@ -132,7 +169,7 @@ struct Fastq {
   }
 };
 
-static void lockstep(const char* what, const Fastq& F) {
+static void lockstep(const char* what, const Fastq& F, int want_words = -1) {
   const uint64_t n = F.names.size(), nbytes = F.raw.size();
   unsigned char* const text = new unsigned char[nbytes ? nbytes : 1];  // exactly the text, nothing behind it
   for (uint64_t i = 0; i < nbytes; i++) text[i] = (unsigned char)F.raw[i];
@@ -184,7 +221,24 @@ static void lockstep(const char* what, const Fastq& F) {
     for (uint64_t k = 0; k + 1 < np; k++)  // a strict total order: neighbours differ one way only
       EXPECT_MSG(less(sorted[k], sorted[k + 1]) && !less(sorted[k + 1], sorted[k]) && !less(sorted[k], sorted[k]), "%s: pair %llu", what, (unsigned long long)k);
     for (uint64_t k = 0; k < np; k++) unpairs_item(sorted.data(), place.data(), k, ranked.data());
+    // ---- the same order from the W + 2 key passes: the pairs entering as made, reversed, and in a seeded shuffle
+    Rng shuffle{np * 2654435761ull + 23};
+    for (int entry = 0; entry < 3; entry++) {
+      std::vector<uint32_t> perm(np);
+      for (uint64_t k = 0; k < np; k++) perm[k] = (uint32_t)(entry == 1 ? np - 1 - k : k);
+      if (entry == 2)
+        for (uint64_t k = np; k-- > 1;) std::swap(perm[k], perm[shuffle.next() % (k + 1)]);
+      const uint32_t W = radix_rank(rd, N, pairs, perm);
+      EXPECT_MSG(W <= CMP_WORDS && (want_words < 0 || W == (uint32_t)want_words), "%s: %u key words", what, W);
+      for (uint64_t k = 0; k < np; k++)
+        EXPECT_MSG(pairs[perm[k]].x == sorted[k].x && pairs[perm[k]].y == sorted[k].y, "%s: entry order %d, pair %llu by keys", what, entry, (unsigned long long)k);
+      std::vector<uint32_t> again(n, 0xFFFFFFFFu);
+      for (uint64_t k = 0; k < np; k++) unpairs_by_perm(pairs.data(), perm.data(), place.data(), k, again.data());
+      for (uint64_t k = 0; k < np; k++) EXPECT_MSG(again[place[k]] == ranked[place[k]], "%s: entry order %d, place %u", what, entry, place[k]);
+    }
   }
+  EXPECT_MSG(want_words < 0 || np, "%s: no pairs", what);
+  for (uint64_t i = 0; i < n; i++) EXPECT_MSG(place_group(ustart.data(), (uint32_t)nu, i) == gid[i], "%s: the group of place %llu", what, (unsigned long long)i);
   // ---- sizes: one item per group; the offsets by scan
   std::vector<uint32_t> tstart(n, 0xFFFFFFFFu), gsum(nu);
   std::vector<uint64_t> roff(nu + 1, 0), loff(nu + 1, 0);
@@ -384,6 +438,40 @@ static void lockstep_all() {
     F.names.push_back("@a\t"), F.seqs.push_back(F.seqs[0]);
     F.raw += "@a\t";
     lockstep("name at the end", F);
+  }
+  // ---- the order of the larger groups by keys: cases of their own (every lock-step text above runs the passes too)
+  const auto filled = [&](std::vector<std::string> ns, size_t k, const std::string& head, uint32_t len) {  // ... up to k members
+    while (ns.size() < k) ns.insert(ns.begin() + (ns.size() * 7) % (ns.size() + 1), rand_name(r, len, head));
+    return ns;
+  };
+  {  // a prefix with one, two and eight 0x00 bytes behind it; a prefix that ends on a word boundary and one inside a word
+    Fastq F;
+    const std::string z8(8, '\0');
+    F.group(filled({std::string("@p\0", 3), "@p", std::string("@p\0\0", 4), "@p" + z8, std::string("@p\0\0\0", 5) + "a"}, 65, "@p", 12), 1);
+    F.group(filled({"@prefix8" + z8, "@prefix8", "@prefix8" + std::string(1, '\0'), "@prefix8" + z8 + z8, "@prefix8" + z8 + "b"}, 70, "@prefix", 20), 6);
+    F.group(filled({"@prefix8_and_more", "@prefix8", "@prefix8_", "@prefix8_and_more_behind_it"}, 66, "@prefix8", 9), 11);
+    F.group(filled({"@prefix_in_a_word_and_more", "@prefix_in_a", "@prefix_in_a_", "@prefix_in_"}, 67, "@prefix_in_a_word", 30), 4);
+    lockstep("prefixes by keys", F);
+  }
+  {  // W = 0, 1, 2, 124 and 125: each in a text of its own, W being the longest name of all the pairs
+    const uint32_t longest[][2] = {{0, 0}, {1, 1}, {8, 1}, {9, 2}, {16, 2}, {985, 124}, {992, 124}, {993, 125}, {1000, 125}, {1001, 125}, {1100, 125}};
+    int i = 0;
+    for (const auto& lw : longest) {
+      Fastq F;
+      std::vector<std::string> ns;
+      for (uint32_t j = 0; j < 65; j++) ns.push_back(rand_name(r, j % 3 == 0 ? lw[0] : lw[0] - lw[0] * (j % 5) / 7));
+      if (lw[0] > 1000) ns.push_back(ns[0].substr(0, 996) + "!" + ns[0].substr(997)), ns.push_back(ns[0].substr(0, 994) + "!" + ns[0].substr(995));
+      F.group({"@a_small_group", "@"}, 3);
+      F.group(ns, (3 * i++) % 16);
+      lockstep("key words", F, (int)lw[1]);
+    }
+  }
+  {  // a larger group in which all names are equal (file order), beside one of distinct names; a group of exactly 65
+    Fastq F;
+    F.group(std::vector<std::string>(70, "@same_name_every_time"), 9);
+    F.group(filled({}, 65, "@sixty-five", 16), 2);
+    F.group(std::vector<std::string>(65, std::string(1100, 'q')), 13);
+    lockstep("equal names", F);
   }
   EXPECT_MSG(loads_outside == 0, "%lld loads outside the text", loads_outside);
 }

@@ -311,6 +311,8 @@ struct musc_ctx {
   DevPtr<uint32_t> res_rank;        // per gene: rank of its text among all genes' texts, RES_ABSENT without an id line
   DevPtr<char> res_ttext;           // every read's count\tnames (musc_results_set_read_text); released with the reads
   DevPtr<uint64_t> res_toff;        // nreads + 1 byte offsets into it
+  DevPtr<uint64_t> rn_loff;         // nreads + 1 byte offsets of the lines seq\tcount\tnames\n, when the read-name stage made the text
+  float rn_ms_text = 0;             // event time of the musc_reads_names_text calls that rendered
   DevBuf<musc_hit> res_hits;        // the ordered tuples
   DevBuf<uint64_t> res_off;         // res_n + 1 line offsets
   DevBuf<unsigned char> res_stage;  // musc_results_text: the bytes on their way to a host buffer
@@ -476,6 +478,7 @@ void drop_gene_text(musc_ctx* c) {
 void drop_read_text(musc_ctx* c) {
   c->res_ttext.release();
   c->res_toff.release();
+  c->rn_loff.release();
   c->st.read_text_dropped();
 }
 
@@ -882,6 +885,7 @@ int musc_hits_copy(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_dev
 #include "muscato_text.hpp"
 // the MaxMatches truncation replayed on the device (musc_maxmatches_*)
 #include "muscato_maxmatches.hpp"
+#include "muscato_read_names.hpp"
 
 extern "C" {
 

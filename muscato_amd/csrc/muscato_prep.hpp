@@ -269,9 +269,12 @@ extern "C" void musc_fastq_prep_free(musc_fastq_prep* p) {
   memset(p, 0, sizeof *p);
 }
 
-static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on_device, int32_t min_len, uint32_t max_len,
-                          musc_fastq_prep* out) {
-  static const char* const who = "musc_reads_prep_fastq";
+// `after(d_text, d_name_off, d_name_len, d_seq_len)` runs behind the sort + collapse, the kept reads' spans as device
+// arrays (null when no read is kept).  keep_text: the text and the record tables stay resident until it has returned
+// (the read-name stage, muscato_read_names.hpp, reads the names in place); else they go before the sort as always.
+template <class After>
+static int fastq_prep_run(musc_ctx* c, const char* who, const char* text, uint64_t nbytes, int on_device, int32_t min_len, uint32_t max_len,
+                          musc_fastq_prep* out, bool keep_text, After after) {
   Marks m;
   int rc = m.start(c);
   if (rc) return rc;
@@ -332,7 +335,7 @@ static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on
     out->order = (uint32_t*)malloc(4);
     out->ustart = (uint32_t*)calloc(1, 4);
     if (!out->order || !out->ustart) return fail(c, 7, "out of host memory");
-    return 0;
+    return after(d_text, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
   }
 
   // ---- the prepared reads, and the kept reads' spans for the host
@@ -350,8 +353,10 @@ static int fastq_prep_run(musc_ctx* c, const char* text, uint64_t nbytes, int on
   HIPCHK(c, hipMemcpyAsync(out->name_len, o32, nkept * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(out->seq_len, o32 + nkept, nkept * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  P.release();
-  return reads_sort_unique_dev(c, who, prep, prep_off, nkept, m, &out->order, &out->ustart, &out->n_unique);
+  if (!keep_text) P.release();
+  if ((rc = reads_sort_unique_dev(c, who, prep, prep_off, nkept, m, &out->order, &out->ustart, &out->n_unique))) return rc;
+  S.release();
+  return after(d_text, (const uint64_t*)o64, (const uint32_t*)o32, (const uint32_t*)(o32 + nkept));
 }
 
 extern "C" int musc_reads_prep_fastq(musc_ctx* c, const char* text, uint64_t nbytes, int on_device, int32_t min_read_len,
@@ -363,7 +368,8 @@ extern "C" int musc_reads_prep_fastq(musc_ctx* c, const char* text, uint64_t nby
   HIPCHK(c, hipSetDevice(c->device));
   free_reads(c);
   if (max_read_len < 0) return reads_load_done(c, fail(c, 2, "musc_reads_prep_fastq: max_read_len %d is negative", max_read_len));
-  const int rc = fastq_prep_run(c, text, nbytes, on_device, min_read_len, (uint32_t)max_read_len, out);
+  const int rc = fastq_prep_run(c, "musc_reads_prep_fastq", text, nbytes, on_device, min_read_len, (uint32_t)max_read_len, out, false,
+                                [](const unsigned char*, const uint64_t*, const uint32_t*, const uint32_t*) { return 0; });
   if (rc) musc_fastq_prep_free(out);  // nothing stale: no arrays, and (reads_load_done) no reads
   return reads_load_done(c, rc);
 }

@@ -1,10 +1,11 @@
 // read_names_lanes.hpp -- everything a lane of the read-name stage computes, in plain C++ that g++ compiles
 // without HIP and hipcc compiles for the device (RN_HD): the compare word of a clipped name, the three-way compare of
 // two names, the first-tab search, the rank of a member by counting, the token starts and sizes of a group, the byte at
-// a place of a record and of a line, and the store shape of the render.  A kernel of the stage is to be nothing but
-// the index arithmetic that hands a lane its item and a call of one `*_item` function below; no such kernel is in the
-// tree (the stage built on these functions did not finish on the device once it reached the comparison
-// sort, and came out).  host/read_names_plan_check.cpp runs the functions item by item in grid order over seeded
+// a place of a record and of a line, and the store shape of the render.  A kernel of the stage
+// (kernels_read_names.hpp) is nothing but the index arithmetic that hands a lane its item and a call of one `*_item`
+// function below, or of a function of read_names_keys.hpp, which orders the larger groups by integer keys in place of
+// the comparison sort under PairLess (PairLess is the specification, run under std::sort in the check
+// program only).  host/read_names_plan_check.cpp runs the functions item by item in grid order over seeded
 // texts, through a reader that reports every load outside the text, and holds what they leave to the reference's
 // string code byte for byte.
 //

@@ -1,10 +1,10 @@
 // read_names_plan.hpp -- the arithmetic of the read-name stage that needs no device: the 1000-byte rule of
 // a name, the bytes of a clipped name that are not in the text, where a token ends, the width of a count, the lengths of
 // a record of the read text and of a line of reads_sorted.txt, the path that ranks a group, and the refusal bound.  Plain
-// C++ that hipcc also compiles for the device (RN_HD): written for the kernels of the stage, which are not in the tree
-// (DESIGN.md 23), and included today by read_names_lanes.hpp -- what a lane of such a kernel computes, in the same
-// plain C++ -- and by host/read_names_plan_check.cpp, the stand-alone program that holds both to a byte-loop
-// restatement of the reference's string code.
+// C++ that hipcc also compiles for the device (RN_HD): included by read_names_lanes.hpp and read_names_keys.hpp -- what
+// a lane of the stage's kernels (kernels_read_names.hpp) computes, in the same plain C++ -- and by
+// host/read_names_plan_check.cpp, the stand-alone program that holds all three to a byte-loop restatement of the
+// reference's string code.
 //
 // Reference: cmd/muscato_prep_reads/main.go:76-79 (a name of more than 1000 bytes becomes its first 995 and "..."),
 // cmd/muscato_uniqify/main.go:83-135 (a name ends at its first tab; the names of a group are joined with ';' and a join
