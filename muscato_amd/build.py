@@ -71,7 +71,7 @@ _HOST_CHAIN = ("host/muscato_host.hpp", "host/cli_config.hpp", "host/cli_maxmatc
 CHECKS = {
     "cli_plan_check": ("cli_plan_check.cpp", ("host/check.hpp", "host/cli_names.hpp", "host/cli_plan.hpp"), 184_205_945, ()),
     "ctx_state_check": ("ctx_state_check.cpp", ("host/check.hpp", "ctx_state.hpp", _API), 58_376_821, ()),
-    "dev_mem_check": ("dev_mem_check.cpp", ("host/check.hpp", "dev_mem.hpp"), 492, ()),
+    "dev_mem_check": ("dev_mem_check.cpp", ("host/check.hpp", "dev_mem.hpp"), 521, ()),
     "index_plan_check": ("index_plan_check.cpp", ("host/check.hpp", "index_plan.hpp"), 567_030, ()),
     "load_plan_check": ("load_plan_check.cpp", ("host/check.hpp", "load_plan.hpp"), 35_240_767, ()),
     "maxmatches_plan_check": ("maxmatches_plan_check.cpp", ("host/check.hpp", "maxmatches_plan.hpp"), 548_365, ()),

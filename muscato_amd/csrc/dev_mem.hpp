@@ -1,12 +1,16 @@
 // dev_mem.hpp -- the owners of device memory and of pinned host memory.  OwnedMem: one block of exactly the size asked
 // for, freed when its owner goes.  DevBuf: a work buffer of the passes, grown by half (grown_cap, grown_bytes).  TmpBufs:
-// the temporary blocks of one call.  All move-only or fixed in place.  This header includes no HIP header and names
-// hipMalloc / hipFree / hipHostMalloc / hipHostFree (and hipError_t, hipSuccess, hipErrorOutOfMemory) unqualified:
-// muscato_hip.hip includes it after <hip/hip_runtime.h>, host/dev_mem_check.cpp after stubs of its own that count what lives.
+// the temporary blocks of one call.  Readback: scalars on their way from the device to the host, through the pinned words
+// of a context, with one wait.  All move-only or fixed in place.  This header includes no HIP header and names
+// hipMalloc / hipFree / hipHostMalloc / hipHostFree / hipMemcpyAsync / hipStreamSynchronize (and hipError_t, hipStream_t,
+// hipSuccess, hipErrorOutOfMemory, hipErrorInvalidValue, hipMemcpyDeviceToHost) unqualified: muscato_hip.hip includes it
+// after <hip/hip_runtime.h>, host/dev_mem_check.cpp after stubs of its own that count what lives and defer every copy.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
+#include <type_traits>
 #include <utility>
 
 template <class Api>
@@ -105,4 +109,68 @@ struct TmpBufs {
     n = 0;
   }
   ~TmpBufs() { release(); }
+};
+
+// The pinned words scalars come back through (musc_ctx::h_pinned), and the Readback that has copies queued into them.
+struct PinnedWords {
+  uint64_t* w = nullptr;
+  unsigned n = 0;
+  const void* holder = nullptr;
+};
+
+// Scalars read back from the device, for one wait: get() queues a copy of a device value into the next free pinned
+// word, zeroed first, and notes where it belongs; wait() waits for the stream once and then hands every word to its
+// destination, zero-extended to the destination's width.  A destination may be a local variable: no copy ever aims at
+// it, and nothing is written to it before a wait() that succeeded.  wait() returns the first error of any get(), else
+// the wait's own.  One request too many, or a get() while another Readback holds the words, is such an error and never
+// a write.  An object that goes with copies queued waits for the stream and delivers nothing.
+class Readback {
+ public:
+  static constexpr unsigned MAX_WORDS = 16;
+  Readback(PinnedWords& words, hipStream_t stream) : P(words), st(stream) {}
+  Readback(const Readback&) = delete;  // (nor assigned: P is a reference)
+  ~Readback() { if (P.holder == this) (void)wait_only(); }
+  // *dst = *src, once wait() has returned hipSuccess
+  template <class S, class T>
+  Readback& get(const S* src, T* dst) {
+    static_assert(std::is_integral<S>::value && std::is_integral<T>::value && sizeof(S) <= sizeof(T) && sizeof(T) <= 8, "a scalar into one as wide or wider");
+    return queue(src, sizeof(S), 1, dst, sizeof(T));
+  }
+  // dst[0 .. nwords) = src[0 .. nwords), consecutive 64-bit words
+  template <class S>
+  Readback& get_words(const S* src, uint64_t* dst, unsigned nwords) {
+    static_assert(std::is_integral<S>::value && sizeof(S) == 8, "64-bit words");
+    return queue(src, 8 * nwords, nwords, dst, 8 * nwords);
+  }
+  hipError_t wait() {
+    const hipError_t es = wait_only(), e = err != hipSuccess ? err : es;
+    if (e == hipSuccess)
+      for (unsigned i = 0; i < nd; i++) memcpy(q[i].dst, P.w + q[i].word, q[i].bytes);
+    nd = 0, err = hipSuccess;
+    return e;
+  }
+
+ private:
+  struct Dest { void* dst; unsigned word, bytes; };
+  Readback& queue(const void* src, unsigned src_bytes, unsigned nwords, void* dst, unsigned dst_bytes) {
+    if (err != hipSuccess) return *this;
+    if ((P.holder && P.holder != this) || nwords > P.n - nq || nwords > MAX_WORDS - nq) return err = hipErrorInvalidValue, *this;
+    P.holder = this;
+    memset(P.w + nq, 0, 8 * nwords);
+    if ((err = hipMemcpyAsync(P.w + nq, src, src_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return *this;
+    q[nd++] = Dest{dst, nq, dst_bytes};
+    nq += nwords;
+    return *this;
+  }
+  hipError_t wait_only() {
+    const hipError_t e = hipStreamSynchronize(st);
+    if (P.holder == this) P.holder = nullptr;
+    nq = 0;
+    return e;
+  }
+  PinnedWords& P;
+  hipStream_t st;
+  hipError_t err = hipSuccess;
+  Dest q[MAX_WORDS];
+  unsigned nq = 0, nd = 0;  // words taken; destinations noted
 };

@@ -1,7 +1,9 @@
 // dev_mem_check.cpp -- the owners of csrc/dev_mem.hpp (DevMem, PinnedMem and their typed forms, DevBuf and its growth
-// rule, TmpBufs) over stubs of the four HIP calls they name, as a program of its own so that it runs under the sanitizers.
-// The stubs hand out heap blocks of exactly the size asked for (a touch past the end is the address sanitizer's),
-// count what lives and record every size.  At exit nothing lives and every size is the one the caller named.
+// rule, TmpBufs, Readback) over stubs of the six HIP calls they name, as a program of its own so that it runs under the
+// sanitizers.  The stubs hand out heap blocks of exactly the size asked for (a touch past the end is the address
+// sanitizer's), count what lives and record every size.  At exit nothing lives and every size is the one the caller named.
+// A stubbed copy is deferred: recorded when it is queued and performed by the stubbed stream wait only, so that a copy
+// whose destination has gone by then is the address sanitizer's too.
 // It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <algorithm>
 #include <cstdio>
@@ -34,8 +36,33 @@ struct Heap {
 } g_dev, g_host;
 }  // namespace
 
+struct Copy {
+  void* dst;
+  const void* src;
+  size_t n;
+};
+struct Stream {
+  std::vector<Copy> pending;
+  int queued = 0, waits = 0;
+  int fail_copy = -1;  // the copy with this number (of all queued so far) is refused
+  bool fail_wait = false;
+} g_stream;
+
 typedef int hipError_t;
-constexpr hipError_t hipSuccess = 0, hipErrorOutOfMemory = 2;
+typedef Stream* hipStream_t;
+constexpr hipError_t hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2, hipErrorStub = 77, hipErrorStubWait = 78;
+enum hipMemcpyKind { hipMemcpyDeviceToHost = 2 };
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t st) {
+  if (st->queued++ == st->fail_copy) return hipErrorStub;
+  st->pending.push_back(Copy{dst, src, n});
+  return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t st) {
+  st->waits++;
+  for (const Copy& k : st->pending) memcpy(k.dst, k.src, k.n);  // (performed even when the wait reports an error)
+  st->pending.clear();
+  return st->fail_wait ? hipErrorStubWait : hipSuccess;
+}
 hipError_t hipMalloc(void** p, size_t n) { return g_dev.get(p, n); }
 hipError_t hipFree(void* p) { return g_dev.put(p); }
 hipError_t hipHostMalloc(void** p, size_t n) { return g_host.get(p, n); }
@@ -202,6 +229,115 @@ void check_tmpbufs() {
   EXPECT(h.live.empty() && h.bad_frees == 0);
 }
 
+// ---- Readback
+
+void check_readback() {
+  Stream& S = g_stream;
+  uint64_t words[4];
+  memset(words, 0xEE, sizeof words);
+  PinnedWords P;
+  P.w = words;
+  P.n = 4;
+  const uint64_t d64 = 0x1122334455667788ull, dpair[2] = {7, ~0ull};
+  const uint32_t d32 = 0xA1B2C3D4u;
+  const unsigned char d8 = '\n';
+  // the words are handed out in order, each zeroed first; a 1-byte and a 4-byte read arrive zero-extended; nothing
+  // reaches a destination before wait()
+  {
+    Readback R(P, &S);
+    uint64_t a = 1, b = 2, c = 3;
+    unsigned char e = 4;
+    R.get(&d64, &a);
+    R.get(&d32, &b);
+    R.get(&d8, &c);
+    R.get(&d8, &e);
+    EXPECT(S.pending.size() == 4 && P.holder == &R);
+    for (size_t i = 0; i < S.pending.size(); i++) EXPECT(S.pending[i].dst == words + i);
+    EXPECT(S.pending[0].n == 8 && S.pending[1].n == 4 && S.pending[2].n == 1 && S.pending[3].n == 1);
+    EXPECT(words[0] == 0 && words[1] == 0 && words[2] == 0 && words[3] == 0);
+    EXPECT(a == 1 && b == 2 && c == 3 && e == 4 && S.waits == 0);
+    EXPECT(R.wait() == hipSuccess && S.waits == 1 && S.pending.empty() && !P.holder);
+    EXPECT(a == d64 && b == d32 && c == d8 && e == d8);
+    // the object serves again, from the first word
+    uint32_t f = 9;
+    R.get(&d32, &f);
+    EXPECT(S.pending.size() == 1 && S.pending[0].dst == words && f == 9);
+    EXPECT(R.wait() == hipSuccess && f == d32 && S.waits == 2);
+  }
+  EXPECT(S.waits == 2);  // (nothing was queued when it went)
+  // a read of consecutive 64-bit words beside a scalar
+  {
+    Readback R(P, &S);
+    uint64_t two[2] = {1, 1};
+    uint32_t x = 0;
+    R.get(&d32, &x);
+    R.get_words(dpair, two, 2);
+    EXPECT(S.pending.size() == 2 && S.pending[1].dst == words + 1 && S.pending[1].n == 16 && two[0] == 1);
+    EXPECT(R.wait() == hipSuccess && two[0] == 7 && two[1] == ~0ull && x == d32);
+  }
+  // one request too many is an error of wait(), and nothing is written: not past the block, not to any destination
+  {
+    Readback R(P, &S);
+    uint64_t v[5] = {10, 11, 12, 13, 14}, two[2] = {5, 5};
+    const uint64_t guard = words[3];
+    for (int i = 0; i < 3; i++) R.get(&d64, &v[i]);
+    R.get_words(dpair, two, 2);  // two words where one is left
+    R.get(&d64, &v[3]);          // (refused as well: the first error stands)
+    EXPECT(S.pending.size() == 3 && words[3] == guard);
+    EXPECT(R.wait() == hipErrorInvalidValue && S.pending.empty() && !P.holder);
+    EXPECT(v[0] == 10 && v[1] == 11 && v[2] == 12 && v[3] == 13 && two[0] == 5 && two[1] == 5);
+    EXPECT(R.wait() == hipSuccess);  // (the error was that wait's)
+  }
+  // the first queueing error wins, over later ones and over the wait's; the wait still happens; no destination is touched
+  {
+    Readback R(P, &S);
+    uint64_t a = 1, b = 2, c = 3;
+    const int waits = S.waits;
+    R.get(&d64, &a);
+    S.fail_copy = S.queued;
+    R.get(&d64, &b);
+    S.fail_copy = -1;
+    R.get(&d64, &c);
+    R.get_words(dpair, &c, 9);
+    S.fail_wait = true;
+    EXPECT(R.wait() == hipErrorStub && S.waits == waits + 1 && S.pending.empty());
+    EXPECT(a == 1 && b == 2 && c == 3);
+    // a failed wait alone: its error, and again nothing is delivered
+    R.get(&d64, &a);
+    EXPECT(R.wait() == hipErrorStubWait && a == 1);
+    S.fail_wait = false;
+    R.get(&d64, &a);
+    EXPECT(R.wait() == hipSuccess && a == d64);
+  }
+  // an object dropped without wait() has waited, nothing of it is pending afterwards and nothing was delivered -- the
+  // destination may be gone by then (a frame that returned early): the deferred copy never aimed at it
+  {
+    const int waits = S.waits;
+    uint64_t* gone = new uint64_t(5);
+    uint64_t kept = 6;
+    {
+      Readback R(P, &S);
+      R.get(&d64, gone);
+      R.get(&d64, &kept);
+      delete gone;
+      EXPECT(S.pending.size() == 2);
+    }
+    EXPECT(S.waits == waits + 1 && S.pending.empty() && !P.holder && kept == 6);
+  }
+  // while one Readback has copies queued, another is refused the words (no two helpers on the same word)
+  {
+    Readback R(P, &S), Q(P, &S);
+    uint64_t a = 1, b = 2;
+    R.get(&d64, &a);
+    Q.get(&d32, &b);
+    EXPECT(S.pending.size() == 1 && Q.wait() == hipErrorInvalidValue && b == 2 && P.holder == &R);
+    EXPECT(R.wait() == hipSuccess && a == d64);
+    Q.get(&d32, &b);  // (free again)
+    EXPECT(Q.wait() == hipSuccess && b == d32);
+  }
+  EXPECT(S.pending.empty() && !P.holder);
+}
+
 struct Holder {  // as musc_ctx holds them: members, freed with the object
   DevPtr<uint32_t> rd;
   DevPtr<char> text;
@@ -233,6 +369,7 @@ int main() {
   check_devbuf();
   check_growth();
   check_tmpbufs();
+  check_readback();
   EXPECT(g_host.asked.size() == host_asked);  // (device memory, all of it)
   EXPECT(g_dev.live.empty() && g_host.live.empty() && g_dev.bad_frees == 0 && g_host.bad_frees == 0);
   return check_done("dev_mem_check");

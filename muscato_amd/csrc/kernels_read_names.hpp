@@ -6,9 +6,8 @@
 // has a loop whose trip count is device data without a constant of the plan above it; k_rn_pairs alone has an atomic,
 // one atomicMax of a clipped length per member of a larger group.
 //
-// The members of the groups above WAVE_GROUP_MAX are ordered by key_passes() stable passes of rocprim::radix_sort_pairs
-// over (uint64_t key, uint32_t pair number), the instantiation of muscato_prep.hpp's sort of the reads; k_rn_keys makes
-// the keys of a pass.  The driver is muscato_read_names.hpp.
+// The members of the groups above WAVE_GROUP_MAX are ordered by key_passes() stable passes of KeyPasses (the sort of
+// the reads, muscato_prep.hpp); k_rn_keys makes the keys of a pass.  The driver is muscato_read_names.hpp.
 #pragma once
 
 #include "read_names_keys.hpp"

@@ -160,10 +160,6 @@ MUSC_KERNEL __launch_bounds__(256) void k_results_compact(const uint4* __restric
     if (keep[i]) out[excl[i]] = in[i];
 }
 
-MUSC_KERNEL __launch_bounds__(256) void k_results_iota(uint32_t* __restrict__ p, uint64_t n) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) p[i] = (uint32_t)i;
-}
-
 MUSC_KERNEL __launch_bounds__(256) void k_results_gather(const uint4* __restrict__ in, const uint32_t* __restrict__ perm, uint64_t n,
                                                         uint4* __restrict__ out) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) out[i] = in[perm[i]];

@@ -1,7 +1,7 @@
 // muscato_db_text.hpp -- the gene file from its raw bytes to the resident database: musc_sz_decode and
 // musc_db_load_text.  Included by muscato_hip.hip behind muscato_load.hpp and muscato_prep.hpp (one translation unit:
-// musc_ctx and the scans; db_alloc / db_finish / db_load_done and the loaders' helpers -- staged, tmp_alloc, text_lines --
-// are muscato_load.hpp's).
+// musc_ctx, the scans, grid, staged, tmp_alloc and Readback; db_alloc / db_finish / db_load_done and text_lines are
+// muscato_load.hpp's).
 //
 // Reference: cmd/muscato_prep_targets/main.go:246-258 writes the gene file through snappy's framed writer;
 // cmd/muscato_screen/main.go:408-452 reads it back line by line, the target being the line up to its first tab.  On the
@@ -135,7 +135,7 @@ static int db_load_text_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
   HIPCHK(c, hipMemsetAsync(end, 0xFF, nlines * 8, c->stream));
   hipLaunchKernelGGL(k_dbt_lines, L.tgrid, dim3(FQ_BLOCK), 0, c->stream, L.base16, L.lo, L.hi, L.ntiles, L.cnt, nlines, L.virt, begin, end);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_dbt_lengths, dim3(std::min(nblk(nlines + 1, 256), MAX_GRID)), dim3(256), 0, c->stream, d_text, ntext, nlines,
+  hipLaunchKernelGGL(k_dbt_lengths, grid(nlines + 1), dim3(256), 0, c->stream, d_text, ntext, nlines,
                      begin, end, len);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, len, len, nlines + 1, stmp2))) return rc;
@@ -151,13 +151,14 @@ static int db_load_text_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, m.mark(c, 2));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2, census, 16, hipMemcpyDeviceToHost, c->stream));
-  if ((rc = db_finish(c))) return rc;  // (waits for the stream)
+  uint64_t odd[2] = {0, 0};  // how many targets hold an odd byte, the first of them
+  Readback R(c->scalars, c->stream);
+  if ((rc = db_finish(c, R.get_words(census, odd, 2)))) return rc;  // (waits for the stream)
   if (out) {
     out->n_targets = nlines;
     out->n_bases = c->nbases;
-    out->n_odd = c->h_pinned[2];
-    out->first_odd_target = out->n_odd ? (uint32_t)c->h_pinned[3] : 0;
+    out->n_odd = odd[0];
+    out->first_odd_target = out->n_odd ? (uint32_t)odd[1] : 0;
     out->n_text_bytes = ntext;
     out->n_chunks = nchunks;
     out->ms_decode = m.ms(0, 1);

@@ -20,6 +20,7 @@
 // There is no CPU fallback in this library.
 
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rccl/rccl.h>  // types and prototypes only: the library is resolved at run time (rccl_api)
 #include <dlfcn.h>
 
@@ -29,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -295,7 +297,8 @@ struct musc_ctx {
   uint32_t last_inst[MUSC_INSTANCE_WORDS] = {0, 0, 0, 0};  // musc_last_instance: what the resolvers of the last pass returned
   bool last_exact_blocks = false;  // block_table holds exact counters of that pass
   DevPtr<unsigned long long> counters;     // CNT_WORDS u64: the pass block and the batch block (kernels_common.hpp)
-  PinnedPtr<uint64_t> h_pinned;            // their pinned mirror (and 16 x u64 of staging for whoever reads a scalar back)
+  PinnedPtr<uint64_t> h_pinned;            // their pinned mirror ...
+  PinnedWords scalars;                     // ... and, between passes, the words a Readback brings scalars back through
 
   DevBuf<musc_hit> hits;
   uint64_t nhits = 0;
@@ -369,6 +372,12 @@ struct musc_ctx {
   musc_state::PassKey pass_key(const musc_params& P, int block_mode) const { return musc_state::PassKey{st.g.pass_inputs, P, block_mode}; }
 };
 
+// p[i] = i: the item numbers a sort by key passes starts from (KeyPasses)
+MUSC_KERNEL void k_prep_iota(uint32_t* __restrict__ p, uint64_t n) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    p[i] = (uint32_t)i;
+}
+
 namespace {
 
 int fail(musc_ctx* c, int code, const char* fmt, ...) {
@@ -416,7 +425,11 @@ int ensure(musc_ctx* c, DevBuf<T>& b, uint64_t n, bool keep = false) {
 // with potentially larger n use grid-stride kernels instead
 inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
-// u32 scan of n elements (in may equal out).  tmp must hold scan_tmp_elems(n).
+// the grid of a grid-stride kernel over k items
+inline dim3 grid(uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); }
+
+// ---- what the host drivers share: the scans, tmp_alloc / staged, KeyPasses; Readback is dev_mem.hpp's
+
 uint64_t scan_tmp_elems(uint64_t n) {
   uint64_t t = 0;
   while (n > SCAN_TILE) {
@@ -426,45 +439,101 @@ uint64_t scan_tmp_elems(uint64_t n) {
   return t + 8;
 }
 
-int scan_u32(musc_ctx* c, const uint32_t* in, uint32_t* out, uint64_t n, bool inclusive, uint32_t* tmp,
-             hipStream_t st = nullptr) {
-  if (!st) st = c->stream;
+// The host recursion of both scans: `top` scans the tiles of the level in hand and leaves their sums in tmp, which are
+// scanned in turn (exclusive, by `below`) and added back.
+template <class T>
+int scan_levels(musc_ctx* c, const T* in, T* out, uint64_t n, T* tmp, hipStream_t st, void (*top)(const T*, T*, T*, uint64_t),
+                void (*below)(const T*, T*, T*, uint64_t), void (*add)(T*, const T*, uint64_t)) {
   const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
   if (nb > 0x7FFFFFFFull) return fail(c, 11, "scan too large");
-  if (nb <= 1) {
-    if (inclusive) hipLaunchKernelGGL(k_scan_block<true>, dim3(1), dim3(SCAN_BLOCK), 0, st, in, out, (uint32_t*)nullptr, n);
-    else hipLaunchKernelGGL(k_scan_block<false>, dim3(1), dim3(SCAN_BLOCK), 0, st, in, out, (uint32_t*)nullptr, n);
-    HIPCHK(c, hipGetLastError());
-    return 0;
-  }
-  uint32_t* sums = tmp;
-  if (inclusive) hipLaunchKernelGGL(k_scan_block<true>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, in, out, sums, n);
-  else hipLaunchKernelGGL(k_scan_block<false>, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, in, out, sums, n);
+  T* const sums = nb <= 1 ? nullptr : tmp;
+  hipLaunchKernelGGL(top, dim3(sums ? (unsigned)nb : 1u), dim3(SCAN_BLOCK), 0, st, in, out, sums, n);
   HIPCHK(c, hipGetLastError());
-  int rc = scan_u32(c, sums, sums, nb, false, tmp + ((nb + 8 + 3) & ~3ull), st);
+  if (!sums) return 0;
+  const int rc = scan_levels(c, (const T*)sums, sums, nb, tmp + ((nb + 8 + 3) & ~3ull), st, below, below, add);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, out, sums, n);
+  hipLaunchKernelGGL(add, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, out, (const T*)sums, n);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
 
+// u32 scan of n elements (in may equal out).  tmp must hold scan_tmp_elems(n).
+int scan_u32(musc_ctx* c, const uint32_t* in, uint32_t* out, uint64_t n, bool inclusive, uint32_t* tmp, hipStream_t st = nullptr) {
+  return scan_levels<uint32_t>(c, in, out, n, tmp, st ? st : c->stream, inclusive ? k_scan_block<true> : k_scan_block<false>, k_scan_block<false>, k_scan_add);
+}
+
 // exclusive u64 scan (in place allowed); tmp must hold scan_tmp_elems(n) u64
 int scan_u64(musc_ctx* c, const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp) {
-  const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-  if (nb > 0x7FFFFFFFull) return fail(c, 11, "scan too large");
-  if (nb <= 1) {
-    hipLaunchKernelGGL(k_scan64_block, dim3(1), dim3(SCAN_BLOCK), 0, c->stream, in, out, (uint64_t*)nullptr, n);
+  return scan_levels<uint64_t>(c, in, out, n, tmp, c->stream, k_scan64_block, k_scan64_block, k_scan64_add);
+}
+
+// A temporary of the public call `who`: a failed device allocation is the library's code for a failed HIP call, and the
+// text says whose, how large and why ("out of memory").
+template <class T>
+int tmp_alloc(musc_ctx* c, const char* who, TmpBufs& B, T** ptr, uint64_t bytes) {
+  const hipError_t e = B.alloc(ptr, bytes);
+  if (e == hipSuccess) return 0;
+  (void)hipGetLastError();
+  return fail(c, 10, "%s: device allocation of %llu bytes failed: %s", who, (unsigned long long)bytes, hipGetErrorString(e));
+}
+
+// An input of `bytes` bytes on the device: the caller's pointer where it is there already, else a temporary of B with
+// `slack` spare bytes behind the input and the copy queued on the context's stream (*d_ptr is device memory either way).
+template <class T>
+int staged(musc_ctx* c, const char* who, TmpBufs& B, const T* ptr, uint64_t bytes, int on_device, uint64_t slack, const T** d_ptr) {
+  *d_ptr = ptr;
+  if (on_device) return 0;
+  T* d = nullptr;
+  const int rc = tmp_alloc(c, who, B, &d, bytes + slack);
+  if (rc) return rc;
+  if (bytes) HIPCHK(c, hipMemcpyAsync(d, ptr, bytes, hipMemcpyHostToDevice, c->stream));
+  *d_ptr = d;
+  return 0;
+}
+
+// The stable sort of n items by passes of 64-bit keys, least significant pass first: LSD over (key, item number) pairs
+// with rocPRIM's device radix sort (a library primitive, not part of the hot path).  start() takes the buffers as
+// temporaries of its own B, sized for the largest of the end bits the passes will name, and numbers the items;
+// pass(end_bit, fill) has `fill(order, keys)` queue the kernel that writes keys[i] = the key of item order[i] and sorts
+// bits [0, end_bit) of them (the end bit decides how many radix passes the primitive runs); order() is the permutation
+// after the passes so far.  Everything is queued on the context's stream; nothing waits.
+struct KeyPasses {
+  TmpBufs B;  // (the caller may add temporaries that live as long as the sort's)
+  int start(musc_ctx* ctx, const char* who, uint64_t items, std::initializer_list<unsigned> end_bits) {
+    c = ctx, n = items;
+    int rc;
+    if ((rc = tmp_alloc(c, who, B, &k0, n * 8)) || (rc = tmp_alloc(c, who, B, &k1, n * 8)) || (rc = tmp_alloc(c, who, B, &p0, n * 4)) ||
+        (rc = tmp_alloc(c, who, B, &p1, n * 4)))
+      return rc;
+    for (unsigned end : end_bits) {
+      size_t tb = 0;
+      HIPCHK(c, sort(nullptr, tb, end));
+      tmp_bytes = std::max(tmp_bytes, tb);
+    }
+    if ((rc = tmp_alloc(c, who, B, &tmp, tmp_bytes))) return rc;
+    hipLaunchKernelGGL(k_prep_iota, grid(n), dim3(256), 0, c->stream, p0, n);
     HIPCHK(c, hipGetLastError());
     return 0;
   }
-  hipLaunchKernelGGL(k_scan64_block, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, c->stream, in, out, tmp, n);
-  HIPCHK(c, hipGetLastError());
-  int rc = scan_u64(c, tmp, tmp, nb, tmp + ((nb + 8 + 3) & ~3ull));
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_scan64_add, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, c->stream, out, tmp, n);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
+  template <class Fill>
+  int pass(unsigned end_bit, Fill fill) {
+    fill((const uint32_t*)p0, k0);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, sort(tmp, tmp_bytes, end_bit));
+    std::swap(p0, p1);
+    return 0;
+  }
+  const uint32_t* order() const { return p0; }
+  hipError_t sort(void* t, size_t& bytes, unsigned end_bit) {
+    return rocprim::radix_sort_pairs(t, bytes, k0, k1, p0, p1, (size_t)n, 0u, end_bit, c->stream);
+  }
+  musc_ctx* c = nullptr;
+  uint64_t n = 0;
+  uint64_t *k0 = nullptr, *k1 = nullptr;
+  uint32_t *p0 = nullptr, *p1 = nullptr;
+  void* tmp = nullptr;
+  size_t tmp_bytes = 0;
+};
 
 void free_index(musc_ctx* c);  // muscato_index.hpp
 
@@ -520,7 +589,9 @@ void free_reads(musc_ctx* c) { drop_reads(c, false); }
 // loaded", until a load succeeds.  (The message of the failure stays the context's last error.)
 int reads_load_done(musc_ctx* c, int rc) {
   if (rc) {
-    if (c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);  // (pieces of a fixed-length load may still be on their way)
+    // (pieces of a fixed-length load, kernels and copies of the failed call may still be queued: none of them is when this returns)
+    if (c->up.s_up) (void)hipStreamSynchronize(c->up.s_up);
+    (void)hipStreamSynchronize(c->stream);
     free_reads(c);
     c->reads_failed = true;
   }
@@ -664,6 +735,8 @@ int musc_init(int device_ordinal, musc_ctx** out) {
     musc_destroy(c);
     return 3;
   }
+  c->scalars.w = c->h_pinned;
+  c->scalars.n = CNT_WORDS;
   c->env.read();
   if (c->env.batch_reads >= 1 && c->env.batch_reads <= (16l << 20)) c->batch_reads = (uint32_t)c->env.batch_reads;  // tests: many small batches
   *out = c;
@@ -808,9 +881,9 @@ static int match_partitions_run(musc_ctx* c, const musc_params* P, uint64_t* nhi
     HIPCHK(c, hipGetLastError());
   }
   if ((rc = scan_u64(c, c->pcnt.p, c->pcnt.p, nr + 1, reinterpret_cast<uint64_t*>(c->pflags_tmp.p)))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->pcnt.p + nr, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t total = c->h_pinned[0];
+  Readback R(c->scalars, c->stream);
+  uint64_t total = 0;
+  HIPCHK(c, R.get(c->pcnt.p + nr, &total).wait());
   if ((rc = ensure(c, c->hits, total ? total : 1))) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
   for (uint32_t p = 0; p < np; p++) {
@@ -835,18 +908,17 @@ static int match_partitions_run(musc_ctx* c, const musc_params* P, uint64_t* nhi
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(ev1, c->stream));
-  c->h_pinned[1] = 0;
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_OVF_BLOCKS, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->h_pinned[1]) return fail(c, 12, "internal: the partition merge overran its %llu tuples", (unsigned long long)total);
+  uint64_t ovf_blocks = 0;
+  uint32_t overran = 0;
+  HIPCHK(c, R.get(c->counters + CNT_OVF_BLOCKS, &ovf_blocks).get(c->d_flag.get(), &overran).wait());
+  if (overran) return fail(c, 12, "internal: the partition merge overran its %llu tuples", (unsigned long long)total);
   float merge_ms = 0;
   (void)hipEventElapsedTime(&merge_ms, ev0, ev1);
   sum.ms_select += merge_ms;
   sum.ms_total += merge_ms;
   sum.n_reads = nr;
   sum.n_hits = c->nhits = total;
-  sum.n_overflow_blocks = check_blocks ? c->h_pinned[0] : ~0ull;
+  sum.n_overflow_blocks = check_blocks ? ovf_blocks : ~0ull;
   c->stats = sum;
   c->last_exact_blocks = check_blocks;
   if (nhits) *nhits = total;
@@ -971,7 +1043,7 @@ int musc_hits_copy_packed(musc_ctx* c, uint64_t* dst, uint64_t capacity, int dst
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
   const uint4* const hits = reinterpret_cast<const uint4*>(c->hits.p);
   auto pack = [&](uint64_t t0, uint64_t t1) {
-    hipLaunchKernelGGL(k_pack_hits, dim3(std::min(nblk(t1 - t0, 256), MAX_GRID)), dim3(256), 0, c->stream, hits + t0, t1 - t0,
+    hipLaunchKernelGGL(k_pack_hits, grid(t1 - t0), dim3(256), 0, c->stream, hits + t0, t1 - t0,
                        read_base, b, out + t0, c->d_flag);
   };
   uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned.get());
@@ -1022,7 +1094,7 @@ int musc_hits_copy_compact(musc_ctx* c, uint32_t* words, uint64_t words_cap, uin
   uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   if (dst_on_device) {
     if (c->nhits) {
-      hipLaunchKernelGGL(k_pack_compact, dim3(std::min(nblk(c->nhits, 256), MAX_GRID)), dim3(256), 0, c->stream, hits, c->nhits,
+      hipLaunchKernelGGL(k_pack_compact, grid(c->nhits), dim3(256), 0, c->stream, hits, c->nhits,
                          b, dw, dc, c->d_flag);
       HIPCHK(c, hipGetLastError());
     }
@@ -1032,7 +1104,7 @@ int musc_hits_copy_compact(musc_ctx* c, uint32_t* words, uint64_t words_cap, uin
     // the words chunk by chunk, then the count bytes: a count is final only when the chunk that holds the head of its
     // read's run has been packed, and the counts are the smaller copy
     int rc = download_chunks(c, c->nhits, 4, dw, words, [&](uint64_t t0, uint64_t t1) {
-      hipLaunchKernelGGL(k_pack_compact_range, dim3(std::min(nblk(t1 - t0, 256), MAX_GRID)), dim3(256), 0, c->stream, hits,
+      hipLaunchKernelGGL(k_pack_compact_range, grid(t1 - t0), dim3(256), 0, c->stream, hits,
                          c->nhits, t0, t1, b, dw, dc, c->d_flag);
     });
     const int rc_end = download_end(c, h_bad, counts, dc, c->nreads);
@@ -1066,7 +1138,7 @@ int musc_hits_unpack(musc_ctx* c, const uint64_t* src, uint64_t n, int on_device
     return 0;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(k_unpack_hits, dim3(std::min(nblk(n, 256), MAX_GRID)), dim3(256), 0, c->stream, src, n, b,
+  hipLaunchKernelGGL(k_unpack_hits, grid(n), dim3(256), 0, c->stream, src, n, b,
                      reinterpret_cast<uint4*>(dst));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1341,7 +1413,7 @@ int musc_gather_rccl(musc_ctx* const* ctxs, int n, const uint64_t* read_base, mu
   for (int i = 0; i < n; i++) {
     const uint64_t base = read_base ? read_base[i] : 0;
     if (!base || !ctxs[i]->nhits) continue;
-    hipLaunchKernelGGL(k_rebase_reads, dim3(std::min(nblk(ctxs[i]->nhits, 256), MAX_GRID)), dim3(256), 0, c0->stream,
+    hipLaunchKernelGGL(k_rebase_reads, grid(ctxs[i]->nhits), dim3(256), 0, c0->stream,
                        reinterpret_cast<uint4*>(c0->gathered.p + off[i]), ctxs[i]->nhits, (uint32_t)base);
     HIPCHK(c0, hipGetLastError());
   }

@@ -2,7 +2,7 @@
 // eligibility, the partition planner and ensure_index, and the musc_db_build_index* / musc_db_*partition* entry points.
 // It owns the resident index (musc_ctx::idx and the four tables) and acts on what index_plan.hpp decides: the planner
 // and the builds ask the same cascade.  Part of libmuscato_hip.so: included by muscato_hip.hip after the context, the
-// scans and the event pool it calls (fail, HIPCHK, ensure, TmpBufs, scan_u64, pool_event, check_params), behind the
+// scans and the event pool it calls (fail, HIPCHK, ensure, TmpBufs, Readback, scan_u64, pool_event, check_params), behind the
 // loaders (muscato_load.hpp: the database it indexes).
 #pragma once
 
@@ -78,11 +78,12 @@ int build_index_table(musc_ctx* c, int bits, uint64_t bucket_b, bool cursors, bo
   int rc = scan_u64(c, tmp, tmp, nb + 1, stmp);
   if (rc) return rc;
   uint64_t novf = 0, e_bytes = 0;
-  HIPCHK(c, hipMemcpyAsync(&novf, tmp + nb, 8, hipMemcpyDeviceToHost, c->stream));
+  Readback R(c->scalars, c->stream);
+  R.get(tmp + nb, &novf);
   set(tmp);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(e2, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, R.wait());
   B.release();  // 8 bytes per bucket: returned before the overflow array is allocated
   if ((rc = cap(&novf, &e_bytes))) return rc;
   c->idx_novf = novf;
@@ -225,8 +226,7 @@ bool reads_x_fit(musc_ctx* c, const musc_params* P, uint32_t max_len, int wide) 
   if (hipMemsetAsync(c->d_flag, 0, 4, c->stream) != hipSuccess) return false;
   hipLaunchKernelGGL(k_xpos_check, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rd, c->rdx.p, c->nreads, c->rw, d_tab,
                      max_len, wide ? XPos<true>::MAX : XPos<false>::MAX, c->d_flag);
-  if (hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return false;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
+  if (Readback(c->scalars, c->stream).get(c->d_flag.get(), &bad).wait() != hipSuccess) return false;
   c->xok.ok = bad == 0;
   c->xok.gen = c->st.g.pass_inputs;
   c->xok.pmatch = P->pmatch;
@@ -250,8 +250,7 @@ bool reads_x_fit_db(musc_ctx* c, const musc_params* P, int wide) {
   if (hipMemsetAsync(c->d_flag, 0, 4, c->stream) != hipSuccess) return false;
   if (wide) hipLaunchKernelGGL(k_xpos_check_db<true>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rdx.p, c->nreads, wn, c->d_flag);
   else hipLaunchKernelGGL(k_xpos_check_db<false>, dim3(nblk(c->nreads, 256)), dim3(256), 0, c->stream, c->rdx.p, c->nreads, wn, c->d_flag);
-  if (hipMemcpyAsync(&bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return false;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return false;
+  if (Readback(c->scalars, c->stream).get(c->d_flag.get(), &bad).wait() != hipSuccess) return false;
   c->xokdb.ok = bad == 0;
   c->xokdb.gen = c->st.g.pass_inputs;
   std::copy(key, key + CTX_MAX_W + 3, c->xokdb.key);

@@ -1,6 +1,7 @@
 // muscato_load.hpp -- the loaders: what brings a database or a read set from the caller's bytes to the resident planes
 // and records.  Part of libmuscato_hip.so: included by muscato_hip.hip after the context, the scans and
-// the event marks (fail, HIPCHK, TmpBufs, scan_u64, free_db, free_reads, reads_load_done, Marks), and in front of
+// the event marks (fail, HIPCHK, grid, TmpBufs, tmp_alloc, staged, Readback, scan_u64, free_db, free_reads,
+// reads_load_done, Marks), and in front of
 // muscato_index.hpp and muscato_pass.hpp, which call upload_prepare, db_xblocks and the read-record functions.  The
 // loaders that start from text follow it in muscato_prep.hpp (FASTQ, sort + collapse) and muscato_db_text.hpp (the gene
 // file).  The arithmetic is load_plan.hpp's.
@@ -11,44 +12,13 @@
 
 // ---------------------------------------------------------------- what the loaders share
 
-// A temporary of the public call `who`: a failed device allocation is the library's code for a failed HIP call, and the
-// text says whose, how large and why ("out of memory").
-template <class T>
-static int tmp_alloc(musc_ctx* c, const char* who, TmpBufs& B, T** ptr, uint64_t bytes) {
-  const hipError_t e = B.alloc(ptr, bytes);
-  if (e == hipSuccess) return 0;
-  (void)hipGetLastError();
-  return fail(c, 10, "%s: device allocation of %llu bytes failed: %s", who, (unsigned long long)bytes, hipGetErrorString(e));
-}
-
-// An input of `bytes` bytes on the device: the caller's pointer where it is there already, else a temporary of B with
-// `slack` spare bytes behind the input and the copy queued on the context's stream (*d_ptr is device memory either way).
-template <class T>
-static int staged(musc_ctx* c, const char* who, TmpBufs& B, const T* ptr, uint64_t bytes, int on_device, uint64_t slack,
-                  const T** d_ptr) {
-  *d_ptr = ptr;
-  if (on_device) return 0;
-  T* d = nullptr;
-  const int rc = tmp_alloc(c, who, B, &d, bytes + slack);
-  if (rc) return rc;
-  if (bytes) HIPCHK(c, hipMemcpyAsync(d, ptr, bytes, hipMemcpyHostToDevice, c->stream));
-  *d_ptr = d;
-  return 0;
-}
-
 // What a loader asks of n + 1 read offsets on the device before it sizes anything: the first, the last and the longest
 // read (k_max_len), read back together, with one wait.
 static int offsets_census(musc_ctx* c, const uint64_t* d_off, uint64_t n, uint64_t* first, uint64_t* last, uint64_t* maxlen) {
   HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, dim3(std::min(nblk(n, 256), MAX_GRID)), dim3(256), 0, c->stream, d_off, n, c->counters + CNT_SCRATCH);
+  hipLaunchKernelGGL(k_max_len, grid(n), dim3(256), 0, c->stream, d_off, n, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, d_off, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2, d_off + n, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *maxlen = c->h_pinned[0];
-  *first = c->h_pinned[1];
-  *last = c->h_pinned[2];
+  HIPCHK(c, Readback(c->scalars, c->stream).get(c->counters + CNT_SCRATCH, maxlen).get(d_off, first).get(d_off + n, last).wait());
   return 0;
 }
 
@@ -77,12 +47,9 @@ static int text_lines(musc_ctx* c, const char* who, TmpBufs& B, const unsigned c
   hipLaunchKernelGGL(k_fq_count, L->tgrid, dim3(FQ_BLOCK), 0, c->stream, L->base16, L->lo, L->hi, L->ntiles, L->cnt);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, L->cnt, L->cnt, L->ntiles + 1, stmp))) return rc;
-  c->h_pinned[1] = 0;
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, L->cnt + L->ntiles, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, d_text + (nbytes - 1), 1, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  L->newlines = c->h_pinned[0];
-  L->virt = *reinterpret_cast<const unsigned char*>(c->h_pinned + 1) != '\n';  // a last line without a newline is a line
+  unsigned char last = 0;
+  HIPCHK(c, Readback(c->scalars, c->stream).get(L->cnt + L->ntiles, &L->newlines).get(d_text + (nbytes - 1), &last).wait());
+  L->virt = last != '\n';  // a last line without a newline is a line
   return 0;
 }
 
@@ -110,11 +77,11 @@ static int db_xblocks(musc_ctx* c) {
   return 0;
 }
 
-// the pack kernel has run: whether it met an X (one wait), and with it the mask plane's fate
-static int db_finish(musc_ctx* c) {
+// the pack kernel has run: whether it met an X (one wait, which also delivers what the caller has queued in R), and with
+// it the mask plane's fate
+static int db_finish(musc_ctx* c, Readback& R) {
   uint32_t hasx = 0;
-  HIPCHK(c, hipMemcpyAsync(&hasx, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, R.get(c->d_flag.get(), &hasx).wait());
   c->db_has_x = hasx != 0;
   if (!hasx) {
     c->dbm2.release();
@@ -182,7 +149,8 @@ static int db_load_ascii_run(musc_ctx* c, const char* seqs, const uint64_t* offs
                        c->db2, c->dbm2, c->db_words, c->d_flag);
     HIPCHK(c, hipGetLastError());
   }
-  return db_finish(c);
+  Readback R(c->scalars, c->stream);
+  return db_finish(c, R);
 }
 
 static int db_load_packed_run(musc_ctx* c, const uint8_t* bases2bit, const uint8_t* nmask, const uint64_t* seq_offsets, uint32_t nseq) {
@@ -206,7 +174,8 @@ static int db_load_packed_run(musc_ctx* c, const uint8_t* bases2bit, const uint8
                        c->d_flag);
     HIPCHK(c, hipGetLastError());
   }
-  return db_finish(c);
+  Readback R(c->scalars, c->stream);
+  return db_finish(c, R);
 }
 
 extern "C" int musc_db_load_ascii(musc_ctx* c, const char* seqs, const uint64_t* offsets, uint32_t nseq, int on_device) {
@@ -333,8 +302,7 @@ static int reads_load(musc_ctx* c, const char* who, const unsigned char* ascii, 
   }
   HIPCHK(c, hipGetLastError());
   uint32_t hasx = 0;
-  HIPCHK(c, hipMemcpyAsync(&hasx, d_hasx, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, Readback(c->scalars, c->stream).get(d_hasx, &hasx).wait());
   reads_settle_x(c, hasx);
   return 0;
 }

@@ -1,5 +1,6 @@
 // muscato_maxmatches.hpp -- the host side of the MaxMatches replay on the device (musc_maxmatches_*).
-// Part of libmuscato_hip.so: included by muscato_hip.hip after muscato_text.hpp (timed, grid).  The kernels are in
+// Part of libmuscato_hip.so: included by muscato_hip.hip after muscato_text.hpp (timed; grid, the scans and Readback are
+// what the drivers share).  The kernels are in
 // kernels_maxmatches.hpp, the decisions that need no device in maxmatches_plan.hpp.
 #pragma once
 
@@ -13,21 +14,19 @@ static int hot_probes_device(musc_ctx* c, DevPtr<uint2>* out, uint64_t* found) {
     HIPCHK(c, out->alloc(cap * sizeof(uint2)));
     uint2* const d_out = out->get();
     hipError_t e = hipMemsetAsync(c->counters + CNT_BATCH, 0, 8, c->stream);
-    const dim3 grid(std::max(1u, std::min(nblk(c->nreads, 256), MAX_GRID))), block(256);
     if (e == hipSuccess) {
       by_rw(c->rw, [&](auto r) {
-        hipLaunchKernelGGL((k_hot_probes<decltype(r)::value>), grid, block, 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp,
+        hipLaunchKernelGGL((k_hot_probes<decltype(r)::value>), grid(c->nreads), dim3(256), 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp,
                            c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH);
       });
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(c->h_pinned, c->counters + CNT_BATCH, 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    uint64_t n = 0;
+    if (e == hipSuccess) e = Readback(c->scalars, c->stream).get(c->counters + CNT_BATCH, &n).wait();
     if (e != hipSuccess) {  // (the block goes with the caller's owner)
       (void)hipGetLastError();
       return fail(c, 10, "the suspect probes: %s", hipGetErrorString(e));
     }
-    const uint64_t n = c->h_pinned[0];
     if (n > cap) {  // again, with room for all of them
       cap = n + 16;
       continue;
@@ -76,7 +75,7 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
   const dim3 B256(256);
   const MmData D = mm_data(c, P);
   const uint4* const hits = reinterpret_cast<const uint4*>(c->hits.p);
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned + 8);
+  Readback R(c->scalars, c->stream);
   int rc;
 
   DevPtr<uint2> probes;
@@ -109,10 +108,9 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
     hipLaunchKernelGGL(k_mm_heads, grid(np), B256, 0, c->stream, D, sorted, np, heads);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u32(c, heads, excl, np, false, stmp))) return rc;
-    HIPCHK(c, hipMemcpyAsync(h32, excl + (np - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h32 + 1, heads + (np - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint32_t nb = h32[0] + h32[1];
+    uint32_t heads_before = 0, head_last = 0;
+    HIPCHK(c, R.get(excl + (np - 1), &heads_before).get(heads + (np - 1), &head_last).wait());
+    const uint32_t nb = heads_before + head_last;
     HIPCHK(c, A.alloc(&blocks, (uint64_t)nb * 8));
     hipLaunchKernelGGL(k_mm_blocks, grid(np), B256, 0, c->stream, sorted, heads, excl, np, blocks);
     HIPCHK(c, hipGetLastError());
@@ -134,11 +132,8 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
     hipLaunchKernelGGL(k_mm_sizes, grid((uint64_t)nb + 1), B256, 0, c->stream, cnt, nb, (uint32_t)P.max_matches, sizes, c->counters + CNT_SCRATCH);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, sizes, off, (uint64_t)nb + 1, tmp64))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, off + nb, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    ntrunc = c->h_pinned[0];
-    const uint64_t M = c->h_pinned[1];
+    uint64_t M = 0;
+    HIPCHK(c, R.get(c->counters + CNT_SCRATCH, &ntrunc).get(off + nb, &M).wait());
     *n_trunc = ntrunc;
     c->mm_pairs = M;
     if (ntrunc == 0) {  // false alarms only
@@ -185,10 +180,9 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
     HIPCHK(c, hipGetLastError());
   }
   if ((rc = scan_u32(c, flags, excl, N, false, stmp))) return rc;
-  HIPCHK(c, hipMemcpyAsync(h32, excl + (N - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h32 + 1, flags + (N - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t m = (uint64_t)h32[0] + h32[1];
+  uint64_t kept_before = 0, kept_last = 0;
+  HIPCHK(c, R.get(excl + (N - 1), &kept_before).get(flags + (N - 1), &kept_last).wait());
+  const uint64_t m = kept_before + kept_last;
   uint4* out = nullptr;
   HIPCHK(c, B.alloc(&out, m * 16));
   hipLaunchKernelGGL(k_mm_compact, grid(N), B256, 0, c->stream, hits, N, flags, excl, out);

@@ -1,7 +1,8 @@
 // muscato_prep.hpp -- read prep on the GPU: bytewise sort of the prepared reads and collapse of
 // identical sequences, and the FASTQ parse in front of it (kernels_fastq.hpp).
 // Included by muscato_hip.hip right behind muscato_load.hpp (one translation unit: it uses musc_ctx,
-// the record functions and the loaders' helpers -- staged, tmp_alloc, offsets_census, text_lines).
+// the record functions, what the drivers share -- staged, tmp_alloc, KeyPasses, Readback -- and the loaders'
+// offsets_census and text_lines).
 //
 // Reference: cmd/muscato/main.go sortReads (GNU `sort` of the `seq\tname` lines under LC_ALL=C)
 // followed by cmd/muscato_uniqify/main.go:83-135 (adjacent lines with the same sequence become
@@ -15,10 +16,7 @@
 // first (the tab that follows it, 9, is below every letter).  A read becomes ceil(maxlen / 21)
 // u64 key words of 3-bit codes (0 = past the end, 1..5 = A C G T other), first base most
 // significant, so that comparing the words as integers from the first to the last is that
-// order; the sort is LSD over the words with a stable radix sort of (word, read number) pairs
-// per word (rocPRIM's device radix sort -- a library primitive, not part of the hot path).
-
-#include <rocprim/device/device_radix_sort.hpp>
+// order; the sort is LSD over the words, one stable pass of KeyPasses per word.
 
 #define PREP_BASES_PER_WORD 21
 
@@ -50,11 +48,6 @@ MUSC_KERNEL __launch_bounds__(256) void k_prep_keys(const unsigned char* __restr
     }
     keys[i] = key;
   }
-}
-
-MUSC_KERNEL void k_prep_iota(uint32_t* __restrict__ p, uint64_t n) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    p[i] = (uint32_t)i;
 }
 
 // head[i] = 1 when the i-th read in sorted order differs from the one before it
@@ -147,24 +140,12 @@ static int reads_sort_unique_dev(musc_ctx* c, const char* who, const unsigned ch
 
   // ---- LSD sort over the key words
   const uint32_t nw = (uint32_t)std::max<uint64_t>((maxlen + PREP_BASES_PER_WORD - 1) / PREP_BASES_PER_WORD, 1);
-  uint64_t *k0 = nullptr, *k1 = nullptr;
-  uint32_t *p0 = nullptr, *p1 = nullptr;
-  if ((rc = tmp_alloc(c, who, B, &k0, n * 8)) || (rc = tmp_alloc(c, who, B, &k1, n * 8)) || (rc = tmp_alloc(c, who, B, &p0, n * 4)) ||
-      (rc = tmp_alloc(c, who, B, &p1, n * 4)))
-    return rc;
-  size_t tmp_bytes = 0;
-  HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, k0, k1, p0, p1, (size_t)n, 0u, 63u, c->stream));
-  void* tmp = nullptr;
-  if ((rc = tmp_alloc(c, who, B, &tmp, tmp_bytes))) return rc;
-  const dim3 grid(std::min(nblk(n, 256), MAX_GRID));
-  hipLaunchKernelGGL(k_prep_iota, grid, dim3(256), 0, c->stream, p0, n);
-  HIPCHK(c, hipGetLastError());
-  for (uint32_t w = nw; w-- > 0;) {
-    hipLaunchKernelGGL(k_prep_keys, grid, dim3(256), 0, c->stream, d_s, d_off, p0, n, w, k0);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, rocprim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, p0, p1, (size_t)n, 0u, 63u, c->stream));
-    std::swap(p0, p1);  // p0 = the order after this word
-  }
+  KeyPasses K;
+  if ((rc = K.start(c, who, n, {63u}))) return rc;
+  for (uint32_t w = nw; w-- > 0 && !rc;)
+    rc = K.pass(63u, [&](const uint32_t* perm, uint64_t* keys) { hipLaunchKernelGGL(k_prep_keys, grid(n), dim3(256), 0, c->stream, d_s, d_off, perm, n, w, keys); });
+  if (rc) return rc;
+  const uint32_t* const p0 = K.order();
 
   // ---- groups of identical sequences
   uint32_t *head = nullptr, *incl = nullptr, *stmp = nullptr, *d_ustart = nullptr, *d_uhead = nullptr;
@@ -172,15 +153,13 @@ static int reads_sort_unique_dev(musc_ctx* c, const char* who, const unsigned ch
       (rc = tmp_alloc(c, who, B, &stmp, scan_tmp_elems(n) * 4)) || (rc = tmp_alloc(c, who, B, &d_ustart, (n + 1) * 4)) ||
       (rc = tmp_alloc(c, who, B, &d_uhead, n * 4)))
     return rc;
-  hipLaunchKernelGGL(k_prep_heads, grid, dim3(256), 0, c->stream, d_s, d_off, p0, n, head);
+  hipLaunchKernelGGL(k_prep_heads, grid(n), dim3(256), 0, c->stream, d_s, d_off, p0, n, head);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, head, incl, n, true, stmp))) return rc;
-  hipLaunchKernelGGL(k_prep_starts, grid, dim3(256), 0, c->stream, head, incl, n, d_ustart, d_uhead, p0);
+  hipLaunchKernelGGL(k_prep_starts, grid(n), dim3(256), 0, c->stream, head, incl, n, d_ustart, d_uhead, p0);
   HIPCHK(c, hipGetLastError());
-  uint32_t nu32 = 0;
-  HIPCHK(c, hipMemcpyAsync(&nu32, incl + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t nu = nu32;
+  uint64_t nu = 0;
+  HIPCHK(c, Readback(c->scalars, c->stream).get(incl + (n - 1), &nu).wait());
 
   // ---- the distinct sequences become the context's reads
   if ((rc = reads_shape(c, nu, maxlen, false, &shape)) || (rc = reads_records(c, shape, nu, maxlen, true, false))) return rc;
@@ -193,27 +172,19 @@ static int reads_sort_unique_dev(musc_ctx* c, const char* who, const unsigned ch
   HIPCHK(c, m.mark(c, 1));
 
   // ---- order and group boundaries for the host (names, counts)
-  uint32_t* h_order = (uint32_t*)malloc(n * 4);
-  uint32_t* h_ustart = (uint32_t*)malloc((nu + 1) * 4);
-  if (!h_order || !h_ustart) {
-    free(h_order);
-    free(h_ustart);
-    return fail(c, 7, "out of host memory for the sort order");
-  }
+  // (the owners free what the two copies target behind the wait alone: no return lies between the first copy and it)
+  std::unique_ptr<uint32_t, decltype(&free)> h_order((uint32_t*)malloc(n * 4), free), h_ustart((uint32_t*)malloc((nu + 1) * 4), free);
+  if (!h_order || !h_ustart) return fail(c, 7, "out of host memory for the sort order");
   uint32_t hasx = 0;
-  hipError_t e = hipMemcpyAsync(h_order, p0, n * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h_ustart, d_ustart, (nu + 1) * 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(&hasx, d_hasx, 4, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    free(h_order);
-    free(h_ustart);
-    return fail(c, 10, "musc_reads_sort_unique: %s", hipGetErrorString(e));
-  }
+  hipError_t e = hipMemcpyAsync(h_order.get(), p0, n * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_ustart.get(), d_ustart, (nu + 1) * 4, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t ew = Readback(c->scalars, c->stream).get(d_hasx, &hasx).wait();
+  if (e == hipSuccess) e = ew;
+  if (e != hipSuccess) return fail(c, 10, "musc_reads_sort_unique: %s", hipGetErrorString(e));
   reads_settle_x(c, hasx);
   c->stats.ms_read_prep = m.ms(0, 1);  // device time of the last sort + collapse
-  *order = h_order;
-  *ustart = h_ustart;
+  *order = h_order.release();
+  *ustart = h_ustart.release();
   *nunique = nu;
   return 0;
 }
@@ -309,19 +280,14 @@ static int fastq_prep_run(musc_ctx* c, const char* who, const char* text, uint64
                        name_begin, name_end, seq_end);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemsetAsync(st, 0, 16, c->stream));
-    hipLaunchKernelGGL(k_fq_records, dim3(std::min(nblk(nrec + 1, 256), MAX_GRID)), dim3(256), 0, c->stream, d_text, nrec,
+    hipLaunchKernelGGL(k_fq_records, grid(nrec + 1), dim3(256), 0, c->stream, d_text, nrec,
                        name_begin, name_end, seq_end, min_len, max_len, kidx, len, name_len, st);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u32(c, kidx, kidx, nrec + 1, false, stmp32)) || (rc = scan_u64(c, len, len, nrec + 1, stmp64))) return rc;
-    uint32_t nk32 = 0;
-    HIPCHK(c, hipMemcpyAsync(&nk32, kidx + nrec, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, len + nrec, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2, st, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    nkept = nk32;
-    total = c->h_pinned[0];
-    out->max_len = (uint32_t)c->h_pinned[2];
-    out->n_short = c->h_pinned[3];
+    uint64_t census[2] = {0, 0};  // the longest kept read, the reads that were too short
+    HIPCHK(c, Readback(c->scalars, c->stream).get(kidx + nrec, &nkept).get(len + nrec, &total).get_words(st, census, 2).wait());
+    out->max_len = (uint32_t)census[0];
+    out->n_short = census[1];
   }
   out->n_records = nrec;
   out->n_reads = nkept;
@@ -368,8 +334,8 @@ extern "C" int musc_reads_prep_fastq(musc_ctx* c, const char* text, uint64_t nby
   HIPCHK(c, hipSetDevice(c->device));
   free_reads(c);
   if (max_read_len < 0) return reads_load_done(c, fail(c, 2, "musc_reads_prep_fastq: max_read_len %d is negative", max_read_len));
-  const int rc = fastq_prep_run(c, "musc_reads_prep_fastq", text, nbytes, on_device, min_read_len, (uint32_t)max_read_len, out, false,
-                                [](const unsigned char*, const uint64_t*, const uint32_t*, const uint32_t*) { return 0; });
-  if (rc) musc_fastq_prep_free(out);  // nothing stale: no arrays, and (reads_load_done) no reads
-  return reads_load_done(c, rc);
+  const int rc = reads_load_done(c, fastq_prep_run(c, "musc_reads_prep_fastq", text, nbytes, on_device, min_read_len, (uint32_t)max_read_len, out, false,
+                                                   [](const unsigned char*, const uint64_t*, const uint32_t*, const uint32_t*) { return 0; }));
+  if (rc) musc_fastq_prep_free(out);  // nothing stale: no reads and (behind reads_load_done's wait for the queued downloads) no arrays
+  return rc;
 }

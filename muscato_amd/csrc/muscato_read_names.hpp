@@ -1,14 +1,14 @@
 // muscato_read_names.hpp -- the host side of the read-name stage: the members of each group of identical
 // prepared reads in the order of their clipped names, the record count\tJ of every group left as the context's read
 // text, and the lines seq\tcount\tJ\n of reads_sorted.txt rendered on demand.  Part of libmuscato_hip.so: included by
-// muscato_hip.hip behind muscato_text.hpp (text_range, grid, drop_read_text) and muscato_prep.hpp (fastq_prep_run).
+// muscato_hip.hip behind muscato_text.hpp (text_range, drop_read_text) and muscato_prep.hpp (fastq_prep_run); grid,
+// tmp_alloc, staged, KeyPasses and Readback are what the drivers share.
 // The kernels are kernels_read_names.hpp; what a lane computes is read_names_lanes.hpp and read_names_keys.hpp.
 //
 // Groups of up to WAVE_GROUP_MAX members are ranked by counting.  The members of the larger ones go, as (group, kept
-// read) pairs, through key_passes() stable passes of rocprim::radix_sort_pairs on (uint64_t key, uint32_t pair number)
-// -- the primitive, the types and the loop of reads_sort_unique_dev (muscato_prep.hpp).  No library sort under a
-// comparator is instantiated here.  What the device reports back (the pairs, the longest clipped name) is clamped
-// before the host sizes or loops by it.
+// read) pairs, through key_passes() stable passes of KeyPasses on (uint64_t key, uint32_t pair number), as the reads do
+// in reads_sort_unique_dev.  No library sort under a comparator is instantiated here.  What the device reports back
+// (the pairs, the longest clipped name) is clamped before the host sizes or loops by it.
 #pragma once
 
 #include "kernels_read_names.hpp"
@@ -41,38 +41,26 @@ static int rn_rank(musc_ctx* c, const char* who, const RnInput& in, uint32_t* ra
   hipLaunchKernelGGL(k_rn_rank, grid(n), B256, 0, c->stream, in.rd, in.N, in.order, in.ustart, gid, ranked, flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, flag, excl, n + 1, false, stmp))) return rc;
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned.get());
-  HIPCHK(c, hipMemcpyAsync(h32, excl + n, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t np = h32[0];
+  Readback R(c->scalars, c->stream);
+  uint64_t np = 0;
+  HIPCHK(c, R.get(excl + n, &np).wait());
   if (np > n) return fail(c, 11, "%s: %llu members of larger groups among %llu reads", who, (unsigned long long)np, (unsigned long long)n);
   if (np == 0) return 0;
 
   // ---- the pairs of the larger groups, ordered by W + 2 stable key passes
   uint2* pairs = nullptr;
-  uint64_t *k0 = nullptr, *k1 = nullptr;
-  uint32_t *place = nullptr, *p0 = nullptr, *p1 = nullptr;
-  if ((rc = tmp_alloc(c, who, B, &pairs, np * 8)) || (rc = tmp_alloc(c, who, B, &place, np * 4)) || (rc = tmp_alloc(c, who, B, &k0, np * 8)) ||
-      (rc = tmp_alloc(c, who, B, &k1, np * 8)) || (rc = tmp_alloc(c, who, B, &p0, np * 4)) || (rc = tmp_alloc(c, who, B, &p1, np * 4)))
-    return rc;
-  size_t tmp_bytes = 0;
-  HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp_bytes, k0, k1, p0, p1, (size_t)np, 0u, 64u, c->stream));
-  void* tmp = nullptr;
-  if ((rc = tmp_alloc(c, who, B, &tmp, tmp_bytes))) return rc;
+  uint32_t* place = nullptr;
+  KeyPasses K;
+  if ((rc = tmp_alloc(c, who, B, &pairs, np * 8)) || (rc = tmp_alloc(c, who, B, &place, np * 4)) || (rc = K.start(c, who, np, {64u}))) return rc;
   hipLaunchKernelGGL(k_rn_pairs, grid(n), B256, 0, c->stream, flag, excl, in.order, gid, in.N, pairs, place, max_clip);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h32, max_clip, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t W = musc_rn::key_words(h32[0]);  // (clamped: at most CMP_WORDS whatever came back)
-  hipLaunchKernelGGL(k_prep_iota, grid(np), B256, 0, c->stream, p0, np);
-  HIPCHK(c, hipGetLastError());
-  for (uint32_t pass = 0; pass < W + 2; pass++) {
-    hipLaunchKernelGGL(k_rn_keys, grid(np), B256, 0, c->stream, in.rd, in.N, pairs, p0, np, pass, W, k0);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, rocprim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, p0, p1, (size_t)np, 0u, 64u, c->stream));
-    std::swap(p0, p1);  // p0 = the order after this pass
-  }
-  hipLaunchKernelGGL(k_rn_unpairs, grid(np), B256, 0, c->stream, pairs, p0, place, np, ranked);
+  uint32_t clip = 0;
+  HIPCHK(c, R.get(max_clip, &clip).wait());
+  const uint32_t W = musc_rn::key_words(clip);  // (clamped: at most CMP_WORDS whatever came back)
+  for (uint32_t pass = 0; pass < W + 2 && !rc; pass++)
+    rc = K.pass(64u, [&](const uint32_t* ord, uint64_t* keys) { hipLaunchKernelGGL(k_rn_keys, grid(np), B256, 0, c->stream, in.rd, in.N, pairs, ord, np, pass, W, keys); });
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_rn_unpairs, grid(np), B256, 0, c->stream, pairs, K.order(), place, np, ranked);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (the temporaries go with B)
   *n_pairs = np;
@@ -195,11 +183,7 @@ static int read_names_stage(musc_ctx* c, const char* who, const unsigned char* d
     hipLaunchKernelGGL(k_rn_sizes, grid(nu), B256, 0, c->stream, ranked, in.ustart, meta, d_seq_len, nu, tstart, gsum, roff, loff);
     HIPCHK(c, hipGetLastError());
     if ((r = scan_u64(c, roff, roff, nu + 1, stmp)) || (r = scan_u64(c, loff, loff, nu + 1, stmp))) return r;
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, roff + nu, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, loff + nu, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    info->text_bytes = c->h_pinned[0];
-    info->line_bytes = c->h_pinned[1];
+    HIPCHK(c, Readback(c->scalars, c->stream).get(roff + nu, &info->text_bytes).get(loff + nu, &info->line_bytes).wait());
     // (a record is at most 10 digits, a tab and JOIN_LIMIT bytes: a total beyond that is not the sizes' own)
     if (info->text_bytes > nu * (uint64_t)(11 + musc_rn::JOIN_LIMIT))
       return fail(c, 11, "%s: %llu bytes of read text for %llu reads", who, (unsigned long long)info->text_bytes, (unsigned long long)nu);
@@ -235,13 +219,12 @@ extern "C" int musc_reads_prep_fastq_names(musc_ctx* c, const char* text, uint64
                                 [&](const unsigned char* d_text, const uint64_t* d_name_off, const uint32_t* d_name_len, const uint32_t* d_seq_len) {
                                   return read_names_stage(c, who, d_text, nbytes, d_name_off, d_name_len, d_seq_len, out, info);
                                 });
-  if (rc) {  // nothing stale: no arrays, no counts, and (reads_load_done) no reads and no read text
-    (void)hipStreamSynchronize(c->stream);
+  if (reads_load_done(c, rc)) {  // nothing stale: no reads and no read text, and behind its wait no arrays and no counts
     musc_fastq_prep_free(out);
     free(info->ranked);
     memset(info, 0, sizeof *info);
   }
-  return reads_load_done(c, rc);
+  return rc;
 }
 
 extern "C" int musc_reads_names_text(musc_ctx* c, int which, uint64_t rec0, uint64_t nrec, char* dst, uint64_t capacity, int dst_on_device,

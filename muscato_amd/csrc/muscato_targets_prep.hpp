@@ -1,7 +1,7 @@
 // muscato_targets_prep.hpp -- target preparation from the raw bytes of a FASTA or id<TAB>sequence file to the two
 // prepared texts, resident in the context, and the framed writer: musc_targets_prep,
 // musc_targets_prep_text, musc_targets_prep_load, musc_targets_prep_free and musc_sz_frame.  Included by
-// muscato_hip.hip behind muscato_db_text.hpp (one translation unit: musc_ctx, the scans, staged / tmp_alloc /
+// muscato_hip.hip behind muscato_db_text.hpp (one translation unit: musc_ctx, the scans, staged, tmp_alloc and Readback,
 // text_lines of muscato_load.hpp, db_load_text_run of muscato_db_text.hpp).  The arithmetic is targets_prep_plan.hpp's.
 //
 // Reference: cmd/muscato_prep_targets/main.go:82-141 (processText), :143-213 (processFasta), :48-80 (revcomp, subx),
@@ -18,8 +18,6 @@ static void tp_free(musc_ctx* c) {
   }
   c->tp_have = false;
 }
-
-static unsigned tp_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, MAX_GRID)); }
 
 // an owning buffer of a prepared text: whole dwords, so that the kernels' last aligned store lies inside it
 static int tp_out_alloc(musc_ctx* c, const char* who, DevPtr<unsigned char>& buf, uint64_t nbytes) {
@@ -45,6 +43,7 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
   int rc = m.start(c);
   if (rc) return rc;
   HIPCHK(c, m.mark(c, 0));
+  Readback R(c->scalars, c->stream);
   TmpBufs B, B2;  // the text and the line tables; the record tables
   const unsigned char* d_text = nullptr;
   // (16 spare bytes: the text's last 16-byte lane lies inside the block; fq_load16 reads no byte past the text itself)
@@ -77,15 +76,13 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
     HIPCHK(c, hipMemsetAsync(ltab, 0, nlines * 8, c->stream));
     hipLaunchKernelGGL(k_tp_lines, L.tgrid, dim3(FQ_BLOCK), 0, c->stream, L.base16, L.lo, L.hi, L.ntiles, L.cnt, nlines, L.virt, begin, eol, ftab, ltab);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_tp_classify<false>, dim3(tp_grid(nlines + 1)), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol, ftab, ltab,
+    hipLaunchKernelGGL(k_tp_classify<false>, grid(nlines + 1), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol, ftab, ltab,
                        (uint64_t*)nullptr, (uint64_t*)nullptr, st);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, st + TP_ST_STOP, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    info.stop_line = c->h_pinned[0];
+    HIPCHK(c, R.get(st + TP_ST_STOP, &info.stop_line).wait());
     nrec = std::min<uint64_t>(info.stop_line, nlines);  // the records are the lines in front of the first stop line
     if (musc_tp::refused(nrec, rev)) return fail(c, 12, "%s: %llu targets do not fit 32-bit target numbers", who, (unsigned long long)musc_tp::n_targets(nrec, rev));
-    hipLaunchKernelGGL(k_tp_text_recs, dim3(tp_grid(nrec + 1)), dim3(256), 0, c->stream, nrec, begin, eol, ftab, ltab, a);
+    hipLaunchKernelGGL(k_tp_text_recs, grid(nrec + 1), dim3(256), 0, c->stream, nrec, begin, eol, ftab, ltab, a);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, a, a, nrec + 1, stmp))) return rc;
     fo = a;
@@ -98,77 +95,70 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
     hipLaunchKernelGGL(k_tp_lines, L.tgrid, dim3(FQ_BLOCK), 0, c->stream, L.base16, L.lo, L.hi, L.ntiles, L.cnt, nlines, L.virt, begin, eol,
                        (unsigned long long*)nullptr, (unsigned long long*)nullptr);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_tp_classify<true>, dim3(tp_grid(nlines + 1)), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol,
+    hipLaunchKernelGGL(k_tp_classify<true>, grid(nlines + 1), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol,
                        (const unsigned long long*)nullptr, (const unsigned long long*)nullptr, hdr, bases, st);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, hdr, hdr, nlines + 1, stmp)) || (rc = scan_u64(c, bases, bases, nlines + 1, stmp))) return rc;
     S = bases;
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, st + TP_ST_EMPTY, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, hdr + nlines, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h_pinned[0] != ~0ull)
-      return fail(c, 14, "%s: empty line in FASTA input (line %llu)", who, (unsigned long long)c->h_pinned[0]);
-    const uint64_t nhdr = c->h_pinned[1], ngroups = nhdr + 1;  // group 0: the lines in front of the first header
+    uint64_t empty_line = 0, nhdr = 0;
+    HIPCHK(c, R.get(st + TP_ST_EMPTY, &empty_line).get(hdr + nlines, &nhdr).wait());
+    if (empty_line != ~0ull) return fail(c, 14, "%s: empty line in FASTA input (line %llu)", who, (unsigned long long)empty_line);
+    const uint64_t ngroups = nhdr + 1;  // group 0: the lines in front of the first header
     uint64_t *hl = nullptr, *kept = nullptr, *a = nullptr;
     if ((rc = tmp_alloc(c, who, B2, &hl, (ngroups + 1) * 8)) || (rc = tmp_alloc(c, who, B2, &kept, (ngroups + 1) * 8)) ||
         (rc = tmp_alloc(c, who, B2, &a, (ngroups + 1) * 8)) || (rc = tmp_alloc(c, who, B2, &fo, (ngroups + 1) * 8)) ||
         (rc = tmp_alloc(c, who, B2, &src0, ngroups * 8)) || (rc = tmp_alloc(c, who, B2, &name_b, ngroups * 8)) ||
         (rc = tmp_alloc(c, who, B2, &name_len, ngroups * 8)))
       return rc;
-    hipLaunchKernelGGL(k_tp_hl, dim3(tp_grid(nlines)), dim3(256), 0, c->stream, nlines, hdr, ngroups, hl);
+    hipLaunchKernelGGL(k_tp_hl, grid(nlines), dim3(256), 0, c->stream, nlines, hdr, ngroups, hl);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_tp_groups, dim3(tp_grid(ngroups + 1)), dim3(256), 0, c->stream, ngroups, hl, S, kept, a);
+    hipLaunchKernelGGL(k_tp_groups, grid(ngroups + 1), dim3(256), 0, c->stream, ngroups, hl, S, kept, a);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, kept, kept, ngroups + 1, stmp)) || (rc = scan_u64(c, a, a, ngroups + 1, stmp))) return rc;
-    hipLaunchKernelGGL(k_tp_compact, dim3(tp_grid(ngroups + 1)), dim3(256), 0, c->stream, ngroups, kept, a, hl, S, begin, eol, fo, src0, name_b,
+    hipLaunchKernelGGL(k_tp_compact, grid(ngroups + 1), dim3(256), 0, c->stream, ngroups, kept, a, hl, S, begin, eol, fo, src0, name_b,
                        name_len, st);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, kept + ngroups, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, st + TP_ST_KEPT0, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    nrec = c->h_pinned[0];
-    info.n_dropped = nhdr - (nrec - c->h_pinned[1]);  // headers whose record has no bases
+    uint64_t kept0 = 0;
+    HIPCHK(c, R.get(kept + ngroups, &nrec).get(st + TP_ST_KEPT0, &kept0).wait());
+    info.n_dropped = nhdr - (nrec - kept0);  // headers whose record has no bases
     if (musc_tp::refused(nrec, rev)) return fail(c, 12, "%s: %llu targets do not fit 32-bit target numbers", who, (unsigned long long)musc_tp::n_targets(nrec, rev));
   }
 
   // ---- the id lines' lengths and offsets; the sizes of both texts
   uint64_t* ioff = nullptr;
   if ((rc = tmp_alloc(c, who, B2, &ioff, (nrec + 1) * 8))) return rc;
-  hipLaunchKernelGGL(k_tp_idlen, dim3(tp_grid(nrec + 1)), dim3(256), 0, c->stream, nrec, fo, name_len, rev, ioff);
+  hipLaunchKernelGGL(k_tp_idlen, grid(nrec + 1), dim3(256), 0, c->stream, nrec, fo, name_len, rev, ioff);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, ioff, ioff, nrec + 1, stmp))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, fo + nrec, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, ioff + nrec, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint64_t fwd_bytes = 0, nid_bytes = 0;
+  HIPCHK(c, R.get(fo + nrec, &fwd_bytes).get(ioff + nrec, &nid_bytes).wait());
   const uint64_t mult = rev ? 2 : 1;
-  const uint64_t nseq_bytes = musc_tp::seq_fwd_off(c->h_pinned[0], rev), nid_bytes = c->h_pinned[1];
+  const uint64_t nseq_bytes = musc_tp::seq_fwd_off(fwd_bytes, rev);
 
   // ---- both texts
   DevPtr<unsigned char> seq, ids;
   if ((rc = tp_out_alloc(c, who, seq, nseq_bytes)) || (rc = tp_out_alloc(c, who, ids, nid_bytes))) return rc;
   if (nseq_bytes) {
-    const unsigned g = tp_grid((nseq_bytes + 3) / 4);
+    const dim3 g = grid((nseq_bytes + 3) / 4);
     if (fasta)
-      hipLaunchKernelGGL(k_tp_seq<true>, dim3(g), dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, src0, S, begin, nlines, mult, nseq_bytes, seq.get(), st);
+      hipLaunchKernelGGL(k_tp_seq<true>, g, dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, src0, S, begin, nlines, mult, nseq_bytes, seq.get(), st);
     else
-      hipLaunchKernelGGL(k_tp_seq<false>, dim3(g), dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, src0, S, begin, nlines, mult, nseq_bytes, seq.get(), st);
+      hipLaunchKernelGGL(k_tp_seq<false>, g, dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, src0, S, begin, nlines, mult, nseq_bytes, seq.get(), st);
     HIPCHK(c, hipGetLastError());
     if (rev) {
-      hipLaunchKernelGGL(k_tp_rev, dim3(g), dim3(256), 0, c->stream, nrec, fo, nseq_bytes, seq.get());
+      hipLaunchKernelGGL(k_tp_rev, g, dim3(256), 0, c->stream, nrec, fo, nseq_bytes, seq.get());
       HIPCHK(c, hipGetLastError());
     }
   }
   if (nid_bytes) {
-    hipLaunchKernelGGL(k_tp_ids, dim3(tp_grid((nid_bytes + 3) / 4)), dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, ioff, name_b, name_len, rev,
+    hipLaunchKernelGGL(k_tp_ids, grid((nid_bytes + 3) / 4), dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, ioff, name_b, name_len, rev,
                        nid_bytes, ids.get());
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, m.mark(c, 1));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, st + TP_ST_SUBX, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, R.get(st + TP_ST_SUBX, &info.n_subx).wait());
   info.n_records = nrec;
   info.n_targets = musc_tp::n_targets(nrec, rev);
-  info.n_subx = c->h_pinned[0];
   info.n_seq_bytes = nseq_bytes;
   info.n_id_bytes = nid_bytes;
   info.ms = m.ms(0, 1);

@@ -1,13 +1,11 @@
 // muscato_text.hpp -- the host side of the texts rendered on the device: results.txt (musc_results_*) and
 // the nonmatch FASTQ, genestats and readstats (musc_side_*).  Part of libmuscato_hip.so: included by
-// muscato_hip.hip after the context, the scans, the event marks (timed) and the loaders (drop_gene_text, drop_read_text).  Both families build
+// muscato_hip.hip after the context, what the drivers share (grid, the scans, tmp_alloc, KeyPasses, Readback), the event
+// marks (timed) and drop_gene_text / drop_read_text.  Both families build
 // record lists with 64-bit byte offsets and render ranges of them through one driver, text_range.
 #pragma once
 
 #include "text_stage.hpp"
-
-// the grid of a grid-stride kernel over k items
-static dim3 grid(uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); }
 
 // A text as musc_results_text and musc_side_text see it: n records, record i = bytes [off[i], off[i + 1]) of the text.
 struct TextDesc {
@@ -34,11 +32,9 @@ static int text_range(musc_ctx* c, const TextDesc& t, uint64_t rec0, uint64_t nr
   uint64_t bytes = 0;
   float ms = 0;
   int rc = timed(c, &ms, [&]() -> int {
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned, t.off + r0, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, t.off + r1, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint64_t o0 = c->h_pinned[0];
-    bytes = c->h_pinned[1] - o0;
+    uint64_t o0 = 0, o1 = 0;
+    HIPCHK(c, Readback(c->scalars, c->stream).get(t.off + r0, &o0).get(t.off + r1, &o1).wait());
+    bytes = o1 - o0;
     if (!dst) return 0;
     if (capacity < bytes)
       return fail(c, 2, "%s: capacity %llu < %llu bytes", t.name, (unsigned long long)capacity, (unsigned long long)bytes);
@@ -72,11 +68,9 @@ static int text_range(musc_ctx* c, const TextDesc& t, uint64_t rec0, uint64_t nr
   });
   if (rc) return rc;
   if (dst) {
-    uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned + 2);
-    *h_bad = 0;
-    HIPCHK(c, hipMemcpyAsync(h_bad, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (*h_bad) return fail(c, 11, "%s: %s", t.name, t.unfit);
+    uint32_t bad = 0;
+    HIPCHK(c, Readback(c->scalars, c->stream).get(c->d_flag.get(), &bad).wait());
+    if (bad) return fail(c, 11, "%s: %s", t.name, t.unfit);
     *t.ms_text += ms;
   }
   *nbytes = bytes;
@@ -228,15 +222,14 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   hipLaunchKernelGGL(k_results_flag, grid(n), B256, 0, c->stream, d_in, n, c->nreads, c->nseq, c->seq_off, c->res_rank, keep, c->d_flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, keep, excl, n, false, stmp))) return rc;
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned.get());
-  HIPCHK(c, hipMemcpyAsync(h32, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h32 + 1, excl + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h32 + 2, keep + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h32[0] & 1u)
+  Readback R(c->scalars, c->stream);
+  uint32_t verdict = 0;
+  uint64_t kept_before = 0, kept_last = 0;
+  HIPCHK(c, R.get(c->d_flag.get(), &verdict).get(excl + (n - 1), &kept_before).get(keep + (n - 1), &kept_last).wait());
+  if (verdict & 1u)
     return fail(c, 2, "musc_results_order: a tuple names a read, a target or a position outside the loaded reads and targets");
-  const bool read_major = !(h32[0] & 2u);
-  const uint64_t m = (uint64_t)h32[1] + h32[2];
+  const bool read_major = !(verdict & 2u);
+  const uint64_t m = kept_before + kept_last;
   if ((rc = ensure(c, c->res_hits, std::max<uint64_t>(m, 1)))) return rc;
   uint4* const out = reinterpret_cast<uint4*>(c->res_hits.p);
   if (m == 0) {
@@ -248,46 +241,25 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   hipLaunchKernelGGL(k_results_compact, grid(n), B256, 0, c->stream, d_in, keep, excl, n, a);
   HIPCHK(c, hipGetLastError());
 
-  uint64_t *k0 = nullptr, *k1 = nullptr;
-  uint32_t *p0 = nullptr, *p1 = nullptr;
-  void* tmp = nullptr;
-  size_t tmp_bytes = 0;
-  auto sort_bufs = [&](TmpBufs& T, uint64_t k) -> int {
-    HIPCHK(c, T.alloc(&k0, k * 8));
-    HIPCHK(c, T.alloc(&k1, k * 8));
-    HIPCHK(c, T.alloc(&p0, k * 4));
-    HIPCHK(c, T.alloc(&p1, k * 4));
-    tmp_bytes = 0;
-    for (unsigned end : {32u, 33u, 60u, 63u}) {
-      size_t tb = 0;
-      HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tb, k0, k1, p0, p1, (size_t)k, 0u, end, c->stream));
-      tmp_bytes = std::max(tmp_bytes, tb);
-    }
-    HIPCHK(c, T.alloc(&tmp, tmp_bytes));
-    return 0;
-  };
-  // one stable LSD pass over (key word, permutation) pairs
-  auto sort_pass = [&](const uint32_t* idx, uint64_t k, uint32_t what, unsigned end_bit) -> int {
-    hipLaunchKernelGGL(k_results_keys, grid(k), B256, 0, c->stream, a, idx, p0, k, what, c->res_rank, c->rd, c->rw, c->db2,
-                       c->db_has_x ? c->dbm2 : (const uint32_t*)nullptr, c->seq_off, k0);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, rocprim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, p0, p1, (size_t)k, 0u, end_bit, c->stream));
-    std::swap(p0, p1);
-    return 0;
+  static const char* const who = "musc_results_order";
+  // one stable pass of K over the k tuples a[idx[.]] (idx null: a itself) on the key word `what`
+  auto sort_pass = [&](KeyPasses& K, const uint32_t* idx, uint64_t k, uint32_t what, unsigned end_bit) {
+    return K.pass(end_bit, [&](const uint32_t* perm, uint64_t* keys) {
+      hipLaunchKernelGGL(k_results_keys, grid(k), B256, 0, c->stream, a, idx, perm, k, what, c->res_rank, c->rd, c->rw, c->db2,
+                         c->db_has_x ? c->dbm2 : (const uint32_t*)nullptr, c->seq_off, keys);
+    });
   };
 
   // ---- a list that is not read-major (a host list in any order): one sort on read_idx first
   if (!read_major) {
-    TmpBufs T;
+    KeyPasses K;
     uint4* a2 = nullptr;
-    if ((rc = sort_bufs(T, m))) return rc;
+    if ((rc = K.start(c, who, m, {32u, 33u, 60u, 63u}))) return rc;
     HIPCHK(c, B.alloc(&a2, m * 16));
-    hipLaunchKernelGGL(k_results_iota, grid(m), B256, 0, c->stream, p0, m);
+    if ((rc = sort_pass(K, nullptr, m, RES_KEY_READ, 32u))) return rc;
+    hipLaunchKernelGGL(k_results_gather, grid(m), B256, 0, c->stream, a, K.order(), m, a2);
     HIPCHK(c, hipGetLastError());
-    if ((rc = sort_pass(nullptr, m, RES_KEY_READ, 32u))) return rc;
-    hipLaunchKernelGGL(k_results_gather, grid(m), B256, 0, c->stream, a, p0, m, a2);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (T is released at the end of this scope)
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (K's buffers are released at the end of this scope)
     a = a2;
   }
 
@@ -299,27 +271,23 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   hipLaunchKernelGGL(k_results_segments, grid(m), B256, 0, c->stream, a, m, c->rd, c->rw, multi, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, multi, incl, m, true, stmp))) return rc;  // (m <= n: stmp is large enough)
-  HIPCHK(c, hipMemcpyAsync(h32, incl + (m - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, c->counters + CNT_SCRATCH, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t k = h32[0], maxlen = c->h_pinned[1];
+  uint64_t k = 0, maxlen = 0;
+  HIPCHK(c, R.get(incl + (m - 1), &k).get(c->counters + CNT_SCRATCH, &maxlen).wait());
   if (k == 0) {
     HIPCHK(c, hipMemcpyAsync(out, a, m * 16, hipMemcpyDeviceToDevice, c->stream));
   } else {
-    TmpBufs T;
-    if ((rc = sort_bufs(T, k))) return rc;
-    HIPCHK(c, T.alloc(&idx, k * 4));
+    KeyPasses K;
+    if ((rc = K.start(c, who, k, {32u, 33u, 60u, 63u})) || (rc = tmp_alloc(c, who, K.B, &idx, k * 4))) return rc;
     hipLaunchKernelGGL(k_results_idx, grid(m), B256, 0, c->stream, multi, incl, m, idx);
-    hipLaunchKernelGGL(k_results_iota, grid(k), B256, 0, c->stream, p0, k);
     HIPCHK(c, hipGetLastError());
     // least significant first: gene rank, the number word, the target words from last to first, the read
     const uint32_t nw = (uint32_t)((maxlen + RES_BASES_PER_WORD - 1) / RES_BASES_PER_WORD);
-    if ((rc = sort_pass(idx, k, RES_KEY_RANK, 32u))) return rc;
-    if ((rc = sort_pass(idx, k, RES_KEY_NUMBER, 60u))) return rc;
+    if ((rc = sort_pass(K, idx, k, RES_KEY_RANK, 32u))) return rc;
+    if ((rc = sort_pass(K, idx, k, RES_KEY_NUMBER, 60u))) return rc;
     for (uint32_t w = nw; w-- > 0;)
-      if ((rc = sort_pass(idx, k, RES_KEY_SPAN + w, 63u))) return rc;
-    if ((rc = sort_pass(idx, k, RES_KEY_READ, 32u))) return rc;
-    hipLaunchKernelGGL(k_results_place, grid(m), B256, 0, c->stream, a, multi, incl, idx, p0, m, out);
+      if ((rc = sort_pass(K, idx, k, RES_KEY_SPAN + w, 63u))) return rc;
+    if ((rc = sort_pass(K, idx, k, RES_KEY_READ, 32u))) return rc;
+    hipLaunchKernelGGL(k_results_place, grid(m), B256, 0, c->stream, a, multi, incl, idx, K.order(), m, out);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -330,10 +298,10 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   hipLaunchKernelGGL(k_results_len, grid(m + 1), B256, 0, c->stream, out, m, res_data(c), c->res_off.p);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, c->res_off.p, c->res_off.p, m + 1, stmp64))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->res_off.p + m, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint64_t res_bytes = 0;
+  HIPCHK(c, R.get(c->res_off.p + m, &res_bytes).wait());
   c->res_n = m;
-  c->res_bytes = c->h_pinned[0];
+  c->res_bytes = res_bytes;
   return 0;
 }
 
@@ -424,11 +392,8 @@ static int side_records(musc_ctx* c, int which, const uint32_t* flag, uint32_t* 
   int rc;
   if ((rc = scan_u32(c, flag, excl, n + 1, false, stmp))) return rc;
   if ((rc = scan_u64(c, len, len, n + 1, stmp64))) return rc;
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned.get());
-  HIPCHK(c, hipMemcpyAsync(h32, excl + n, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned + 1, len + n, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t nrec = h32[0], nbytes = c->h_pinned[1];
+  uint64_t nrec = 0, nbytes = 0;
+  HIPCHK(c, Readback(c->scalars, c->stream).get(excl + n, &nrec).get(len + n, &nbytes).wait());
   if ((rc = ensure(c, c->side_idx[which], std::max<uint64_t>(nrec, 1)))) return rc;
   if ((rc = ensure(c, c->side_off[which], nrec + 1))) return rc;
   hipLaunchKernelGGL(k_side_compact, grid(n + 1), dim3(256), 0, c->stream, flag, excl, len, n, c->side_idx[which].p, c->side_off[which].p);
@@ -442,9 +407,9 @@ static int side_prepare_impl(musc_ctx* c) {
   const dim3 B256(256);
   const uint64_t nreads = c->nreads, m = c->res_n, nnames = c->side_nnames;
   const uint4* const hits = reinterpret_cast<const uint4*>(c->res_hits.p);
-  uint32_t* const h32 = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   int rc;
   TmpBufs B;
+  Readback R(c->scalars, c->stream);
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
 
   // ---- tokens: once per read text
@@ -472,9 +437,9 @@ static int side_prepare_impl(musc_ctx* c) {
                        c->side_cnt.p, c->d_flag);
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipMemcpyAsync(h32 + 4, c->d_flag, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (h32[4]) return fail(c, 11, "musc_side_prepare: a read's text is longer than 4 GiB, or the ordered list no longer fits the reads and the gene text in hand");
+  uint32_t bad = 0;
+  HIPCHK(c, R.get(c->d_flag.get(), &bad).wait());
+  if (bad) return fail(c, 11, "musc_side_prepare: a read's text is longer than 4 GiB, or the ordered list no longer fits the reads and the gene text in hand");
   c->st.tokens_made();
   const SideData D = side_data(c);
 
@@ -496,9 +461,8 @@ static int side_prepare_impl(musc_ctx* c) {
   hipLaunchKernelGGL(k_side_rs_flag, grid(nreads + 1), B256, 0, c->stream, matched, c->side_tok.p, nreads, flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, flag, excl, nreads + 1, false, stmp))) return rc;
-  HIPCHK(c, hipMemcpyAsync(h32, excl + nreads, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t ncr = h32[0];
+  uint64_t ncr = 0;
+  HIPCHK(c, R.get(excl + nreads, &ncr).wait());
   if (ncr == 0 || m == 0) return 0;
   uint32_t *cr = nullptr, *head = nullptr, *incl = nullptr, *runof = nullptr;
   HIPCHK(c, B.alloc(&cr, ncr * 4));
@@ -509,9 +473,8 @@ static int side_prepare_impl(musc_ctx* c) {
   hipLaunchKernelGGL(k_side_rs_heads, grid(ncr), B256, 0, c->stream, cr, ncr, D, head);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, head, incl, ncr, true, stmp))) return rc;
-  HIPCHK(c, hipMemcpyAsync(h32, incl + (ncr - 1), 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t nruns = h32[0];
+  uint64_t nruns = 0;
+  HIPCHK(c, R.get(incl + (ncr - 1), &nruns).wait());
   if ((rc = ensure(c, c->side_runread, nruns))) return rc;
   if ((rc = ensure(c, c->side_first, nruns + 1))) return rc;
   if ((rc = ensure(c, c->side_off[MUSC_SIDE_READSTATS], nruns + 1))) return rc;
@@ -534,9 +497,8 @@ static int side_prepare_impl(musc_ctx* c) {
   hipLaunchKernelGGL(k_side_rs_uniq, grid(m + 1), B256, 0, c->stream, k1, m, flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, flag, excl, m + 1, false, stmp))) return rc;
-  HIPCHK(c, hipMemcpyAsync(h32, excl + m, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t nel = h32[0];
+  uint64_t nel = 0;
+  HIPCHK(c, R.get(excl + m, &nel).wait());
   if (nel < nruns) return fail(c, 11, "musc_side_prepare: a run of reads without an element");
   if ((rc = ensure(c, c->side_el, nel))) return rc;
   if ((rc = ensure(c, c->side_eloff, nel + 1))) return rc;
@@ -548,11 +510,11 @@ static int side_prepare_impl(musc_ctx* c) {
   hipLaunchKernelGGL(k_side_rs_lines, grid(nruns + 1), B256, 0, c->stream, c->side_first.p, c->side_eloff.p, nruns,
                      c->side_off[MUSC_SIDE_READSTATS].p);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->side_eloff.p + nel, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint64_t rs_bytes = 0;
+  HIPCHK(c, R.get(c->side_eloff.p + nel, &rs_bytes).wait());
   c->side_nel = nel;
   c->side_nrec[MUSC_SIDE_READSTATS] = nruns;
-  c->side_nbytes[MUSC_SIDE_READSTATS] = c->h_pinned[0];
+  c->side_nbytes[MUSC_SIDE_READSTATS] = rs_bytes;
   return 0;
 }
 

@@ -64,6 +64,8 @@ def test_sort_unique_edge_cases(eng):
     assert len(order) == 0 and ustart.tolist() == [0] and eng.n_reads == 0
     order, ustart = eng.sort_unique_reads([b"ACGT"])
     assert order.tolist() == [0] and ustart.tolist() == [0, 1]
+    order, ustart = eng.sort_unique_reads([b"ACGT"] * 2)
+    assert order.tolist() == [0, 1] and ustart.tolist() == [0, 2] and eng.n_reads == 1
     order, ustart = eng.sort_unique_reads([b"GATTACA"] * 7)
     assert order.tolist() == list(range(7)) and ustart.tolist() == [0, 7]
     # every key-word boundary (21 bases per word), X last, a prefix before its extensions

@@ -94,6 +94,18 @@ def test_gene_tie_break_and_absent_gene(eng):
     assert [ln.split(b"\t")[4] for ln in exp.split(b"\n")[:-1]] == [b"g1", b"g1", b"g10", b"g9"]
 
 
+def test_one_read_of_two_tuples(eng):
+    """The smallest list that goes through the key passes: one read, two tuples that tie up to the gene text, handed
+    over in line order and reversed."""
+    reads = [b"ACGTACGTAC"]
+    targets = [b"TTACGTACGTACTT", b"GGACGTACGTACGG"]
+    rests = rests_of(targets, [b"g2", b"g1"])
+    load(eng, reads, targets, rests, [b"1\tr"])
+    for hits in ([(0, 1, 2, 0), (0, 0, 2, 0)], [(0, 0, 2, 0), (0, 1, 2, 0)]):
+        exp = check(eng, reads, targets, rests, hits, [b"1\tr"])
+        assert [ln.split(b"\t")[4] for ln in exp.split(b"\n")[:-1]] == [b"g1", b"g2"]
+
+
 LENS = [1, 20, 21, 22, 42, 43, 63, 64, 100, 253, 300]
 
 
