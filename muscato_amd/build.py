@@ -73,6 +73,7 @@ CHECKS = {
     "ctx_state_check": ("ctx_state_check.cpp", ("host/check.hpp", "ctx_state.hpp", _API), 58_376_821, ()),
     "dev_mem_check": ("dev_mem_check.cpp", ("host/check.hpp", "dev_mem.hpp"), 521, ()),
     "index_plan_check": ("index_plan_check.cpp", ("host/check.hpp", "index_plan.hpp"), 567_030, ()),
+    "launch_plan_check": ("launch_plan_check.cpp", ("host/check.hpp", "launch_plan.hpp"), 113_302_959, ()),
     "load_plan_check": ("load_plan_check.cpp", ("host/check.hpp", "load_plan.hpp"), 35_240_767, ()),
     "maxmatches_plan_check": ("maxmatches_plan_check.cpp", ("host/check.hpp", "maxmatches_plan.hpp"), 548_365, ()),
     "read_names_plan_check": ("read_names_plan_check.cpp", ("host/check.hpp", "read_names_keys.hpp", "read_names_lanes.hpp", "read_names_plan.hpp"), 21_928_502, ()),
@@ -106,7 +107,7 @@ def build_checks(force: bool = False, verbose: bool = False, sanitize: bool = Fa
             subprocess.check_call(cmd)
         return out
 
-    with ThreadPoolExecutor(max_workers=len(CHECKS)) as ex:  # (one compiler each: eleven small programs)
+    with ThreadPoolExecutor(max_workers=len(CHECKS)) as ex:  # (one compiler each: twelve small programs)
         return dict(zip(CHECKS, ex.map(one, CHECKS)))
 
 

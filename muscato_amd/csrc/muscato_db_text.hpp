@@ -41,7 +41,7 @@ static int sz_decode_run(musc_ctx* c, const char* who, const musc_sz::Plan& plan
   HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), nch * sizeof(SzChunkDev), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_x2n, x2n.t, sizeof x2n.t, hipMemcpyHostToDevice, c->stream));
   const uint64_t slo = (uint64_t)((uintptr_t)d_stream & 15u);
-  hipLaunchKernelGGL(k_sz_decode, dim3((unsigned)std::min<uint64_t>(nch, 8 * MAX_GRID)), dim3(SZ_BLOCK), 0, c->stream,
+  hipLaunchKernelGGL(k_sz_decode, stage_grid(c, nch, musc_launch::CAP_CHUNKS), dim3(SZ_BLOCK), 0, c->stream,
                      d_stream - slo, slo, d_tab, (uint32_t)nch, d_x2n, d_dst, d_status);
   HIPCHK(c, hipGetLastError());
   std::vector<uint32_t> status(nch);
@@ -135,7 +135,7 @@ static int db_load_text_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
   HIPCHK(c, hipMemsetAsync(end, 0xFF, nlines * 8, c->stream));
   hipLaunchKernelGGL(k_dbt_lines, L.tgrid, dim3(FQ_BLOCK), 0, c->stream, L.base16, L.lo, L.hi, L.ntiles, L.cnt, nlines, L.virt, begin, end);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_dbt_lengths, grid(nlines + 1), dim3(256), 0, c->stream, d_text, ntext, nlines,
+  hipLaunchKernelGGL(k_dbt_lengths, grid(c, nlines + 1), dim3(256), 0, c->stream, d_text, ntext, nlines,
                      begin, end, len);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, len, len, nlines + 1, stmp2))) return rc;

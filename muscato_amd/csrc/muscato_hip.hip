@@ -41,6 +41,7 @@
 #include "ctx_state.hpp"
 #include "dev_mem.hpp"
 #include "index_plan.hpp"
+#include "launch_plan.hpp"
 #include "load_plan.hpp"
 
 #include "kernels_common.hpp"
@@ -160,6 +161,7 @@ struct EnvKnobs : musc_index::Knobs {
   uint64_t stage_bytes = 64ull << 20;  // MUSC_DEBUG_STAGE_BYTES: device staging of a text call for a host destination (tests)
   uint64_t stage_lines = 1ull << 20;   // MUSC_DEBUG_STAGE_LINES: record offsets such a call fetches to the host at a time (tests)
   long mm_heap_lds = 0;                // MUSC_DEBUG_MM_HEAP_LDS: LDS heap entries of k_mm_replay, lowered (tests; 0: not set)
+  uint64_t stage_grid = 0;             // MUSC_DEBUG_STAGE_GRID: the cap of every stage grid, lowered (tests; 0: not set)
   void read() {
     *this = EnvKnobs();
     auto is = [](const char* v, const char* w) { return v && !strcmp(v, w); };
@@ -184,6 +186,7 @@ struct EnvKnobs : musc_index::Knobs {
     if ((e = getenv("MUSC_DEBUG_STAGE_BYTES")) && atoll(e) > 0) stage_bytes = (uint64_t)atoll(e);
     if ((e = getenv("MUSC_DEBUG_STAGE_LINES")) && atoll(e) > 0) stage_lines = (uint64_t)atoll(e);
     if ((e = getenv("MUSC_DEBUG_MM_HEAP_LDS"))) mm_heap_lds = atol(e);
+    if ((e = getenv("MUSC_DEBUG_STAGE_GRID")) && atoll(e) > 0) stage_grid = std::min<uint64_t>((uint64_t)atoll(e), musc_launch::KNOB_MAX);
   }
 };
 
@@ -425,32 +428,30 @@ int ensure(musc_ctx* c, DevBuf<T>& b, uint64_t n, bool keep = false) {
 // with potentially larger n use grid-stride kernels instead
 inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
+// The grid of a persistent stage kernel (launch_plan.hpp): `wanted` blocks under the launch's cap, or under
+// MUSC_DEBUG_STAGE_GRID.  Every capped launch of the host drivers but the pass's own (muscato_pass.hpp) comes through here.
+static_assert(musc_launch::CAP_GRID == MAX_GRID && musc_launch::SCAN_TILE_ELEMS == SCAN_TILE, "launch_plan.hpp restates two constants of kernels_common.hpp");
+inline dim3 stage_grid(const musc_ctx* c, uint64_t wanted, uint64_t cap) { return dim3(musc_launch::stage_blocks(wanted, cap, c->env.stage_grid)); }
+
 // the grid of a grid-stride kernel over k items
-inline dim3 grid(uint64_t k) { return dim3(std::max(1u, std::min(nblk(k, 256), MAX_GRID))); }
+inline dim3 grid(const musc_ctx* c, uint64_t k) { return stage_grid(c, (k + 255) / 256, musc_launch::CAP_GRID); }
 
 // ---- what the host drivers share: the scans, tmp_alloc / staged, KeyPasses; Readback is dev_mem.hpp's
 
-uint64_t scan_tmp_elems(uint64_t n) {
-  uint64_t t = 0;
-  while (n > SCAN_TILE) {
-    n = (n + SCAN_TILE - 1) / SCAN_TILE;
-    t += (n + 8 + 3) & ~3ull;
-  }
-  return t + 8;
-}
+using musc_launch::scan_tmp_elems;  // (the scratch plan of the recursion below: launch_plan.hpp)
 
 // The host recursion of both scans: `top` scans the tiles of the level in hand and leaves their sums in tmp, which are
 // scanned in turn (exclusive, by `below`) and added back.
 template <class T>
 int scan_levels(musc_ctx* c, const T* in, T* out, uint64_t n, T* tmp, hipStream_t st, void (*top)(const T*, T*, T*, uint64_t),
                 void (*below)(const T*, T*, T*, uint64_t), void (*add)(T*, const T*, uint64_t)) {
-  const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+  const uint64_t nb = musc_launch::scan_tiles(n);
   if (nb > 0x7FFFFFFFull) return fail(c, 11, "scan too large");
   T* const sums = nb <= 1 ? nullptr : tmp;
   hipLaunchKernelGGL(top, dim3(sums ? (unsigned)nb : 1u), dim3(SCAN_BLOCK), 0, st, in, out, sums, n);
   HIPCHK(c, hipGetLastError());
   if (!sums) return 0;
-  const int rc = scan_levels(c, (const T*)sums, sums, nb, tmp + ((nb + 8 + 3) & ~3ull), st, below, below, add);
+  const int rc = scan_levels(c, (const T*)sums, sums, nb, tmp + musc_launch::scan_next_level(nb), st, below, below, add);
   if (rc) return rc;
   hipLaunchKernelGGL(add, dim3((unsigned)nb), dim3(SCAN_BLOCK), 0, st, out, (const T*)sums, n);
   HIPCHK(c, hipGetLastError());
@@ -511,7 +512,7 @@ struct KeyPasses {
       tmp_bytes = std::max(tmp_bytes, tb);
     }
     if ((rc = tmp_alloc(c, who, B, &tmp, tmp_bytes))) return rc;
-    hipLaunchKernelGGL(k_prep_iota, grid(n), dim3(256), 0, c->stream, p0, n);
+    hipLaunchKernelGGL(k_prep_iota, grid(c, n), dim3(256), 0, c->stream, p0, n);
     HIPCHK(c, hipGetLastError());
     return 0;
   }
@@ -846,7 +847,7 @@ static int match_partitions_run(musc_ctx* c, const musc_params* P, uint64_t* nhi
     if (nh) {
       if ((rc = ensure(c, c->pacc, seg[p] + nh, true))) break;
       HIPCHK(c, hipMemcpyAsync(c->pacc.p + seg[p], c->hits.p, nh * sizeof(musc_hit), hipMemcpyDeviceToDevice, c->stream));
-      hipLaunchKernelGGL(k_part_best, dim3(std::min(nblk(nh, 256), 4u * MAX_GRID)), dim3(256), 0, c->stream,
+      hipLaunchKernelGGL(k_part_best, stage_grid(c, nblk(nh, 256), musc_launch::CAP_TILES), dim3(256), 0, c->stream,
                          reinterpret_cast<const uint4*>(c->pacc.p + seg[p]), nh, c->pbest.p);
       HIPCHK(c, hipGetLastError());
     }
@@ -875,7 +876,7 @@ static int match_partitions_run(musc_ctx* c, const musc_params* P, uint64_t* nhi
     return rc;  // (scan_u64 borrows it too, in u64 units)
   HIPCHK(c, hipMemsetAsync(c->pcnt.p, 0, (nr + 1) * 8, c->stream));
   if (total_in) {
-    hipLaunchKernelGGL(k_part_count, dim3(std::min(nblk(total_in, 256), 4u * MAX_GRID)), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_part_count, stage_grid(c, nblk(total_in, 256), musc_launch::CAP_TILES), dim3(256), 0, c->stream,
                        reinterpret_cast<const uint4*>(c->pacc.p), total_in, c->pbest.p, mmtol, P->apply_mmtol,
                        reinterpret_cast<unsigned long long*>(c->pcnt.p));
     HIPCHK(c, hipGetLastError());
@@ -890,13 +891,13 @@ static int match_partitions_run(musc_ctx* c, const musc_params* P, uint64_t* nhi
     const uint64_t n = seg[p + 1] - seg[p];
     if (!n) continue;
     const uint4* const h = reinterpret_cast<const uint4*>(c->pacc.p + seg[p]);
-    const dim3 grid(std::min(nblk(n + 1, 256), 4u * MAX_GRID));
-    hipLaunchKernelGGL(k_part_flags, grid, dim3(256), 0, c->stream, h, n, c->pbest.p, mmtol, P->apply_mmtol, c->pflags.p);
+    const dim3 sgrid = stage_grid(c, nblk(n + 1, 256), musc_launch::CAP_TILES);
+    hipLaunchKernelGGL(k_part_flags, sgrid, dim3(256), 0, c->stream, h, n, c->pbest.p, mmtol, P->apply_mmtol, c->pflags.p);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u32(c, c->pflags.p, c->pflags.p, n + 1, false, c->pflags_tmp.p, c->stream))) return rc;
-    hipLaunchKernelGGL(k_part_head, grid, dim3(256), 0, c->stream, h, n, c->pflags.p, c->pcnt.p, c->padj.p);
+    hipLaunchKernelGGL(k_part_head, sgrid, dim3(256), 0, c->stream, h, n, c->pflags.p, c->pcnt.p, c->padj.p);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_part_scatter, grid, dim3(256), 0, c->stream, h, n, c->pflags.p, c->padj.p, c->pcnt.p,
+    hipLaunchKernelGGL(k_part_scatter, sgrid, dim3(256), 0, c->stream, h, n, c->pflags.p, c->padj.p, c->pcnt.p,
                        reinterpret_cast<uint4*>(c->hits.p), total, c->d_flag);
     HIPCHK(c, hipGetLastError());
   }
@@ -1043,7 +1044,7 @@ int musc_hits_copy_packed(musc_ctx* c, uint64_t* dst, uint64_t capacity, int dst
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
   const uint4* const hits = reinterpret_cast<const uint4*>(c->hits.p);
   auto pack = [&](uint64_t t0, uint64_t t1) {
-    hipLaunchKernelGGL(k_pack_hits, grid(t1 - t0), dim3(256), 0, c->stream, hits + t0, t1 - t0,
+    hipLaunchKernelGGL(k_pack_hits, grid(c, t1 - t0), dim3(256), 0, c->stream, hits + t0, t1 - t0,
                        read_base, b, out + t0, c->d_flag);
   };
   uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned.get());
@@ -1094,7 +1095,7 @@ int musc_hits_copy_compact(musc_ctx* c, uint32_t* words, uint64_t words_cap, uin
   uint32_t* const h_bad = reinterpret_cast<uint32_t*>(c->h_pinned.get());
   if (dst_on_device) {
     if (c->nhits) {
-      hipLaunchKernelGGL(k_pack_compact, grid(c->nhits), dim3(256), 0, c->stream, hits, c->nhits,
+      hipLaunchKernelGGL(k_pack_compact, grid(c, c->nhits), dim3(256), 0, c->stream, hits, c->nhits,
                          b, dw, dc, c->d_flag);
       HIPCHK(c, hipGetLastError());
     }
@@ -1104,7 +1105,7 @@ int musc_hits_copy_compact(musc_ctx* c, uint32_t* words, uint64_t words_cap, uin
     // the words chunk by chunk, then the count bytes: a count is final only when the chunk that holds the head of its
     // read's run has been packed, and the counts are the smaller copy
     int rc = download_chunks(c, c->nhits, 4, dw, words, [&](uint64_t t0, uint64_t t1) {
-      hipLaunchKernelGGL(k_pack_compact_range, grid(t1 - t0), dim3(256), 0, c->stream, hits,
+      hipLaunchKernelGGL(k_pack_compact_range, grid(c, t1 - t0), dim3(256), 0, c->stream, hits,
                          c->nhits, t0, t1, b, dw, dc, c->d_flag);
     });
     const int rc_end = download_end(c, h_bad, counts, dc, c->nreads);
@@ -1138,7 +1139,7 @@ int musc_hits_unpack(musc_ctx* c, const uint64_t* src, uint64_t n, int on_device
     return 0;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(k_unpack_hits, grid(n), dim3(256), 0, c->stream, src, n, b,
+  hipLaunchKernelGGL(k_unpack_hits, grid(c, n), dim3(256), 0, c->stream, src, n, b,
                      reinterpret_cast<uint4*>(dst));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1413,7 +1414,7 @@ int musc_gather_rccl(musc_ctx* const* ctxs, int n, const uint64_t* read_base, mu
   for (int i = 0; i < n; i++) {
     const uint64_t base = read_base ? read_base[i] : 0;
     if (!base || !ctxs[i]->nhits) continue;
-    hipLaunchKernelGGL(k_rebase_reads, grid(ctxs[i]->nhits), dim3(256), 0, c0->stream,
+    hipLaunchKernelGGL(k_rebase_reads, grid(c0, ctxs[i]->nhits), dim3(256), 0, c0->stream,
                        reinterpret_cast<uint4*>(c0->gathered.p + off[i]), ctxs[i]->nhits, (uint32_t)base);
     HIPCHK(c0, hipGetLastError());
   }

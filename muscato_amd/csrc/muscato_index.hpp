@@ -104,11 +104,11 @@ int build_index_table(musc_ctx* c, int bits, uint64_t bucket_b, bool cursors, bo
 template <class BT>
 int build_window_index(musc_ctx* c, const mi::Resident& w, const IdxRange& R) {
   const uint64_t nb = 1ull << w.bits;
-  const unsigned blocks = (unsigned)std::min<uint64_t>((R.b1 - R.b0 + 255) / 256, 1u << 22);
+  const dim3 blocks = stage_grid(c, (R.b1 - R.b0 + 255) / 256, musc_launch::CAP_INDEX);
   auto T = [c] { return static_cast<BT*>(c->idx_T.p); };
   auto index = [&](auto filling, uint4* E) {
     if (R.b1 > R.b0)
-      hipLaunchKernelGGL((k_index<decltype(filling)::value, BT>), dim3(blocks), dim3(256), 0, c->stream, c->db2, c->dbm2, c->seq_off, c->nseq,
+      hipLaunchKernelGGL((k_index<decltype(filling)::value, BT>), blocks, dim3(256), 0, c->stream, c->db2, c->dbm2, c->seq_off, c->nseq,
                          R.b0, R.b1, w.ww, w.bits, w.direct, c->wide, T(), E);
   };
   return build_index_table(
@@ -130,14 +130,14 @@ int build_window_index(musc_ctx* c, const mi::Resident& w, const IdxRange& R) {
 int build_ctx_index(musc_ctx* c, const mi::Resident& w, const IdxRange& R) {
   const uint64_t nb = 1ull << w.bits;
   const bool wide = w.kind == mi::K_CTXW;
-  const unsigned blocks = (unsigned)std::min<uint64_t>((R.b1 - R.b0 + 255) / 256, 1u << 22);
+  const dim3 blocks = stage_grid(c, (R.b1 - R.b0 + 255) / 256, musc_launch::CAP_INDEX);
   // a database with X: its windows with an X stay out, entries whose context touches one are flagged
   const uint32_t* const xm2 = c->db_has_x ? c->dbm2 : nullptr;
   const uint32_t* const xbl = c->db_has_x ? c->dbx : nullptr;
   auto T = [c] { return static_cast<CtxBucket*>(c->ctx_T.p); };
   auto index = [&](auto kern, void* E, uint32_t* cursor) {
     if (R.b1 > R.b0)
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases, R.b0, R.b1, w.ww,
+      hipLaunchKernelGGL(kern, blocks, dim3(256), 0, c->stream, c->db2, xm2, xbl, c->seq_off, c->nseq, c->nbases, R.b0, R.b1, w.ww,
                          w.bits, w.direct, w.CL, T(), E, cursor);
   };
   return build_index_table(

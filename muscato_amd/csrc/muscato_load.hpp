@@ -16,7 +16,7 @@
 // read (k_max_len), read back together, with one wait.
 static int offsets_census(musc_ctx* c, const uint64_t* d_off, uint64_t n, uint64_t* first, uint64_t* last, uint64_t* maxlen) {
   HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_max_len, grid(n), dim3(256), 0, c->stream, d_off, n, c->counters + CNT_SCRATCH);
+  hipLaunchKernelGGL(k_max_len, grid(c, n), dim3(256), 0, c->stream, d_off, n, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, Readback(c->scalars, c->stream).get(c->counters + CNT_SCRATCH, maxlen).get(d_off, first).get(d_off + n, last).wait());
   return 0;
@@ -38,7 +38,7 @@ static int text_lines(musc_ctx* c, const char* who, TmpBufs& B, const unsigned c
   L->hi = L->lo + nbytes;
   L->base16 = d_text - L->lo;
   L->ntiles = (L->hi + FQ_TILE_BYTES - 1) / FQ_TILE_BYTES;
-  L->tgrid = dim3((unsigned)std::min<uint64_t>(L->ntiles, 4 * MAX_GRID));
+  L->tgrid = stage_grid(c, L->ntiles, musc_launch::CAP_TILES);
   uint64_t* stmp = nullptr;
   int rc = 0;
   if ((rc = tmp_alloc(c, who, B, &L->cnt, (L->ntiles + 1) * 8)) || (rc = tmp_alloc(c, who, B, &stmp, scan_tmp_elems(L->ntiles + 1) * 8)))

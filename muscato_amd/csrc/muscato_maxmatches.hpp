@@ -16,7 +16,7 @@ static int hot_probes_device(musc_ctx* c, DevPtr<uint2>* out, uint64_t* found) {
     hipError_t e = hipMemsetAsync(c->counters + CNT_BATCH, 0, 8, c->stream);
     if (e == hipSuccess) {
       by_rw(c->rw, [&](auto r) {
-        hipLaunchKernelGGL((k_hot_probes<decltype(r)::value>), grid(c->nreads), dim3(256), 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp,
+        hipLaunchKernelGGL((k_hot_probes<decltype(r)::value>), grid(c, c->nreads), dim3(256), 0, c->stream, c->rd, c->rdm, c->nreads, c->rw, c->d_pp,
                            c->block_table.p, c->last_max_matches, d_out, cap, c->counters + CNT_BATCH);
       });
       e = hipGetLastError();
@@ -105,14 +105,14 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
     HIPCHK(c, A.alloc(&heads, np * 4));
     HIPCHK(c, A.alloc(&excl, np * 4));
     HIPCHK(c, A.alloc(&stmp, scan_tmp_elems(np) * 4));
-    hipLaunchKernelGGL(k_mm_heads, grid(np), B256, 0, c->stream, D, sorted, np, heads);
+    hipLaunchKernelGGL(k_mm_heads, grid(c, np), B256, 0, c->stream, D, sorted, np, heads);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u32(c, heads, excl, np, false, stmp))) return rc;
     uint32_t heads_before = 0, head_last = 0;
     HIPCHK(c, R.get(excl + (np - 1), &heads_before).get(heads + (np - 1), &head_last).wait());
     const uint32_t nb = heads_before + head_last;
     HIPCHK(c, A.alloc(&blocks, (uint64_t)nb * 8));
-    hipLaunchKernelGGL(k_mm_blocks, grid(np), B256, 0, c->stream, sorted, heads, excl, np, blocks);
+    hipLaunchKernelGGL(k_mm_blocks, grid(c, np), B256, 0, c->stream, sorted, heads, excl, np, blocks);
     HIPCHK(c, hipGetLastError());
 
     // ---- 2. pairs: every (tuple, window) finds its block; the blocks count what their windows emit
@@ -127,9 +127,9 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
     HIPCHK(c, hipMemsetAsync(cnt, 0, (uint64_t)nb * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(fill, 0, (uint64_t)nb * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_mm_pairs, grid(N * (uint64_t)W), B256, 0, c->stream, D, hits, N, blocks, nb, words, cnt);
+    hipLaunchKernelGGL(k_mm_pairs, grid(c, N * (uint64_t)W), B256, 0, c->stream, D, hits, N, blocks, nb, words, cnt);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_mm_sizes, grid((uint64_t)nb + 1), B256, 0, c->stream, cnt, nb, (uint32_t)P.max_matches, sizes, c->counters + CNT_SCRATCH);
+    hipLaunchKernelGGL(k_mm_sizes, grid(c, (uint64_t)nb + 1), B256, 0, c->stream, cnt, nb, (uint32_t)P.max_matches, sizes, c->counters + CNT_SCRATCH);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, sizes, off, (uint64_t)nb + 1, tmp64))) return rc;
     uint64_t M = 0;
@@ -144,7 +144,7 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
       uint2 *pairs = nullptr, *psorted = nullptr, *gheap = nullptr;
       HIPCHK(c, B.alloc(&pairs, M * 8));
       HIPCHK(c, A.alloc(&psorted, M * 8));
-      hipLaunchKernelGGL(k_mm_fill, grid(N * (uint64_t)W), B256, 0, c->stream, words, N, W, sizes, off, fill, pairs);
+      hipLaunchKernelGGL(k_mm_fill, grid(c, N * (uint64_t)W), B256, 0, c->stream, words, N, W, sizes, off, fill, pairs);
       HIPCHK(c, hipGetLastError());
       if ((rc = mm_sort(c, B, pairs, psorted, M, MmPairLess{D, hits, blocks}))) return rc;
       // ---- 4. replay
@@ -153,7 +153,7 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
       if (!in_lds && P.match_mode == 0) HIPCHK(c, B.alloc(&gheap, M * 8));
       hipEvent_t e0 = pool_event(c), e1 = pool_event(c);
       if (e0) (void)hipEventRecord(e0, c->stream);
-      hipLaunchKernelGGL(k_mm_replay, dim3(std::min<uint32_t>(nb, 65536u)), dim3(64), 0, c->stream, hits, psorted, blocks, sizes, off, nb, W,
+      hipLaunchKernelGGL(k_mm_replay, stage_grid(c, nb, musc_launch::CAP_REPLAY), dim3(64), 0, c->stream, hits, psorted, blocks, sizes, off, nb, W,
                          (uint32_t)P.max_matches, P.match_mode == 1 ? 1 : 0, lds_cap, gheap, words);
       HIPCHK(c, hipGetLastError());
       if (e1) (void)hipEventRecord(e1, c->stream);
@@ -173,10 +173,10 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
     HIPCHK(c, B.alloc(&best, c->nreads * 4));
     HIPCHK(c, hipMemsetAsync(best, 0xFF, c->nreads * 4, c->stream));
   }
-  hipLaunchKernelGGL(k_mm_survive, grid(N), B256, 0, c->stream, hits, N, words, W, sizes, apply_mmtol ? 1 : 0, flags, best);
+  hipLaunchKernelGGL(k_mm_survive, grid(c, N), B256, 0, c->stream, hits, N, words, W, sizes, apply_mmtol ? 1 : 0, flags, best);
   HIPCHK(c, hipGetLastError());
   if (apply_mmtol) {
-    hipLaunchKernelGGL(k_mm_best, grid(N), B256, 0, c->stream, hits, N, best, (uint32_t)P.mmtol, flags);
+    hipLaunchKernelGGL(k_mm_best, grid(c, N), B256, 0, c->stream, hits, N, best, (uint32_t)P.mmtol, flags);
     HIPCHK(c, hipGetLastError());
   }
   if ((rc = scan_u32(c, flags, excl, N, false, stmp))) return rc;
@@ -185,7 +185,7 @@ int mm_apply_impl(musc_ctx* c, const musc_params& P, int apply_mmtol, uint64_t* 
   const uint64_t m = kept_before + kept_last;
   uint4* out = nullptr;
   HIPCHK(c, B.alloc(&out, m * 16));
-  hipLaunchKernelGGL(k_mm_compact, grid(N), B256, 0, c->stream, hits, N, flags, excl, out);
+  hipLaunchKernelGGL(k_mm_compact, grid(c, N), B256, 0, c->stream, hits, N, flags, excl, out);
   HIPCHK(c, hipGetLastError());
   // from here on the list changes.  (The survivors go back into the pass's own buffer: a captured graph of the pass
   // holds its address.)

@@ -143,7 +143,7 @@ static int reads_sort_unique_dev(musc_ctx* c, const char* who, const unsigned ch
   KeyPasses K;
   if ((rc = K.start(c, who, n, {63u}))) return rc;
   for (uint32_t w = nw; w-- > 0 && !rc;)
-    rc = K.pass(63u, [&](const uint32_t* perm, uint64_t* keys) { hipLaunchKernelGGL(k_prep_keys, grid(n), dim3(256), 0, c->stream, d_s, d_off, perm, n, w, keys); });
+    rc = K.pass(63u, [&](const uint32_t* perm, uint64_t* keys) { hipLaunchKernelGGL(k_prep_keys, grid(c, n), dim3(256), 0, c->stream, d_s, d_off, perm, n, w, keys); });
   if (rc) return rc;
   const uint32_t* const p0 = K.order();
 
@@ -153,10 +153,10 @@ static int reads_sort_unique_dev(musc_ctx* c, const char* who, const unsigned ch
       (rc = tmp_alloc(c, who, B, &stmp, scan_tmp_elems(n) * 4)) || (rc = tmp_alloc(c, who, B, &d_ustart, (n + 1) * 4)) ||
       (rc = tmp_alloc(c, who, B, &d_uhead, n * 4)))
     return rc;
-  hipLaunchKernelGGL(k_prep_heads, grid(n), dim3(256), 0, c->stream, d_s, d_off, p0, n, head);
+  hipLaunchKernelGGL(k_prep_heads, grid(c, n), dim3(256), 0, c->stream, d_s, d_off, p0, n, head);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, head, incl, n, true, stmp))) return rc;
-  hipLaunchKernelGGL(k_prep_starts, grid(n), dim3(256), 0, c->stream, head, incl, n, d_ustart, d_uhead, p0);
+  hipLaunchKernelGGL(k_prep_starts, grid(c, n), dim3(256), 0, c->stream, head, incl, n, d_ustart, d_uhead, p0);
   HIPCHK(c, hipGetLastError());
   uint64_t nu = 0;
   HIPCHK(c, Readback(c->scalars, c->stream).get(incl + (n - 1), &nu).wait());
@@ -280,7 +280,7 @@ static int fastq_prep_run(musc_ctx* c, const char* who, const char* text, uint64
                        name_begin, name_end, seq_end);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemsetAsync(st, 0, 16, c->stream));
-    hipLaunchKernelGGL(k_fq_records, grid(nrec + 1), dim3(256), 0, c->stream, d_text, nrec,
+    hipLaunchKernelGGL(k_fq_records, grid(c, nrec + 1), dim3(256), 0, c->stream, d_text, nrec,
                        name_begin, name_end, seq_end, min_len, max_len, kidx, len, name_len, st);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u32(c, kidx, kidx, nrec + 1, false, stmp32)) || (rc = scan_u64(c, len, len, nrec + 1, stmp64))) return rc;
@@ -311,7 +311,7 @@ static int fastq_prep_run(musc_ctx* c, const char* who, const char* text, uint64
   if ((rc = tmp_alloc(c, who, S, &prep, total + 64)) || (rc = tmp_alloc(c, who, S, &prep_off, (nkept + 1) * 8)) ||
       (rc = tmp_alloc(c, who, P, &o64, 2 * nkept * 8)) || (rc = tmp_alloc(c, who, P, &o32, 2 * nkept * 4)))
     return rc;
-  hipLaunchKernelGGL(k_fq_gather, dim3(std::min(nblk(nrec, 256 / FQ_GROUP), 4 * MAX_GRID)), dim3(256), 0, c->stream, d_text, nbytes,
+  hipLaunchKernelGGL(k_fq_gather, stage_grid(c, nblk(nrec, 256 / FQ_GROUP), musc_launch::CAP_TILES), dim3(256), 0, c->stream, d_text, nbytes,
                      nrec, lines, lines + (nrec + 1), kidx, len, name_len, prep, prep_off, o64, o64 + nkept, o32, o32 + nkept);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out->name_off, o64, nkept * 8, hipMemcpyDeviceToHost, c->stream));

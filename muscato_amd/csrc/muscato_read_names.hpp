@@ -34,11 +34,11 @@ static int rn_rank(musc_ctx* c, const char* who, const RnInput& in, uint32_t* ra
   if ((rc = tmp_alloc(c, who, B, &flag, (n + 1) * 4)) || (rc = tmp_alloc(c, who, B, &excl, (n + 1) * 4)) ||
       (rc = tmp_alloc(c, who, B, &stmp, scan_tmp_elems(n + 1) * 4)) || (rc = tmp_alloc(c, who, B, &max_clip, 4)))
     return rc;
-  hipLaunchKernelGGL(k_rn_gid, grid(n), B256, 0, c->stream, in.ustart, (uint32_t)in.nu, n, gid);
+  hipLaunchKernelGGL(k_rn_gid, grid(c, n), B256, 0, c->stream, in.ustart, (uint32_t)in.nu, n, gid);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemsetAsync(flag + n, 0, 4, c->stream));
   HIPCHK(c, hipMemsetAsync(max_clip, 0, 4, c->stream));
-  hipLaunchKernelGGL(k_rn_rank, grid(n), B256, 0, c->stream, in.rd, in.N, in.order, in.ustart, gid, ranked, flag);
+  hipLaunchKernelGGL(k_rn_rank, grid(c, n), B256, 0, c->stream, in.rd, in.N, in.order, in.ustart, gid, ranked, flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, flag, excl, n + 1, false, stmp))) return rc;
   Readback R(c->scalars, c->stream);
@@ -52,15 +52,15 @@ static int rn_rank(musc_ctx* c, const char* who, const RnInput& in, uint32_t* ra
   uint32_t* place = nullptr;
   KeyPasses K;
   if ((rc = tmp_alloc(c, who, B, &pairs, np * 8)) || (rc = tmp_alloc(c, who, B, &place, np * 4)) || (rc = K.start(c, who, np, {64u}))) return rc;
-  hipLaunchKernelGGL(k_rn_pairs, grid(n), B256, 0, c->stream, flag, excl, in.order, gid, in.N, pairs, place, max_clip);
+  hipLaunchKernelGGL(k_rn_pairs, grid(c, n), B256, 0, c->stream, flag, excl, in.order, gid, in.N, pairs, place, max_clip);
   HIPCHK(c, hipGetLastError());
   uint32_t clip = 0;
   HIPCHK(c, R.get(max_clip, &clip).wait());
   const uint32_t W = musc_rn::key_words(clip);  // (clamped: at most CMP_WORDS whatever came back)
   for (uint32_t pass = 0; pass < W + 2 && !rc; pass++)
-    rc = K.pass(64u, [&](const uint32_t* ord, uint64_t* keys) { hipLaunchKernelGGL(k_rn_keys, grid(np), B256, 0, c->stream, in.rd, in.N, pairs, ord, np, pass, W, keys); });
+    rc = K.pass(64u, [&](const uint32_t* ord, uint64_t* keys) { hipLaunchKernelGGL(k_rn_keys, grid(c, np), B256, 0, c->stream, in.rd, in.N, pairs, ord, np, pass, W, keys); });
   if (rc) return rc;
-  hipLaunchKernelGGL(k_rn_unpairs, grid(np), B256, 0, c->stream, pairs, K.order(), place, np, ranked);
+  hipLaunchKernelGGL(k_rn_unpairs, grid(c, np), B256, 0, c->stream, pairs, K.order(), place, np, ranked);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (the temporaries go with B)
   *n_pairs = np;
@@ -126,13 +126,13 @@ extern "C" int musc_reads_names_order(musc_ctx* c, const char* text, uint64_t nb
 // ---------------------------------------------------------------- the whole stage behind the FASTQ prep
 
 static void launch_rn_lines(musc_ctx* c, uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) {
-  const unsigned blocks = (unsigned)std::min<uint64_t>(bytes / 256 + 1, 4 * MAX_GRID);
+  const dim3 blocks = stage_grid(c, bytes / 256 + 1, musc_launch::CAP_TILES);
   const musc_rn::Reads S{c->rd, c->reads_have_x ? c->rdm.get() : nullptr, c->rw};
-  hipLaunchKernelGGL(k_rn_lines, dim3(blocks), dim3(256), 0, c->stream, S, c->res_ttext.get(), c->res_toff.get(), c->rn_loff.get(), r0, r1, out);
+  hipLaunchKernelGGL(k_rn_lines, blocks, dim3(256), 0, c->stream, S, c->res_ttext.get(), c->res_toff.get(), c->rn_loff.get(), r0, r1, out);
 }
 static void launch_rn_copy(musc_ctx* c, uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) {
-  const unsigned blocks = (unsigned)std::min<uint64_t>(bytes / 256 + 1, 4 * MAX_GRID);
-  hipLaunchKernelGGL(k_rn_copy, dim3(blocks), dim3(256), 0, c->stream, c->res_ttext.get(), c->res_toff.get(), r0, r1, out);
+  const dim3 blocks = stage_grid(c, bytes / 256 + 1, musc_launch::CAP_TILES);
+  hipLaunchKernelGGL(k_rn_copy, blocks, dim3(256), 0, c->stream, c->res_ttext.get(), c->res_toff.get(), r0, r1, out);
 }
 
 // Behind the sort + collapse of fastq_prep_run, the text still resident: rank, measure, size, and render the records
@@ -171,7 +171,7 @@ static int read_names_stage(musc_ctx* c, const char* who, const unsigned char* d
         (r = tmp_alloc(c, who, B, &gid, n * 4)) || (r = tmp_alloc(c, who, B, &meta, n * 4)) || (r = tmp_alloc(c, who, B, &tstart, n * 4)) ||
         (r = tmp_alloc(c, who, B, &gsum, nu * 4)) || (r = tmp_alloc(c, who, B, &stmp, scan_tmp_elems(nu + 1) * 8)))
       return r;
-    hipLaunchKernelGGL(k_rn_measure, grid(n), B256, 0, c->stream, in.rd, in.N, meta);
+    hipLaunchKernelGGL(k_rn_measure, grid(c, n), B256, 0, c->stream, in.rd, in.N, meta);
     HIPCHK(c, hipGetLastError());
     uint32_t passes = 0;
     if ((r = rn_rank(c, who, in, ranked, gid, &info->n_pairs, &passes))) return r;
@@ -180,7 +180,7 @@ static int read_names_stage(musc_ctx* c, const char* who, const unsigned char* d
     uint64_t *roff = c->res_toff.get(), *loff = c->rn_loff.get();
     HIPCHK(c, hipMemsetAsync(roff + nu, 0, 8, c->stream));
     HIPCHK(c, hipMemsetAsync(loff + nu, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_rn_sizes, grid(nu), B256, 0, c->stream, ranked, in.ustart, meta, d_seq_len, nu, tstart, gsum, roff, loff);
+    hipLaunchKernelGGL(k_rn_sizes, grid(c, nu), B256, 0, c->stream, ranked, in.ustart, meta, d_seq_len, nu, tstart, gsum, roff, loff);
     HIPCHK(c, hipGetLastError());
     if ((r = scan_u64(c, roff, roff, nu + 1, stmp)) || (r = scan_u64(c, loff, loff, nu + 1, stmp))) return r;
     HIPCHK(c, Readback(c->scalars, c->stream).get(roff + nu, &info->text_bytes).get(loff + nu, &info->line_bytes).wait());
@@ -190,8 +190,8 @@ static int read_names_stage(musc_ctx* c, const char* who, const unsigned char* d
     // ---- the records, where musc_results_set_read_text would have put them
     HIPCHK(c, c->res_ttext.alloc(info->text_bytes + 16));
     const musc_rn::Groups G{ranked, in.ustart, meta, tstart, gsum};
-    const unsigned blocks = (unsigned)std::min<uint64_t>(info->text_bytes / 256 + 1, 4 * MAX_GRID);
-    hipLaunchKernelGGL(k_rn_records, dim3(blocks), B256, 0, c->stream, in.rd, in.N, G, roff, (uint64_t)0, nu,
+    const dim3 blocks = stage_grid(c, info->text_bytes / 256 + 1, musc_launch::CAP_TILES);
+    hipLaunchKernelGGL(k_rn_records, blocks, B256, 0, c->stream, in.rd, in.N, G, roff, (uint64_t)0, nu,
                        reinterpret_cast<unsigned char*>(c->res_ttext.get()));
     HIPCHK(c, hipGetLastError());
     if (!(info->ranked = (uint32_t*)malloc(n * 4))) return fail(c, 7, "out of host memory for the ranked members");

@@ -76,13 +76,13 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
     HIPCHK(c, hipMemsetAsync(ltab, 0, nlines * 8, c->stream));
     hipLaunchKernelGGL(k_tp_lines, L.tgrid, dim3(FQ_BLOCK), 0, c->stream, L.base16, L.lo, L.hi, L.ntiles, L.cnt, nlines, L.virt, begin, eol, ftab, ltab);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_tp_classify<false>, grid(nlines + 1), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol, ftab, ltab,
+    hipLaunchKernelGGL(k_tp_classify<false>, grid(c, nlines + 1), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol, ftab, ltab,
                        (uint64_t*)nullptr, (uint64_t*)nullptr, st);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, R.get(st + TP_ST_STOP, &info.stop_line).wait());
     nrec = std::min<uint64_t>(info.stop_line, nlines);  // the records are the lines in front of the first stop line
     if (musc_tp::refused(nrec, rev)) return fail(c, 12, "%s: %llu targets do not fit 32-bit target numbers", who, (unsigned long long)musc_tp::n_targets(nrec, rev));
-    hipLaunchKernelGGL(k_tp_text_recs, grid(nrec + 1), dim3(256), 0, c->stream, nrec, begin, eol, ftab, ltab, a);
+    hipLaunchKernelGGL(k_tp_text_recs, grid(c, nrec + 1), dim3(256), 0, c->stream, nrec, begin, eol, ftab, ltab, a);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, a, a, nrec + 1, stmp))) return rc;
     fo = a;
@@ -95,7 +95,7 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
     hipLaunchKernelGGL(k_tp_lines, L.tgrid, dim3(FQ_BLOCK), 0, c->stream, L.base16, L.lo, L.hi, L.ntiles, L.cnt, nlines, L.virt, begin, eol,
                        (unsigned long long*)nullptr, (unsigned long long*)nullptr);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_tp_classify<true>, grid(nlines + 1), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol,
+    hipLaunchKernelGGL(k_tp_classify<true>, grid(c, nlines + 1), dim3(256), 0, c->stream, d_text, nbytes, nlines, begin, eol,
                        (const unsigned long long*)nullptr, (const unsigned long long*)nullptr, hdr, bases, st);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, hdr, hdr, nlines + 1, stmp)) || (rc = scan_u64(c, bases, bases, nlines + 1, stmp))) return rc;
@@ -110,12 +110,12 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
         (rc = tmp_alloc(c, who, B2, &src0, ngroups * 8)) || (rc = tmp_alloc(c, who, B2, &name_b, ngroups * 8)) ||
         (rc = tmp_alloc(c, who, B2, &name_len, ngroups * 8)))
       return rc;
-    hipLaunchKernelGGL(k_tp_hl, grid(nlines), dim3(256), 0, c->stream, nlines, hdr, ngroups, hl);
+    hipLaunchKernelGGL(k_tp_hl, grid(c, nlines), dim3(256), 0, c->stream, nlines, hdr, ngroups, hl);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_tp_groups, grid(ngroups + 1), dim3(256), 0, c->stream, ngroups, hl, S, kept, a);
+    hipLaunchKernelGGL(k_tp_groups, grid(c, ngroups + 1), dim3(256), 0, c->stream, ngroups, hl, S, kept, a);
     HIPCHK(c, hipGetLastError());
     if ((rc = scan_u64(c, kept, kept, ngroups + 1, stmp)) || (rc = scan_u64(c, a, a, ngroups + 1, stmp))) return rc;
-    hipLaunchKernelGGL(k_tp_compact, grid(ngroups + 1), dim3(256), 0, c->stream, ngroups, kept, a, hl, S, begin, eol, fo, src0, name_b,
+    hipLaunchKernelGGL(k_tp_compact, grid(c, ngroups + 1), dim3(256), 0, c->stream, ngroups, kept, a, hl, S, begin, eol, fo, src0, name_b,
                        name_len, st);
     HIPCHK(c, hipGetLastError());
     uint64_t kept0 = 0;
@@ -127,7 +127,7 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
   // ---- the id lines' lengths and offsets; the sizes of both texts
   uint64_t* ioff = nullptr;
   if ((rc = tmp_alloc(c, who, B2, &ioff, (nrec + 1) * 8))) return rc;
-  hipLaunchKernelGGL(k_tp_idlen, grid(nrec + 1), dim3(256), 0, c->stream, nrec, fo, name_len, rev, ioff);
+  hipLaunchKernelGGL(k_tp_idlen, grid(c, nrec + 1), dim3(256), 0, c->stream, nrec, fo, name_len, rev, ioff);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, ioff, ioff, nrec + 1, stmp))) return rc;
   uint64_t fwd_bytes = 0, nid_bytes = 0;
@@ -139,7 +139,7 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
   DevPtr<unsigned char> seq, ids;
   if ((rc = tp_out_alloc(c, who, seq, nseq_bytes)) || (rc = tp_out_alloc(c, who, ids, nid_bytes))) return rc;
   if (nseq_bytes) {
-    const dim3 g = grid((nseq_bytes + 3) / 4);
+    const dim3 g = grid(c, (nseq_bytes + 3) / 4);
     if (fasta)
       hipLaunchKernelGGL(k_tp_seq<true>, g, dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, src0, S, begin, nlines, mult, nseq_bytes, seq.get(), st);
     else
@@ -151,7 +151,7 @@ static int targets_prep_run(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, 
     }
   }
   if (nid_bytes) {
-    hipLaunchKernelGGL(k_tp_ids, grid((nid_bytes + 3) / 4), dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, ioff, name_b, name_len, rev,
+    hipLaunchKernelGGL(k_tp_ids, grid(c, (nid_bytes + 3) / 4), dim3(256), 0, c->stream, d_text, nbytes, nrec, fo, ioff, name_b, name_len, rev,
                        nid_bytes, ids.get());
     HIPCHK(c, hipGetLastError());
   }
@@ -246,7 +246,7 @@ extern "C" int musc_sz_frame(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes,
   if ((rc = staged(c, who, B, bytes, nbytes, on_device, 0, &d_src)) || (rc = tmp_alloc(c, who, B, &d_x2n, sizeof x2n.t))) return rc;
   if (!dst_on_device && (rc = tmp_alloc(c, who, B, &d_out, size))) return rc;
   HIPCHK(c, hipMemcpyAsync(d_x2n, x2n.t, sizeof x2n.t, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_sz_frame, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nch, 8 * MAX_GRID))), dim3(TPF_BLOCK), 0, c->stream, d_src,
+  hipLaunchKernelGGL(k_sz_frame, stage_grid(c, nch, musc_launch::CAP_CHUNKS), dim3(TPF_BLOCK), 0, c->stream, d_src,
                      nbytes, nch, d_x2n, d_out);
   HIPCHK(c, hipGetLastError());
   if (!dst_on_device) HIPCHK(c, hipMemcpyAsync(dst, d_out, size, hipMemcpyDeviceToHost, c->stream));

@@ -219,7 +219,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   HIPCHK(c, B.alloc(&excl, n * 4));
   HIPCHK(c, B.alloc(&stmp, scan_tmp_elems(n) * 4));
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
-  hipLaunchKernelGGL(k_results_flag, grid(n), B256, 0, c->stream, d_in, n, c->nreads, c->nseq, c->seq_off, c->res_rank, keep, c->d_flag);
+  hipLaunchKernelGGL(k_results_flag, grid(c, n), B256, 0, c->stream, d_in, n, c->nreads, c->nseq, c->seq_off, c->res_rank, keep, c->d_flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, keep, excl, n, false, stmp))) return rc;
   Readback R(c->scalars, c->stream);
@@ -238,14 +238,14 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
     return 0;
   }
   HIPCHK(c, B.alloc(&a, m * 16));
-  hipLaunchKernelGGL(k_results_compact, grid(n), B256, 0, c->stream, d_in, keep, excl, n, a);
+  hipLaunchKernelGGL(k_results_compact, grid(c, n), B256, 0, c->stream, d_in, keep, excl, n, a);
   HIPCHK(c, hipGetLastError());
 
   static const char* const who = "musc_results_order";
   // one stable pass of K over the k tuples a[idx[.]] (idx null: a itself) on the key word `what`
   auto sort_pass = [&](KeyPasses& K, const uint32_t* idx, uint64_t k, uint32_t what, unsigned end_bit) {
     return K.pass(end_bit, [&](const uint32_t* perm, uint64_t* keys) {
-      hipLaunchKernelGGL(k_results_keys, grid(k), B256, 0, c->stream, a, idx, perm, k, what, c->res_rank, c->rd, c->rw, c->db2,
+      hipLaunchKernelGGL(k_results_keys, grid(c, k), B256, 0, c->stream, a, idx, perm, k, what, c->res_rank, c->rd, c->rw, c->db2,
                          c->db_has_x ? c->dbm2 : (const uint32_t*)nullptr, c->seq_off, keys);
     });
   };
@@ -257,7 +257,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
     if ((rc = K.start(c, who, m, {32u, 33u, 60u, 63u}))) return rc;
     HIPCHK(c, B.alloc(&a2, m * 16));
     if ((rc = sort_pass(K, nullptr, m, RES_KEY_READ, 32u))) return rc;
-    hipLaunchKernelGGL(k_results_gather, grid(m), B256, 0, c->stream, a, K.order(), m, a2);
+    hipLaunchKernelGGL(k_results_gather, grid(c, m), B256, 0, c->stream, a, K.order(), m, a2);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (K's buffers are released at the end of this scope)
     a = a2;
@@ -268,7 +268,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   HIPCHK(c, B.alloc(&multi, m * 4));
   HIPCHK(c, B.alloc(&incl, m * 4));
   HIPCHK(c, hipMemsetAsync(c->counters + CNT_SCRATCH, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_results_segments, grid(m), B256, 0, c->stream, a, m, c->rd, c->rw, multi, c->counters + CNT_SCRATCH);
+  hipLaunchKernelGGL(k_results_segments, grid(c, m), B256, 0, c->stream, a, m, c->rd, c->rw, multi, c->counters + CNT_SCRATCH);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, multi, incl, m, true, stmp))) return rc;  // (m <= n: stmp is large enough)
   uint64_t k = 0, maxlen = 0;
@@ -278,7 +278,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   } else {
     KeyPasses K;
     if ((rc = K.start(c, who, k, {32u, 33u, 60u, 63u})) || (rc = tmp_alloc(c, who, K.B, &idx, k * 4))) return rc;
-    hipLaunchKernelGGL(k_results_idx, grid(m), B256, 0, c->stream, multi, incl, m, idx);
+    hipLaunchKernelGGL(k_results_idx, grid(c, m), B256, 0, c->stream, multi, incl, m, idx);
     HIPCHK(c, hipGetLastError());
     // least significant first: gene rank, the number word, the target words from last to first, the read
     const uint32_t nw = (uint32_t)((maxlen + RES_BASES_PER_WORD - 1) / RES_BASES_PER_WORD);
@@ -287,7 +287,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
     for (uint32_t w = nw; w-- > 0;)
       if ((rc = sort_pass(K, idx, k, RES_KEY_SPAN + w, 63u))) return rc;
     if ((rc = sort_pass(K, idx, k, RES_KEY_READ, 32u))) return rc;
-    hipLaunchKernelGGL(k_results_place, grid(m), B256, 0, c->stream, a, multi, incl, idx, K.order(), m, out);
+    hipLaunchKernelGGL(k_results_place, grid(c, m), B256, 0, c->stream, a, multi, incl, idx, K.order(), m, out);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
@@ -295,7 +295,7 @@ static int results_order_impl(musc_ctx* c, const musc_hit* hits, uint64_t n, int
   // ---- line lengths -> offsets
   uint64_t* stmp64 = nullptr;
   HIPCHK(c, B.alloc(&stmp64, scan_tmp_elems(m + 1) * 8));
-  hipLaunchKernelGGL(k_results_len, grid(m + 1), B256, 0, c->stream, out, m, res_data(c), c->res_off.p);
+  hipLaunchKernelGGL(k_results_len, grid(c, m + 1), B256, 0, c->stream, out, m, res_data(c), c->res_off.p);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, c->res_off.p, c->res_off.p, m + 1, stmp64))) return rc;
   uint64_t res_bytes = 0;
@@ -337,8 +337,8 @@ int musc_results_hits(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_
 
 static void launch_render(musc_ctx* c, uint64_t l0, uint64_t l1, unsigned char* out) {
   const uint64_t nl = l1 - l0;
-  const unsigned blocks = (unsigned)std::min<uint64_t>((nl + 3) / 4, 4 * MAX_GRID);
-  hipLaunchKernelGGL(k_results_render, dim3(blocks), dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(c->res_hits.p), c->res_off.p, l0, l1,
+  const dim3 blocks = stage_grid(c, (nl + 3) / 4, musc_launch::CAP_TILES);
+  hipLaunchKernelGGL(k_results_render, blocks, dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(c->res_hits.p), c->res_off.p, l0, l1,
                      res_data(c), out, c->d_flag);
 }
 
@@ -396,7 +396,7 @@ static int side_records(musc_ctx* c, int which, const uint32_t* flag, uint32_t* 
   HIPCHK(c, Readback(c->scalars, c->stream).get(excl + n, &nrec).get(len + n, &nbytes).wait());
   if ((rc = ensure(c, c->side_idx[which], std::max<uint64_t>(nrec, 1)))) return rc;
   if ((rc = ensure(c, c->side_off[which], nrec + 1))) return rc;
-  hipLaunchKernelGGL(k_side_compact, grid(n + 1), dim3(256), 0, c->stream, flag, excl, len, n, c->side_idx[which].p, c->side_off[which].p);
+  hipLaunchKernelGGL(k_side_compact, grid(c, n + 1), dim3(256), 0, c->stream, flag, excl, len, n, c->side_idx[which].p, c->side_off[which].p);
   HIPCHK(c, hipGetLastError());
   c->side_nrec[which] = nrec;
   c->side_nbytes[which] = nbytes;
@@ -415,7 +415,7 @@ static int side_prepare_impl(musc_ctx* c) {
   // ---- tokens: once per read text
   if (!c->st.tokens_current()) {
     if ((rc = ensure(c, c->side_tok, std::max<uint64_t>(nreads, 1)))) return rc;
-    hipLaunchKernelGGL(k_side_tokens, grid(nreads), B256, 0, c->stream, c->res_ttext, c->res_toff, nreads, c->side_tok.p, c->d_flag);
+    hipLaunchKernelGGL(k_side_tokens, grid(c, nreads), B256, 0, c->stream, c->res_ttext, c->res_toff, nreads, c->side_tok.p, c->d_flag);
     HIPCHK(c, hipGetLastError());
   }
 
@@ -433,7 +433,7 @@ static int side_prepare_impl(musc_ctx* c) {
   HIPCHK(c, hipMemsetAsync(matched, 0, (nreads + 1) * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(c->side_cnt.p, 0, std::max<uint64_t>(nnames, 1) * 4, c->stream));
   if (m) {
-    hipLaunchKernelGGL(k_side_mark, grid(m), B256, 0, c->stream, hits, m, c->side_nrank, nreads, c->nseq, (uint32_t)nnames, matched,
+    hipLaunchKernelGGL(k_side_mark, grid(c, m), B256, 0, c->stream, hits, m, c->side_nrank, nreads, c->nseq, (uint32_t)nnames, matched,
                        c->side_cnt.p, c->d_flag);
     HIPCHK(c, hipGetLastError());
   }
@@ -444,12 +444,12 @@ static int side_prepare_impl(musc_ctx* c) {
   const SideData D = side_data(c);
 
   // ---- nonmatch: the unmatched reads that have a token
-  hipLaunchKernelGGL(k_side_nm_len, grid(nreads + 1), B256, 0, c->stream, D, matched, flag, len);
+  hipLaunchKernelGGL(k_side_nm_len, grid(c, nreads + 1), B256, 0, c->stream, D, matched, flag, len);
   HIPCHK(c, hipGetLastError());
   if ((rc = side_records(c, MUSC_SIDE_NONMATCH, flag, excl, len, nreads, stmp, stmp64))) return rc;
 
   // ---- genestats: the names with a tuple
-  hipLaunchKernelGGL(k_side_gs_len, grid(nnames + 1), B256, 0, c->stream, D, c->side_cnt.p, flag, len);
+  hipLaunchKernelGGL(k_side_gs_len, grid(c, nnames + 1), B256, 0, c->stream, D, c->side_cnt.p, flag, len);
   HIPCHK(c, hipGetLastError());
   if ((rc = side_records(c, MUSC_SIDE_GENESTATS, flag, excl, len, nnames, stmp, stmp64))) return rc;
 
@@ -458,7 +458,7 @@ static int side_prepare_impl(musc_ctx* c) {
   c->side_nrec[MUSC_SIDE_READSTATS] = c->side_nbytes[MUSC_SIDE_READSTATS] = 0;
   if ((rc = ensure(c, c->side_off[MUSC_SIDE_READSTATS], 1))) return rc;
   HIPCHK(c, hipMemsetAsync(c->side_off[MUSC_SIDE_READSTATS].p, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_side_rs_flag, grid(nreads + 1), B256, 0, c->stream, matched, c->side_tok.p, nreads, flag);
+  hipLaunchKernelGGL(k_side_rs_flag, grid(c, nreads + 1), B256, 0, c->stream, matched, c->side_tok.p, nreads, flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, flag, excl, nreads + 1, false, stmp))) return rc;
   uint64_t ncr = 0;
@@ -469,8 +469,8 @@ static int side_prepare_impl(musc_ctx* c) {
   HIPCHK(c, B.alloc(&head, ncr * 4));
   HIPCHK(c, B.alloc(&incl, ncr * 4));
   HIPCHK(c, B.alloc(&runof, nreads * 4));
-  hipLaunchKernelGGL(k_side_compact, grid(nreads + 1), B256, 0, c->stream, flag, excl, (const uint64_t*)nullptr, nreads, cr, (uint64_t*)nullptr);
-  hipLaunchKernelGGL(k_side_rs_heads, grid(ncr), B256, 0, c->stream, cr, ncr, D, head);
+  hipLaunchKernelGGL(k_side_compact, grid(c, nreads + 1), B256, 0, c->stream, flag, excl, (const uint64_t*)nullptr, nreads, cr, (uint64_t*)nullptr);
+  hipLaunchKernelGGL(k_side_rs_heads, grid(c, ncr), B256, 0, c->stream, cr, ncr, D, head);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, head, incl, ncr, true, stmp))) return rc;
   uint64_t nruns = 0;
@@ -480,7 +480,7 @@ static int side_prepare_impl(musc_ctx* c) {
   if ((rc = ensure(c, c->side_off[MUSC_SIDE_READSTATS], nruns + 1))) return rc;
   HIPCHK(c, hipMemsetAsync(runof, 0xFF, nreads * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(c->side_first.p, 0, (nruns + 1) * 4, c->stream));  // (every run has an element; were one without, it reads element 0)
-  hipLaunchKernelGGL(k_side_rs_runs, grid(ncr), B256, 0, c->stream, cr, head, incl, ncr, runof, c->side_runread.p);
+  hipLaunchKernelGGL(k_side_rs_runs, grid(c, ncr), B256, 0, c->stream, cr, head, incl, ncr, runof, c->side_runread.p);
   HIPCHK(c, hipGetLastError());
 
   // one key per kept tuple, sorted; the distinct keys are the elements of the lines
@@ -491,10 +491,10 @@ static int side_prepare_impl(musc_ctx* c) {
   HIPCHK(c, B.alloc(&k1, m * 8));
   HIPCHK(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, k0, k1, (size_t)m, 0u, 64u, c->stream));
   HIPCHK(c, B.alloc(&tmp, tmp_bytes));
-  hipLaunchKernelGGL(k_side_rs_keys, grid(m), B256, 0, c->stream, hits, m, runof, c->side_nrank, k0);
+  hipLaunchKernelGGL(k_side_rs_keys, grid(c, m), B256, 0, c->stream, hits, m, runof, c->side_nrank, k0);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, rocprim::radix_sort_keys(tmp, tmp_bytes, k0, k1, (size_t)m, 0u, 64u, c->stream));
-  hipLaunchKernelGGL(k_side_rs_uniq, grid(m + 1), B256, 0, c->stream, k1, m, flag);
+  hipLaunchKernelGGL(k_side_rs_uniq, grid(c, m + 1), B256, 0, c->stream, k1, m, flag);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u32(c, flag, excl, m + 1, false, stmp))) return rc;
   uint64_t nel = 0;
@@ -502,12 +502,12 @@ static int side_prepare_impl(musc_ctx* c) {
   if (nel < nruns) return fail(c, 11, "musc_side_prepare: a run of reads without an element");
   if ((rc = ensure(c, c->side_el, nel))) return rc;
   if ((rc = ensure(c, c->side_eloff, nel + 1))) return rc;
-  hipLaunchKernelGGL(k_side_rs_elems, grid(m), B256, 0, c->stream, k1, flag, excl, m, c->side_el.p);
-  hipLaunchKernelGGL(k_side_rs_len, grid(nel + 1), B256, 0, c->stream, c->side_el.p, nel, (uint32_t)nruns, D, c->side_runread.p,
+  hipLaunchKernelGGL(k_side_rs_elems, grid(c, m), B256, 0, c->stream, k1, flag, excl, m, c->side_el.p);
+  hipLaunchKernelGGL(k_side_rs_len, grid(c, nel + 1), B256, 0, c->stream, c->side_el.p, nel, (uint32_t)nruns, D, c->side_runread.p,
                      c->side_eloff.p, c->side_first.p);
   HIPCHK(c, hipGetLastError());
   if ((rc = scan_u64(c, c->side_eloff.p, c->side_eloff.p, nel + 1, stmp64))) return rc;  // (nel <= m: stmp64 is large enough)
-  hipLaunchKernelGGL(k_side_rs_lines, grid(nruns + 1), B256, 0, c->stream, c->side_first.p, c->side_eloff.p, nruns,
+  hipLaunchKernelGGL(k_side_rs_lines, grid(c, nruns + 1), B256, 0, c->stream, c->side_first.p, c->side_eloff.p, nruns,
                      c->side_off[MUSC_SIDE_READSTATS].p);
   HIPCHK(c, hipGetLastError());
   uint64_t rs_bytes = 0;
@@ -546,15 +546,15 @@ int musc_side_prepare(musc_ctx* c, uint64_t* nrecords, uint64_t* nbytes) {
 }
 
 static void launch_side(musc_ctx* c, int which, uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) {
-  const unsigned blocks = (unsigned)std::min<uint64_t>(bytes / 256 + 1, 4 * MAX_GRID);
+  const dim3 blocks = stage_grid(c, bytes / 256 + 1, musc_launch::CAP_TILES);
   const SideData D = side_data(c);
   if (which == MUSC_SIDE_NONMATCH)
-    hipLaunchKernelGGL(k_side_nm_render, dim3(blocks), dim3(256), 0, c->stream, c->side_idx[0].p, c->side_off[0].p, r0, r1, D, out, c->d_flag);
+    hipLaunchKernelGGL(k_side_nm_render, blocks, dim3(256), 0, c->stream, c->side_idx[0].p, c->side_off[0].p, r0, r1, D, out, c->d_flag);
   else if (which == MUSC_SIDE_GENESTATS)
-    hipLaunchKernelGGL(k_side_gs_render, dim3(blocks), dim3(256), 0, c->stream, c->side_idx[1].p, c->side_off[1].p, r0, r1, D, c->side_cnt.p, out,
+    hipLaunchKernelGGL(k_side_gs_render, blocks, dim3(256), 0, c->stream, c->side_idx[1].p, c->side_off[1].p, r0, r1, D, c->side_cnt.p, out,
                        c->d_flag);
   else
-    hipLaunchKernelGGL(k_side_rs_render, dim3(blocks), dim3(256), 0, c->stream, c->side_el.p, c->side_nel, c->side_eloff.p, c->side_first.p,
+    hipLaunchKernelGGL(k_side_rs_render, blocks, dim3(256), 0, c->stream, c->side_el.p, c->side_nel, c->side_eloff.p, c->side_first.p,
                        (uint32_t)c->side_nrec[2], r0, r1, D, c->side_runread.p, out, c->d_flag);
 }
 

@@ -42,7 +42,7 @@ def sanitized(tmp_path_factory):
 def test_every_check_program_is_listed():
     on_disk = {os.path.basename(p)[:-len(".cpp")] for p in glob.glob(os.path.join(CSRC, "host", "*_check.cpp"))}
     assert on_disk == set(mbuild.CHECKS)
-    assert len(NAMES) == 11
+    assert len(NAMES) == 12
     for name, (src, _, _, _) in mbuild.CHECKS.items():
         assert src == name + ".cpp"
 

@@ -1,6 +1,6 @@
 """What a lane of the read-name stage computes (muscato_amd/csrc/read_names_lanes.hpp), without a GPU:
 the header is plain C++ that g++ compiles without HIP, it holds no cross-lane primitive and no loop without a constant
-bound, and host/read_names_plan_check.cpp -- one of the eleven check programs, built and run plain and under the
+bound, and host/read_names_plan_check.cpp -- one of the twelve check programs, built and run plain and under the
 sanitizers by tests/test_check_programs.py -- runs every item function of it in lock step against the reference's
 string code."""
 import os
