@@ -634,6 +634,28 @@ int musc_targets_prep_free(musc_ctx* ctx);
 int musc_sz_frame(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int on_device, uint8_t* dst, uint64_t capacity,
                   int dst_on_device, uint64_t* nout);
 
+/* ---- The compressing writer (additions, MUSC_ABI_VERSION stays 3)
+ *
+ * musc_sz_compress: `bytes` as a framed snappy stream whose chunks (65 536 bytes of data, the last one shorter) are
+ * compressed by the rule of csrc/sz_compress_plan.hpp, or stored where a chunk's block would take n - n / 8 bytes or
+ * more: byte for byte what the host writer makes with MUSC_SZ_WRITE=compressed (host/sz.hpp, sz_encode_compressed).
+ * musc_sz_decode, musc_db_load_text and golang/snappy's reader take the stream.  `bytes` and dst in host or device
+ * memory at any alignment.  dst == NULL only sizes, and unlike musc_sz_frame's its answer is a bound, not the length:
+ * *nout = 10 + 8 * chunks + nbytes, which no stream exceeds.  Otherwise capacity must be at least that bound, and
+ * *nout = the stream's length.  Everything is allocated before a byte of dst is written: a failed call leaves dst as
+ * it was.  Nothing outside [dst, dst + *nout) is written.
+ *
+ * musc_targets_prep_sz: a resident prepared text (which: 0 sequences, 1 ids) framed where it lies -- compressed = 1 as
+ * musc_sz_compress, compressed = 0 as musc_sz_frame (dst == NULL sizes as that call does).  Without a prepared
+ * text: 2.
+ *
+ * Codes: 2 bad arguments (a NULL pointer with bytes, a capacity below the bound, which or compressed outside 0 / 1,
+ * no prepared text); 10 a HIP failure ("out of memory" in the text when an allocation failed). */
+int musc_sz_compress(musc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, int on_device, uint8_t* dst, uint64_t capacity,
+                     int dst_on_device, uint64_t* nout);
+int musc_targets_prep_sz(musc_ctx* ctx, int which, int compressed, uint8_t* dst, uint64_t capacity, int dst_on_device,
+                         uint64_t* nout);
+
 #ifdef __cplusplus
 }
 #endif

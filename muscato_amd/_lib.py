@@ -106,6 +106,7 @@ SYMBOLS = [
     "musc_maxmatches_apply", "musc_maxmatches_last_ms", "musc_maxmatches_last_detail",
     "musc_sz_decode", "musc_db_load_text",
     "musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame",
+    "musc_sz_compress", "musc_targets_prep_sz",
 ]
 
 # `which` of musc_side_text (include/muscato_hip.h)
@@ -212,7 +213,10 @@ def load() -> ctypes.CDLL:
     lib.musc_targets_prep_load.argtypes = [vp, ctypes.POINTER(MuscDbTextInfo)]
     lib.musc_targets_prep_free.argtypes = [vp]
     lib.musc_sz_frame.argtypes = [vp, vp, u64, ctypes.c_int, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
-    for name in ("musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame"):
+    lib.musc_sz_compress.argtypes = lib.musc_sz_frame.argtypes
+    lib.musc_targets_prep_sz.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
+    for name in ("musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame",
+                 "musc_sz_compress", "musc_targets_prep_sz"):
         getattr(lib, name).restype = ctypes.c_int
     for name in ("musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits",
                  "musc_results_text", "musc_results_last_ms", "musc_results_number_key",

@@ -317,6 +317,27 @@ class Engine:
         self._check(self._lib.musc_sz_frame(self._h, sp, len(src), 0, out.ctypes.data, int(n.value), 0, ctypes.byref(n)), "musc_sz_frame")
         return out[:int(n.value)].tobytes()
 
+    def sz_compress(self, data: bytes) -> bytes:
+        """`data` as a framed snappy stream of compressed chunks, made on the GPU (musc_sz_compress): the bytes of the
+        host writer under MUSC_SZ_WRITE=compressed."""
+        src = np.frombuffer(data, dtype=np.uint8)
+        sp = src.ctypes.data if len(src) else None
+        n = ctypes.c_uint64()
+        self._check(self._lib.musc_sz_compress(self._h, sp, len(src), 0, None, 0, 0, ctypes.byref(n)), "musc_sz_compress")
+        out = np.empty(int(n.value), dtype=np.uint8)  # (the bound)
+        self._check(self._lib.musc_sz_compress(self._h, sp, len(src), 0, out.ctypes.data, int(n.value), 0, ctypes.byref(n)), "musc_sz_compress")
+        return out[:int(n.value)].tobytes()
+
+    def prepared_sz(self, which: int, compressed: bool) -> bytes:
+        """A resident prepared text (which: 0 sequences, 1 ids) as a framed snappy stream, made where the text lies
+        (musc_targets_prep_sz): sz_compress's bytes of it, or sz_frame's."""
+        n = ctypes.c_uint64()
+        self._check(self._lib.musc_targets_prep_sz(self._h, int(which), int(bool(compressed)), None, 0, 0, ctypes.byref(n)), "musc_targets_prep_sz")
+        out = np.empty(int(n.value), dtype=np.uint8)
+        self._check(self._lib.musc_targets_prep_sz(self._h, int(which), int(bool(compressed)), out.ctypes.data, int(n.value), 0, ctypes.byref(n)),
+                    "musc_targets_prep_sz")
+        return out[:int(n.value)].tobytes()
+
     def build_index(self, window_width: int) -> None:
         self._check(self._lib.musc_db_build_index(self._h, int(window_width)), "musc_db_build_index")
 

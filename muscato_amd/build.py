@@ -67,7 +67,7 @@ def build_tools(force: bool = False, verbose: bool = False) -> None:
 # program cannot be hollowed out and still pass, and the libraries it links).
 _API = "../../include/muscato_hip.h"
 _HOST_CHAIN = ("host/muscato_host.hpp", "host/cli_config.hpp", "host/cli_maxmatches_host.hpp", "host/cli_names.hpp", "host/cli_plan.hpp",
-               "host/cli_text.hpp", "host/sz.hpp", _API)
+               "host/cli_text.hpp", "host/sz.hpp", "sz_compress_plan.hpp", _API)
 CHECKS = {
     "cli_plan_check": ("cli_plan_check.cpp", ("host/check.hpp", "host/cli_names.hpp", "host/cli_plan.hpp"), 184_205_945, ()),
     "ctx_state_check": ("ctx_state_check.cpp", ("host/check.hpp", "ctx_state.hpp", _API), 58_376_821, ()),
@@ -78,7 +78,7 @@ CHECKS = {
     "maxmatches_plan_check": ("maxmatches_plan_check.cpp", ("host/check.hpp", "maxmatches_plan.hpp"), 548_365, ()),
     "read_names_plan_check": ("read_names_plan_check.cpp", ("host/check.hpp", "read_names_keys.hpp", "read_names_lanes.hpp", "read_names_plan.hpp"), 21_928_502, ()),
     "side_names_check": ("side_names_check.cpp", ("host/check.hpp", "side_names.hpp"), 100_517, ()),
-    "sz_plan_check": ("sz_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "host/sz.hpp"), 3_599_466, ("-lz",)),
+    "sz_plan_check": ("sz_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "sz_compress_plan.hpp", "host/sz.hpp"), 12_267_430, ("-lz",)),
     "targets_prep_plan_check": ("targets_prep_plan_check.cpp", ("host/check.hpp", "sz_plan.hpp", "targets_prep_plan.hpp") + _HOST_CHAIN, 12_757_977, ("-lz",)),
     "text_stage_check": ("text_stage_check.cpp", ("host/check.hpp", "text_stage.hpp"), 1_711_086, ()),
 }

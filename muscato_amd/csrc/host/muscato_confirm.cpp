@@ -83,7 +83,7 @@ int main(int argc, char** argv) {
     } else {
       log.printf("No matches found, done.");
     }
-    spit(join_path(tmpdir, "rmatch_" + std::to_string(win) + ".txt.sz"), sz_encode(out));
+    spit(join_path(tmpdir, "rmatch_" + std::to_string(win) + ".txt.sz"), sz_write(out));
     log.printf("done");
     return 0;
   } catch (const Die& d) {

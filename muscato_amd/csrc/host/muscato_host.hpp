@@ -152,7 +152,7 @@ inline PrepTargetsNames prep_targets_names(const std::string& path) {
   return n;
 }
 
-// The device side (musc_targets_prep, musc_sz_frame).  false, after one line on stderr: the host chain
+// The device side (musc_targets_prep, musc_targets_prep_sz).  false, after one line on stderr: the host chain
 // runs instead -- no device, no device memory (10, "out of memory"), a refusal (12), or a bad .sz stream (13), which
 // the host decoder then ends with its own message.  An empty FASTA line (14) ends the run as the host's Die does.
 inline bool prep_targets_device(const std::string& path, const PrepTargetsNames& n, bool rev) {
@@ -182,15 +182,16 @@ inline bool prep_targets_device(const std::string& path, const PrepTargetsNames&
   int rc = musc_targets_prep(c, u8(raw), raw.size(), 0, n.fasta ? 1 : 0, rev ? 1 : 0, &info);
   if (rc == 14) throw Die(1, "muscato_prep_targets: empty line in FASTA input (the reference panics here)");
   if (rc) return demoted(rc, musc_last_error(c));
+  // both texts are framed where they lie (musc_targets_prep_sz): one crossing each, of the stream's bytes
   std::string framed[2];
   const uint64_t nb[2] = {info.n_seq_bytes, info.n_id_bytes};
+  const int compressed = sz_write_compressed() ? 1 : 0;
   for (int w = 0; w < 2; w++) {
-    std::string text(nb[w], '\0');
-    if ((rc = musc_targets_prep_text(c, w, 0, nb[w], m8(text), 0))) return demoted(rc, musc_last_error(c));
     uint64_t nout = 0;
-    if ((rc = musc_sz_frame(c, u8(text), text.size(), 0, nullptr, 0, 0, &nout))) return demoted(rc, musc_last_error(c));
+    if ((rc = musc_targets_prep_sz(c, w, compressed, nullptr, 0, 0, &nout))) return demoted(rc, musc_last_error(c));
     framed[w].resize(nout);
-    if ((rc = musc_sz_frame(c, u8(text), text.size(), 0, m8(framed[w]), nout, 0, &nout))) return demoted(rc, musc_last_error(c));
+    if ((rc = musc_targets_prep_sz(c, w, compressed, m8(framed[w]), nout, 0, &nout))) return demoted(rc, musc_last_error(c));
+    framed[w].resize(nout);
   }
   spit(n.seq_out, framed[0]);
   spit(n.id_out, framed[1]);
@@ -213,8 +214,8 @@ inline void prep_targets_file(const std::string& path, bool rev, std::string* se
   std::string a, b;
   for (auto& s : pt.seqs) { a += s; a += '\n'; }
   for (auto& s : pt.ids) { b += s; b += '\n'; }
-  spit(*seq_out, sz_encode(a));
-  spit(*id_out, sz_encode(b));
+  spit(*seq_out, sz_write(a));
+  spit(*id_out, sz_write(b));
 }
 
 // A whole text of `nrec` records and `nbytes` bytes from the device, in ranges of 2^20 records: `fetch(rec0, n, dst,
@@ -855,7 +856,7 @@ inline std::vector<UniqueRead> stage_read_prep(const Config& cfg, Placement& pla
     if (plan.prep_names == Where::Device) t.swap(line_text);  // (the same bytes, framed as they came)
     else
       for (auto& u : reads) t += u.seq + "\t" + std::to_string(u.count) + "\t" + u.names + "\n";
-    spit(join_path(cfg.TempDir, "reads_sorted.txt.sz"), sz_encode(t));
+    spit(join_path(cfg.TempDir, "reads_sorted.txt.sz"), sz_write(t));
   }
   return reads;
 }

@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
         snprintf(b, sizeof b, "\t%011u\t%lld\n", cd.first, (long long)jx);
         out += b;
       }
-      spit(join_path(tmpdir, "bmatch_" + std::to_string(k) + ".txt.sz"), sz_encode(out));
+      spit(join_path(tmpdir, "bmatch_" + std::to_string(k) + ".txt.sz"), sz_write(out));
       log.printf("window %zu: %zu candidates", k, cand.size());
     }
     log.printf("Done checking target sequences for matches");

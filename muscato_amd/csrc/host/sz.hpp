@@ -8,17 +8,23 @@
 // (format_description.txt) are implemented here: stream identifier ff 06 00 00 "sNaPpY";
 // chunk 0x00 = compressed, 0x01 = uncompressed, both prefixed by a masked CRC-32C of the
 // uncompressed bytes; 0x80-0xfd skippable; 0xfe padding; 0x02-0x7f reserved (error).
-// The writer emits uncompressed chunks only (always valid, readable by golang/snappy).
+// The writer emits uncompressed chunks (sz_encode: always valid, readable by golang/snappy) or, with
+// MUSC_SZ_WRITE=compressed, chunks compressed by the rule of ../sz_compress_plan.hpp (sz_encode_compressed; DESIGN.md
+// 27); sz_write chooses, and every .sz file of the tools goes through it.
 #pragma once
 
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "../sz_compress_plan.hpp"
 
 namespace musc {
 
@@ -174,6 +180,50 @@ inline std::string sz_encode(const std::string& data) {
   }
   return out;
 }
+
+// The same stream with every chunk compressed by the rule of sz_compress_plan.hpp, or stored where the rule says so.
+// musc_sz_compress (k_sz_compress) writes the same bytes.
+inline std::string sz_encode_compressed(const std::string& data) {
+  namespace zc = musc_szc;
+  std::string out;
+  out.append("\xff\x06\x00\x00sNaPpY", 10);
+  std::vector<uint32_t> in(zc::IN_DWORDS);
+  std::vector<uint8_t> block(zc::CHUNK);
+  for (size_t pos = 0; pos < data.size(); pos += zc::CHUNK) {
+    const uint32_t n = (uint32_t)std::min<size_t>(zc::CHUNK, data.size() - pos);
+    std::fill(in.begin(), in.end(), 0u);
+    memcpy(in.data(), data.data() + pos, n);  // (the tools run on little-endian hosts: dword k holds bytes 4k .. 4k + 3)
+    const uint32_t cap = n - n / 8;
+    const uint32_t* const dw = in.data();
+    auto rd = [dw](uint32_t k) { return dw[k]; };
+    uint8_t* const bp = block.data();
+    auto w = [bp, cap](uint32_t at, uint8_t b) { if (at < cap) bp[at] = b; };
+    const uint32_t bsz = zc::chunk_block(rd, n, w);
+    const bool keep = !zc::stored(bsz, n);
+    const uint32_t c = mask_crc(crc32c((const uint8_t*)data.data() + pos, n));
+    const size_t len = (keep ? bsz : n) + 4;
+    const char hdr[8] = {(char)(keep ? 0x00 : 0x01), (char)(len & 0xFF), (char)((len >> 8) & 0xFF), (char)((len >> 16) & 0xFF),
+                         (char)(c & 0xFF), (char)((c >> 8) & 0xFF), (char)((c >> 16) & 0xFF), (char)((c >> 24) & 0xFF)};
+    out.append(hdr, 8);
+    if (keep) out.append((const char*)bp, bsz);
+    else out.append(data, pos, n);
+  }
+  return out;
+}
+
+// 1: the tools write compressed .sz files unless MUSC_SZ_WRITE=stored; 0: only with MUSC_SZ_WRITE=compressed (read as
+// MUSC_RESULTS is: unset, empty or anything else is the compiled default).  DESIGN.md 27.
+#ifndef MUSC_SZ_WRITE_DEFAULT_COMPRESSED
+#define MUSC_SZ_WRITE_DEFAULT_COMPRESSED 0
+#endif
+inline bool sz_write_compressed() {
+  const char* v = getenv("MUSC_SZ_WRITE");
+  if (v && !strcmp(v, "compressed")) return true;
+  if (v && !strcmp(v, "stored")) return false;
+  return MUSC_SZ_WRITE_DEFAULT_COMPRESSED != 0;
+}
+// what every .sz file of the tools is written with
+inline std::string sz_write(const std::string& data) { return sz_write_compressed() ? sz_encode_compressed(data) : sz_encode(data); }
 
 inline std::string gz_decode_file(const std::string& path) {
   gzFile f = gzopen(path.c_str(), "rb");

@@ -381,47 +381,17 @@ MUSC_KERNEL __launch_bounds__(TPF_BLOCK) void k_sz_frame(const unsigned char* __
   __shared__ uint32_t s_tab[256];
   __shared__ uint32_t s_red[TPF_BLOCK / 64];
   const uint32_t tid = threadIdx.x;
-  {
-    uint32_t c = tid;
-#pragma unroll
-    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
-    s_tab[tid] = c;
-  }
+  sz_crc_table(s_tab, tid);
   if (blockIdx.x == 0 && tid < 10)  // ff 06 00 00 "sNaPpY", out of two constants (no table in memory)
     dst[tid] = tid < 8 ? (unsigned char)(0x50614e73000006ffull >> (8 * tid)) : (unsigned char)(0x5970u >> (8 * (tid - 8)));
   __syncthreads();
   for (uint64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
     const uint64_t off = ch * musc_tp::SZ_CHUNK;
     const uint32_t ulen = musc_tp::sz_chunk_len(nbytes, ch);
-    const uint32_t sd = musc_tp::crc_slice_dwords(ulen, TPF_BLOCK);
-    const uint32_t b0 = tid * sd * 4;
-    const uint32_t b1 = b0 + sd * 4 < ulen ? b0 + sd * 4 : ulen;
-    uint32_t c = 0;
-    if (b0 < ulen) {
-      c = 0xFFFFFFFFu;
-      uint32_t i = b0;
-      for (; i + 4 <= b1; i += 4) {
-        uint32_t v = fq_src_dword(src, nbytes, off + i);
-#pragma unroll
-        for (int k = 0; k < 4; k++, v >>= 8) c = s_tab[(c ^ v) & 0xFFu] ^ (c >> 8);
-      }
-      for (; i < b1; i++) c = s_tab[(c ^ src[off + i]) & 0xFFu] ^ (c >> 8);
-      c ^= 0xFFFFFFFFu;
-      uint32_t m = 0x80000000u;
-      uint32_t behind = ulen - b1;
-      for (uint32_t k = 3; behind; behind >>= 1, k++)
-        if (behind & 1u) m = sz_gf2_mul(x2n[k], m);
-      c = sz_gf2_mul(m, c);
-    }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) c ^= __shfl_xor(c, d);
-    if ((tid & 63u) == 0) s_red[tid >> 6] = c;
-    __syncthreads();
-    c = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < TPF_BLOCK / 64; k++) c ^= s_red[k];
+    const uint32_t c = sz_crc_slice(ulen, tid, TPF_BLOCK, s_tab, x2n, [&](uint32_t i) { return fq_src_dword(src, nbytes, off + i); },
+                                    [&](uint32_t i) { return (uint32_t)src[off + i]; });
+    const uint32_t masked = sz_crc_join(c, s_red, tid);
     __syncthreads();  // (s_red is written again for the next chunk)
-    const uint32_t masked = ((c >> 15) | (c << 17)) + 0xa282ead8u;
     unsigned char* const h = dst + musc_tp::sz_chunk_pos(ch);
     if (tid < 8) {
       const uint32_t len = ulen + 4;

@@ -779,6 +779,7 @@ void musc_destroy(musc_ctx* c) {
 #include "muscato_prep.hpp"
 #include "muscato_db_text.hpp"
 #include "muscato_targets_prep.hpp"
+#include "muscato_sz_compress.hpp"
 
 // the index layer: the build driver, eligibility, the partition planner, ensure_index, musc_db_build_index*
 #include "muscato_index.hpp"

@@ -223,10 +223,9 @@ extern "C" int musc_targets_prep_free(musc_ctx* c) {
   return 0;
 }
 
-extern "C" int musc_sz_frame(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, int on_device, uint8_t* dst, uint64_t capacity,
-                             int dst_on_device, uint64_t* nout) {
-  static const char* const who = "musc_sz_frame";
-  if (!c) return 1;
+// musc_sz_frame, and musc_targets_prep_sz (muscato_sz_compress.hpp) on a resident text
+static int sz_frame_call(musc_ctx* c, const char* who, const uint8_t* bytes, uint64_t nbytes, int on_device, uint8_t* dst, uint64_t capacity,
+                         int dst_on_device, uint64_t* nout) {
   if (!nout) return fail(c, 2, "%s: NULL output pointer", who);
   *nout = 0;
   if (!bytes && nbytes) return fail(c, 2, "%s: NULL input", who);
@@ -252,4 +251,10 @@ extern "C" int musc_sz_frame(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes,
   if (!dst_on_device) HIPCHK(c, hipMemcpyAsync(dst, d_out, size, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
+}
+
+extern "C" int musc_sz_frame(musc_ctx* c, const uint8_t* bytes, uint64_t nbytes, int on_device, uint8_t* dst, uint64_t capacity,
+                             int dst_on_device, uint64_t* nout) {
+  if (!c) return 1;
+  return sz_frame_call(c, "musc_sz_frame", bytes, nbytes, on_device, dst, capacity, dst_on_device, nout);
 }
