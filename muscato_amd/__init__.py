@@ -7,4 +7,4 @@ libmuscato_hip.so is missing (no CPU fallback).
 """
 from .api import Config, DbTextInfo, Engine, MuscatoError, TargetsPrepInfo, gather, number_key, sorted_hits  # noqa: F401
 
-__all__ = ["Config", "Engine", "MuscatoError", "gather", "number_key", "sorted_hits"]
+__all__ = ["Config", "DbTextInfo", "Engine", "MuscatoError", "TargetsPrepInfo", "gather", "number_key", "sorted_hits"]

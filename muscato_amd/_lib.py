@@ -90,24 +90,76 @@ class MuscTargetsPrepInfo(ctypes.Structure):
     ]
 
 
-# every symbol include/muscato_hip.h declares
-SYMBOLS = [
-    "musc_abi_version", "musc_init", "musc_destroy", "musc_last_error", "musc_reload_env",
-    "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for",
-    "musc_db_set_partition_bases", "musc_db_partitions",
-    "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique",
-    "musc_reads_prep_fastq", "musc_fastq_prep_free",
-    "musc_reads_names_order", "musc_reads_prep_fastq_names", "musc_reads_names_text",
-    "musc_match_device", "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_free_hits",
-    "musc_get_stats", "musc_last_instance", "musc_instances", "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe", "musc_overflow_probes", "musc_free_u32",
-    "musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits", "musc_results_text",
-    "musc_results_last_ms", "musc_results_number_key",
-    "musc_side_prepare", "musc_side_text", "musc_side_last_ms",
-    "musc_maxmatches_apply", "musc_maxmatches_last_ms", "musc_maxmatches_last_detail",
-    "musc_sz_decode", "musc_db_load_text",
-    "musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame",
-    "musc_sz_compress", "musc_targets_prep_sz",
-]
+_int, _i32, _u32, _u64, _f32 = ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
+_vp, _str, _P = ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER
+_TEXT_RANGE = [_vp, _int, _u64, _u64, _vp, _u64, _int, _P(_u64)]          # (ctx, which, rec0, nrec, dst, capacity, dst_on_device, &nbytes)
+_LAST_MS = [_vp, _P(_f32), _P(_f32)]
+_GATHER = [_P(_vp), _int, _P(_u64), _P(_vp), _P(_u64)]
+_SZ_WRITE = [_vp, _vp, _u64, _int, _vp, _u64, _int, _P(_u64)]
+
+# The binding, stated once: every prototype of include/muscato_hip.h in the header's order, name -> (restype, argtypes).
+# tests/test_abi.py holds each row to the header type for type, and the seven structs above to a compiled C program.
+PROTOTYPES = {
+    "musc_abi_version": (_int, []),
+    "musc_init": (_int, [_int, _P(_vp)]),
+    "musc_destroy": (None, [_vp]),
+    "musc_last_error": (_str, [_vp]),
+    "musc_reload_env": (_int, [_vp]),
+    "musc_db_load_ascii": (_int, [_vp, _vp, _vp, _u32, _int]),
+    "musc_db_load_packed": (_int, [_vp, _vp, _vp, _vp, _u32]),
+    "musc_db_build_index": (_int, [_vp, _i32]),
+    "musc_db_build_index_for": (_int, [_vp, _P(MuscParams), _i32]),
+    "musc_db_set_partition_bases": (_int, [_vp, _u64]),
+    "musc_db_partitions": (_int, [_vp, _vp, _u32, _P(_u32)]),
+    "musc_reads_load_ascii": (_int, [_vp, _vp, _vp, _u64, _int]),
+    "musc_reads_load_packed": (_int, [_vp, _vp, _vp, _vp, _u64]),
+    "musc_reads_load_packed32": (_int, [_vp, _vp, _vp, _vp, _u32, _u64, _int]),
+    "musc_reads_sort_unique": (_int, [_vp, _vp, _vp, _u64, _int, _P(_vp), _P(_vp), _P(_u64)]),
+    "musc_reads_prep_fastq": (_int, [_vp, _vp, _u64, _int, _i32, _i32, _P(MuscFastqPrep)]),
+    "musc_fastq_prep_free": (None, [_P(MuscFastqPrep)]),
+    "musc_reads_names_order": (_int, [_vp, _vp, _u64, _int, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "musc_reads_prep_fastq_names": (_int, [_vp, _vp, _u64, _int, _i32, _i32, _P(MuscFastqPrep), _P(MuscReadNames)]),
+    "musc_reads_names_text": (_int, _TEXT_RANGE),
+    "musc_match_device": (_int, [_vp, _P(MuscParams), _P(_u64)]),
+    "musc_hits_copy": (_int, [_vp, _vp, _u64, _int]),
+    "musc_hits_copy_packed": (_int, [_vp, _vp, _u64, _int, _u64, _P(_i32)]),
+    "musc_hits_unpack": (_int, [_vp, _vp, _u64, _int, _P(_i32), _vp]),
+    "musc_hits_copy_compact": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _P(_i32)]),
+    "musc_match": (_int, [_vp, _P(MuscParams), _P(_vp), _P(_u64)]),
+    "musc_free_hits": (None, [_vp]),
+    "musc_get_stats": (_int, [_vp, _P(MuscStats)]),
+    "musc_results_set_gene_text": (_int, [_vp, _vp, _vp, _vp, _u32]),
+    "musc_results_set_read_text": (_int, [_vp, _vp, _vp, _u64]),
+    "musc_results_order": (_int, [_vp, _vp, _u64, _int, _P(_u64), _P(_u64)]),
+    "musc_results_hits": (_int, [_vp, _vp, _u64, _int]),
+    "musc_results_text": (_int, [_vp, _u64, _u64, _vp, _u64, _int, _P(_u64)]),
+    "musc_results_last_ms": (_int, _LAST_MS),
+    "musc_results_number_key": (_int, [_u32, _u32, _P(_u64)]),
+    "musc_side_prepare": (_int, [_vp, _P(_u64), _P(_u64)]),
+    "musc_side_text": (_int, _TEXT_RANGE),
+    "musc_side_last_ms": (_int, _LAST_MS),
+    "musc_last_instance": (_int, [_vp, _P(_u32)]),
+    "musc_instances": (_int, [_P(_u32), _u32, _P(_u32)]),
+    "musc_stream_plan": (_int, [_u64, _u32, _u32, _vp, _vp, _u64, _P(_u64), _P(_u64)]),
+    "musc_overflow_probes": (_int, [_vp, _P(_vp), _P(_vp), _P(_u64)]),
+    "musc_free_u32": (None, [_vp]),
+    "musc_maxmatches_apply": (_int, [_vp, _int, _P(_u64), _P(_u64), _P(_u64)]),
+    "musc_maxmatches_last_ms": (_int, [_vp, _P(_f32)]),
+    "musc_maxmatches_last_detail": (_int, [_vp, _P(_u64), _P(_f32)]),
+    "musc_gather": (_int, _GATHER),
+    "musc_gather_rccl": (_int, _GATHER),
+    "musc_rccl_probe": (_int, [_str, _u64]),
+    "musc_sz_decode": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _P(_u64)]),
+    "musc_db_load_text": (_int, [_vp, _vp, _u64, _int, _int, _P(MuscDbTextInfo)]),
+    "musc_targets_prep": (_int, [_vp, _vp, _u64, _int, _int, _int, _P(MuscTargetsPrepInfo)]),
+    "musc_targets_prep_text": (_int, [_vp, _int, _u64, _u64, _vp, _int]),
+    "musc_targets_prep_load": (_int, [_vp, _P(MuscDbTextInfo)]),
+    "musc_targets_prep_free": (_int, [_vp]),
+    "musc_sz_frame": (_int, _SZ_WRITE),
+    "musc_sz_compress": (_int, _SZ_WRITE),
+    "musc_targets_prep_sz": (_int, [_vp, _int, _int, _vp, _u64, _int, _P(_u64)]),
+}
+SYMBOLS = list(PROTOTYPES)
 
 # `which` of musc_side_text (include/muscato_hip.h)
 SIDE_NONMATCH, SIDE_GENESTATS, SIDE_READSTATS = 0, 1, 2
@@ -137,96 +189,10 @@ def load() -> ctypes.CDLL:
         except Exception:
             pass
     lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS:
-        if not hasattr(lib, s):
-            raise ImportError("muscato_amd: %s does not export %s" % (LIB_PATH, s))
-    vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32
-    lib.musc_abi_version.restype = ctypes.c_int
-    lib.musc_init.argtypes = [ctypes.c_int, ctypes.POINTER(vp)]
-    lib.musc_destroy.argtypes = [vp]
-    lib.musc_destroy.restype = None
-    lib.musc_last_error.argtypes = [vp]
-    lib.musc_last_error.restype = ctypes.c_char_p
-    lib.musc_reload_env.argtypes = [vp]
-    lib.musc_db_load_ascii.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_int]
-    lib.musc_db_load_packed.argtypes = [vp, vp, vp, vp, ctypes.c_uint32]
-    lib.musc_db_build_index.argtypes = [vp, i32]
-    lib.musc_db_build_index_for.argtypes = [vp, ctypes.POINTER(MuscParams), i32]
-    lib.musc_db_set_partition_bases.argtypes = [vp, u64]
-    lib.musc_db_partitions.argtypes = [vp, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
-    lib.musc_reads_load_ascii.argtypes = [vp, vp, vp, u64, ctypes.c_int]
-    lib.musc_reads_load_packed.argtypes = [vp, vp, vp, vp, u64]
-    lib.musc_reads_load_packed32.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u64, ctypes.c_int]
-    lib.musc_reads_sort_unique.argtypes = [vp, vp, vp, u64, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                           ctypes.POINTER(u64)]
-    lib.musc_reads_prep_fastq.argtypes = [vp, vp, u64, ctypes.c_int, i32, i32, ctypes.POINTER(MuscFastqPrep)]
-    lib.musc_reads_prep_fastq.restype = ctypes.c_int
-    lib.musc_fastq_prep_free.argtypes = [ctypes.POINTER(MuscFastqPrep)]
-    lib.musc_fastq_prep_free.restype = None
-    lib.musc_reads_names_order.argtypes = [vp, vp, u64, ctypes.c_int, vp, vp, u64, vp, vp, u64, vp]
-    lib.musc_reads_prep_fastq_names.argtypes = [vp, vp, u64, ctypes.c_int, i32, i32, ctypes.POINTER(MuscFastqPrep), ctypes.POINTER(MuscReadNames)]
-    lib.musc_reads_names_text.argtypes = [vp, ctypes.c_int, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
-    for name in ("musc_reads_names_order", "musc_reads_prep_fastq_names", "musc_reads_names_text"):
-        getattr(lib, name).restype = ctypes.c_int
-    lib.musc_match_device.argtypes = [vp, ctypes.POINTER(MuscParams), ctypes.POINTER(u64)]
-    lib.musc_hits_copy.argtypes = [vp, vp, u64, ctypes.c_int]
-    lib.musc_hits_copy_packed.argtypes = [vp, vp, u64, ctypes.c_int, u64, ctypes.POINTER(i32)]
-    lib.musc_hits_copy_compact.argtypes = [vp, vp, u64, vp, u64, ctypes.c_int, ctypes.POINTER(i32)]
-    lib.musc_hits_unpack.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.POINTER(i32), vp]
-    lib.musc_match.argtypes = [vp, ctypes.POINTER(MuscParams), ctypes.POINTER(vp), ctypes.POINTER(u64)]
-    lib.musc_free_hits.argtypes = [vp]
-    lib.musc_free_hits.restype = None
-    lib.musc_get_stats.argtypes = [vp, ctypes.POINTER(MuscStats)]
-    lib.musc_last_instance.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
-    lib.musc_instances.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
-    lib.musc_stream_plan.argtypes = [u64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    lib.musc_overflow_probes.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(u64)]
-    lib.musc_overflow_probes.restype = ctypes.c_int
-    lib.musc_free_u32.argtypes = [vp]
-    lib.musc_free_u32.restype = None
-    lib.musc_gather.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(u64),
-                                ctypes.POINTER(vp), ctypes.POINTER(u64)]
-    lib.musc_gather_rccl.argtypes = lib.musc_gather.argtypes
-    lib.musc_rccl_probe.argtypes = [ctypes.c_char_p, ctypes.c_uint64]
-    lib.musc_results_set_gene_text.argtypes = [vp, vp, vp, vp, ctypes.c_uint32]
-    lib.musc_results_set_read_text.argtypes = [vp, vp, vp, u64]
-    lib.musc_results_order.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    lib.musc_results_hits.argtypes = [vp, vp, u64, ctypes.c_int]
-    lib.musc_results_text.argtypes = [vp, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
-    lib.musc_results_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
-    lib.musc_results_number_key.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(u64)]
-    lib.musc_side_prepare.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    lib.musc_side_text.argtypes = [vp, ctypes.c_int, u64, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
-    lib.musc_side_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
-    lib.musc_maxmatches_apply.argtypes = [vp, ctypes.c_int, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
-    lib.musc_maxmatches_apply.restype = ctypes.c_int
-    lib.musc_maxmatches_last_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    lib.musc_maxmatches_last_ms.restype = ctypes.c_int
-    lib.musc_maxmatches_last_detail.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]
-    lib.musc_maxmatches_last_detail.restype = ctypes.c_int
-    lib.musc_sz_decode.argtypes = [vp, vp, u64, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
-    lib.musc_sz_decode.restype = ctypes.c_int
-    lib.musc_db_load_text.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MuscDbTextInfo)]
-    lib.musc_db_load_text.restype = ctypes.c_int
-    lib.musc_targets_prep.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MuscTargetsPrepInfo)]
-    lib.musc_targets_prep_text.argtypes = [vp, ctypes.c_int, u64, u64, vp, ctypes.c_int]
-    lib.musc_targets_prep_load.argtypes = [vp, ctypes.POINTER(MuscDbTextInfo)]
-    lib.musc_targets_prep_free.argtypes = [vp]
-    lib.musc_sz_frame.argtypes = [vp, vp, u64, ctypes.c_int, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
-    lib.musc_sz_compress.argtypes = lib.musc_sz_frame.argtypes
-    lib.musc_targets_prep_sz.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, u64, ctypes.c_int, ctypes.POINTER(u64)]
-    for name in ("musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame",
-                 "musc_sz_compress", "musc_targets_prep_sz"):
-        getattr(lib, name).restype = ctypes.c_int
-    for name in ("musc_results_set_gene_text", "musc_results_set_read_text", "musc_results_order", "musc_results_hits",
-                 "musc_results_text", "musc_results_last_ms", "musc_results_number_key",
-                 "musc_side_prepare", "musc_side_text", "musc_side_last_ms"):
-        getattr(lib, name).restype = ctypes.c_int
-    for name in ("musc_init", "musc_reload_env", "musc_db_load_ascii", "musc_db_load_packed", "musc_db_build_index", "musc_db_build_index_for", "musc_db_build_index_for",
-                 "musc_db_set_partition_bases", "musc_db_partitions",
-                 "musc_reads_load_ascii", "musc_reads_load_packed", "musc_reads_load_packed32", "musc_reads_sort_unique", "musc_match_device",
-                 "musc_hits_copy", "musc_hits_copy_packed", "musc_hits_copy_compact", "musc_hits_unpack", "musc_match", "musc_get_stats", "musc_last_instance", "musc_instances",
-                 "musc_stream_plan", "musc_gather", "musc_gather_rccl", "musc_rccl_probe"):
-        getattr(lib, name).restype = ctypes.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if not hasattr(lib, name):
+            raise ImportError("muscato_amd: %s does not export %s" % (LIB_PATH, name))
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib

@@ -174,6 +174,23 @@ def pack_2bit(buf: np.ndarray, nbases: int) -> Tuple[np.ndarray, Optional[np.nda
     return packed, mask
 
 
+def _host_ptr(data) -> Tuple[Optional[int], int]:
+    """Host bytes -> (their address, or None when there are none; their number).  `data` owns the memory: the caller
+    holds it across the call."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    return (buf.ctypes.data if len(buf) else None), len(buf)
+
+
+def _array(p, count: int) -> np.ndarray:
+    """A copy of `count` elements at the typed pointer `p`; a count of 0 does not look at the pointer."""
+    return np.ctypeslib.as_array(p, shape=(count,)).copy() if count else np.zeros(0, dtype=p._type_)
+
+
+def _plain(s: ctypes.Structure, cls):
+    """A struct of the library as the dataclass `cls` of its fields (all but `reserved`): Python ints and floats."""
+    return cls(**{k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"})
+
+
 class Engine:
     """One context per GPU: resident target database + index, resident reads, match()."""
 
@@ -210,78 +227,95 @@ class Engine:
         if rc != 0:
             raise MuscatoError("%s failed (%d): %s" % (what, rc, self._lib.musc_last_error(self._h).decode()))
 
+    def _call(self, name: str, *args) -> None:
+        """The library's `name(ctx, *args)`, checked: the name that is called is the name that is reported."""
+        self._check(getattr(self._lib, name)(self._h, *args), name)
+
+    def _sized(self, fill, skip_empty: bool = False) -> bytes:
+        """Size, then fill: `fill(dst, capacity, &nbytes)` once with a NULL dst for the size, once more into a host buffer
+        of that size (of one byte when the size is 0; skip_empty: no second call then) -> the bytes the second call
+        reports."""
+        n = ctypes.c_uint64()
+        fill(None, 0, ctypes.byref(n))
+        if skip_empty and not n.value:
+            return b""
+        out = np.empty(max(n.value, 1), dtype=np.uint8)
+        fill(out.ctypes.data, n.value, ctypes.byref(n))
+        return out[:n.value].tobytes()
+
+    def _take_u32(self, *arrays) -> List[np.ndarray]:
+        """Copies of uint32 arrays the library malloc'ed, each given as (pointer, count); every one of them is freed,
+        whatever happens."""
+        try:
+            return [_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint32)), int(n)) for p, n in arrays]
+        finally:
+            for p, _ in arrays:
+                self._lib.musc_free_u32(ctypes.cast(p, ctypes.c_void_p))
+
+    def _ms_pair(self, name: str) -> Tuple[float, float]:
+        """The two HIP-event times of a `*_last_ms` call."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._call(name, ctypes.byref(a), ctypes.byref(b))
+        return float(a.value), float(b.value)
+
+    def _packed(self, name: str, seqs: Sequence[bytes]) -> int:
+        """`seqs` through the packed loader `name` (2 bits a base, an X mask when there is an X) -> their number."""
+        buf, off = concat(seqs)
+        packed, mask = pack_2bit(buf, int(off[-1]))
+        packed = np.concatenate([packed, np.zeros(8, np.uint8)])
+        self._call(name, packed.ctypes.data, mask.ctypes.data if mask is not None else None, off.ctypes.data, len(off) - 1)
+        return len(off) - 1
+
     # ---- database (gene number = index in the list = line index of GeneFileName)
     def reload_env(self) -> None:
-        """Re-read the MUSC_* knobs (the library reads them once, at musc_init)."""
-        self._check(self._lib.musc_reload_env(self._h), "musc_reload_env")
+        """Re-read the MUSC_* knobs (the library reads them once, at musc_init).
+        The rule: every MUSC_* knob is latched when the context is made.  Setting or clearing one in the environment of
+        a live Engine changes nothing until this call, which latches all of them again -- except MUSC_BATCH_READS, which
+        keeps its value of musc_init, and MUSC_RCCL_LIB, which is read once per process."""
+        self._call("musc_reload_env")
 
     def load_targets(self, seqs: Sequence[bytes]) -> None:
         buf, off = concat(seqs)
         self.load_targets_arrays(buf, off)
 
     def load_targets_arrays(self, buf: np.ndarray, off: np.ndarray) -> None:
-        self._check(self._lib.musc_db_load_ascii(self._h, buf.ctypes.data, off.ctypes.data, len(off) - 1, 0),
-                    "musc_db_load_ascii")
+        self._call("musc_db_load_ascii", buf.ctypes.data, off.ctypes.data, len(off) - 1, 0)
         self.n_targets = len(off) - 1
 
     def load_targets_device(self, seqs_ptr: int, off_ptr: int, nseq: int) -> None:
-        self._check(self._lib.musc_db_load_ascii(self._h, seqs_ptr, off_ptr, nseq, 1), "musc_db_load_ascii")
+        self._call("musc_db_load_ascii", seqs_ptr, off_ptr, nseq, 1)
         self.n_targets = nseq
 
     def load_targets_packed(self, seqs: Sequence[bytes]) -> None:
-        buf, off = concat(seqs)
-        packed, mask = pack_2bit(buf, int(off[-1]))
-        packed = np.concatenate([packed, np.zeros(8, np.uint8)])
-        mp = mask.ctypes.data if mask is not None else None
-        self._check(self._lib.musc_db_load_packed(self._h, packed.ctypes.data, mp, off.ctypes.data, len(off) - 1),
-                    "musc_db_load_packed")
-        self.n_targets = len(off) - 1
+        self.n_targets = self._packed("musc_db_load_packed", seqs)
 
     def sz_decode(self, data: bytes) -> bytes:
         """A framed snappy stream decoded on the GPU (musc_sz_decode)."""
-        src = np.frombuffer(data, dtype=np.uint8)
-        sp = src.ctypes.data if len(src) else None
-        n = ctypes.c_uint64()
-        self._check(self._lib.musc_sz_decode(self._h, sp, len(src), None, 0, 0, ctypes.byref(n)), "musc_sz_decode")
-        out = np.empty(max(int(n.value), 1), dtype=np.uint8)
-        self._check(self._lib.musc_sz_decode(self._h, sp, len(src), out.ctypes.data, int(n.value), 0, ctypes.byref(n)),
-                    "musc_sz_decode")
-        return out[:int(n.value)].tobytes()
+        sp, n = _host_ptr(data)
+        return self._sized(lambda dst, cap, nout: self._call("musc_sz_decode", sp, n, dst, cap, 0, nout))
 
     def load_db_text(self, data, framed: int = -1, on_device: bool = False) -> "DbTextInfo":
         """The raw bytes of a gene file -- a framed snappy stream or plain text, one target per line up to its first
         tab -- decoded, split and packed on the GPU (musc_db_load_text).  data: bytes, or (on_device) a pair
         (device pointer, nbytes) of plain text at any alignment.  framed: 1, 0, or -1 to go by the stream identifier."""
-        if on_device:
-            ptr, nbytes = data
-        else:
-            buf = np.frombuffer(data, dtype=np.uint8)
-            ptr, nbytes = (buf.ctypes.data if len(buf) else None), len(buf)
+        ptr, nbytes = data if on_device else _host_ptr(data)
         info = _lib.MuscDbTextInfo()
         self.n_targets = 0
-        self._check(self._lib.musc_db_load_text(self._h, ptr, int(nbytes), 1 if on_device else 0, int(framed), ctypes.byref(info)),
-                    "musc_db_load_text")
+        self._call("musc_db_load_text", ptr, int(nbytes), 1 if on_device else 0, int(framed), ctypes.byref(info))
         self.n_targets = int(info.n_targets)
-        return DbTextInfo(int(info.n_targets), int(info.n_bases), int(info.n_odd), int(info.first_odd_target),
-                          int(info.n_text_bytes), int(info.n_chunks), float(info.ms_decode), float(info.ms_parse))
+        return _plain(info, DbTextInfo)
 
     # ---- target preparation on the device (musc_targets_prep*, musc_sz_frame)
     def prep_targets(self, data, fasta: bool, rev: bool, on_device: bool = False) -> "TargetsPrepInfo":
         """The raw bytes of a target file -- FASTA, or id<TAB>sequence text -- prepared on the GPU: the sequence text and
         the id text stay resident (prepared_text, load_db_prepared) until the next call, free_prepared or close.  data:
         bytes, or (on_device) a pair (device pointer, nbytes) at any alignment."""
-        if on_device:
-            ptr, nbytes = data
-        else:
-            buf = np.frombuffer(data, dtype=np.uint8)
-            ptr, nbytes = (buf.ctypes.data if len(buf) else None), len(buf)
+        ptr, nbytes = data if on_device else _host_ptr(data)
         info = _lib.MuscTargetsPrepInfo()
         self._prep_bytes = None
-        self._check(self._lib.musc_targets_prep(self._h, ptr, int(nbytes), 1 if on_device else 0, int(fasta), int(rev), ctypes.byref(info)),
-                    "musc_targets_prep")
+        self._call("musc_targets_prep", ptr, int(nbytes), 1 if on_device else 0, int(fasta), int(rev), ctypes.byref(info))
         self._prep_bytes = (int(info.n_seq_bytes), int(info.n_id_bytes))
-        return TargetsPrepInfo(int(info.n_lines), int(info.n_records), int(info.n_targets), int(info.n_dropped), int(info.stop_line),
-                               int(info.n_subx), int(info.n_seq_bytes), int(info.n_id_bytes), float(info.ms))
+        return _plain(info, TargetsPrepInfo)
 
     def prepared_text(self, which: int, off: int = 0, nbytes: Optional[int] = None) -> bytes:
         """Bytes [off, off + nbytes) of a prepared text (which: 0 sequences, 1 ids); nbytes None: to the text's end."""
@@ -291,63 +325,49 @@ class Engine:
                 raise MuscatoError("prepared_text: no prepared text (prep_targets first)" if have is None else "prepared_text: which must be 0 or 1")
             nbytes = max(have[which] - int(off), 0)
         out = np.empty(max(int(nbytes), 1), dtype=np.uint8)
-        self._check(self._lib.musc_targets_prep_text(self._h, int(which), int(off), int(nbytes), out.ctypes.data, 0), "musc_targets_prep_text")
+        self._call("musc_targets_prep_text", int(which), int(off), int(nbytes), out.ctypes.data, 0)
         return out[:int(nbytes)].tobytes()
 
     def load_db_prepared(self) -> "DbTextInfo":
         """The resident sequence text becomes the database (musc_targets_prep_load); the prepared texts stay."""
         info = _lib.MuscDbTextInfo()
         self.n_targets = 0
-        self._check(self._lib.musc_targets_prep_load(self._h, ctypes.byref(info)), "musc_targets_prep_load")
+        self._call("musc_targets_prep_load", ctypes.byref(info))
         self.n_targets = int(info.n_targets)
-        return DbTextInfo(int(info.n_targets), int(info.n_bases), int(info.n_odd), int(info.first_odd_target),
-                          int(info.n_text_bytes), int(info.n_chunks), float(info.ms_decode), float(info.ms_parse))
+        return _plain(info, DbTextInfo)
 
     def free_prepared(self) -> None:
         self._prep_bytes = None
-        self._check(self._lib.musc_targets_prep_free(self._h), "musc_targets_prep_free")
+        self._call("musc_targets_prep_free")
+
+    def _sz_write(self, name: str, data: bytes) -> bytes:
+        # (a stream is never empty -- its size, or bound, is 10 + 8 * chunks + nbytes -- so _sized's one-byte rule is idle)
+        sp, n = _host_ptr(data)
+        return self._sized(lambda dst, cap, nout: self._call(name, sp, n, 0, dst, cap, 0, nout))
 
     def sz_frame(self, data: bytes) -> bytes:
         """`data` as a framed snappy stream of uncompressed chunks, made on the GPU (musc_sz_frame)."""
-        src = np.frombuffer(data, dtype=np.uint8)
-        sp = src.ctypes.data if len(src) else None
-        n = ctypes.c_uint64()
-        self._check(self._lib.musc_sz_frame(self._h, sp, len(src), 0, None, 0, 0, ctypes.byref(n)), "musc_sz_frame")
-        out = np.empty(int(n.value), dtype=np.uint8)
-        self._check(self._lib.musc_sz_frame(self._h, sp, len(src), 0, out.ctypes.data, int(n.value), 0, ctypes.byref(n)), "musc_sz_frame")
-        return out[:int(n.value)].tobytes()
+        return self._sz_write("musc_sz_frame", data)
 
     def sz_compress(self, data: bytes) -> bytes:
         """`data` as a framed snappy stream of compressed chunks, made on the GPU (musc_sz_compress): the bytes of the
         host writer under MUSC_SZ_WRITE=compressed."""
-        src = np.frombuffer(data, dtype=np.uint8)
-        sp = src.ctypes.data if len(src) else None
-        n = ctypes.c_uint64()
-        self._check(self._lib.musc_sz_compress(self._h, sp, len(src), 0, None, 0, 0, ctypes.byref(n)), "musc_sz_compress")
-        out = np.empty(int(n.value), dtype=np.uint8)  # (the bound)
-        self._check(self._lib.musc_sz_compress(self._h, sp, len(src), 0, out.ctypes.data, int(n.value), 0, ctypes.byref(n)), "musc_sz_compress")
-        return out[:int(n.value)].tobytes()
+        return self._sz_write("musc_sz_compress", data)
 
     def prepared_sz(self, which: int, compressed: bool) -> bytes:
         """A resident prepared text (which: 0 sequences, 1 ids) as a framed snappy stream, made where the text lies
         (musc_targets_prep_sz): sz_compress's bytes of it, or sz_frame's."""
-        n = ctypes.c_uint64()
-        self._check(self._lib.musc_targets_prep_sz(self._h, int(which), int(bool(compressed)), None, 0, 0, ctypes.byref(n)), "musc_targets_prep_sz")
-        out = np.empty(int(n.value), dtype=np.uint8)
-        self._check(self._lib.musc_targets_prep_sz(self._h, int(which), int(bool(compressed)), out.ctypes.data, int(n.value), 0, ctypes.byref(n)),
-                    "musc_targets_prep_sz")
-        return out[:int(n.value)].tobytes()
+        return self._sized(lambda dst, cap, nout: self._call("musc_targets_prep_sz", int(which), int(bool(compressed)), dst, cap, 0, nout))
 
     def build_index(self, window_width: int) -> None:
-        self._check(self._lib.musc_db_build_index(self._h, int(window_width)), "musc_db_build_index")
+        self._call("musc_db_build_index", int(window_width))
 
     def build_index_for(self, cfg: "Config", max_read_len: int = 0) -> None:
         """Build the index match() will pick for `cfg` (context buckets when the run fits them; with several
         partitions, the first one's)."""
         p = cfg.to_params(True)
         self._apply_partition_bases(cfg)
-        self._check(self._lib.musc_db_build_index_for(self._h, ctypes.byref(p), int(max_read_len)),
-                    "musc_db_build_index_for")
+        self._call("musc_db_build_index_for", ctypes.byref(p), int(max_read_len))
 
     def set_partition_bases(self, max_bases: int) -> None:
         """Most target bases indexed at once (musc_db_set_partition_bases): the database is matched in partitions of
@@ -355,17 +375,17 @@ class Engine:
         whenever the index fits the device."""
         if max_bases < 0:
             raise MuscatoError("partition bases must be >= 0")
-        self._check(self._lib.musc_db_set_partition_bases(self._h, int(max_bases)), "musc_db_set_partition_bases")
+        self._call("musc_db_set_partition_bases", int(max_bases))
 
     def partitions(self) -> List[int]:
         """The plan of the last build or match: partition boundaries as target numbers (n partitions, n + 1 entries;
         empty before any)."""
         n = ctypes.c_uint32()
-        self._check(self._lib.musc_db_partitions(self._h, None, 0, ctypes.byref(n)), "musc_db_partitions")
+        self._call("musc_db_partitions", None, 0, ctypes.byref(n))
         if not n.value:
             return []
         out = (ctypes.c_uint32 * (n.value + 1))()
-        self._check(self._lib.musc_db_partitions(self._h, out, n.value + 1, ctypes.byref(n)), "musc_db_partitions")
+        self._call("musc_db_partitions", out, n.value + 1, ctypes.byref(n))
         return list(out)
 
     def _apply_partition_bases(self, cfg: "Config") -> None:
@@ -380,12 +400,11 @@ class Engine:
         self.load_reads_arrays(buf, off)
 
     def load_reads_arrays(self, buf: np.ndarray, off: np.ndarray) -> None:
-        self._check(self._lib.musc_reads_load_ascii(self._h, buf.ctypes.data, off.ctypes.data, len(off) - 1, 0),
-                    "musc_reads_load_ascii")
+        self._call("musc_reads_load_ascii", buf.ctypes.data, off.ctypes.data, len(off) - 1, 0)
         self.n_reads = len(off) - 1
 
     def load_reads_device(self, seqs_ptr: int, off_ptr: int, nreads: int) -> None:
-        self._check(self._lib.musc_reads_load_ascii(self._h, seqs_ptr, off_ptr, nreads, 1), "musc_reads_load_ascii")
+        self._call("musc_reads_load_ascii", seqs_ptr, off_ptr, nreads, 1)
         self.n_reads = nreads
 
     def sort_unique_reads(self, seqs: Sequence[bytes]):
@@ -398,15 +417,9 @@ class Engine:
 
     def sort_unique_reads_arrays(self, seqs_ptr: int, off_ptr: int, nreads: int, on_device: bool):
         po, pu, nu = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
-        self._check(self._lib.musc_reads_sort_unique(self._h, seqs_ptr, off_ptr, nreads, 1 if on_device else 0,
-                                                     ctypes.byref(po), ctypes.byref(pu), ctypes.byref(nu)),
-                    "musc_reads_sort_unique")
-        try:
-            order = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_uint32)), shape=(max(nreads, 1),))[:nreads].copy()
-            ustart = np.ctypeslib.as_array(ctypes.cast(pu, ctypes.POINTER(ctypes.c_uint32)), shape=(nu.value + 1,)).copy()
-        finally:
-            self._lib.musc_free_u32(po)
-            self._lib.musc_free_u32(pu)
+        self._call("musc_reads_sort_unique", seqs_ptr, off_ptr, nreads, 1 if on_device else 0, ctypes.byref(po), ctypes.byref(pu),
+                   ctypes.byref(nu))
+        order, ustart = self._take_u32((po, nreads), (pu, nu.value + 1))
         self.n_reads = int(nu.value)
         return order, ustart
 
@@ -415,34 +428,47 @@ class Engine:
         the distinct prepared sequences in bytewise order as the context's reads and returns the counts (n_records,
         n_short, n_reads, n_unique, max_len) and, as numpy arrays over the kept reads in file order, their spans in
         `raw` (name_off, name_len, seq_off, seq_len) and order / ustart as sort_unique_reads returns them."""
-        buf = np.frombuffer(raw, dtype=np.uint8)
-        return self.prep_fastq_device(buf.ctypes.data if len(buf) else None, len(buf), min_len, max_len, on_device=False)
+        return self._prep_fastq(False, *_host_ptr(raw), min_len, max_len, False)
 
     def prep_fastq_device(self, ptr: Optional[int], nbytes: int, min_len: int, max_len: int, on_device: bool = True) -> dict:
         """The same for `nbytes` of text at `ptr`: a device pointer of any alignment (the spans are offsets from it)."""
-        fp = _lib.MuscFastqPrep()
-        self.n_reads = 0
-        self._check(self._lib.musc_reads_prep_fastq(self._h, ptr, int(nbytes), 1 if on_device else 0, int(min_len), int(max_len),
-                                                    ctypes.byref(fp)), "musc_reads_prep_fastq")
-        try:
-            n, nu = int(fp.n_reads), int(fp.n_unique)
+        return self._prep_fastq(False, ptr, nbytes, min_len, max_len, on_device)
 
-            def arr(p, count):
-                return np.ctypeslib.as_array(p, shape=(max(count, 1),))[:count].copy()
-            out = {"n_records": int(fp.n_records), "n_short": int(fp.n_short), "n_reads": n, "n_unique": nu,
-                   "max_len": int(fp.max_len), "name_off": arr(fp.name_off, n), "seq_off": arr(fp.seq_off, n),
-                   "name_len": arr(fp.name_len, n), "seq_len": arr(fp.seq_len, n), "order": arr(fp.order, n),
-                   "ustart": arr(fp.ustart, nu + 1)}
+    def _prep_fastq(self, names: bool, ptr: Optional[int], nbytes: int, min_len: int, max_len: int, on_device: bool) -> dict:
+        """musc_reads_prep_fastq, or (names) musc_reads_prep_fastq_names, and what it filled in as the documented dict."""
+        fp, info = _lib.MuscFastqPrep(), _lib.MuscReadNames()
+        args = (ptr, int(nbytes), 1 if on_device else 0, int(min_len), int(max_len), ctypes.byref(fp))
+        self.n_reads = 0
+        if names:
+            self._call("musc_reads_prep_fastq_names", *args, ctypes.byref(info))
+        else:
+            self._call("musc_reads_prep_fastq", *args)
+        try:
+            out = self._fastq_dict(fp, info if names else None)
         finally:
             self._lib.musc_fastq_prep_free(ctypes.byref(fp))
-        self.n_reads = nu
+        self.n_reads = out["n_unique"]
+        return out
+
+    def _fastq_dict(self, fp: _lib.MuscFastqPrep, info: Optional[_lib.MuscReadNames]) -> dict:
+        """Copies of what the structs hold: uint64 offsets; uint32 lengths, order, ustart and ranked.  Takes (frees)
+        info.ranked; fp stays the caller's to free."""
+        n, nu = int(fp.n_reads), int(fp.n_unique)
+        ranked = self._take_u32((info.ranked, n)) if info is not None else None  # (first: it is freed whatever follows)
+        out = {"n_records": int(fp.n_records), "n_short": int(fp.n_short), "n_reads": n, "n_unique": nu, "max_len": int(fp.max_len)}
+        for k in ("name_off", "seq_off", "name_len", "seq_len", "order"):
+            out[k] = _array(getattr(fp, k), n)
+        out["ustart"] = _array(fp.ustart, nu + 1)
+        if info is not None:
+            out["ranked"] = ranked[0]
+            out["names"] = {k: getattr(info, k) for k, _ in info._fields_ if k != "ranked"}
         return out
 
     # ---- the names of the reads on the device (DESIGN.md 23)
     def names_order(self, raw: bytes, name_off, name_len, order, ustart) -> np.ndarray:
         """The members of hand-fed groups in the order of their clipped names (musc_reads_names_order): the arrays are
         those prep_fastq returns for `raw`.  -> the kept reads, group by group, ranked.  Touches no loaded reads."""
-        buf = np.frombuffer(raw, dtype=np.uint8)
+        text, nbytes = _host_ptr(raw)
         no = np.ascontiguousarray(name_off, dtype=np.uint64)
         nl = np.ascontiguousarray(name_len, dtype=np.uint32)
         od = np.ascontiguousarray(order, dtype=np.uint32)
@@ -451,9 +477,8 @@ class Engine:
         if len(no) != n or len(nl) != n or len(us) < 1:
             raise MuscatoError("names_order: name_off, name_len and order must have one entry per kept read, ustart one more than the groups")
         ranked = np.zeros(max(n, 1), dtype=np.uint32)
-        self._check(self._lib.musc_reads_names_order(self._h, buf.ctypes.data if len(buf) else None, len(buf), 0, no.ctypes.data, nl.ctypes.data,
-                                                     n, od.ctypes.data, us.ctypes.data, len(us) - 1, ranked.ctypes.data),
-                    "musc_reads_names_order")
+        self._call("musc_reads_names_order", text, nbytes, 0, no.ctypes.data, nl.ctypes.data, n, od.ctypes.data, us.ctypes.data, len(us) - 1,
+                   ranked.ctypes.data)
         return ranked[:n]
 
     def prep_fastq_names(self, raw: bytes, min_len: int, max_len: int) -> dict:
@@ -461,56 +486,30 @@ class Engine:
         ``count\\tnames`` of every distinct read is left as the context's read text, as set_read_text would leave it.
         -> the dict of prep_fastq, and "ranked" (the kept reads group by group in name order) and "names" (text_bytes,
         line_bytes, n_single, n_counted, n_sorted, n_pairs, key_passes, ms_names)."""
-        buf = np.frombuffer(raw, dtype=np.uint8)
-        return self.prep_fastq_names_device(buf.ctypes.data if len(buf) else None, len(buf), min_len, max_len, on_device=False)
+        return self._prep_fastq(True, *_host_ptr(raw), min_len, max_len, False)
 
     def prep_fastq_names_device(self, ptr: Optional[int], nbytes: int, min_len: int, max_len: int, on_device: bool = True) -> dict:
-        fp, info = _lib.MuscFastqPrep(), _lib.MuscReadNames()
-        self.n_reads = 0
-        self._check(self._lib.musc_reads_prep_fastq_names(self._h, ptr, int(nbytes), 1 if on_device else 0, int(min_len), int(max_len),
-                                                          ctypes.byref(fp), ctypes.byref(info)), "musc_reads_prep_fastq_names")
-        try:
-            n, nu = int(fp.n_reads), int(fp.n_unique)
-
-            def arr(p, count):
-                return np.ctypeslib.as_array(p, shape=(max(count, 1),))[:count].copy() if count else np.zeros(0, dtype=p._type_)
-            out = {"n_records": int(fp.n_records), "n_short": int(fp.n_short), "n_reads": n, "n_unique": nu,
-                   "max_len": int(fp.max_len), "name_off": arr(fp.name_off, n), "seq_off": arr(fp.seq_off, n),
-                   "name_len": arr(fp.name_len, n), "seq_len": arr(fp.seq_len, n), "order": arr(fp.order, n),
-                   "ustart": arr(fp.ustart, nu + 1), "ranked": arr(info.ranked, n),
-                   "names": {k: getattr(info, k) for k, _ in _lib.MuscReadNames._fields_ if k != "ranked"}}
-        finally:
-            self._lib.musc_fastq_prep_free(ctypes.byref(fp))
-            self._lib.musc_free_u32(ctypes.cast(info.ranked, ctypes.c_void_p))
-        self.n_reads = nu
-        return out
+        return self._prep_fastq(True, ptr, nbytes, min_len, max_len, on_device)
 
     def names_text(self, which: int = 0, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
         """Records [rec0, rec0 + nrec) of what prep_fastq_names rendered: which 0, the records ``count\\tnames``; which
         1, the lines ``seq\\tcount\\tnames\\n`` of reads_sorted.txt."""
-        return self._text_range("musc_reads_names_text", self._lib.musc_reads_names_text, (self._h, int(which)), rec0, nrec)
+        return self._text_range("musc_reads_names_text", (int(which),), rec0, nrec)
 
     def names_text_into(self, which: int, rec0: int, nrec: int, dst_ptr: int, capacity: int, on_device: bool) -> int:
         """The same into a buffer of the caller's, on the host or on the device -> the bytes written."""
         nb = ctypes.c_uint64()
-        self._check(self._lib.musc_reads_names_text(self._h, int(which), int(rec0), int(nrec), dst_ptr, int(capacity), 1 if on_device else 0,
-                                                    ctypes.byref(nb)), "musc_reads_names_text")
+        self._call("musc_reads_names_text", int(which), int(rec0), int(nrec), dst_ptr, int(capacity), 1 if on_device else 0,
+                   ctypes.byref(nb))
         return int(nb.value)
 
     def load_reads_packed(self, seqs: Sequence[bytes]) -> None:
-        buf, off = concat(seqs)
-        packed, mask = pack_2bit(buf, int(off[-1]))
-        packed = np.concatenate([packed, np.zeros(8, np.uint8)])
-        mp = mask.ctypes.data if mask is not None else None
-        self._check(self._lib.musc_reads_load_packed(self._h, packed.ctypes.data, mp, off.ctypes.data, len(off) - 1),
-                    "musc_reads_load_packed")
-        self.n_reads = len(off) - 1
+        self.n_reads = self._packed("musc_reads_load_packed", seqs)
 
     def load_reads_packed_ptr(self, bases_ptr: int, mask_ptr: int, off_ptr: int, nreads: int) -> None:
         """musc_reads_load_packed on caller-owned host buffers (e.g. pinned memory): 2-bit bases,
         optional 1-bit X mask (0 = none), uint64 offsets[nreads + 1] in bases."""
-        self._check(self._lib.musc_reads_load_packed(self._h, bases_ptr, mask_ptr or None, off_ptr, nreads),
-                    "musc_reads_load_packed")
+        self._call("musc_reads_load_packed", bases_ptr, mask_ptr or None, off_ptr, nreads)
         self.n_reads = nreads
 
     def load_reads_packed32_ptr(self, bases_ptr: int, mask_ptr: int, lengths_ptr: int, fixed_len: int, nreads: int,
@@ -519,9 +518,8 @@ class Engine:
         lengths (0 = every read has fixed_len bases).  async_upload (fixed length, no mask): returns
         once the upload is queued; the next match overlaps it batch by batch -- the host buffer must
         stay valid until that match returns."""
-        self._check(self._lib.musc_reads_load_packed32(self._h, bases_ptr, mask_ptr or None, lengths_ptr or None,
-                                                       fixed_len, nreads, 1 if async_upload else 0),
-                    "musc_reads_load_packed32")
+        self._call("musc_reads_load_packed32", bases_ptr, mask_ptr or None, lengths_ptr or None, fixed_len, nreads,
+                   1 if async_upload else 0)
         self.n_reads = nreads
 
     # ---- hot path
@@ -533,29 +531,27 @@ class Engine:
         p = cfg.to_params(apply_mmtol, skip_block_check, n_shards)
         self._apply_partition_bases(cfg)
         n = ctypes.c_uint64()
-        self._check(self._lib.musc_match_device(self._h, ctypes.byref(p), ctypes.byref(n)), "musc_match_device")
+        self._call("musc_match_device", ctypes.byref(p), ctypes.byref(n))
         return int(n.value)
 
     def hits_to(self, ptr: int, capacity: int, on_device: bool) -> None:
-        self._check(self._lib.musc_hits_copy(self._h, ptr, capacity, 1 if on_device else 0), "musc_hits_copy")
+        self._call("musc_hits_copy", ptr, capacity, 1 if on_device else 0)
 
     def hits_to_packed(self, ptr: int, capacity: int, on_device: bool, bits: Sequence[int], read_base: int = 0) -> None:
         """The last pass's tuples as one u64 each (read+base | gene | pos | nmiss, widths `bits`)."""
         b = (ctypes.c_int32 * 4)(*bits)
-        self._check(self._lib.musc_hits_copy_packed(self._h, ptr, capacity, 1 if on_device else 0, read_base, b),
-                    "musc_hits_copy_packed")
+        self._call("musc_hits_copy_packed", ptr, capacity, 1 if on_device else 0, read_base, b)
 
     def hits_to_compact(self, words_ptr: int, words_cap: int, counts_ptr: int, counts_cap: int, on_device: bool,
                         bits: Sequence[int]) -> None:
         """The last pass's tuples as one u32 word each (gene | pos | nmiss, widths `bits`) plus one
         byte per loaded read = its number of tuples (musc_hits_copy_compact: the list is read-major)."""
         b = (ctypes.c_int32 * 3)(*bits)
-        self._check(self._lib.musc_hits_copy_compact(self._h, words_ptr, words_cap, counts_ptr, counts_cap,
-                                                     1 if on_device else 0, b), "musc_hits_copy_compact")
+        self._call("musc_hits_copy_compact", words_ptr, words_cap, counts_ptr, counts_cap, 1 if on_device else 0, b)
 
     def unpack_hits(self, src_ptr: int, n: int, on_device: bool, bits: Sequence[int], dst_ptr: int) -> None:
         b = (ctypes.c_int32 * 4)(*bits)
-        self._check(self._lib.musc_hits_unpack(self._h, src_ptr, n, 1 if on_device else 0, b, dst_ptr), "musc_hits_unpack")
+        self._call("musc_hits_unpack", src_ptr, n, 1 if on_device else 0, b, dst_ptr)
 
     def match(self, cfg: Config, apply_mmtol: bool = True, n_shards: int = 1) -> np.ndarray:
         """-> uint32 array [n, 4] of (read_idx, gene_idx, pos, nmiss), order unspecified."""
@@ -569,15 +565,8 @@ class Engine:
         """(read_idx, window) of the probes whose (window,key) block may exceed MaxMatches after
         the last match (empty when n_overflow_blocks == 0).  uint32 [n, 2]."""
         pr, pw, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
-        self._check(self._lib.musc_overflow_probes(self._h, ctypes.byref(pr), ctypes.byref(pw), ctypes.byref(n)),
-                    "musc_overflow_probes")
-        out = np.zeros((n.value, 2), dtype=np.uint32)
-        if n.value:
-            out[:, 0] = np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value,))
-            out[:, 1] = np.ctypeslib.as_array(ctypes.cast(pw, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value,))
-        self._lib.musc_free_u32(pr)
-        self._lib.musc_free_u32(pw)
-        return out
+        self._call("musc_overflow_probes", ctypes.byref(pr), ctypes.byref(pw), ctypes.byref(n))
+        return np.stack(self._take_u32((pr, n.value), (pw, n.value)), axis=1)
 
     def apply_maxmatches(self, apply_mmtol: bool = True) -> dict:
         """Replay the reference's MaxMatches truncation on the device (musc_maxmatches_apply): after a match with
@@ -586,20 +575,19 @@ class Engine:
         -> {"nhits", "suspect_probes", "truncated_blocks"}.  MuscatoError "(2)": no such pass; "(12)": a shape the
         device stage does not take (the context is untouched)."""
         n, ns, nt = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        self._check(self._lib.musc_maxmatches_apply(self._h, 1 if apply_mmtol else 0, ctypes.byref(n), ctypes.byref(ns),
-                                                    ctypes.byref(nt)), "musc_maxmatches_apply")
+        self._call("musc_maxmatches_apply", 1 if apply_mmtol else 0, ctypes.byref(n), ctypes.byref(ns), ctypes.byref(nt))
         return {"nhits": int(n.value), "suspect_probes": int(ns.value), "truncated_blocks": int(nt.value)}
 
     def maxmatches_ms(self) -> float:
         """HIP-event time of the last apply_maxmatches."""
         ms = ctypes.c_float()
-        self._check(self._lib.musc_maxmatches_last_ms(self._h, ctypes.byref(ms)), "musc_maxmatches_last_ms")
+        self._call("musc_maxmatches_last_ms", ctypes.byref(ms))
         return float(ms.value)
 
     def maxmatches_detail(self) -> dict:
         """Of the last apply_maxmatches: the pairs its truncated blocks held, and the time of k_mm_replay alone."""
         n, ms = ctypes.c_uint64(), ctypes.c_float()
-        self._check(self._lib.musc_maxmatches_last_detail(self._h, ctypes.byref(n), ctypes.byref(ms)), "musc_maxmatches_last_detail")
+        self._call("musc_maxmatches_last_detail", ctypes.byref(n), ctypes.byref(ms))
         return {"pairs": int(n.value), "replay_ms": float(ms.value)}
 
     def hits(self) -> np.ndarray:
@@ -615,8 +603,8 @@ class Engine:
         {"path": "fused" | "two-kernel" | "none", "match": k_match_t / k_match_g descriptor or None, "screen": k_screen /
         k_screen_t descriptor or None, "confirm": k_confirm descriptor or None, "block_mode": 0 | 1 | 2, "exact_rerun":
         the pass repeated one whose MaxMatches screening was inconclusive}; a descriptor is decode_instance's dict."""
-        w = (ctypes.c_uint32 * 4)()
-        self._check(self._lib.musc_last_instance(self._h, w), "musc_last_instance")
+        w = (ctypes.c_uint32 * _INSTANCE_WORDS)()
+        self._call("musc_last_instance", w)
         return {"path": "fused" if w[0] else "two-kernel" if w[1] else "none",
                 "match": decode_instance(w[0]), "screen": decode_instance(w[1]), "confirm": decode_instance(w[2]),
                 "block_mode": w[3] & 0xFF, "exact_rerun": bool(w[3] & 0x100)}
@@ -633,16 +621,14 @@ class Engine:
             ab = np.ascontiguousarray(np.asarray(absent, dtype=bool).astype(np.uint8))
             if len(ab) != len(id_rests):
                 raise MuscatoError("absent must have one entry per gene")
-        self._check(self._lib.musc_results_set_gene_text(self._h, buf.ctypes.data, off.ctypes.data,
-                                                         ab.ctypes.data if ab is not None else None, len(off) - 1),
-                    "musc_results_set_gene_text")
+        self._call("musc_results_set_gene_text", buf.ctypes.data, off.ctypes.data, ab.ctypes.data if ab is not None else None,
+                   len(off) - 1)
 
     def set_read_text(self, tails: Sequence[bytes]) -> None:
         """Read r's ``count\\tnames`` tail.  Without it a line ends after its sixth column.  Forgotten by the next
         read load."""
         buf, off = concat(list(tails))
-        self._check(self._lib.musc_results_set_read_text(self._h, buf.ctypes.data, off.ctypes.data, len(off) - 1),
-                    "musc_results_set_read_text")
+        self._call("musc_results_set_read_text", buf.ctypes.data, off.ctypes.data, len(off) - 1)
 
     def results_order(self, hits: Optional[np.ndarray] = None) -> Tuple[int, int]:
         """Order tuples as the lines of results.txt are ordered and compute the line offsets -> (nlines, nbytes).
@@ -650,45 +636,36 @@ class Engine:
         on the device.  Tuples of absent genes are dropped."""
         nl, nb = ctypes.c_uint64(), ctypes.c_uint64()
         self._res_nlines = 0
-        if hits is None:
-            rc = self._lib.musc_results_order(self._h, None, 0, 0, ctypes.byref(nl), ctypes.byref(nb))
-        else:
+        ptr, n = None, 0
+        if hits is not None:
             # (a NULL list means "the device list": an empty host list still passes a pointer)
             a = np.ascontiguousarray(np.asarray(hits, dtype=np.uint32).reshape(-1, 4))
-            ptr = a.ctypes.data if len(a) else np.zeros((1, 4), dtype=np.uint32).ctypes.data
-            rc = self._lib.musc_results_order(self._h, ptr, len(a), 0, ctypes.byref(nl), ctypes.byref(nb))
-        self._check(rc, "musc_results_order")
+            pad = np.zeros((1, 4), dtype=np.uint32)
+            ptr, n = (a.ctypes.data if len(a) else pad.ctypes.data), len(a)
+        self._call("musc_results_order", ptr, n, 0, ctypes.byref(nl), ctypes.byref(nb))
         self._res_nlines = int(nl.value)
         return int(nl.value), int(nb.value)
 
     def results_hits(self) -> np.ndarray:
         """The tuples of the last results_order, in line order: uint32 [nlines, 4]."""
         out = np.zeros((self._res_nlines, 4), dtype=np.uint32)
-        self._check(self._lib.musc_results_hits(self._h, out.ctypes.data, self._res_nlines, 0), "musc_results_hits")
+        self._call("musc_results_hits", out.ctypes.data, self._res_nlines, 0)
         return out
 
-    def _text_range(self, name: str, fn, head: tuple, rec0: int, nrec: Optional[int]) -> bytes:
-        """Records [rec0, rec0 + nrec) of a text call `fn(*head, rec0, nrec, dst, capacity, on_device, &nbytes)`: one
-        call for the size, one that fills a host buffer of that size."""
+    def _text_range(self, name: str, head: tuple, rec0: int, nrec: Optional[int]) -> bytes:
+        """Records [rec0, rec0 + nrec) of the text call `name(ctx, *head, rec0, nrec, dst, capacity, on_device, &nbytes)`;
+        an empty range is b"" after the sizing call alone."""
         count = (1 << 62) if nrec is None else int(nrec)
-        nb = ctypes.c_uint64()
-        self._check(fn(*head, int(rec0), count, None, 0, 0, ctypes.byref(nb)), name)
-        if not nb.value:
-            return b""
-        buf = np.empty(nb.value, dtype=np.uint8)
-        self._check(fn(*head, int(rec0), count, buf.ctypes.data, nb.value, 0, ctypes.byref(nb)), name)
-        return buf.tobytes()
+        return self._sized(lambda dst, cap, nb: self._call(name, *head, int(rec0), count, dst, cap, 0, nb), skip_empty=True)
 
     def results_text(self, line0: int = 0, nlines: Optional[int] = None) -> bytes:
         """The bytes of lines [line0, line0 + nlines) of the last results_order (nlines None: to the end); the
         concatenation over consecutive ranges is results.txt."""
-        return self._text_range("musc_results_text", self._lib.musc_results_text, (self._h,), line0, nlines)
+        return self._text_range("musc_results_text", (), line0, nlines)
 
     def results_ms(self) -> Tuple[float, float]:
         """HIP-event milliseconds of the last results_order and of the results_text calls since."""
-        a, b = ctypes.c_float(), ctypes.c_float()
-        self._check(self._lib.musc_results_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "musc_results_last_ms")
-        return float(a.value), float(b.value)
+        return self._ms_pair("musc_results_last_ms")
 
     # ---- the side outputs of a pass from the resident tuples (DESIGN.md 17)
     def side_prepare(self) -> dict:
@@ -696,11 +673,11 @@ class Engine:
         {"nonmatch": (nrecords, nbytes), "genestats": ..., "readstats": ...}.  Needs the read text, and a gene text
         whose entries are all ``name\\tlen`` without blanks (MuscatoError with code 12 otherwise)."""
         nr, nb = (ctypes.c_uint64 * 3)(), (ctypes.c_uint64 * 3)()
-        self._check(self._lib.musc_side_prepare(self._h, nr, nb), "musc_side_prepare")
+        self._call("musc_side_prepare", nr, nb)
         return {k: (int(nr[w]), int(nb[w])) for w, k in enumerate(("nonmatch", "genestats", "readstats"))}
 
     def _side_text(self, which: int, rec0: int, nrec: Optional[int]) -> bytes:
-        return self._text_range("musc_side_text", self._lib.musc_side_text, (self._h, which), rec0, nrec)
+        return self._text_range("musc_side_text", (which,), rec0, nrec)
 
     def nonmatch_text(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
         """FASTQ records [rec0, rec0 + nrec) of the reads without a results line (nrec None: to the end)."""
@@ -716,16 +693,16 @@ class Engine:
 
     def side_ms(self) -> Tuple[float, float]:
         """HIP-event milliseconds of the last side_prepare and of the text calls since."""
-        a, b = ctypes.c_float(), ctypes.c_float()
-        self._check(self._lib.musc_side_last_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "musc_side_last_ms")
-        return float(a.value), float(b.value)
+        return self._ms_pair("musc_side_last_ms")
 
     def stats(self) -> dict:
         s = _lib.MuscStats()
-        self._check(self._lib.musc_get_stats(self._h, ctypes.byref(s)), "musc_get_stats")
+        self._call("musc_get_stats", ctypes.byref(s))
         return {k: getattr(s, k) for k, _ in s._fields_}
 
 
+_INSTANCE_WORDS = 4  # MUSC_INSTANCE_WORDS
+# family (MUSC_INST_*) -> the kernel and its template arguments after RW, in descriptor order
 _INST_FIELDS = {1: ("k_match_t", ("W", "XM", "WIDE", "SG")), 2: ("k_match_g", (None, None, None, "SG")),
                 3: ("k_screen", ("mask", "one", "lines")), 4: ("k_screen_t", ()), 5: ("k_confirm", ("mask", "w2"))}
 

@@ -39,9 +39,9 @@ def test_cli_partition_flag_help_and_errors(tmp_path):
 def test_lib_exports_partition_entry_points():
     from muscato_amd import _lib
     assert "musc_db_set_partition_bases" in _lib.SYMBOLS and "musc_db_partitions" in _lib.SYMBOLS
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "muscato_hip.h")).read()
-    assert "int musc_db_set_partition_bases(musc_ctx* ctx, uint64_t max_bases);" in hdr
-    assert "int musc_db_partitions(musc_ctx* ctx, uint32_t* first_target, uint32_t cap, uint32_t* n);" in hdr
+    import abi_header as ah
+    assert ah.prototype("musc_db_set_partition_bases") == ("int", ["musc_ctx* ctx", "uint64_t max_bases"])
+    assert ah.prototype("musc_db_partitions") == ("int", ["musc_ctx* ctx", "uint32_t* first_target", "uint32_t cap", "uint32_t* n"])
     from muscato_amd import Config
     assert Config().DbPartitionBases == 0
 

@@ -2,16 +2,14 @@
 the symbols, the layout of musc_db_text_info against the header's declaration, the argtypes, and a refusal of the library
 surfacing as MuscatoError."""
 import ctypes
-import os
-import re
 
 import pytest
 
 from muscato_amd import DbTextInfo, Engine, MuscatoError, _lib, build as mbuild
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header as ah
+
 NEW = ("musc_sz_decode", "musc_db_load_text")
-CTYPE = {"uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float}
 
 
 @pytest.fixture(scope="module")
@@ -20,29 +18,16 @@ def lib():
     return _lib.load()
 
 
-@pytest.fixture(scope="module")
-def hdr():
-    with open(os.path.join(ROOT, "include", "muscato_hip.h")) as f:
-        return re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-
-
-def test_symbols(lib, hdr):
+def test_symbols(lib):
     for s in NEW:
         assert s in _lib.SYMBOLS and hasattr(lib, s) and getattr(lib, s).restype is ctypes.c_int
-        assert re.search(r"\bint\s+%s\s*\(" % s, hdr), s
+        assert ah.prototype(s)[0] == "int", s
     assert lib.musc_abi_version() == 3  # additions only
-    assert re.search(r"#define\s+MUSC_ABI_VERSION\s+3\b", hdr)
+    assert ah.constants()["MUSC_ABI_VERSION"] == 3
 
 
-def test_struct_layout(hdr):
-    m = re.search(r"typedef\s+struct\s+musc_db_text_info\s*\{(.*?)\}\s*musc_db_text_info\s*;", hdr, flags=re.S)
-    assert m
-    fields = []
-    for decl in m.group(1).split(";"):
-        decl = decl.strip()
-        if decl:
-            ctype, names = decl.split(None, 1)
-            fields += [(n.strip(), CTYPE[ctype]) for n in names.split(",")]
+def test_struct_layout():
+    fields = [(n, ah.SCALARS[ctype]) for n, ctype, _ in ah.struct_fields("musc_db_text_info")]
     assert fields == list(_lib.MuscDbTextInfo._fields_)
     assert [n for n, _ in fields] == ["n_targets", "n_bases", "n_odd", "first_odd_target", "reserved", "n_text_bytes", "n_chunks",
                                       "ms_decode", "ms_parse"]

@@ -3,17 +3,16 @@ case covers, and the ABI of musc_reads_prep_fastq -- header, ctypes struct and t
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
 from muscato_amd import _lib
 from oracle import muscato_oracle as orc
 
+import abi_header as ah
 import fastq_cases as fc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "muscato_hip.h")
 KERNELS = os.path.join(ROOT, "muscato_amd", "csrc", "kernels_fastq.hpp")
 
 BY_NAME = {c.name: c for c in fc.cases()}
@@ -151,26 +150,19 @@ FIELDS = ("n_records", "n_short", "n_reads", "n_unique", "max_len", "reserved", 
           "order", "ustart")
 
 
-def test_struct_layout_equals_the_header(tmp_path):
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "muscato_hip.h"\nint main(void) {\n'
-    src += '  printf("%zu\\n", sizeof(musc_fastq_prep));\n'
-    for f in FIELDS:
-        src += '  printf("%%zu\\n", offsetof(musc_fastq_prep, %s));\n' % f
-    src += "  return 0;\n}\n"
-    (tmp_path / "layout.c").write_text(src)
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.dirname(HEADER), "-o", exe, str(tmp_path / "layout.c")])
-    nums = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert nums[0] == ctypes.sizeof(_lib.MuscFastqPrep)
-    assert [n for n, _ in _lib.MuscFastqPrep._fields_] == list(FIELDS)
-    assert nums[1:] == [getattr(_lib.MuscFastqPrep, f).offset for f in FIELDS]
+def test_struct_layout_equals_the_header():
+    c = ah.c_layout(["musc_fastq_prep"])["musc_fastq_prep"]
+    assert c["sizeof"] == ctypes.sizeof(_lib.MuscFastqPrep)
+    assert [n for n, _ in _lib.MuscFastqPrep._fields_] == list(FIELDS) == [n for n, _, _ in ah.struct_fields("musc_fastq_prep")]
+    assert [c["fields"][f][0] for f in FIELDS] == [getattr(_lib.MuscFastqPrep, f).offset for f in FIELDS]
 
 
 def test_header_declares_and_library_exports():
-    text = open(HEADER).read()
-    assert re.search(r"\bint\s+musc_reads_prep_fastq\(musc_ctx\*", text)
-    assert re.search(r"\bvoid\s+musc_fastq_prep_free\(musc_fastq_prep\*", text)
-    assert "#define MUSC_ABI_VERSION 3" in text
+    ret, params = ah.prototype("musc_reads_prep_fastq")
+    assert ret == "int" and params[0].startswith("musc_ctx*")
+    ret, params = ah.prototype("musc_fastq_prep_free")
+    assert ret == "void" and params[0].startswith("musc_fastq_prep*")
+    assert ah.constants()["MUSC_ABI_VERSION"] == 3
     assert {"musc_reads_prep_fastq", "musc_fastq_prep_free"} <= set(_lib.SYMBOLS)
     lib = _lib.load()  # raises when a symbol of SYMBOLS is not exported
     assert hasattr(lib, "musc_reads_prep_fastq") and hasattr(lib, "musc_fastq_prep_free")

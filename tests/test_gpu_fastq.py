@@ -63,6 +63,26 @@ def test_prep_fastq_against_model(eng, name):
         assert eng.stats()["ms_read_prep"] > 0
 
 
+def test_prep_fastq_and_prep_fastq_names_fill_one_dict(eng):
+    """One converter serves both entry points: on the same text the two dicts agree on every common key, in value and in
+    dtype -- with no record at all, with no kept read (every record below min_len), and with a duplicated sequence."""
+    five = b"".join(fc.record(b"n%d" % i, s) for i, s in enumerate((b"ACGTACGT", b"GGGTTT", b"ACGTACGT", b"TTTTT", b"ACGTA")))
+    for raw, records, kept, groups in ((b"", 0, 0, 0), (fc.record(b"s0", b"ACG") + fc.record(b"s1", b"TT"), 2, 0, 0), (five, 5, 5, 4)):
+        a = eng.prep_fastq(raw, 4, 50)
+        b = eng.prep_fastq_names(raw, 4, 50)
+        assert (a["n_records"], a["n_reads"], a["n_unique"], eng.n_reads) == (records, kept, groups, groups)
+        assert list(a) == ["n_records", "n_short", "n_reads", "n_unique", "max_len", "name_off", "seq_off", "name_len", "seq_len", "order",
+                           "ustart"]
+        assert list(b) == list(a) + ["ranked", "names"]
+        for k, v in a.items():
+            if isinstance(v, np.ndarray):
+                assert v.dtype == b[k].dtype == (np.uint64 if k.endswith("_off") else np.uint32), k
+                assert v.shape == b[k].shape == ((groups + 1,) if k == "ustart" else (kept,)) and (v == b[k]).all(), k
+            else:
+                assert type(v) is type(b[k]) is int and v == b[k], k
+        assert b["ranked"].dtype == np.uint32 and sorted(b["ranked"].tolist()) == list(range(kept))
+
+
 def match_case():
     rng = random.Random(31)
     targets = [rand_seq(rng, 300, b"ACGT") for _ in range(20)]

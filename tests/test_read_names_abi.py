@@ -2,16 +2,13 @@
 DESIGN.md 23) as the library exports them and as Python binds them, without a GPU: the symbols, the layout of
 musc_read_names against the header, the Engine methods, and a refusal of the library surfacing as MuscatoError."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
 from muscato_amd import Engine, MuscatoError, _lib, build as mbuild
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "muscato_hip.h")
+import abi_header as ah
+
 NAMES = ("musc_reads_names_order", "musc_reads_prep_fastq_names", "musc_reads_names_text")
 
 
@@ -22,29 +19,20 @@ def lib():
 
 
 def test_symbols(lib):
-    hdr = open(HEADER).read()
     for s in NAMES:
         assert s in _lib.SYMBOLS and hasattr(lib, s) and getattr(lib, s).argtypes is not None and getattr(lib, s).restype is ctypes.c_int
-        assert re.search(r"\bint\s+%s\s*\(" % s, hdr), s
+        assert ah.prototype(s)[0] == "int", s
     assert [len(getattr(lib, s).argtypes) for s in NAMES] == [11, 8, 8]
     assert lib.musc_abi_version() == 3  # additions only
 
 
-def test_struct_layout_against_the_header(tmp_path):
+def test_struct_layout_against_the_header():
     """A C program that includes the header prints the size and every field's offset; ctypes must agree."""
     fields = [k for k, _ in _lib.MuscReadNames._fields_]
-    body = "".join('  printf("%s %%zu\\n", offsetof(musc_read_names, %s));\n' % (k, k) for k in fields)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "%s"\nint main(void) {\n  printf("sizeof %%zu\\n", sizeof(musc_read_names));\n%s  return 0;\n}\n'
-                   % (HEADER, body), encoding="ascii")
-    exe = str(tmp_path / "layout")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-o", exe, str(src)])
-    got = dict(line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(got.pop("sizeof")) == ctypes.sizeof(_lib.MuscReadNames)
-    assert {k: int(v) for k, v in got.items()} == {k: getattr(_lib.MuscReadNames, k).offset for k in fields}
-    m = re.search(r"typedef struct musc_read_names \{(.*?)\} musc_read_names;", open(HEADER).read(), flags=re.S)
-    declared = re.findall(r"\b(\w+)\s*[,;]", re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S))
-    assert declared == fields
+    c = ah.c_layout(["musc_read_names"])["musc_read_names"]
+    assert c["sizeof"] == ctypes.sizeof(_lib.MuscReadNames)
+    assert {k: off for k, (off, _) in c["fields"].items()} == {k: getattr(_lib.MuscReadNames, k).offset for k in fields}
+    assert [k for k, _, _ in ah.struct_fields("musc_read_names")] == fields
 
 
 def test_wrappers_raise_when_the_library_refuses(lib):

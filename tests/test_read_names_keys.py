@@ -12,6 +12,7 @@ import pytest
 
 from muscato_amd import build as mbuild
 
+import abi_header as ah
 import read_names_cases as rn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +24,7 @@ CMP_WORDS = (rn.NAME_KEEP + rn.DOTS + 7) // 8
 def code(path):
     """The file without its comments."""
     src = open(path).read()
-    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", " ", src, flags=re.S))
+    return ah.strip_comments(src, line_comments=True)
 
 
 def test_the_header_is_plain_cxx_and_listed(tmp_path):

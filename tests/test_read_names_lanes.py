@@ -9,6 +9,8 @@ import subprocess
 
 from muscato_amd import build as mbuild
 
+import abi_header as ah
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "muscato_amd", "csrc")
 LANES = os.path.join(CSRC, "read_names_lanes.hpp")
@@ -18,7 +20,7 @@ CHECK = os.path.join(CSRC, "host", "read_names_plan_check.cpp")
 def code(path):
     """The file without its comments."""
     src = open(path).read()
-    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", " ", src, flags=re.S))
+    return ah.strip_comments(src, line_comments=True)
 
 
 def test_the_header_is_plain_cxx_and_listed():

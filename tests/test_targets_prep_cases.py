@@ -4,7 +4,6 @@ plain-text fixtures, the coverage the GPU tests rely on, and the new entry point
 Python binds them."""
 import ctypes
 import os
-import re
 import subprocess
 
 import pytest
@@ -12,13 +11,13 @@ import pytest
 from muscato_amd import Engine, MuscatoError, TargetsPrepInfo, _lib, build as mbuild
 from oracle import muscato_oracle as orc
 
+import abi_header as ah
 import sz_cases as sc
 import targets_prep_cases as tp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "muscato_amd", "bin")
 NEW = ("musc_targets_prep", "musc_targets_prep_text", "musc_targets_prep_load", "musc_targets_prep_free", "musc_sz_frame")
-CTYPE = {"uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float}
 
 
 def check_against_oracle(text, fasta, rev):
@@ -118,29 +117,16 @@ def lib():
     return _lib.load()
 
 
-@pytest.fixture(scope="module")
-def hdr():
-    with open(os.path.join(ROOT, "include", "muscato_hip.h")) as f:
-        return re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-
-
-def test_symbols(lib, hdr):
+def test_symbols(lib):
     for s in NEW:
         assert s in _lib.SYMBOLS and hasattr(lib, s) and getattr(lib, s).restype is ctypes.c_int
-        assert re.search(r"\bint\s+%s\s*\(" % s, hdr), s
+        assert ah.prototype(s)[0] == "int", s
     assert lib.musc_abi_version() == 3  # additions only
-    assert re.search(r"#define\s+MUSC_ABI_VERSION\s+3\b", hdr)
+    assert ah.constants()["MUSC_ABI_VERSION"] == 3
 
 
-def test_struct_layout(hdr):
-    m = re.search(r"typedef\s+struct\s+musc_targets_prep_info\s*\{(.*?)\}\s*musc_targets_prep_info\s*;", hdr, flags=re.S)
-    assert m
-    fields = []
-    for decl in m.group(1).split(";"):
-        decl = decl.strip()
-        if decl:
-            ctype, names = decl.split(None, 1)
-            fields += [(n.strip(), CTYPE[ctype]) for n in names.split(",")]
+def test_struct_layout():
+    fields = [(n, ah.SCALARS[ctype]) for n, ctype, _ in ah.struct_fields("musc_targets_prep_info")]
     assert fields == list(_lib.MuscTargetsPrepInfo._fields_)
     assert [n for n, _ in fields] == ["n_lines", "n_records", "n_targets", "n_dropped", "stop_line", "n_subx", "n_seq_bytes", "n_id_bytes",
                                       "ms", "reserved"]
@@ -149,7 +135,7 @@ def test_struct_layout(hdr):
     assert [f for f in TargetsPrepInfo.__dataclass_fields__] == [n for n, _ in fields if n != "reserved"]
 
 
-def test_argtypes(lib, hdr):
+def test_argtypes(lib):
     vp, u64, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
     assert lib.musc_targets_prep.argtypes == [vp, vp, u64, ci, ci, ci, ctypes.POINTER(_lib.MuscTargetsPrepInfo)]
     assert lib.musc_targets_prep_text.argtypes == [vp, ci, u64, u64, vp, ci]
@@ -158,8 +144,7 @@ def test_argtypes(lib, hdr):
     assert lib.musc_sz_frame.argtypes == [vp, vp, u64, ci, vp, u64, ci, ctypes.POINTER(u64)]
     # and against the prototypes: as many parameters, pointers as pointers, 64-bit integers as 64-bit
     for name in NEW:
-        args = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr).group(1)
-        params = [a.strip() for a in args.split(",")]
+        params = ah.prototype(name)[1]
         at = getattr(lib, name).argtypes
         assert len(at) == len(params), name
         for decl, ct in zip(params, at):
