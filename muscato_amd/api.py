@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _sam
 
 
 class MuscatoError(RuntimeError):
@@ -694,6 +694,41 @@ class Engine:
     def side_ms(self) -> Tuple[float, float]:
         """HIP-event milliseconds of the last side_prepare and of the text calls since."""
         return self._ms_pair("musc_side_last_ms")
+
+    # ---- SAM output from the resident tuples (DESIGN.md 28)
+    def sam_prepare(self, rev_pairs: bool = False) -> dict:
+        """Compare every span of the last results_order with its read and lay out the SAM records and the header ->
+        {"records": n, "header_bytes": b, "record_bytes": b}.  rev_pairs: the database holds reverse complements, target
+        2k + 1 that of target 2k.  MuscatoError with code 12: rev_pairs with an odd number of targets or a pair of
+        unequal lengths, or a gene text whose first token is empty."""
+        _sam.bind()
+        n, hb, rb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._call("musc_sam_prepare", 1 if rev_pairs else 0, ctypes.byref(n), ctypes.byref(hb), ctypes.byref(rb))
+        return {"records": int(n.value), "header_bytes": int(hb.value), "record_bytes": int(rb.value)}
+
+    def sam_header(self) -> bytes:
+        """The header of the last sam_prepare: @HD, one @SQ per target with an id line, @PG."""
+        _sam.bind()
+        return self._text_range("musc_sam_text", (_sam.SAM_HEADER,), 0, None)
+
+    def sam_text(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
+        """Records [rec0, rec0 + nrec) of the last sam_prepare (nrec None: to the end), one per line of results.txt in
+        the same order; header + the concatenation over consecutive ranges is the SAM file."""
+        _sam.bind()
+        return self._text_range("musc_sam_text", (_sam.SAM_RECORDS,), rec0, nrec)
+
+    def sam_text_into(self, which: int, rec0: int, nrec: int, dst_ptr: int, capacity: int, on_device: bool) -> int:
+        """Records [rec0, rec0 + nrec) of text `which` (0 header, 1 records) into caller memory (host or device) ->
+        the bytes written."""
+        _sam.bind()
+        nb = ctypes.c_uint64()
+        self._call("musc_sam_text", int(which), int(rec0), int(nrec), dst_ptr, int(capacity), 1 if on_device else 0, ctypes.byref(nb))
+        return int(nb.value)
+
+    def sam_ms(self) -> Tuple[float, float]:
+        """HIP-event milliseconds of the last sam_prepare and of the text calls since."""
+        _sam.bind()
+        return self._ms_pair("musc_sam_last_ms")
 
     def stats(self) -> dict:
         s = _lib.MuscStats()

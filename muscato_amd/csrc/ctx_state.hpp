@@ -32,6 +32,7 @@ struct State {
   struct Ordered { uint64_t reads = 0, db = 0, gtext = 0, ttext = 0, list = 0, order = 0; } ordered;  // res_hits / res_off
   uint64_t tokens = 0;  // side_tok: the ttext it was cut from
   uint64_t side = 0;    // the side tables: the order they describe
+  uint64_t sam = 0;     // the SAM tables: the order they describe
 
   // ---- the causes
   void reads_dropped() { g.reads++, g.pass_inputs++; }
@@ -48,6 +49,8 @@ struct State {
   void tokens_made() { tokens = g.ttext; }
   void side_begins() { side = 0; }
   void side_made() { side = g.order; }
+  void sam_begins() { sam = 0; }
+  void sam_made() { sam = g.order; }
 
   // ---- the questions
   bool may_order_resident() const { return list.origin != LIST_NONE && list.reads == g.reads && list.db == g.db; }
@@ -62,6 +65,7 @@ struct State {
            : !form_ok ? SIDE_FORM : nreads >= 0xFFFFFFF0ull ? SIDE_TOO_MANY_READS : SIDE_OK;
   }
   bool may_side_text() const { return side == g.order && ordered_current() && !list_changed_since_order(); }
+  bool may_sam_text() const { return sam == g.order && ordered_current(); }  // (as results.txt: a later pass does not outdate the ordered list)
 };
 
 // What a cache of the pass driver was made for: compared field by field (musc_params may carry padding, and a caller

@@ -39,6 +39,8 @@ struct Config {
   int GPUs = 1;          // --GPUs: shard the unique reads over this many devices
   int Device = 0;        // --Device: first device ordinal
   long long DbPartitionBases = 0;  // --DbPartitionBases: most target bases indexed at once, 0 = automatic
+  std::string SamFileName;         // --SamFileName: also write the results as SAM; empty = no SAM file
+  bool SamRev = false;             // --SamRev: the gene file was prepared with -rev, odd targets are reverse strands
 };
 
 struct Die : std::runtime_error {
@@ -99,7 +101,7 @@ inline void config_from_json(const std::string& text, Config& c) {
       else if (key == "geneidfilename") c.GeneIdFileName = v; else if (key == "resultsfilename") c.ResultsFileName = v;
       else if (key == "tempdir") c.TempDir = v; else if (key == "logdir") c.LogDir = v;
       else if (key == "matchmode") c.MatchMode = v; else if (key == "sorttemp") c.SortTemp = v;
-      else if (key == "sortmem") c.SortMem = v;
+      else if (key == "sortmem") c.SortMem = v; else if (key == "samfilename") c.SamFileName = v;
     } else if (j.p < text.size() && text[j.p] == '[') {
       j.need('[');
       std::vector<int> v;
@@ -121,7 +123,7 @@ inline void config_from_json(const std::string& text, Config& c) {
       else if (key == "sortpar") c.SortPar = (int)d; else if (key == "nocleantemp") c.NoCleanTemp = b;
       else if (key == "cpuprofile") c.CPUProfile = b; else if (key == "maxmismatch") c.MaxMismatch = (int)d;
       else if (key == "gpus") c.GPUs = (int)d; else if (key == "device") c.Device = (int)d;
-      else if (key == "dbpartitionbases") c.DbPartitionBases = (long long)d;
+      else if (key == "dbpartitionbases") c.DbPartitionBases = (long long)d; else if (key == "samrev") c.SamRev = b;
     }
   } while (j.eat(','));
   j.need('}');
@@ -157,7 +159,9 @@ inline std::string config_to_json(const Config& c) {
          "," + N("SortPar", c.SortPar) + "," + S("SortTemp", c.SortTemp) + "," + S("SortMem", c.SortMem) + "," +
          B("NoCleanTemp", c.NoCleanTemp) + "," + B("CPUProfile", c.CPUProfile) + "," +
          N("MaxMismatch", c.MaxMismatch) + "," + N("GPUs", c.GPUs) + "," + N("Device", c.Device) + "," +
-         N("DbPartitionBases", c.DbPartitionBases) + "}\n";
+         N("DbPartitionBases", c.DbPartitionBases) +
+         // (the SAM keys only when a SAM file is asked for: without the flag the saved configuration is what it always was)
+         (c.SamFileName.empty() ? std::string() : "," + S("SamFileName", c.SamFileName) + "," + B("SamRev", c.SamRev)) + "}\n";
 }
 
 // ---- Go `flag` syntax: -name, --name, -name=value, -name value; bools take no value unless
@@ -194,6 +198,8 @@ inline const std::vector<FlagSpec>& muscato_flags() {
       {"GPUs", 'i', "(addition) number of GPUs to shard the reads over"},
       {"Device", 'i', "(addition) first GPU ordinal"},
       {"DbPartitionBases", 'i', "(addition) most target bases indexed at once; 0 = automatic"},
+      {"SamFileName", 's', "(addition) also write the results as a SAM file of this name"},
+      {"SamRev", 'b', "(addition) the gene file was prepared with -rev: odd targets are reverse strands in the SAM file"},
   };
   return f;
 }
@@ -286,6 +292,8 @@ inline Config handle_args(int argc, char** argv) {
   if (has("GPUs") && I("GPUs")) c.GPUs = I("GPUs");
   if (has("Device")) c.Device = I("Device");
   if (has("DbPartitionBases")) c.DbPartitionBases = strtoll(fl["DbPartitionBases"].c_str(), nullptr, 0);
+  if (has("SamFileName") && !fl["SamFileName"].empty()) c.SamFileName = fl["SamFileName"];
+  if (has("SamRev")) c.SamRev = fl["SamRev"] == "true";
   if (c.ResultsFileName.empty()) {
     c.ResultsFileName = "results.txt";
     fputs("ResultsFileName not specified, defaulting to 'results.txt'\n", stderr);

@@ -9,10 +9,13 @@
 // after the plan, is held to its boolean expression in that product too -- its value, its default and its demotion
 // change with the combination, so that every pair of it with another input occurs -- and over the whole product of
 // what the expression reads (check_names_plan).
+// MUSC_SAM (the SAM file) is held to its boolean expression in the same way (check_sam_plan), and the size
+// rules of a SAM record (sam_plan.hpp) to text that is built byte by byte (check_sam_sizes).
 // The name rules run on fixed cases and on seeded random groups whose names sit in heap blocks of their exact size.
 // It needs no GPU and is not part of the library.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <random>
 #include <string>
@@ -21,6 +24,7 @@
 #include "check.hpp"
 #include "cli_names.hpp"
 #include "cli_plan.hpp"
+#include "../sam_plan.hpp"
 
 namespace {
 
@@ -233,6 +237,125 @@ unsigned long long check_names_plan() {
   return n;
 }
 
+// MUSC_SAM over its six values, both defaults and the refusal of the device stage, with every other variable over
+// {unset, host, device}, GPUs over {1, 2, 3}, odd target bytes or none, an overflow or none and a refused replay or none:
+// the SAM file is the device's exactly when results.txt was ordered there from the resident list, the variable or the
+// default says device, and musc_sam_prepare did not refuse; and no other stage moves with it.
+unsigned long long check_sam_plan() {
+  static const char* const V[6] = {nullptr, "", "host", "device", "rccl", "junk"};
+  static const char* const O[3] = {nullptr, "host", "device"};
+  unsigned long long n = 0;
+  for (int d = 0; d < 2; d++)
+    for (int e = 0; e < 6; e++)
+      for (int o = 0; o < 81; o++)
+        for (int gpus = 1; gpus <= 3; gpus++)
+          for (int x = 0; x < 16; x++) {
+            PlanDefaults D;
+            D.sam = d != 0;
+            PlanEnv env;
+            env.sam = V[e];
+            env.maxmatches = O[o % 3], env.results = O[o / 3 % 3], env.side = O[o / 9 % 3], env.targets = O[o / 27];
+            const bool overflow = (x & 1) != 0, replay_refused = (x & 2) != 0, sam_refused = (x & 4) != 0;
+            const size_t nodd = (x & 8) != 0;
+            const Events ev = {overflow, false, false, false, replay_refused, false, false};
+            // the expression
+            const Outcome old = old_run(env, gpus, nodd, ev, D);
+            const bool env_device = env.sam && !strcmp(env.sam, "device"), env_host = env.sam && !strcmp(env.sam, "host");
+            const bool want = env_device || (!env_host && D.sam);
+            const bool tried = old.results_on_device && old.list_on_device && want;
+            // the plan, as stage_results and stage_sam use it
+            Placement plan = make_placement(env, gpus, D);
+            if (nodd) plan.demote(Demotion::OddTargetBytes);
+            if (overflow && plan.maxmatches == Where::Device && replay_refused) plan.demote(Demotion::ReplayRefused);
+            const bool resident = plan.list_on_device(overflow);
+            EXPECT(resident == old.list_on_device);
+            EXPECT_MSG(plan.sam_on_device(resident) == tried, "sam plan differs: default %d env %d others %d GPUs %d events %d", d, e, o, gpus, x);
+            if (plan.sam_on_device(resident) && sam_refused) plan.demote(Demotion::SamRefused);
+            EXPECT(plan.sam_on_device(resident) == (tried && !sam_refused));
+            EXPECT(plan.sam == Where::Host || plan.results == Where::Device);
+            // nothing else moves
+            PlanEnv unset = env;
+            unset.sam = nullptr;
+            EXPECT(new_run(env, gpus, nodd, ev, D) == new_run(unset, gpus, nodd, ev, PlanDefaults()));
+            n++;
+          }
+  EXPECT(!PlanDefaults().sam);  // unmeasured: the host writes the SAM file unless MUSC_SAM=device
+  return n;
+}
+
+// The size rules of sam_plan.hpp against text built byte by byte: decimal widths, the CIGAR, MD over random mismatch
+// places (forward and reverse: the same length), a whole record, and the name rules on blocks of their exact size.
+unsigned long long check_sam_sizes() {
+  using namespace musc_sam;
+  unsigned long long n = 0;
+  for (uint64_t v : {0ull, 9ull, 10ull, 99ull, 100ull, 65535ull, 4294967295ull, 4294967296ull, 9999999999ull, 10000000000ull})
+    EXPECT(ndigits(v) == std::to_string(v).size());
+  EXPECT(flag(false, true) == 0 && flag(true, true) == 16 && flag(false, false) == 256 && flag(true, false) == 272);
+  EXPECT(pos1(false, 100, 7, 20) == 8 && pos1(true, 100, 7, 20) == 74 && pos1(true, 100, 100, 0) == 1 && pos1(false, 100, 100, 0) == 101);
+  std::mt19937 rng(28);
+  for (int it = 0; it < 20000; it++) {
+    const uint32_t L = 1 + rng() % (it % 50 == 0 ? 5000 : 300), S = it % 7 == 0 ? rng() % (L + 1) : L;
+    std::string cigar = S == 0 ? "*" : std::to_string(S) + "M" + (L > S ? std::to_string(L - S) + "S" : "");
+    EXPECT(cigar_bytes(L, S) == cigar.size());
+    // mismatch places: none, all, or each with a probability that leaves runs of every width
+    const unsigned mode = rng() % 8;
+    std::vector<bool> mis(S);
+    for (uint32_t j = 0; j < S; j++) mis[j] = mode == 0 ? false : mode == 1 ? true : rng() % (mode == 2 ? 2 : 120) == 0;
+    MdSize z;
+    std::string fwd, rev;
+    size_t run = 0;
+    for (uint32_t j = 0; j < S; j++) {
+      if (!mis[j]) { run++; continue; }
+      z.mismatch(j);
+      fwd += std::to_string(run) + "A";
+      run = 0;
+    }
+    fwd += std::to_string(run);
+    run = 0;
+    for (uint32_t j = S; j-- > 0;) {
+      if (!mis[j]) { run++; continue; }
+      rev += std::to_string(run) + "A";
+      run = 0;
+    }
+    rev += std::to_string(run);
+    EXPECT(z.finish(S) == fwd.size() && fwd.size() == rev.size());
+    const RecordSizes r = {1 + (uint32_t)(rng() % 254), flag(rng() & 1, rng() & 1), 1 + (uint32_t)(rng() % 40), 1 + rng() % 5000000000ull, L, S, z.nmis,
+                           z.finish(S), 1 + (uint32_t)(rng() % 3000), 1 + (uint32_t)(rng() % 3000), (uint32_t)(rng() % 70000), (uint32_t)(rng() % 9)};
+    const std::string text = std::string(r.qname, 'q') + "\t" + std::to_string(r.flag) + "\t" + std::string(r.rname, 'r') + "\t" + std::to_string(r.pos1) +
+                             "\t255\t" + cigar + "\t*\t0\t0\t" + std::string(L, 'A') + "\t*\tNM:i:" + std::to_string(r.d) + "\tMD:Z:" + fwd + "\tNH:i:" +
+                             std::to_string(r.nh) + "\tHI:i:" + std::to_string(r.hi) + "\tXM:i:" + std::to_string(r.nmiss) +
+                             (r.count_len ? "\tXC:i:" + std::string(r.count_len, '7') : std::string()) + "\n";
+    EXPECT(record_bytes(r) == text.size());
+    n++;
+  }
+  EXPECT(sq_bytes(4, 12345) == std::string("@SQ\tSN:chr1\tLN:12345\n").size());
+  EXPECT(std::string(HD_LINE).size() == HD_BYTES && std::string(PG_LINE).size() == PG_BYTES && HD_LINE[HD_BYTES - 1] == '\n');
+  // the name rules, each text in a heap block of its exact size
+  struct T { const char* tail; size_t n; uint32_t count_len, q0, qlen; };
+  const std::string long_name = "5\t" + std::string(300, 'n');
+  const T tails[] = {{"12\tname;x", 9, 2, 3, 4}, {"1\t@name rest", 12, 1, 3, 4}, {"1\t>n", 4, 1, 3, 1}, {"1\t@@n", 5, 1, 3, 2}, {"7", 1, 1, 1, 0},
+                     {"", 0, 0, 0, 0}, {"\tn", 2, 0, 1, 1}, {"x1\tn", 4, 0, 3, 1}, {"3\t", 2, 1, 2, 0}, {"3\t;n", 4, 1, 2, 0}, {"3\t n", 4, 1, 2, 0},
+                     {"3\t@", 3, 1, 3, 0}, {"3\tn\x0bm", 5, 1, 2, 1}, {long_name.c_str(), long_name.size(), 1, 2, QNAME_MAX}};
+  for (const T& t : tails) {
+    std::unique_ptr<unsigned char[]> b(new unsigned char[t.n ? t.n : 1]);
+    memcpy(b.get(), t.tail, t.n);
+    const TailSpans s = tail_spans(b.get(), t.n);
+    EXPECT_MSG(s.count_len == t.count_len && s.qlen == t.qlen && (s.qlen == 0 || s.q0 == t.q0), "tail_spans(%s)", t.tail);
+    n++;
+  }
+  struct G { const char* text; size_t n; uint32_t n0, len; };
+  const G genes[] = {{"chr1\t300", 8, 0, 4}, {">chr1 x\t300", 11, 1, 4}, {"  chr2", 6, 2, 4}, {">>a", 3, 1, 2}, {">", 1, 1, 0}, {"> a", 3, 1, 0},
+                     {"", 0, 0, 0}, {" \t ", 3, 3, 0}, {"\t30", 3, 1, 2}};
+  for (const G& g : genes) {
+    std::unique_ptr<unsigned char[]> b(new unsigned char[g.n ? g.n : 1]);
+    memcpy(b.get(), g.text, g.n);
+    const NameSpan s = rname_span(b.get(), g.n);
+    EXPECT_MSG(s.len == g.len && (s.len == 0 || s.n0 == g.n0), "rname_span(%s)", g.text);
+    n++;
+  }
+  return n;
+}
+
 // ---- the names ------------------------------------------------------------------------------------------------
 
 // a name in a heap block of its exact size (no terminator, no slack): a read past it is the sanitizer's to see
@@ -340,8 +463,9 @@ unsigned long long check_names() {  // -> the random groups seen
 }  // namespace
 
 int main() {
-  char census[96];
-  const unsigned long long n_plans = check_plan() + check_names_plan(), n_groups = check_names();
-  snprintf(census, sizeof census, "%llu plan combinations, %llu random name groups", n_plans, n_groups);
+  char census[128];
+  const unsigned long long n_plans = check_plan() + check_names_plan() + check_sam_plan(), n_groups = check_names();
+  const unsigned long long n_sam = check_sam_sizes();
+  snprintf(census, sizeof census, "%llu plan combinations, %llu random name groups, %llu SAM size cases", n_plans, n_groups, n_sam);
   return check_done("cli_plan_check", census);
 }

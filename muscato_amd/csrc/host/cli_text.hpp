@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../../include/muscato_hip.h"
+#include "../sam_plan.hpp"
 
 namespace musc {
 
@@ -70,11 +71,14 @@ inline std::vector<std::string> fields(const std::string& s) {
 // of ResultsFileName: sort -k5 + join with the id file + cut (:524-611) turns the gene number
 // into "name\tlen" (hits whose number is absent from the id file are unpairable and vanish);
 // sort -k1 (:657) orders the six-column lines bytewise; join (:659) appends count and names.
-inline std::string results_text(const musc_hit* hits, size_t nhits, const std::vector<UniqueRead>& reads,
-                                const std::vector<std::string>& targets,
-                                const std::map<uint64_t, std::string>& id_rest) {
-  struct Line { std::string six; uint32_t read; };
-  std::vector<Line> lines;
+struct ResultsLine {
+  std::string six;  // the first six columns
+  musc_hit hit;
+};
+inline std::vector<ResultsLine> results_lines(const musc_hit* hits, size_t nhits, const std::vector<UniqueRead>& reads,
+                                              const std::vector<std::string>& targets,
+                                              const std::map<uint64_t, std::string>& id_rest) {
+  std::vector<ResultsLine> lines;
   lines.reserve(nhits);
   for (size_t i = 0; i < nhits; i++) {
     const musc_hit& h = hits[i];
@@ -90,19 +94,146 @@ inline std::string results_text(const musc_hit* hits, size_t nhits, const std::v
     six += std::to_string(h.nmiss);
     six += '\t';
     six += it->second;
-    lines.push_back(Line{std::move(six), h.read_idx});
+    lines.push_back(ResultsLine{std::move(six), h});
   }
-  std::sort(lines.begin(), lines.end(), [](const Line& a, const Line& b) { return a.six < b.six; });
+  std::sort(lines.begin(), lines.end(), [](const ResultsLine& a, const ResultsLine& b) { return a.six < b.six; });
+  return lines;
+}
+
+inline std::string results_text(const std::vector<ResultsLine>& lines, const std::vector<UniqueRead>& reads) {
   std::string out;
   for (auto& l : lines) {
     out += l.six;
     out += '\t';
-    out += std::to_string(reads[l.read].count);
+    out += std::to_string(reads[l.hit.read_idx].count);
     out += '\t';
-    out += reads[l.read].names;
+    out += reads[l.hit.read_idx].names;
     out += '\n';
   }
   return out;
+}
+
+inline std::string results_text(const musc_hit* hits, size_t nhits, const std::vector<UniqueRead>& reads,
+                                const std::vector<std::string>& targets,
+                                const std::map<uint64_t, std::string>& id_rest) {
+  return results_text(results_lines(hits, nhits, reads, targets, id_rest), reads);
+}
+
+// ---- SAM: the format's C++ copy, and what the CLI writes when the device does not.  One record per
+// tuple of `ordered`, the tuples of results.txt in its line order (results_lines, or musc_results_hits); tails[r] is
+// read r's count\tnames, tails == nullptr: no read text.  The sizes, the name rules and the refusals are sam_plan.hpp's,
+// which the device shares.  False: refused (what musc_sam_prepare answers with code 12), *why says which rule.
+inline char sam_base(char c, bool rev) {
+  switch (c) {
+    case 'A': return rev ? 'T' : 'A';
+    case 'C': return rev ? 'G' : 'C';
+    case 'G': return rev ? 'C' : 'G';
+    case 'T': return rev ? 'A' : 'T';
+  }
+  return 'N';
+}
+
+// seq(r) -> the bases of read r (a const std::string&), tail(r) -> its count\tnames (a std::string), asked only when have_tails
+template <class Seq, class Tail>
+inline bool sam_text_of(const musc_hit* ordered, size_t n, Seq seq, Tail tail_of, bool have_tails, const std::vector<std::string>& targets,
+                        const std::map<uint64_t, std::string>& id_rest, bool rev_pairs, std::string* out, std::string* why) {
+  auto u = [](const std::string& s) { return reinterpret_cast<const unsigned char*>(s.data()); };
+  const size_t nt = targets.size();
+  auto rest = [&](size_t g) -> const std::string* {
+    auto it = id_rest.find(g);
+    return it == id_rest.end() ? nullptr : &it->second;
+  };
+  // ---- the refusals
+  if (rev_pairs && (nt & 1)) return *why = "rev_pairs with an odd number of targets", false;
+  for (size_t g = 0; rev_pairs && g + 1 < nt; g += 2)
+    if (targets[g].size() != targets[g + 1].size()) return *why = "rev_pairs, and the two targets of a pair differ in length", false;
+  std::vector<musc_sam::NameSpan> name(nt, musc_sam::NameSpan{0, 0});
+  for (size_t g = 0; g < nt; g++)
+    if (const std::string* r = rest(g)) name[g] = musc_sam::rname_span(u(*r), r->size());
+  for (size_t g = 0; g < nt; g++) {
+    if (!rest(g)) continue;
+    const size_t f = rev_pairs && (g & 1) ? g - 1 : g;
+    if (!rest(f) || name[f].len == 0) return *why = "the gene text of a target with an id line (or of its even partner) has an empty first token", false;
+  }
+  // ---- the header
+  std::string& o = *out;
+  o = musc_sam::HD_LINE;
+  for (size_t t = 0; t < nt; t++) {
+    if (!rest(t) || (rev_pairs && (t & 1))) continue;
+    o += "@SQ\tSN:";
+    o.append(*rest(t), name[t].n0, name[t].len);
+    o += "\tLN:" + std::to_string(targets[t].size()) + "\n";
+  }
+  o += musc_sam::PG_LINE;
+  // ---- the records: NH from the runs of equal reads (the list is read-major)
+  for (size_t i = 0, run0 = 0, run1 = 0; i < n; i++) {
+    if (i == run1) {
+      run0 = i;
+      while (run1 < n && ordered[run1].read_idx == ordered[i].read_idx) run1++;
+    }
+    const musc_hit& h = ordered[i];
+    const std::string &read = seq(h.read_idx), &t = targets[h.gene_idx];
+    const size_t L = read.size(), S = std::min(L, t.size() - h.pos);
+    const bool rev = rev_pairs && (h.gene_idx & 1);
+    const size_t f = rev ? h.gene_idx - 1 : h.gene_idx;
+    const std::string tail_text = have_tails ? tail_of(h.read_idx) : std::string();
+    const std::string* tail = &tail_text;
+    const musc_sam::TailSpans ts = have_tails ? musc_sam::tail_spans(u(*tail), tail->size()) : musc_sam::TailSpans{0, 0, 0, 0};
+    const size_t before = o.size();
+    if (ts.qlen) o.append(*tail, ts.q0, ts.qlen);
+    else o += '*';
+    o += '\t' + std::to_string(musc_sam::flag(rev, i == run0)) + '\t';
+    o.append(*rest(f), name[f].n0, name[f].len);
+    const uint64_t p1 = musc_sam::pos1(rev, t.size(), h.pos, S);
+    o += '\t' + std::to_string(p1) + "\t255\t";
+    const std::string clip = L > S ? std::to_string(L - S) + "S" : "", m = std::to_string(S) + "M";
+    o += S == 0 ? "*" : rev ? clip + m : m + clip;
+    o += "\t*\t0\t0\t";
+    if (L == 0) o += '*';
+    for (size_t j = 0; j < L; j++) o += sam_base(read[rev ? L - 1 - j : j], rev);
+    // NM and MD, walked in forward-strand order
+    std::string md;
+    size_t d = 0, run = 0;
+    for (size_t w = 0; w < S; w++) {
+      const size_t j = rev ? S - 1 - w : w;
+      const char a = read[j], b = t[h.pos + j];
+      auto code = [](char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T' ? c : 'X'; };
+      if (code(a) == code(b)) {
+        run++;
+        continue;
+      }
+      d++;
+      md += std::to_string(run);
+      md += sam_base(b, rev);
+      run = 0;
+    }
+    md += std::to_string(run);
+    o += "\t*\tNM:i:" + std::to_string(d) + "\tMD:Z:" + md + "\tNH:i:" + std::to_string(run1 - run0) + "\tHI:i:" + std::to_string(i - run0 + 1) +
+         "\tXM:i:" + std::to_string(h.nmiss);
+    if (ts.count_len) o += "\tXC:i:" + tail->substr(0, ts.count_len);
+    o += '\n';
+    // (the size rule the device lays its records out by)
+    musc_sam::RecordSizes z{ts.qlen ? ts.qlen : 1u, musc_sam::flag(rev, i == run0), name[f].len, p1, (uint32_t)L, (uint32_t)S, (uint32_t)d,
+                            (uint32_t)md.size(), (uint32_t)(run1 - run0), (uint32_t)(i - run0 + 1), h.nmiss, ts.count_len};
+    if (musc_sam::record_bytes(z) != o.size() - before) return *why = "sam_plan.hpp's size rule and sam_text disagree", false;
+  }
+  return true;
+}
+
+// ... over reads and tails given as strings (tails == nullptr: no read text)
+inline bool sam_text(const musc_hit* ordered, size_t n, const std::vector<std::string>& read_seqs, const std::vector<std::string>& targets,
+                     const std::map<uint64_t, std::string>& id_rest, const std::vector<std::string>* tails, bool rev_pairs,
+                     std::string* out, std::string* why) {
+  return sam_text_of(ordered, n, [&](uint32_t r) -> const std::string& { return read_seqs[r]; },
+                     [&](uint32_t r) { return (*tails)[r]; }, tails != nullptr, targets, id_rest, rev_pairs, out, why);
+}
+
+// ... over the unique reads of a run: the tail of a read is its count, a tab and its names, as in results.txt
+inline bool sam_text(const musc_hit* ordered, size_t n, const std::vector<UniqueRead>& reads, const std::vector<std::string>& targets,
+                     const std::map<uint64_t, std::string>& id_rest, bool rev_pairs, std::string* out, std::string* why) {
+  return sam_text_of(ordered, n, [&](uint32_t r) -> const std::string& { return reads[r].seq; },
+                     [&](uint32_t r) { return std::to_string(reads[r].count) + "\t" + reads[r].names; }, true, targets, id_rest, rev_pairs, out,
+                     why);
 }
 
 inline std::string nonmatch_name(const std::string& results) {  // cmd/muscato_nonmatch/main.go:67-73

@@ -18,6 +18,7 @@
 #include <random>
 #include <thread>
 
+#include "../../../include/muscato_sam.h"
 #include "cli_config.hpp"
 #include "cli_maxmatches_host.hpp"
 #include "cli_names.hpp"
@@ -238,7 +239,7 @@ inline std::string device_text(const char* what, uint64_t nrec, uint64_t nbytes,
 // the tuples are the list the last pass left on the device, else `hits`.  Throws Die on a library error.
 inline std::string results_text_device(musc_ctx* c, bool device_list, const std::vector<musc_hit>& hits, const std::vector<UniqueRead>& reads,
                                        size_t n_targets, const std::map<uint64_t, std::string>& id_rest,
-                                       float* ms_order, float* ms_text) {
+                                       float* ms_order, float* ms_text, uint64_t* nlines_out = nullptr) {
   auto check = [&](int rc) { if (rc) throw Die(1, std::string("results on the device failed: ") + musc_last_error(c)); };
   {
     std::string text;
@@ -275,6 +276,7 @@ inline std::string results_text_device(musc_ctx* c, bool device_list, const std:
     check(musc_results_text(c, l0, n, dst, cap, 0, nb));
   });
   musc_results_last_ms(c, ms_order, ms_text);
+  if (nlines_out) *nlines_out = nlines;
   return out;
 }
 
@@ -292,6 +294,26 @@ inline bool side_texts_device(musc_ctx* c, std::string out[3], float* ms_prepare
       check(musc_side_text(c, w, r0, n, dst, cap, 0, nb));
     });
   musc_side_last_ms(c, ms_prepare, ms_text);
+  return true;
+}
+
+// The SAM file (header, then one record per line of results.txt) from the device (musc_sam_*): `c` has just
+// ordered and rendered results.txt from the list the pass left there.  false: the library refuses (12: rev_pairs on a
+// database that is not in pairs, a gene text without a name) or found no memory (10), *why says which, and the host
+// function of cli_text.hpp is to run.  Throws Die on any other library error.
+inline bool sam_text_device(musc_ctx* c, bool rev_pairs, size_t n_targets, std::string* out, std::string* why, float* ms_prepare, float* ms_text) {
+  uint64_t nrec = 0, hbytes = 0, rbytes = 0;
+  const int rc = musc_sam_prepare(c, rev_pairs ? 1 : 0, &nrec, &hbytes, &rbytes);
+  if (rc == 12 || rc == 10) return *why = "the device stage returned " + std::to_string(rc) + " (" + musc_last_error(c) + ")", false;
+  auto check = [&](int r) { if (r) throw Die(1, std::string("sam file on the device failed: ") + musc_last_error(c)); };
+  check(rc);
+  *out = device_text("sam file on the device", n_targets + 2, hbytes, [&](uint64_t r0, uint64_t n, char* dst, uint64_t cap, uint64_t* nb) {
+    check(musc_sam_text(c, 0, r0, n, dst, cap, 0, nb));
+  });
+  *out += device_text("sam file on the device", nrec, rbytes, [&](uint64_t r0, uint64_t n, char* dst, uint64_t cap, uint64_t* nb) {
+    check(musc_sam_text(c, 1, r0, n, dst, cap, 0, nb));
+  });
+  musc_sam_last_ms(c, ms_prepare, ms_text);
   return true;
 }
 
@@ -351,6 +373,7 @@ struct StageClock {
     return ts.tv_sec + 1e-9 * ts.tv_nsec;
   }
   explicit StageClock(Logger& l) : log(l), t0(now()), last(t0) {}
+  void skip() { last = now(); }  // the time since the last lap belongs to no lap
   void lap(const char* what) {
     const double t = now();
     log.printf("stage %-28s %8.3f s (total %.3f s)", what, t - last, t - t0);
@@ -556,6 +579,7 @@ struct HotResult {
   std::vector<musc_hit> hits;   // matches.txt: the per-read best + MMTol selection
   Ctx ctx;                      // context 0, with the database and every read, when results.txt is ordered on the device
   bool list_on_device = false;  // `hits` is the list the last pass left in ctx (Placement::list_on_device)
+  uint64_t res_lines = 0;       // lines of results.txt, when it was ordered on the device
   musc_stats st{};              // of the first GPU
 };
 
@@ -809,10 +833,10 @@ inline HotResult run_hot_path(const Config& cfg, const std::vector<UniqueRead>& 
 // the pipeline (cmd/muscato/main.go:1005-1058) as its stages, in the order run_muscato calls them
 // ------------------------------------------------------------------------------------
 
-// the seven values the plan is made from: the only place the host tools read the environment
+// the eight values the plan is made from: the only place the host tools read the environment
 inline PlanEnv plan_env_of_process() {
   return PlanEnv{getenv("MUSC_PREP"), getenv("MUSC_MAXMATCHES"), getenv("MUSC_RESULTS"), getenv("MUSC_SIDE"), getenv("MUSC_GATHER"),
-                 getenv("MUSC_TARGETS"), getenv("MUSC_PREP_NAMES")};
+                 getenv("MUSC_TARGETS"), getenv("MUSC_PREP_NAMES"), getenv("MUSC_SAM")};
 }
 
 // setupEnvs/makeTemp/setupLog/saveConfig (cmd/muscato/main.go:906-967, 680-706)
@@ -951,22 +975,65 @@ inline HotResult stage_hot_path(const Config& cfg, const std::vector<UniqueRead>
 }
 
 // results.txt, ordered and rendered where the plan says (MUSC_RESULTS).  Context 0 goes here unless the
-// side outputs are to come from it.
+// side outputs or the SAM file are to come from it.  With a SAM file to write, *ordered gets the tuples of the lines in
+// line order -- from the host's own sort, or from the device's ordered list.
 inline std::string stage_results(const Config& cfg, const Placement& plan, HotResult& hot, const std::vector<UniqueRead>& reads,
-                                 const TargetFiles& tf, Logger& log) {
+                                 const TargetFiles& tf, Logger& log, std::vector<musc_hit>* ordered) {
   fputs("Combining windows...\nJoining gene names...\nJoining read names...\n", stderr);
+  const bool sam = !cfg.SamFileName.empty();
   std::string res;
   if (plan.results == Where::Device) {
     float ms_order = 0, ms_text = 0;
-    res = results_text_device(hot.ctx.get(), hot.list_on_device, hot.hits, reads, tf.n_targets, tf.id_rest, &ms_order, &ms_text);
+    uint64_t nlines = 0;
+    res = results_text_device(hot.ctx.get(), hot.list_on_device, hot.hits, reads, tf.n_targets, tf.id_rest, &ms_order, &ms_text, &nlines);
     log.printf("results on the device: %zu bytes, order %.3f ms, text %.3f ms", res.size(), ms_order, ms_text);
-    if (plan.side == Where::Host) hot.ctx.reset();
+    hot.res_lines = nlines;
+    if (sam && !plan.sam_on_device(hot.list_on_device)) {
+      ordered->resize(nlines);
+      if (musc_results_hits(hot.ctx.get(), ordered->data(), nlines, 0))
+        throw Die(1, std::string("results on the device failed: ") + musc_last_error(hot.ctx.get()));
+    }
+    if (plan.side == Where::Host && !(sam && plan.sam_on_device(hot.list_on_device))) hot.ctx.reset();
+  } else if (sam) {
+    const std::vector<ResultsLine> lines = results_lines(hot.hits.data(), hot.hits.size(), reads, tf.targets(), tf.id_rest);
+    res = results_text(lines, reads);
+    ordered->reserve(lines.size());
+    for (auto& l : lines) ordered->push_back(l.hit);
+    log.printf("results on the host: %zu bytes", res.size());
   } else {
     res = results_text(hot.hits.data(), hot.hits.size(), reads, tf.targets(), tf.id_rest);
     log.printf("results on the host: %zu bytes", res.size());
   }
   spit(cfg.ResultsFileName, res);
   return res;
+}
+
+// The SAM file (-SamFileName, MUSC_SAM), written where results.txt was made: on the device when the plan
+// says so and the list results.txt was ordered from is the one the pass left there, else by the host function over
+// `ordered`.  A refusal of the device stage (12) or no memory (10) logs one line and the host function runs.
+inline void stage_sam(const Config& cfg, Placement& plan, HotResult& hot, const std::vector<UniqueRead>& reads, const TargetFiles& tf,
+                      std::vector<musc_hit>& ordered, Logger& log) {
+  fputs("Writing SAM file...\n", stderr);
+  const double t0 = StageClock::now();
+  std::string sam, why;
+  if (plan.sam_on_device(hot.list_on_device)) {
+    float ms_prepare = 0, ms_text = 0;
+    musc_ctx* c = hot.ctx.get();
+    if (sam_text_device(c, cfg.SamRev, tf.n_targets, &sam, &why, &ms_prepare, &ms_text)) {
+      log.printf("sam on the device: %zu bytes, prepare %.3f ms, text %.3f ms", sam.size(), ms_prepare, ms_text);
+    } else {
+      log.printf("sam on the host: %s", why.c_str());
+      plan.demote(Demotion::SamRefused);
+      ordered.resize(hot.res_lines);  // (a refused call leaves the ordered list as it was)
+      if (musc_results_hits(c, ordered.data(), ordered.size(), 0)) throw Die(1, std::string("sam file: ") + musc_last_error(c));
+    }
+    if (plan.side == Where::Host) hot.ctx.reset();
+  }
+  const bool from_device = plan.sam_on_device(hot.list_on_device);
+  if (!from_device && !sam_text(ordered.data(), ordered.size(), reads, tf.targets(), tf.id_rest, cfg.SamRev, &sam, &why))
+    throw Die(1, "SamFileName: " + why + "\n");
+  spit(cfg.SamFileName, sam);
+  log.printf("sam file on the %s: %.3f s", from_device ? "device" : "host", StageClock::now() - t0);
 }
 
 // The nonmatch FASTQ and the two stats files (MUSC_SIDE): from the device, which takes them from the
@@ -1020,8 +1087,13 @@ inline int run_muscato(Config cfg) {
   clk.lap("windows check, target files");
   HotResult hot = stage_hot_path(cfg, reads, tf, plan, log);
   clk.lap("hot path (init, load, match)");
-  const std::string res = stage_results(cfg, plan, hot, reads, tf, log);
+  std::vector<musc_hit> ordered;  // the tuples of results.txt in line order, kept only for a SAM file the host writes
+  const std::string res = stage_results(cfg, plan, hot, reads, tf, log, &ordered);
   clk.lap("results.txt");
+  if (!cfg.SamFileName.empty()) {
+    stage_sam(cfg, plan, hot, reads, tf, ordered, log);
+    clk.skip();  // (the stage logs its own line)
+  }
   stage_side_outputs(cfg, plan, std::move(hot.ctx), res, reads, log);
   clk.lap("nonmatch + stats files");
   return 0;

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/muscato_hip.h"
+#include "../../include/muscato_sam.h"
 
 #include "ctx_state.hpp"
 #include "dev_mem.hpp"
@@ -55,6 +56,7 @@
 #include "kernels_results.hpp"
 #include "side_names.hpp"
 #include "kernels_side.hpp"
+#include "kernels_sam.hpp"
 #include "kernels_maxmatches.hpp"
 #include "kernels_fastq.hpp"
 MUSC_LANE_INSTANCES_4(extern)
@@ -340,6 +342,15 @@ struct musc_ctx {
   uint64_t side_nel = 0;
   uint64_t side_nrec[3] = {0, 0, 0}, side_nbytes[3] = {0, 0, 0};
   float side_ms_prepare = 0, side_ms_text = 0;
+
+  // SAM output on the device: what musc_sam_prepare leaves for musc_sam_text (valid: st.may_sam_text())
+  DevBuf<uint4> sam_tok;            // per read: bytes of the count, QNAME's first byte within the tail and its bytes
+  DevBuf<uint2> sam_gname;          // per gene: the RNAME token's first byte within its text and its bytes
+  DevBuf<uint4> sam_info;           // per line: NM, bytes of MD, NH, HI
+  DevBuf<uint64_t> sam_off, sam_hoff;  // res_n + 1 record offsets; nseq + 3 offsets of the header's slots
+  uint64_t sam_n = 0, sam_bytes = 0, sam_hbytes = 0;
+  uint32_t sam_rev = 0;
+  float sam_ms_prepare = 0, sam_ms_text = 0;
 
   // the MaxMatches replay on the device
   musc_params mm_params;            // of the last musc_match* that succeeded (its list may be replayed: st.may_replay())

@@ -576,3 +576,133 @@ int musc_side_last_ms(musc_ctx* c, float* ms_prepare, float* ms_text) {
   if (ms_text) *ms_text = c->side_ms_text;
   return 0;
 }
+
+// ---------------------------------------------------------------- SAM output on the device
+// One record per line of the ordered list of the last musc_results_order, and the header: musc_sam_prepare compares
+// every span with its read and computes the offsets, musc_sam_text renders a range of records or of header slots
+// (kernels_sam.hpp) through text_range.
+
+static const int MUSC_SAM_ERR_REFUSED = 12;  // the database or the gene text does not allow SAM as asked: the caller's cue for its host path
+
+static SamData sam_data(const musc_ctx* c) {
+  SamData D;
+  D.R = res_data(c);
+  D.tok = c->sam_tok.p;
+  D.gname = c->sam_gname.p;
+  D.rank = c->res_rank;
+  D.rev_pairs = c->sam_rev;
+  return D;
+}
+
+// the refusals that need the device: the RNAME tokens of every gene, and under rev_pairs the lengths of every pair
+static int sam_names(musc_ctx* c, uint32_t rev_pairs, uint32_t* verdict) {
+  int rc;
+  if ((rc = ensure(c, c->sam_gname, std::max<uint64_t>(c->nseq, 1)))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
+  if (c->nseq) {
+    hipLaunchKernelGGL(k_sam_gnames, grid(c, c->nseq), dim3(256), 0, c->stream, c->res_gtext.get(), c->res_goff.get(), c->res_rank.get(),
+                       c->seq_off.get(), c->nseq, rev_pairs, c->sam_gname.p, c->d_flag.get());
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, Readback(c->scalars, c->stream).get(c->d_flag.get(), verdict).wait());
+  return 0;
+}
+
+static int sam_prepare_impl(musc_ctx* c) {
+  const dim3 B256(256);
+  const uint64_t nreads = c->nreads, m = c->res_n, nh = (uint64_t)c->nseq + 2;
+  const uint4* const hits = reinterpret_cast<const uint4*>(c->res_hits.p);
+  static const char* const who = "musc_sam_prepare";
+  int rc;
+  TmpBufs B;
+  Readback R(c->scalars, c->stream);
+  if (c->res_ttext) {
+    if ((rc = ensure(c, c->sam_tok, std::max<uint64_t>(nreads, 1)))) return rc;
+    hipLaunchKernelGGL(k_sam_tokens, grid(c, nreads), B256, 0, c->stream, c->res_ttext.get(), c->res_toff.get(), nreads, c->sam_tok.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  if ((rc = ensure(c, c->sam_hoff, nh + 1)) || (rc = ensure(c, c->sam_off, m + 1)) || (rc = ensure(c, c->sam_info, std::max<uint64_t>(m, 1))))
+    return rc;
+  const SamData D = sam_data(c);
+  uint32_t *first = nullptr, *last = nullptr;
+  uint64_t* stmp64 = nullptr;
+  if ((rc = tmp_alloc(c, who, B, &first, (nreads + 1) * 4)) || (rc = tmp_alloc(c, who, B, &last, (nreads + 1) * 4)) ||
+      (rc = tmp_alloc(c, who, B, &stmp64, scan_tmp_elems(std::max(m, nh) + 1) * 8)))
+    return rc;
+  // ---- the header's slots
+  hipLaunchKernelGGL(k_sam_hdr_len, grid(c, nh + 1), B256, 0, c->stream, D, c->sam_hoff.p);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u64(c, c->sam_hoff.p, c->sam_hoff.p, nh + 1, stmp64))) return rc;
+  // ---- the records: NH / HI from the runs of equal reads, NM and MD from the planes, then the offsets
+  if (m) {
+    hipLaunchKernelGGL(k_sam_runs, grid(c, m), B256, 0, c->stream, hits, m, first, last);
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_sam_count, grid(c, m + 1), B256, 0, c->stream, hits, m, D, first, last, c->sam_info.p, c->sam_off.p);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = scan_u64(c, c->sam_off.p, c->sam_off.p, m + 1, stmp64))) return rc;
+  uint64_t hbytes = 0, bytes = 0;
+  HIPCHK(c, R.get(c->sam_hoff.p + nh, &hbytes).get(c->sam_off.p + m, &bytes).wait());
+  c->sam_n = m;
+  c->sam_bytes = bytes;
+  c->sam_hbytes = hbytes;
+  return 0;
+}
+
+int musc_sam_prepare(musc_ctx* c, int rev_pairs, uint64_t* nrecords, uint64_t* header_bytes, uint64_t* record_bytes) {
+  if (!c) return 1;
+  if (nrecords) *nrecords = 0;
+  if (header_bytes) *header_bytes = 0;
+  if (record_bytes) *record_bytes = 0;
+  c->st.sam_begins();
+  if (!c->st.ordered_current() || !c->db2 || !c->res_gtext || !c->res_rank)
+    return fail(c, 2, "musc_sam_prepare: no ordered list (musc_results_order) of the reads, the database and the texts in hand");
+  if (rev_pairs && (c->nseq & 1u))
+    return fail(c, MUSC_SAM_ERR_REFUSED, "musc_sam_prepare: rev_pairs with an odd number of targets (%u)", c->nseq);
+  HIPCHK(c, hipSetDevice(c->device));
+  uint32_t verdict = 0;
+  int rc = sam_names(c, rev_pairs ? 1u : 0u, &verdict);
+  if (rc) return rc;
+  if (verdict & 2u) return fail(c, MUSC_SAM_ERR_REFUSED, "musc_sam_prepare: rev_pairs, and the two targets of a pair differ in length");
+  if (verdict & 1u)
+    return fail(c, MUSC_SAM_ERR_REFUSED, "musc_sam_prepare: the gene text of a target with an id line%s has an empty first token",
+                rev_pairs ? " (or of its even partner)" : "");
+  c->sam_rev = rev_pairs ? 1u : 0u;
+  rc = timed(c, &c->sam_ms_prepare, [&] { return sam_prepare_impl(c); });
+  if (rc) return rc;
+  c->sam_ms_text = 0;
+  c->st.sam_made();
+  if (nrecords) *nrecords = c->sam_n;
+  if (header_bytes) *header_bytes = c->sam_hbytes;
+  if (record_bytes) *record_bytes = c->sam_bytes;
+  return 0;
+}
+
+static void launch_sam(musc_ctx* c, int which, uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) {
+  const dim3 blocks = stage_grid(c, bytes / 256 + 1, musc_launch::CAP_TILES);
+  const SamData D = sam_data(c);
+  if (which == 0)
+    hipLaunchKernelGGL(k_sam_hdr_render, blocks, dim3(256), 0, c->stream, c->sam_hoff.p, r0, r1, D, out, c->d_flag.get());
+  else
+    hipLaunchKernelGGL(k_sam_render, blocks, dim3(256), 0, c->stream, reinterpret_cast<const uint4*>(c->res_hits.p), c->sam_info.p,
+                       c->sam_off.p, r0, r1, D, out, c->d_flag.get());
+}
+
+int musc_sam_text(musc_ctx* c, int which, uint64_t rec0, uint64_t nrec, char* dst, uint64_t capacity, int dst_on_device, uint64_t* nbytes) {
+  if (!c) return 1;
+  if (!nbytes) return fail(c, 2, "musc_sam_text: nbytes is NULL");
+  *nbytes = 0;
+  if (which < 0 || which > 1) return fail(c, 2, "musc_sam_text: no such text (%d)", which);
+  if (!c->st.may_sam_text()) return fail(c, 2, "musc_sam_text: nothing prepared (musc_sam_prepare)");
+  const TextDesc t = {which ? c->sam_off.p : c->sam_hoff.p, which ? c->sam_n : (uint64_t)c->nseq + 2, "musc_sam_text",
+                      "a record no longer fits the reads, the database or the texts in hand", &c->sam_ms_text};
+  return text_range(c, t, rec0, nrec, dst, capacity, dst_on_device, nbytes,
+                    [&](uint64_t r0, uint64_t r1, uint64_t bytes, unsigned char* out) { launch_sam(c, which, r0, r1, bytes, out); });
+}
+
+int musc_sam_last_ms(musc_ctx* c, float* ms_prepare, float* ms_text) {
+  if (!c) return 1;
+  if (ms_prepare) *ms_prepare = c->sam_ms_prepare;
+  if (ms_text) *ms_text = c->sam_ms_text;
+  return 0;
+}
