@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib, _sam
+from . import _cov, _lib, _sam
 
 
 class MuscatoError(RuntimeError):
@@ -729,6 +729,44 @@ class Engine:
         """HIP-event milliseconds of the last sam_prepare and of the text calls since."""
         _sam.bind()
         return self._ms_pair("musc_sam_last_ms")
+
+    # ---- coverage from the resident tuples (DESIGN.md 29)
+    def cov_prepare(self, rev_pairs: bool = False, weighted: bool = False, unique: bool = False) -> dict:
+        """Sort the interval ends of the last results_order, sum them to depths and lay out the bedGraph and the summary
+        -> {"runs": n, "run_bytes": b, "targets": n, "summary_bytes": b}.  rev_pairs: target 2k + 1 is the reverse strand
+        of target 2k; weighted: a line counts by its read's count; unique: only the lines of reads with one line count.
+        MuscatoError with code 12: a total weight of 2^32 or more, 2^31 lines or more, rev_pairs with an odd number of
+        targets or a pair of unequal lengths, or a gene text whose first token is empty."""
+        _cov.bind()
+        flags = (_cov.COV_REV_PAIRS if rev_pairs else 0) | (_cov.COV_WEIGHTED if weighted else 0) | (_cov.COV_UNIQUE if unique else 0)
+        n, rb, nt, sb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._call("musc_cov_prepare", flags, ctypes.byref(n), ctypes.byref(rb), ctypes.byref(nt), ctypes.byref(sb))
+        return {"runs": int(n.value), "run_bytes": int(rb.value), "targets": int(nt.value), "summary_bytes": int(sb.value)}
+
+    def cov_bedgraph(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
+        """Records [rec0, rec0 + nrec) of the bedGraph of the last cov_prepare (nrec None: to the end): one per run of
+        constant non-zero depth, `rname start end depth`, in target order."""
+        _cov.bind()
+        return self._text_range("musc_cov_text", (_cov.COV_BEDGRAPH,), rec0, nrec)
+
+    def cov_summary(self, rec0: int = 0, nrec: Optional[int] = None) -> bytes:
+        """Records [rec0, rec0 + nrec) of the summary of the last cov_prepare: one per target with an id line,
+        `rname len numreads covbases sumdepth maxdepth`."""
+        _cov.bind()
+        return self._text_range("musc_cov_text", (_cov.COV_SUMMARY,), rec0, nrec)
+
+    def cov_text_into(self, which: int, rec0: int, nrec: int, dst_ptr: int, capacity: int, on_device: bool) -> int:
+        """Records [rec0, rec0 + nrec) of text `which` (0 bedGraph, 1 summary) into caller memory (host or device) ->
+        the bytes written."""
+        _cov.bind()
+        nb = ctypes.c_uint64()
+        self._call("musc_cov_text", int(which), int(rec0), int(nrec), dst_ptr, int(capacity), 1 if on_device else 0, ctypes.byref(nb))
+        return int(nb.value)
+
+    def cov_ms(self) -> Tuple[float, float]:
+        """HIP-event milliseconds of the last cov_prepare and of the text calls since."""
+        _cov.bind()
+        return self._ms_pair("musc_cov_last_ms")
 
     def stats(self) -> dict:
         s = _lib.MuscStats()

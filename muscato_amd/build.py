@@ -14,7 +14,7 @@ OBJ = os.path.join(HERE, "build")
 # (kernels_match_lane_inst.hpp): they compile side by side
 SOURCES = [os.path.join(CSRC, f) for f in ("muscato_hip.hip", "match_lane_rw4.hip", "match_lane_rw8.hip", "match_lane_rw12.hip",
                                            "match_lane_rw8w.hip", "match_lane_rw12w.hip", "match_lane_rw16w.hip", "match_lane_rw8s.hip", "match_dma_rw8.hip")]
-HEADERS = [os.path.join(os.path.dirname(HERE), "include", f) for f in ("muscato_hip.h", "muscato_sam.h")] + \
+HEADERS = [os.path.join(os.path.dirname(HERE), "include", f) for f in ("muscato_hip.h", "muscato_sam.h", "muscato_cov.h")] + \
     [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp")]
 LANE_ONLY = os.path.join(CSRC, "kernels_match_lane.hpp")  # k_match_t's definition: muscato_hip.hip sees its declaration only
 DMA_ONLY = os.path.join(CSRC, "kernels_match_dma.hpp")    # k_match_g's definition, likewise
@@ -67,10 +67,10 @@ def build_tools(force: bool = False, verbose: bool = False) -> None:
 # program cannot be hollowed out and still pass, and the libraries it links).
 _API = "../../include/muscato_hip.h"
 _HOST_CHAIN = ("host/muscato_host.hpp", "host/cli_config.hpp", "host/cli_maxmatches_host.hpp", "host/cli_names.hpp", "host/cli_plan.hpp",
-               "host/cli_text.hpp", "host/sz.hpp", "sz_compress_plan.hpp", "sam_plan.hpp", _API, "../../include/muscato_sam.h")
+               "host/cli_text.hpp", "host/sz.hpp", "sz_compress_plan.hpp", "sam_plan.hpp", "cov_plan.hpp", _API, "../../include/muscato_sam.h")
 CHECKS = {
-    "cli_plan_check": ("cli_plan_check.cpp", ("host/check.hpp", "host/cli_names.hpp", "host/cli_plan.hpp", "sam_plan.hpp"), 184_779_199, ()),
-    "ctx_state_check": ("ctx_state_check.cpp", ("host/check.hpp", "ctx_state.hpp", _API), 58_376_821, ()),
+    "cli_plan_check": ("cli_plan_check.cpp", ("host/check.hpp", "host/cli_names.hpp", "host/cli_plan.hpp", "sam_plan.hpp", "cov_plan.hpp"), 185_601_401, ()),
+    "ctx_state_check": ("ctx_state_check.cpp", ("host/check.hpp", "ctx_state.hpp", _API), 65_485_234, ()),
     "dev_mem_check": ("dev_mem_check.cpp", ("host/check.hpp", "dev_mem.hpp"), 521, ()),
     "index_plan_check": ("index_plan_check.cpp", ("host/check.hpp", "index_plan.hpp"), 567_030, ()),
     "launch_plan_check": ("launch_plan_check.cpp", ("host/check.hpp", "launch_plan.hpp"), 113_302_959, ()),

@@ -33,6 +33,7 @@ struct State {
   uint64_t tokens = 0;  // side_tok: the ttext it was cut from
   uint64_t side = 0;    // the side tables: the order they describe
   uint64_t sam = 0;     // the SAM tables: the order they describe
+  uint64_t cov = 0;     // the coverage tables: the order they describe
 
   // ---- the causes
   void reads_dropped() { g.reads++, g.pass_inputs++; }
@@ -51,6 +52,8 @@ struct State {
   void side_made() { side = g.order; }
   void sam_begins() { sam = 0; }
   void sam_made() { sam = g.order; }
+  void cov_begins() { cov = 0; }
+  void cov_made() { cov = g.order; }
 
   // ---- the questions
   bool may_order_resident() const { return list.origin != LIST_NONE && list.reads == g.reads && list.db == g.db; }
@@ -66,6 +69,7 @@ struct State {
   }
   bool may_side_text() const { return side == g.order && ordered_current() && !list_changed_since_order(); }
   bool may_sam_text() const { return sam == g.order && ordered_current(); }  // (as results.txt: a later pass does not outdate the ordered list)
+  bool may_cov_text() const { return cov == g.order && ordered_current(); }  // (likewise)
 };
 
 // What a cache of the pass driver was made for: compared field by field (musc_params may carry padding, and a caller

@@ -41,6 +41,10 @@ struct Config {
   long long DbPartitionBases = 0;  // --DbPartitionBases: most target bases indexed at once, 0 = automatic
   std::string SamFileName;         // --SamFileName: also write the results as SAM; empty = no SAM file
   bool SamRev = false;             // --SamRev: the gene file was prepared with -rev, odd targets are reverse strands
+  std::string CoverageFileName;    // --CoverageFileName: also write a bedGraph here and a summary to <name>_targets
+  bool CoverageRev = false;        // --CoverageRev: the same fact as SamRev, for the coverage files
+  bool CoverageWeighted = false;   // --CoverageWeighted: a line counts by its read's count
+  bool CoverageUnique = false;     // --CoverageUnique: only the lines of reads with one line count
 };
 
 struct Die : std::runtime_error {
@@ -102,6 +106,7 @@ inline void config_from_json(const std::string& text, Config& c) {
       else if (key == "tempdir") c.TempDir = v; else if (key == "logdir") c.LogDir = v;
       else if (key == "matchmode") c.MatchMode = v; else if (key == "sorttemp") c.SortTemp = v;
       else if (key == "sortmem") c.SortMem = v; else if (key == "samfilename") c.SamFileName = v;
+      else if (key == "coveragefilename") c.CoverageFileName = v;
     } else if (j.p < text.size() && text[j.p] == '[') {
       j.need('[');
       std::vector<int> v;
@@ -124,6 +129,8 @@ inline void config_from_json(const std::string& text, Config& c) {
       else if (key == "cpuprofile") c.CPUProfile = b; else if (key == "maxmismatch") c.MaxMismatch = (int)d;
       else if (key == "gpus") c.GPUs = (int)d; else if (key == "device") c.Device = (int)d;
       else if (key == "dbpartitionbases") c.DbPartitionBases = (long long)d; else if (key == "samrev") c.SamRev = b;
+      else if (key == "coveragerev") c.CoverageRev = b; else if (key == "coverageweighted") c.CoverageWeighted = b;
+      else if (key == "coverageunique") c.CoverageUnique = b;
     }
   } while (j.eat(','));
   j.need('}');
@@ -161,7 +168,12 @@ inline std::string config_to_json(const Config& c) {
          N("MaxMismatch", c.MaxMismatch) + "," + N("GPUs", c.GPUs) + "," + N("Device", c.Device) + "," +
          N("DbPartitionBases", c.DbPartitionBases) +
          // (the SAM keys only when a SAM file is asked for: without the flag the saved configuration is what it always was)
-         (c.SamFileName.empty() ? std::string() : "," + S("SamFileName", c.SamFileName) + "," + B("SamRev", c.SamRev)) + "}\n";
+         (c.SamFileName.empty() ? std::string() : "," + S("SamFileName", c.SamFileName) + "," + B("SamRev", c.SamRev)) +
+         // (the coverage keys likewise, only when a coverage file is asked for)
+         (c.CoverageFileName.empty() ? std::string()
+                                     : "," + S("CoverageFileName", c.CoverageFileName) + "," + B("CoverageRev", c.CoverageRev) + "," +
+                                           B("CoverageWeighted", c.CoverageWeighted) + "," + B("CoverageUnique", c.CoverageUnique)) +
+         "}\n";
 }
 
 // ---- Go `flag` syntax: -name, --name, -name=value, -name value; bools take no value unless
@@ -200,6 +212,10 @@ inline const std::vector<FlagSpec>& muscato_flags() {
       {"DbPartitionBases", 'i', "(addition) most target bases indexed at once; 0 = automatic"},
       {"SamFileName", 's', "(addition) also write the results as a SAM file of this name"},
       {"SamRev", 'b', "(addition) the gene file was prepared with -rev: odd targets are reverse strands in the SAM file"},
+      {"CoverageFileName", 's', "(addition) also write a bedGraph of the depth runs to this file and a per-target summary to <name>_targets"},
+      {"CoverageRev", 'b', "(addition) the gene file was prepared with -rev: odd targets fold onto the even ones in the coverage files"},
+      {"CoverageWeighted", 'b', "(addition) a line counts by its read's count in the coverage files"},
+      {"CoverageUnique", 'b', "(addition) only reads with one line count in the coverage files"},
   };
   return f;
 }
@@ -294,6 +310,10 @@ inline Config handle_args(int argc, char** argv) {
   if (has("DbPartitionBases")) c.DbPartitionBases = strtoll(fl["DbPartitionBases"].c_str(), nullptr, 0);
   if (has("SamFileName") && !fl["SamFileName"].empty()) c.SamFileName = fl["SamFileName"];
   if (has("SamRev")) c.SamRev = fl["SamRev"] == "true";
+  if (has("CoverageFileName") && !fl["CoverageFileName"].empty()) c.CoverageFileName = fl["CoverageFileName"];
+  if (has("CoverageRev")) c.CoverageRev = fl["CoverageRev"] == "true";
+  if (has("CoverageWeighted")) c.CoverageWeighted = fl["CoverageWeighted"] == "true";
+  if (has("CoverageUnique")) c.CoverageUnique = fl["CoverageUnique"] == "true";
   if (c.ResultsFileName.empty()) {
     c.ResultsFileName = "results.txt";
     fputs("ResultsFileName not specified, defaulting to 'results.txt'\n", stderr);

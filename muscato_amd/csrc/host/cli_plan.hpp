@@ -57,14 +57,21 @@ namespace musc {
 #define MUSC_SAM_DEFAULT_DEVICE 0
 #endif
 
+// 1: when the ordered list is resident the CLI makes the coverage files (-CoverageFileName) on the device
+// unless MUSC_COVERAGE=host; 0: only with MUSC_COVERAGE=device.  Unmeasured: 0 until profiles/coverage.py has been run.
+#ifndef MUSC_COVERAGE_DEFAULT_DEVICE
+#define MUSC_COVERAGE_DEFAULT_DEVICE 0
+#endif
+
 enum class Where { Host, Device };
 
-// the eight environment values as the process has them, each possibly null
+// the nine environment values as the process has them, each possibly null
 struct PlanEnv {
   const char *prep = nullptr, *maxmatches = nullptr, *results = nullptr, *side = nullptr, *gather = nullptr;
   const char* targets = nullptr;
   const char* prep_names = nullptr;
   const char* sam = nullptr;
+  const char* coverage = nullptr;
 };
 
 // what a stage does when its variable does not say: the *_DEFAULT_DEVICE macros (arguments, so that the check program
@@ -75,11 +82,13 @@ struct PlanDefaults {
   bool targets = MUSC_TARGETS_DEFAULT_DEVICE != 0;
   bool prep_names = MUSC_PREP_NAMES_DEFAULT_DEVICE != 0;
   bool sam = MUSC_SAM_DEFAULT_DEVICE != 0;
+  bool coverage = MUSC_COVERAGE_DEFAULT_DEVICE != 0;
 };
 
 // The parse rules, which are not the same for every variable (and stay so here):
 //   MUSC_RESULTS, MUSC_SIDE, MUSC_MAXMATCHES,
-//   MUSC_TARGETS, MUSC_PREP_NAMES, MUSC_SAM    "device" and "host" say so; unset, empty and every other value mean the
+//   MUSC_TARGETS, MUSC_PREP_NAMES, MUSC_SAM,
+//   MUSC_COVERAGE                              "device" and "host" say so; unset, empty and every other value mean the
 //                                              compiled default
 //   MUSC_PREP                                  unset means the compiled default; once set, only "device" means the
 //                                              device: empty and every other value mean the host
@@ -109,6 +118,7 @@ enum class Demotion {
   TargetsRefused,    // ... returned 12: a chunk that declares more than 65 536 bytes, which sz_decode takes
   TargetsBadStream,  // ... returned 13: the host decoder then ends the run with its own message
   SamRefused,        // musc_sam_prepare returned 12 (refusal) or 10 (no memory): the host function writes the SAM file
+  CoverageRefused,   // musc_cov_prepare returned 12 or 10: the host function makes the coverage files
 };
 
 struct Placement {
@@ -126,6 +136,8 @@ struct Placement {
   // the SAM file: on the device only from an ordered list that is there, so whatever takes the results
   // to the host takes it along
   Where sam = Where::Host;
+  // the coverage files: likewise
+  Where coverage = Where::Host;
 
   // The one place a stage is moved to the host.  The side outputs are made from the ordered list behind results.txt,
   // which exists on the device only when results.txt was ordered there: whatever takes the results to the host takes
@@ -134,11 +146,11 @@ struct Placement {
     switch (why) {
       case Demotion::SeveralGpus:
         note_replay_gpus = maxmatches == Where::Device;
-        maxmatches = results = side = sam = Where::Host;
+        maxmatches = results = side = sam = coverage = Where::Host;
         break;
       case Demotion::OddTargetBytes:
         note_odd_targets = gpus == 1 && !results_env_host;
-        results = side = sam = Where::Host;
+        results = side = sam = coverage = Where::Host;
         break;
       case Demotion::PrepNoMemory: prep = prep_names = Where::Host; break;
       case Demotion::PrepNamesNoMemory: prep_names = Where::Host; break;
@@ -150,6 +162,7 @@ struct Placement {
       case Demotion::TargetsRefused:
       case Demotion::TargetsBadStream: targets = Where::Host; break;
       case Demotion::SamRefused: sam = Where::Host; break;
+      case Demotion::CoverageRefused: coverage = Where::Host; break;
     }
   }
 
@@ -159,6 +172,8 @@ struct Placement {
   bool list_on_device(bool overflow) const { return results == Where::Device && (!overflow || maxmatches == Where::Device); }
   // Is the SAM file the device's?  Only when its variable or the default says so and the list is resident.
   bool sam_on_device(bool list_resident) const { return sam == Where::Device && list_resident; }
+  // ... the coverage files?  By the same rule.
+  bool coverage_on_device(bool list_resident) const { return coverage == Where::Device && list_resident; }
 };
 
 // The plan of a run, from what is known before any stage: the environment and the number of GPUs.  The target files
@@ -176,6 +191,7 @@ inline Placement make_placement(const PlanEnv& env, int gpus, const PlanDefaults
   p.gather_rccl = gpus > 1 && env.gather && !strcmp(env.gather, "rccl");
   p.targets = place_by_env(env.targets, def.targets);
   p.sam = p.results == Where::Device ? place_by_env(env.sam, def.sam) : Where::Host;
+  p.coverage = p.results == Where::Device ? place_by_env(env.coverage, def.coverage) : Where::Host;
   if (gpus > 1) p.demote(Demotion::SeveralGpus);
   return p;
 }

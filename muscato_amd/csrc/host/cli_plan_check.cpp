@@ -9,10 +9,14 @@
 // after the plan, is held to its boolean expression in that product too -- its value, its default and its demotion
 // change with the combination, so that every pair of it with another input occurs -- and over the whole product of
 // what the expression reads (check_names_plan).
+// MUSC_COVERAGE (the coverage files) likewise (check_cov_plan).
 // MUSC_SAM (the SAM file) is held to its boolean expression in the same way (check_sam_plan), and the size
 // rules of a SAM record (sam_plan.hpp) to text that is built byte by byte (check_sam_sizes).
+// The size rules of the coverage stage (cov_plan.hpp) are held to text built byte by byte, to a brute-force
+// per-base count on small inputs, and their key arithmetic up to 2^36 bases and 2^24 targets (check_cov_sizes).
 // The name rules run on fixed cases and on seeded random groups whose names sit in heap blocks of their exact size.
 // It needs no GPU and is not part of the library.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +28,7 @@
 #include "check.hpp"
 #include "cli_names.hpp"
 #include "cli_plan.hpp"
+#include "../cov_plan.hpp"
 #include "../sam_plan.hpp"
 
 namespace {
@@ -283,6 +288,57 @@ unsigned long long check_sam_plan() {
   return n;
 }
 
+// MUSC_COVERAGE over its six values, both defaults and the refusal of the device stage, with every other variable over
+// {unset, host, device}, GPUs over {1, 2, 3}, odd target bytes or none, an overflow or none and a refused replay or none:
+// the coverage files are the device's exactly when results.txt was ordered there from the resident list, the variable or the
+// default says device, and musc_cov_prepare did not refuse; and no other stage moves with it.
+unsigned long long check_cov_plan() {
+  static const char* const V[6] = {nullptr, "", "host", "device", "rccl", "junk"};
+  static const char* const O[3] = {nullptr, "host", "device"};
+  unsigned long long n = 0;
+  for (int d = 0; d < 2; d++)
+    for (int e = 0; e < 6; e++)
+      for (int o = 0; o < 81; o++)
+        for (int gpus = 1; gpus <= 3; gpus++)
+          for (int x = 0; x < 16; x++) {
+            PlanDefaults D;
+            D.coverage = d != 0;
+            PlanEnv env;
+            env.coverage = V[e];
+            env.maxmatches = O[o % 3], env.results = O[o / 3 % 3], env.side = O[o / 9 % 3], env.targets = O[o / 27];
+            const bool overflow = (x & 1) != 0, replay_refused = (x & 2) != 0, cov_refused = (x & 4) != 0;
+            const size_t nodd = (x & 8) != 0;
+            const Events ev = {overflow, false, false, false, replay_refused, false, false};
+            // the expression
+            const Outcome old = old_run(env, gpus, nodd, ev, D);
+            const bool env_device = env.coverage && !strcmp(env.coverage, "device"), env_host = env.coverage && !strcmp(env.coverage, "host");
+            const bool want = env_device || (!env_host && D.coverage);
+            const bool tried = old.results_on_device && old.list_on_device && want;
+            // the plan, as stage_results and stage_coverage use it
+            Placement plan = make_placement(env, gpus, D);
+            if (nodd) plan.demote(Demotion::OddTargetBytes);
+            if (overflow && plan.maxmatches == Where::Device && replay_refused) plan.demote(Demotion::ReplayRefused);
+            const bool resident = plan.list_on_device(overflow);
+            EXPECT(resident == old.list_on_device);
+            EXPECT_MSG(plan.coverage_on_device(resident) == tried, "coverage plan differs: default %d env %d others %d GPUs %d events %d", d, e, o, gpus, x);
+            if (plan.coverage_on_device(resident) && cov_refused) plan.demote(Demotion::CoverageRefused);
+            EXPECT(plan.coverage_on_device(resident) == (tried && !cov_refused));
+            EXPECT(plan.coverage == Where::Host || plan.results == Where::Device);
+            // nothing else moves
+            PlanEnv unset = env;
+            unset.coverage = nullptr;
+            EXPECT(new_run(env, gpus, nodd, ev, D) == new_run(unset, gpus, nodd, ev, PlanDefaults()));
+            // ... the SAM file included: each of the two moves on its own
+            Placement both = make_placement(env, gpus, D), none = make_placement(unset, gpus, PlanDefaults());
+            EXPECT(both.sam == none.sam);
+            both.demote(Demotion::SamRefused);
+            EXPECT(both.coverage == make_placement(env, gpus, D).coverage);
+            n++;
+          }
+  EXPECT(!PlanDefaults().coverage);  // unmeasured: the host makes the coverage files unless MUSC_COVERAGE=device
+  return n;
+}
+
 // The size rules of sam_plan.hpp against text built byte by byte: decimal widths, the CIGAR, MD over random mismatch
 // places (forward and reverse: the same length), a whole record, and the name rules on blocks of their exact size.
 unsigned long long check_sam_sizes() {
@@ -351,6 +407,104 @@ unsigned long long check_sam_sizes() {
     memcpy(b.get(), g.text, g.n);
     const NameSpan s = rname_span(b.get(), g.n);
     EXPECT_MSG(s.len == g.len && (s.len == 0 || s.n0 == g.n0), "rname_span(%s)", g.text);
+    n++;
+  }
+  return n;
+}
+
+// The rules of cov_plan.hpp: the weight parse with its saturation against strtoull on blocks of their exact size, the
+// record byte counts against text built byte by byte, the refusal bounds, the key arithmetic at the largest database
+// the library loads (2^36 bases, 2^24 targets), and the whole event scheme -- interval, slot, sort, running sum, runs --
+// against a per-base count on small random databases, pairs folded or not.
+unsigned long long check_cov_sizes() {
+  using namespace musc_cov;
+  unsigned long long n = 0;
+  // ---- the weight
+  struct W { const char* tail; size_t len; uint64_t w; };
+  const W tails[] = {{"0\tn", 3, 0}, {"1\tn", 3, 1}, {"12345\tn", 7, 12345}, {"007\tn", 5, 7}, {"x9\tn", 4, 1}, {"9x\tn", 4, 1}, {"\tn", 2, 1},
+                     {"42", 2, 42}, {"nocount", 7, 1}, {"", 0, 1}, {"5 \tn", 4, 1}, {"-3\tn", 4, 1}, {"4294967295\tn", 12, 4294967295ull},
+                     {"4294967296\tn", 12, WEIGHT_LIMIT}, {"4294967297", 10, WEIGHT_LIMIT}, {"10000000000\tn", 13, WEIGHT_LIMIT},
+                     {"99999999999999999999999999\tn", 28, WEIGHT_LIMIT}, {"000000000000000000000000012\tn", 29, 12}};
+  for (const W& t : tails) {
+    std::unique_ptr<unsigned char[]> b(new unsigned char[t.len ? t.len : 1]);
+    memcpy(b.get(), t.tail, t.len);
+    EXPECT_MSG(weight(b.get(), t.len) == t.w, "weight(%s)", t.tail);
+    n++;
+  }
+  std::mt19937_64 rng(29);
+  for (int it = 0; it < 20000; it++) {
+    const uint64_t v = it % 3 == 0 ? rng() : it % 3 == 1 ? rng() >> 31 : rng() % 100000;
+    const std::string text = std::to_string(v) + (it & 1 ? "\tname" : "");
+    std::unique_ptr<unsigned char[]> b(new unsigned char[text.size()]);
+    memcpy(b.get(), text.data(), text.size());
+    EXPECT(weight(b.get(), text.size()) == (v < WEIGHT_LIMIT ? v : WEIGHT_LIMIT));
+    n++;
+  }
+  // ---- the refusal bounds
+  EXPECT(!total_refused(0) && !total_refused(WEIGHT_LIMIT - 1) && total_refused(WEIGHT_LIMIT) && total_refused(~0ull));
+  EXPECT(!lines_refused(0) && !lines_refused(LINES_LIMIT - 1) && lines_refused(LINES_LIMIT));
+  EXPECT(ALL_FLAGS == 7u);
+  // ---- the records
+  for (int it = 0; it < 20000; it++) {
+    const uint32_t name = 1 + (uint32_t)(rng() % 40), depth = (uint32_t)(rng() >> (32 + rng() % 32)), nr = (uint32_t)(rng() >> (32 + rng() % 32));
+    const uint64_t start = rng() >> (28 + rng() % 36), end = start + 1 + (rng() >> (30 + rng() % 34)), cov = rng() >> (28 + rng() % 36), sum = rng() >> (16 + rng() % 48);
+    const std::string run = std::string(name, 'r') + "\t" + std::to_string(start) + "\t" + std::to_string(end) + "\t" + std::to_string(depth) + "\n";
+    EXPECT(run_bytes(name, start, end, depth) == run.size());
+    const std::string rec = std::string(name, 'r') + "\t" + std::to_string(end) + "\t" + std::to_string(nr) + "\t" + std::to_string(cov) + "\t" +
+                            std::to_string(sum) + "\t" + std::to_string(depth) + "\n";
+    EXPECT(summary_bytes(name, end, nr, cov, sum, depth) == rec.size());
+    n++;
+  }
+  // ---- the keys at the library's bounds: every slot of a database of nbases bases in nseq targets is below
+  // nbases + nseq, which the end bit covers; the slots of consecutive targets do not meet
+  for (unsigned bb = 0; bb <= 36; bb++)
+    for (unsigned sb = 0; sb <= 24; sb++)
+      for (int d = -1; d <= 1; d++) {
+        const uint64_t nbases = (1ull << bb) + (uint64_t)d, nseq = 1ull << sb;
+        if (nbases > (1ull << 36)) continue;
+        const unsigned end = sort_end_bit(nbases, nseq);
+        const uint64_t top = slot(nbases - (nbases ? 1 : 0), (uint32_t)(nseq - 1), nbases ? 1 : 0);  // the last slot of a last target of one base
+        EXPECT(end >= 1 && end <= 37 && top == nbases + nseq - 1);
+        EXPECT(end == 64 || top < (1ull << end));
+        EXPECT(end == 1 || ((nbases + nseq) >> (end - 1)) == 1);  // the width, and not a bit more
+        n++;
+      }
+  EXPECT(sort_end_bit(1ull << 36, 1ull << 24) == 37 && sort_end_bit(0, 0) == 1 && sort_end_bit(3, 1) == 3);
+  // ---- the scheme against a per-base count
+  for (int it = 0; it < 3000; it++) {
+    const bool rev_pairs = it & 1;
+    const uint32_t nt = 2 * (1 + (uint32_t)(rng() % 4));
+    std::vector<uint64_t> len(nt), off(nt + 1, 0);
+    for (uint32_t g = 0; g < nt; g++) len[g] = rev_pairs && (g & 1) ? len[g - 1] : rng() % 40;
+    for (uint32_t g = 0; g < nt; g++) off[g + 1] = off[g] + len[g];
+    std::vector<std::vector<uint64_t>> depth(nt);
+    for (uint32_t g = 0; g < nt; g++) depth[g].assign(len[g], 0);
+    std::vector<std::pair<uint64_t, uint32_t>> ev;
+    const int lines = (int)(rng() % 30);
+    for (int i = 0; i < lines; i++) {
+      const uint32_t g = (uint32_t)(rng() % nt);
+      const uint64_t pos = rng() % (len[g] + 1), L = rng() % 25, w = rng() % 4;
+      const Interval v = interval(rev_pairs, g, pos, len[g], L);
+      EXPECT(v.S == std::min(L, len[g] - pos) && v.a + v.S <= len[v.f] && (!rev_pairs || !(v.f & 1)));
+      // by hand: base pos + j of an odd target is base len - 1 - pos - j of the even one
+      for (uint64_t j = 0; j < v.S; j++) depth[v.f][rev_pairs && (g & 1) ? len[g] - 1 - pos - j : pos + j] += w;
+      ev.push_back({slot(off[v.f], v.f, v.a), (uint32_t)w});
+      ev.push_back({slot(off[v.f], v.f, v.a + v.S), 0u - (uint32_t)w});
+    }
+    std::stable_sort(ev.begin(), ev.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    for (const auto& e : ev) EXPECT(e.first < (1ull << sort_end_bit(off[nt], nt)));
+    // the depth from every slot on is the running sum at the last event of the slot; between targets it is zero
+    std::vector<std::vector<uint64_t>> swept(nt);
+    size_t e = 0;
+    uint32_t sum = 0;
+    for (uint32_t g = 0; g < nt; g++) {
+      EXPECT(sum == 0);
+      for (uint64_t x = 0; x <= len[g]; x++) {
+        for (; e < ev.size() && ev[e].first == slot(off[g], g, x); e++) sum += ev[e].second;
+        if (x < len[g]) swept[g].push_back(sum);
+      }
+    }
+    EXPECT(e == ev.size() && sum == 0 && swept == depth);
     n++;
   }
   return n;
@@ -463,9 +617,9 @@ unsigned long long check_names() {  // -> the random groups seen
 }  // namespace
 
 int main() {
-  char census[128];
-  const unsigned long long n_plans = check_plan() + check_names_plan() + check_sam_plan(), n_groups = check_names();
-  const unsigned long long n_sam = check_sam_sizes();
-  snprintf(census, sizeof census, "%llu plan combinations, %llu random name groups, %llu SAM size cases", n_plans, n_groups, n_sam);
+  char census[160];
+  const unsigned long long n_plans = check_plan() + check_names_plan() + check_sam_plan() + check_cov_plan(), n_groups = check_names();
+  const unsigned long long n_sam = check_sam_sizes(), n_cov = check_cov_sizes();
+  snprintf(census, sizeof census, "%llu plan combinations, %llu random name groups, %llu SAM size cases, %llu coverage cases", n_plans, n_groups, n_sam, n_cov);
   return check_done("cli_plan_check", census);
 }

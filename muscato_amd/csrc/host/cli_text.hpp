@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../../include/muscato_hip.h"
+#include "../cov_plan.hpp"
 #include "../sam_plan.hpp"
 
 namespace musc {
@@ -234,6 +235,115 @@ inline bool sam_text(const musc_hit* ordered, size_t n, const std::vector<Unique
   return sam_text_of(ordered, n, [&](uint32_t r) -> const std::string& { return reads[r].seq; },
                      [&](uint32_t r) { return std::to_string(reads[r].count) + "\t" + reads[r].names; }, true, targets, id_rest, rev_pairs, out,
                      why);
+}
+
+// ---- coverage: the stage's C++ copy, and what the CLI writes when the device does not.  `ordered` as for
+// sam_text; len_of(r) -> the bases of read r, tail_of(r) -> its count\tnames, asked only when have_tails.  *bed gets the
+// bedGraph and *summary the per-target records.  The rules and the sizes are cov_plan.hpp's and sam_plan.hpp's, which
+// the device shares; like the device it sorts events, so its memory goes with the lines and not with the database.
+// False: refused (what musc_cov_prepare answers with code 12), *why says which rule.
+template <class Len, class Tail>
+inline bool coverage_text_of(const musc_hit* ordered, size_t n, Len len_of, Tail tail_of, bool have_tails, const std::vector<std::string>& targets,
+                             const std::map<uint64_t, std::string>& id_rest, uint32_t flags, std::string* bed, std::string* summary,
+                             std::string* why) {
+  auto u = [](const std::string& s) { return reinterpret_cast<const unsigned char*>(s.data()); };
+  const size_t nt = targets.size();
+  const bool rev_pairs = (flags & MUSC_COV_REV_PAIRS) != 0, weighted = (flags & MUSC_COV_WEIGHTED) != 0, unique = (flags & MUSC_COV_UNIQUE) != 0;
+  auto rest = [&](size_t g) -> const std::string* {
+    auto it = id_rest.find(g);
+    return it == id_rest.end() ? nullptr : &it->second;
+  };
+  // ---- the refusals
+  if (musc_cov::lines_refused(n)) return *why = "the list has 2^31 lines or more", false;
+  if (rev_pairs && (nt & 1)) return *why = "rev_pairs with an odd number of targets", false;
+  for (size_t g = 0; rev_pairs && g + 1 < nt; g += 2)
+    if (targets[g].size() != targets[g + 1].size()) return *why = "rev_pairs, and the two targets of a pair differ in length", false;
+  std::vector<musc_sam::NameSpan> name(nt, musc_sam::NameSpan{0, 0});
+  for (size_t g = 0; g < nt; g++)
+    if (const std::string* r = rest(g)) name[g] = musc_sam::rname_span(u(*r), r->size());
+  for (size_t g = 0; g < nt; g++) {
+    if (!rest(g)) continue;
+    const size_t f = rev_pairs && (g & 1) ? g - 1 : g;
+    if (!rest(f) || name[f].len == 0) return *why = "the gene text of a target with an id line (or of its even partner) has an empty first token", false;
+  }
+  // ---- the events of the contributing lines, their weights per target and in all
+  struct Event { uint64_t slot; uint32_t delta; };
+  std::vector<Event> ev;
+  ev.reserve(2 * n);
+  std::vector<uint64_t> seq_off(nt + 1, 0), numreads(nt, 0);
+  for (size_t g = 0; g < nt; g++) seq_off[g + 1] = seq_off[g] + targets[g].size();
+  uint64_t total = 0;
+  for (size_t i = 0, run1 = 0; i < n; i++) {
+    if (i == run1)
+      while (run1 < n && ordered[run1].read_idx == ordered[i].read_idx) run1++;  // (the list is read-major)
+    const musc_hit& h = ordered[i];
+    if (unique && !((i == 0 || ordered[i - 1].read_idx != h.read_idx) && run1 == i + 1)) continue;
+    uint64_t w = 1;
+    if (weighted && have_tails) {
+      const std::string tail = tail_of(h.read_idx);
+      w = musc_cov::weight(u(tail), tail.size());
+    }
+    // (musc_results_order and results_lines drop the lines of targets without an id line; one that comes here all the
+    // same has no name to be written under)
+    if (h.gene_idx >= nt || !rest(h.gene_idx) || h.pos > targets[h.gene_idx].size())
+      return *why = "a line of the ordered list is on a target without an id line, or past its target's end", false;
+    const musc_cov::Interval v = musc_cov::interval(rev_pairs, h.gene_idx, h.pos, targets[h.gene_idx].size(), len_of(h.read_idx));
+    total += w;
+    if (musc_cov::total_refused(total)) return *why = "the weights of the contributing lines add up to 2^32 or more", false;
+    numreads[v.f] += w;
+    if (w == 0 || v.S == 0) continue;
+    ev.push_back(Event{musc_cov::slot(seq_off[v.f], v.f, v.a), (uint32_t)w});
+    ev.push_back(Event{musc_cov::slot(seq_off[v.f], v.f, v.a + v.S), 0u - (uint32_t)w});
+  }
+  std::sort(ev.begin(), ev.end(), [](const Event& a, const Event& b) { return a.slot < b.slot; });
+  // ---- the runs, target by target (the slots of a target are consecutive), and the summary
+  bed->clear(), summary->clear();
+  size_t e = 0;
+  for (size_t t = 0; t < nt; t++) {
+    const uint64_t base = seq_off[t] + t, len = targets[t].size();
+    uint64_t covbases = 0, sumdepth = 0, start = 0;
+    uint32_t depth = 0, maxdepth = 0;
+    while (e < ev.size() && ev[e].slot <= base + len) {
+      const uint64_t x = ev[e].slot - base;
+      uint32_t d = depth;
+      for (; e < ev.size() && ev[e].slot == base + x; e++) d += ev[e].delta;
+      if (d == depth) continue;
+      if (depth) {
+        const size_t before = bed->size();
+        bed->append(*rest(t), name[t].n0, name[t].len);
+        *bed += '\t' + std::to_string(start) + '\t' + std::to_string(x) + '\t' + std::to_string(depth) + '\n';
+        if (musc_cov::run_bytes(name[t].len, start, x, depth) != bed->size() - before) return *why = "cov_plan.hpp's size rule and coverage_text disagree", false;
+        covbases += x - start, sumdepth += (x - start) * depth;
+        if (depth > maxdepth) maxdepth = depth;
+      }
+      depth = d, start = x;
+    }
+    if (depth) return *why = "coverage_text: a run does not end within its target", false;
+    if (!rest(t) || (rev_pairs && (t & 1))) continue;
+    const size_t before = summary->size();
+    summary->append(*rest(t), name[t].n0, name[t].len);
+    *summary += '\t' + std::to_string(len) + '\t' + std::to_string(numreads[t]) + '\t' + std::to_string(covbases) + '\t' + std::to_string(sumdepth) +
+                '\t' + std::to_string(maxdepth) + '\n';
+    if (musc_cov::summary_bytes(name[t].len, len, (uint32_t)numreads[t], covbases, sumdepth, maxdepth) != summary->size() - before)
+      return *why = "cov_plan.hpp's size rule and coverage_text disagree", false;
+  }
+  return true;
+}
+
+// ... over reads and tails given as strings (tails == nullptr: no read text)
+inline bool coverage_text(const musc_hit* ordered, size_t n, const std::vector<std::string>& read_seqs, const std::vector<std::string>& targets,
+                          const std::map<uint64_t, std::string>& id_rest, const std::vector<std::string>* tails, uint32_t flags, std::string* bed,
+                          std::string* summary, std::string* why) {
+  return coverage_text_of(ordered, n, [&](uint32_t r) { return read_seqs[r].size(); }, [&](uint32_t r) { return (*tails)[r]; }, tails != nullptr,
+                          targets, id_rest, flags, bed, summary, why);
+}
+
+// ... over the unique reads of a run: the tail of a read is its count, a tab and its names, as in results.txt
+inline bool coverage_text(const musc_hit* ordered, size_t n, const std::vector<UniqueRead>& reads, const std::vector<std::string>& targets,
+                          const std::map<uint64_t, std::string>& id_rest, uint32_t flags, std::string* bed, std::string* summary, std::string* why) {
+  return coverage_text_of(ordered, n, [&](uint32_t r) { return reads[r].seq.size(); },
+                          [&](uint32_t r) { return std::to_string(reads[r].count) + "\t" + reads[r].names; }, true, targets, id_rest, flags, bed,
+                          summary, why);
 }
 
 inline std::string nonmatch_name(const std::string& results) {  // cmd/muscato_nonmatch/main.go:67-73

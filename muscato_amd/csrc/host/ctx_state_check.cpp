@@ -6,6 +6,9 @@
 // ctx_state.hpp has the same answer in both -- with one exception, which is the point of the change: a
 // musc_maxmatches_apply that fails after its first write into the list.  Old went on calling the half-written list
 // that of a pass; New must say LIST_NONE, and from there on Old is told so.
+// The stamp of the coverage tables (cov_begins, cov_made, may_cov_text) came after the booleans; it is held
+// to one kept here the old way -- set by a prepare that succeeds over a current order, cleared by every order and by
+// whatever replaces the reads, the database or either text -- and by hand to be independent of the SAM stamp.
 // It needs no GPU and is not part of the library; muscato_amd/build.py (CHECKS) builds it, plain and sanitized.
 #include <cstdio>
 #include <cstdlib>
@@ -156,15 +159,17 @@ struct New {
   }
 };
 
-enum Event { LOAD_READS, LOAD_DB, FREE_INDEX, SET_GENE_TEXT, SET_READ_TEXT, PASS, ORDER, SIDE_PREPARE, SIDE_TEXT, APPLY, RELOAD_ENV, N_EVENTS };
+enum Event { LOAD_READS, LOAD_DB, FREE_INDEX, SET_GENE_TEXT, SET_READ_TEXT, PASS, ORDER, SIDE_PREPARE, SIDE_TEXT, APPLY, RELOAD_ENV, COV_PREPARE, N_EVENTS };
 
 struct World {
   Old o;
   New n;
   Facts f;
   uint64_t pass_inputs_seen = 1;
+  bool cov_valid = false;  // the coverage tables, kept as a boolean
 
   void agree() {
+    EXPECT(cov_valid == n.st.may_cov_text());
     EXPECT(o.may_order_resident() == n.st.may_order_resident());
     EXPECT(o.may_results() == n.st.ordered_current());
     EXPECT(o.side_refusal(f) == n.side_refusal(f));
@@ -179,6 +184,7 @@ struct World {
   bool step(Event e, How how, bool form_ok = true) {
     bool ro = true, rn = true;
     const uint64_t inputs = n.st.g.pass_inputs;
+    if (e == LOAD_READS || e == LOAD_DB || e == SET_READ_TEXT || e == ORDER || (e == SET_GENE_TEXT && f.db && how != BAD_NSEQ)) cov_valid = false;
     switch (e) {
       case LOAD_READS:
         o.load_reads(how), n.load_reads(how);
@@ -228,6 +234,11 @@ struct World {
         break;
       }
       case RELOAD_ENV: break;  // (the sized key and graph.failed: no standing of any list)
+      case COV_PREPARE:  // musc_cov_prepare: needs a current order; a refusal or a failure leaves nothing prepared
+        n.st.cov_begins();
+        ro = rn = cov_valid = n.st.ordered_current() && how == OK;
+        if (rn) n.st.cov_made();
+        break;
       default: break;
     }
     EXPECT(ro == rn);
@@ -313,11 +324,36 @@ void by_hand() {
   EXPECT(!w.step(ORDER, RESIDENT_OK));
 }
 
+// the coverage stamp beside SAM's: each is made and lost on its own, both go with the order
+void cov_stamp() {
+  World w;
+  w.step(LOAD_DB, OK), w.step(LOAD_READS, OK), w.step(SET_GENE_TEXT, OK), w.step(SET_READ_TEXT, OK);
+  EXPECT(!w.step(COV_PREPARE, OK));  // no ordered list
+  EXPECT(w.step(ORDER, OK) && !w.n.st.may_cov_text());
+  EXPECT(w.step(COV_PREPARE, OK) && w.n.st.may_cov_text() && !w.n.st.may_sam_text());
+  w.n.st.sam_begins(), w.n.st.sam_made();
+  EXPECT(w.n.st.may_cov_text() && w.n.st.may_sam_text());
+  w.n.st.sam_begins();
+  EXPECT(w.n.st.may_cov_text() && !w.n.st.may_sam_text());
+  w.n.st.sam_made();
+  EXPECT(!w.step(COV_PREPARE, FAIL) && !w.n.st.may_cov_text() && w.n.st.may_sam_text());  // a refusal: SAM's tables stay
+  EXPECT(w.step(COV_PREPARE, OK));
+  EXPECT(w.step(PASS, OK) && w.n.st.may_cov_text());  // as results.txt: a later pass does not outdate the ordered list
+  EXPECT(w.step(SIDE_PREPARE, OK) == false && w.n.st.may_cov_text());
+  for (Event e : {ORDER, LOAD_READS, LOAD_DB, SET_GENE_TEXT, SET_READ_TEXT}) {
+    w.step(LOAD_DB, OK), w.step(LOAD_READS, OK), w.step(SET_GENE_TEXT, OK), w.step(SET_READ_TEXT, OK);
+    EXPECT(w.step(ORDER, OK) && w.step(COV_PREPARE, OK) && w.n.st.may_cov_text());
+    w.step(e, OK);
+    EXPECT(!w.n.st.may_cov_text());
+  }
+}
+
 }  // namespace
 
 int main() {
   test_refusals_sequence();
   by_hand();
+  cov_stamp();
   std::mt19937_64 rng(19);
   const int rounds = 120000;
   for (int round = 0; round < rounds && !failures; round++) {
@@ -331,7 +367,7 @@ int main() {
       const unsigned r = (unsigned)(rng() % 16);
       How how = OK;
       switch (e) {
-        case LOAD_READS: case LOAD_DB: case SET_READ_TEXT: case PASS: how = r < 3 ? FAIL : OK; break;
+        case LOAD_READS: case LOAD_DB: case SET_READ_TEXT: case PASS: case COV_PREPARE: how = r < 3 ? FAIL : OK; break;
         case SET_GENE_TEXT: how = r < 2 ? FAIL : r < 4 ? BAD_NSEQ : OK; break;
         case ORDER: how = r < 2 ? FAIL : r < 4 ? RESIDENT_FAIL : r < 10 ? RESIDENT_OK : OK; break;
         case SIDE_PREPARE: how = r < 2 ? FAIL : r < 4 ? FAIL_AFTER_TOKENS : OK; break;

@@ -18,6 +18,7 @@
 #include <random>
 #include <thread>
 
+#include "../../../include/muscato_cov.h"
 #include "../../../include/muscato_sam.h"
 #include "cli_config.hpp"
 #include "cli_maxmatches_host.hpp"
@@ -314,6 +315,25 @@ inline bool sam_text_device(musc_ctx* c, bool rev_pairs, size_t n_targets, std::
     check(musc_sam_text(c, 1, r0, n, dst, cap, 0, nb));
   });
   musc_sam_last_ms(c, ms_prepare, ms_text);
+  return true;
+}
+
+// The two coverage files (the bedGraph and the per-target summary) from the device (musc_cov_*), under the
+// same conditions and with the same answers as sam_text_device.
+inline bool coverage_text_device(musc_ctx* c, uint32_t flags, std::string* bed, std::string* summary, std::string* why, float* ms_prepare,
+                                 float* ms_text) {
+  uint64_t nruns = 0, rbytes = 0, nt = 0, sbytes = 0;
+  const int rc = musc_cov_prepare(c, flags, &nruns, &rbytes, &nt, &sbytes);
+  if (rc == 12 || rc == 10) return *why = "the device stage returned " + std::to_string(rc) + " (" + musc_last_error(c) + ")", false;
+  auto check = [&](int r) { if (r) throw Die(1, std::string("coverage files on the device failed: ") + musc_last_error(c)); };
+  check(rc);
+  *bed = device_text("coverage files on the device", nruns, rbytes, [&](uint64_t r0, uint64_t n, char* dst, uint64_t cap, uint64_t* nb) {
+    check(musc_cov_text(c, 0, r0, n, dst, cap, 0, nb));
+  });
+  *summary = device_text("coverage files on the device", nt, sbytes, [&](uint64_t r0, uint64_t n, char* dst, uint64_t cap, uint64_t* nb) {
+    check(musc_cov_text(c, 1, r0, n, dst, cap, 0, nb));
+  });
+  musc_cov_last_ms(c, ms_prepare, ms_text);
   return true;
 }
 
@@ -833,10 +853,10 @@ inline HotResult run_hot_path(const Config& cfg, const std::vector<UniqueRead>& 
 // the pipeline (cmd/muscato/main.go:1005-1058) as its stages, in the order run_muscato calls them
 // ------------------------------------------------------------------------------------
 
-// the eight values the plan is made from: the only place the host tools read the environment
+// the nine values the plan is made from: the only place the host tools read the environment
 inline PlanEnv plan_env_of_process() {
   return PlanEnv{getenv("MUSC_PREP"), getenv("MUSC_MAXMATCHES"), getenv("MUSC_RESULTS"), getenv("MUSC_SIDE"), getenv("MUSC_GATHER"),
-                 getenv("MUSC_TARGETS"), getenv("MUSC_PREP_NAMES"), getenv("MUSC_SAM")};
+                 getenv("MUSC_TARGETS"), getenv("MUSC_PREP_NAMES"), getenv("MUSC_SAM"), getenv("MUSC_COVERAGE")};
 }
 
 // setupEnvs/makeTemp/setupLog/saveConfig (cmd/muscato/main.go:906-967, 680-706)
@@ -975,12 +995,13 @@ inline HotResult stage_hot_path(const Config& cfg, const std::vector<UniqueRead>
 }
 
 // results.txt, ordered and rendered where the plan says (MUSC_RESULTS).  Context 0 goes here unless the
-// side outputs or the SAM file are to come from it.  With a SAM file to write, *ordered gets the tuples of the lines in
-// line order -- from the host's own sort, or from the device's ordered list.
+// side outputs, the SAM file or the coverage files are to come from it.  With a SAM file or coverage files for the host
+// to write, *ordered gets the tuples of the lines in line order -- from the host's own sort, or from the device's
+// ordered list.
 inline std::string stage_results(const Config& cfg, const Placement& plan, HotResult& hot, const std::vector<UniqueRead>& reads,
                                  const TargetFiles& tf, Logger& log, std::vector<musc_hit>* ordered) {
   fputs("Combining windows...\nJoining gene names...\nJoining read names...\n", stderr);
-  const bool sam = !cfg.SamFileName.empty();
+  const bool sam = !cfg.SamFileName.empty(), cov = !cfg.CoverageFileName.empty();
   std::string res;
   if (plan.results == Where::Device) {
     float ms_order = 0, ms_text = 0;
@@ -988,13 +1009,14 @@ inline std::string stage_results(const Config& cfg, const Placement& plan, HotRe
     res = results_text_device(hot.ctx.get(), hot.list_on_device, hot.hits, reads, tf.n_targets, tf.id_rest, &ms_order, &ms_text, &nlines);
     log.printf("results on the device: %zu bytes, order %.3f ms, text %.3f ms", res.size(), ms_order, ms_text);
     hot.res_lines = nlines;
-    if (sam && !plan.sam_on_device(hot.list_on_device)) {
+    const bool ctx_for_sam = sam && plan.sam_on_device(hot.list_on_device), ctx_for_cov = cov && plan.coverage_on_device(hot.list_on_device);
+    if ((sam && !ctx_for_sam) || (cov && !ctx_for_cov)) {
       ordered->resize(nlines);
       if (musc_results_hits(hot.ctx.get(), ordered->data(), nlines, 0))
         throw Die(1, std::string("results on the device failed: ") + musc_last_error(hot.ctx.get()));
     }
-    if (plan.side == Where::Host && !(sam && plan.sam_on_device(hot.list_on_device))) hot.ctx.reset();
-  } else if (sam) {
+    if (plan.side == Where::Host && !ctx_for_sam && !ctx_for_cov) hot.ctx.reset();
+  } else if (sam || cov) {
     const std::vector<ResultsLine> lines = results_lines(hot.hits.data(), hot.hits.size(), reads, tf.targets(), tf.id_rest);
     res = results_text(lines, reads);
     ordered->reserve(lines.size());
@@ -1027,13 +1049,51 @@ inline void stage_sam(const Config& cfg, Placement& plan, HotResult& hot, const 
       ordered.resize(hot.res_lines);  // (a refused call leaves the ordered list as it was)
       if (musc_results_hits(c, ordered.data(), ordered.size(), 0)) throw Die(1, std::string("sam file: ") + musc_last_error(c));
     }
-    if (plan.side == Where::Host) hot.ctx.reset();
+    if (plan.side == Where::Host && !(!cfg.CoverageFileName.empty() && plan.coverage_on_device(hot.list_on_device))) hot.ctx.reset();
   }
   const bool from_device = plan.sam_on_device(hot.list_on_device);
   if (!from_device && !sam_text(ordered.data(), ordered.size(), reads, tf.targets(), tf.id_rest, cfg.SamRev, &sam, &why))
     throw Die(1, "SamFileName: " + why + "\n");
   spit(cfg.SamFileName, sam);
   log.printf("sam file on the %s: %.3f s", from_device ? "device" : "host", StageClock::now() - t0);
+}
+
+inline std::string coverage_targets_name(const std::string& coverage) { return coverage + "_targets"; }
+
+inline uint32_t coverage_flags(const Config& cfg) {
+  return (cfg.CoverageRev ? MUSC_COV_REV_PAIRS : 0u) | (cfg.CoverageWeighted ? MUSC_COV_WEIGHTED : 0u) | (cfg.CoverageUnique ? MUSC_COV_UNIQUE : 0u);
+}
+
+// The coverage files (-CoverageFileName, MUSC_COVERAGE): the bedGraph to the name given and the summary to
+// <name>_targets, made where results.txt was made, by the rule of stage_sam: on the device when the plan says so and
+// the list is the one the pass left there, else by coverage_text over `ordered`.  A refusal of the device stage (12) or
+// no memory (10) logs one line and the host function runs; it holds the same refusals and ends the run with the reason.
+inline void stage_coverage(const Config& cfg, Placement& plan, HotResult& hot, const std::vector<UniqueRead>& reads, const TargetFiles& tf,
+                           std::vector<musc_hit>& ordered, Logger& log) {
+  fputs("Writing coverage files...\n", stderr);
+  const double t0 = StageClock::now();
+  const uint32_t flags = coverage_flags(cfg);
+  std::string bed, summary, why;
+  if (plan.coverage_on_device(hot.list_on_device)) {
+    float ms_prepare = 0, ms_text = 0;
+    musc_ctx* c = hot.ctx.get();
+    if (coverage_text_device(c, flags, &bed, &summary, &why, &ms_prepare, &ms_text)) {
+      log.printf("coverage on the device: %zu + %zu bytes, %llu events, prepare %.3f ms, text %.3f ms", bed.size(), summary.size(),
+                 2ull * hot.res_lines, ms_prepare, ms_text);
+    } else {
+      log.printf("coverage on the host: %s", why.c_str());
+      plan.demote(Demotion::CoverageRefused);
+      ordered.resize(hot.res_lines);  // (a refused call leaves the ordered list as it was)
+      if (musc_results_hits(c, ordered.data(), ordered.size(), 0)) throw Die(1, std::string("coverage files: ") + musc_last_error(c));
+    }
+    if (plan.side == Where::Host) hot.ctx.reset();
+  }
+  const bool from_device = plan.coverage_on_device(hot.list_on_device);
+  if (!from_device && !coverage_text(ordered.data(), ordered.size(), reads, tf.targets(), tf.id_rest, flags, &bed, &summary, &why))
+    throw Die(1, "CoverageFileName: " + why + "\n");
+  spit(cfg.CoverageFileName, bed);
+  spit(coverage_targets_name(cfg.CoverageFileName), summary);
+  log.printf("coverage files on the %s: %.3f s", from_device ? "device" : "host", StageClock::now() - t0);
 }
 
 // The nonmatch FASTQ and the two stats files (MUSC_SIDE): from the device, which takes them from the
@@ -1087,12 +1147,16 @@ inline int run_muscato(Config cfg) {
   clk.lap("windows check, target files");
   HotResult hot = stage_hot_path(cfg, reads, tf, plan, log);
   clk.lap("hot path (init, load, match)");
-  std::vector<musc_hit> ordered;  // the tuples of results.txt in line order, kept only for a SAM file the host writes
+  std::vector<musc_hit> ordered;  // the tuples of results.txt in line order, kept only for a SAM file or coverage files the host writes
   const std::string res = stage_results(cfg, plan, hot, reads, tf, log, &ordered);
   clk.lap("results.txt");
   if (!cfg.SamFileName.empty()) {
     stage_sam(cfg, plan, hot, reads, tf, ordered, log);
     clk.skip();  // (the stage logs its own line)
+  }
+  if (!cfg.CoverageFileName.empty()) {
+    stage_coverage(cfg, plan, hot, reads, tf, ordered, log);
+    clk.skip();
   }
   stage_side_outputs(cfg, plan, std::move(hot.ctx), res, reads, log);
   clk.lap("nonmatch + stats files");

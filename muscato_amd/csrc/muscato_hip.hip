@@ -38,6 +38,7 @@
 
 #include "../../include/muscato_hip.h"
 #include "../../include/muscato_sam.h"
+#include "../../include/muscato_cov.h"
 
 #include "ctx_state.hpp"
 #include "dev_mem.hpp"
@@ -57,6 +58,7 @@
 #include "side_names.hpp"
 #include "kernels_side.hpp"
 #include "kernels_sam.hpp"
+#include "kernels_cov.hpp"
 #include "kernels_maxmatches.hpp"
 #include "kernels_fastq.hpp"
 MUSC_LANE_INSTANCES_4(extern)
@@ -351,6 +353,18 @@ struct musc_ctx {
   uint64_t sam_n = 0, sam_bytes = 0, sam_hbytes = 0;
   uint32_t sam_rev = 0;
   float sam_ms_prepare = 0, sam_ms_text = 0;
+
+  // coverage on the device: what musc_cov_prepare leaves for musc_cov_text (valid: st.may_cov_text())
+  DevBuf<uint2> cov_gname;                     // per gene: the RNAME token, as sam_gname (SAM's own stays untouched)
+  DevBuf<uint32_t> cov_run_f, cov_run_d;       // per run: its target, its depth
+  DevBuf<uint64_t> cov_run_s, cov_run_e;       // ... its first base and the one behind its last
+  DevBuf<uint64_t> cov_off, cov_soff;          // cov_nruns + 1 offsets of the bedGraph records; cov_nt + 1 of the summary's
+  DevBuf<uint32_t> cov_target;                 // per summary record: its target
+  DevBuf<uint32_t> cov_numreads, cov_maxdepth; // per target
+  DevBuf<uint64_t> cov_covbases, cov_sumdepth;
+  uint64_t cov_nruns = 0, cov_bytes = 0, cov_nt = 0, cov_sbytes = 0;
+  uint32_t cov_flags = 0;
+  float cov_ms_prepare = 0, cov_ms_text = 0;
 
   // the MaxMatches replay on the device
   musc_params mm_params;            // of the last musc_match* that succeeded (its list may be replayed: st.may_replay())
@@ -968,6 +982,7 @@ int musc_hits_copy(musc_ctx* c, musc_hit* dst, uint64_t capacity, int dst_on_dev
 
 // results.txt and the side outputs as text from the resident tuples (musc_results_*, musc_side_*)
 #include "muscato_text.hpp"
+#include "muscato_cov.hpp"
 // the MaxMatches truncation replayed on the device (musc_maxmatches_*)
 #include "muscato_maxmatches.hpp"
 #include "muscato_read_names.hpp"

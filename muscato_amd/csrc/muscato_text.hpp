@@ -595,13 +595,14 @@ static SamData sam_data(const musc_ctx* c) {
 }
 
 // the refusals that need the device: the RNAME tokens of every gene, and under rev_pairs the lengths of every pair
-static int sam_names(musc_ctx* c, uint32_t rev_pairs, uint32_t* verdict) {
+// (into `gname`: SAM's table, or the coverage stage's own)
+static int sam_names(musc_ctx* c, DevBuf<uint2>& gname, uint32_t rev_pairs, uint32_t* verdict) {
   int rc;
-  if ((rc = ensure(c, c->sam_gname, std::max<uint64_t>(c->nseq, 1)))) return rc;
+  if ((rc = ensure(c, gname, std::max<uint64_t>(c->nseq, 1)))) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, c->stream));
   if (c->nseq) {
     hipLaunchKernelGGL(k_sam_gnames, grid(c, c->nseq), dim3(256), 0, c->stream, c->res_gtext.get(), c->res_goff.get(), c->res_rank.get(),
-                       c->seq_off.get(), c->nseq, rev_pairs, c->sam_gname.p, c->d_flag.get());
+                       c->seq_off.get(), c->nseq, rev_pairs, gname.p, c->d_flag.get());
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, Readback(c->scalars, c->stream).get(c->d_flag.get(), verdict).wait());
@@ -661,7 +662,7 @@ int musc_sam_prepare(musc_ctx* c, int rev_pairs, uint64_t* nrecords, uint64_t* h
     return fail(c, MUSC_SAM_ERR_REFUSED, "musc_sam_prepare: rev_pairs with an odd number of targets (%u)", c->nseq);
   HIPCHK(c, hipSetDevice(c->device));
   uint32_t verdict = 0;
-  int rc = sam_names(c, rev_pairs ? 1u : 0u, &verdict);
+  int rc = sam_names(c, c->sam_gname, rev_pairs ? 1u : 0u, &verdict);
   if (rc) return rc;
   if (verdict & 2u) return fail(c, MUSC_SAM_ERR_REFUSED, "musc_sam_prepare: rev_pairs, and the two targets of a pair differ in length");
   if (verdict & 1u)
